@@ -2,6 +2,7 @@
 
   resampler_ref.safetensors  -- weights, input and output of the REFERENCE's own ip_adapter/resampler.py imported verbatim
                                 (the one hot-path file that imports without diffusers): pins oracle/resampler.py.
+  resampler_ref_small.safetensors -- the same at a second, one-layer configuration.
   reference_unet_tiny.safetensors -- outputs of the REFERENCE's own TryonNet / GarmentNet forwards, hacked transformer blocks
                                 and attention processors on seeded tiny inputs (oracle/make_golden_ref.py; diffusers supplied by
                                 the test-only stand-in tests/compat/refstub): pins oracle/unet.py and oracle/layers.py.
@@ -40,6 +41,23 @@ def resampler_fixture():
     t["x"], t["y"] = x, y
     save_file(t, os.path.join(OUT, "resampler_ref.safetensors"),
               metadata={"kw": repr(kw), "source": REF_RESAMPLER, "generator": "oracle/make_golden.py"})
+
+
+def resampler_small_fixture():
+    """resampler_ref_small.safetensors: the REFERENCE's Resampler at a second configuration (one layer, seeded init), its input and
+    output -- what tests/test_oracle.py::test_resampler_matches_reference_file checks where no reference checkout is present."""
+    spec = importlib.util.spec_from_file_location("ref_resampler", REF_RESAMPLER)
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    kw = dict(dim=64, depth=1, dim_head=32, heads=2, num_queries=8, embedding_dim=48, output_dim=96, ff_mult=2)
+    torch.manual_seed(0)
+    ref = m.Resampler(**kw).eval()
+    x = torch.randn(3, 21, 48)
+    with torch.no_grad():
+        y = ref(x)
+    t = {"sd." + k: v.contiguous() for k, v in ref.state_dict().items()}
+    t["x"], t["y"] = x, y
+    save_file(t, os.path.join(OUT, "resampler_ref_small.safetensors"), metadata={"kw": repr(kw), "generator": "oracle/make_golden.py"})
 
 
 @torch.no_grad()
@@ -115,6 +133,7 @@ if __name__ == "__main__":
     if "--signatures-only" in sys.argv:
         sys.exit(0)
     resampler_fixture()
+    resampler_small_fixture()
     reference_unet_fixture()
     tiny_pipeline_fixture()
     print("wrote", os.listdir(OUT))

@@ -404,6 +404,44 @@ def test_bench_rank_logic_at_world_8_under_gloo(tmp_path):
     assert time.time() - t0 < 300
 
 
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_output(tmp_path):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` (stand-in engine): exactly W + N calls, `ms_per_step` on the line, none of the
+    --full legs, and --dump-outputs writes what the last timed call returned as float32 .npy."""
+    import json
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    env["IDMVTON_STUB_TRACE"] = str(tmp_path / "trace")
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--stub-engine",
+                        "--dump-outputs", str(out)], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["unit"] == "images/s" and d["higher_is_better"] is True and d["dtype"] == "bf16" and d["steps"] == 3 and d["warmup"] == 2
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 2 / (d["ms_per_step"] / 1e3)) < 1e-6 * d["value"]
+    assert not {"parity", "roofline", "fp16", "fp16_fp8", "cpu_baseline"} & set(d)
+    assert len(open(f"{env['IDMVTON_STUB_TRACE']}.0").read().splitlines()) == 2 + 3
+    img = np.load(out / "images.npy")
+    assert img.dtype == np.float32 and img.shape == (2, 3, 8, 8)
+
+
+def test_bench_dump_outputs_samples_a_large_output_the_same_way_every_time(tmp_path):
+    import numpy as np
+    import bench
+    x = (torch.arange(20_000_000) % 1_000_003).float().view(2, 10, 1000, 1000)            # 80 MB > the 64 MB limit
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), images=x)
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= bench.DUMP_LIMIT_BYTES
+    v, i = np.load(tmp_path / "a" / "images.npy"), np.load(tmp_path / "a" / "images_index.npy")
+    assert v.dtype == np.float32 and i.dtype == np.float64 and len(v) == len(i) > 1_000_000
+    assert np.array_equal(v, i % 1_000_003) and np.all(np.diff(i) > 0)                      # the elements at those flat indices; sorted, distinct
+    assert np.array_equal(v, np.load(tmp_path / "b" / "images.npy"))
+    small = torch.rand(2, 3, 4, 4)
+    bench.dump_outputs(str(tmp_path / "c"), images=small)
+    assert np.array_equal(np.load(tmp_path / "c" / "images.npy"), small.numpy()) and not (tmp_path / "c" / "images_index.npy").exists()
+
+
 def test_feature_tokens_follow_the_topology_not_the_channel_count():
     """block_out_channels may repeat a width ((64, 128, 128)): the resolution level of every transformer is recorded while the topology
     is walked, so the real token count of each exported feature stays right (a {channels: level} map collapsed two levels)."""

@@ -33,14 +33,24 @@ def test_resampler_matches_golden_from_reference_file():
     assert torch.equal(y, t["y"]), (y - t["y"]).abs().max()
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference checkout not present (GPU box)")
 def test_resampler_matches_reference_file():
+    """Live against the reference's file where a checkout is present; elsewhere against that file's recorded run at the same
+    configuration (tests/golden/resampler_ref_small.safetensors, oracle/make_golden.py)."""
+    kw = dict(dim=64, depth=1, dim_head=32, heads=2, num_queries=8, embedding_dim=48, output_dim=96, ff_mult=2)
+    b = Resampler(**kw).eval()
+    if not os.path.exists(REF):
+        t, meta = _load("resampler_ref_small.safetensors")
+        assert eval(meta["kw"]) == kw
+        b.load_state_dict({k[3:]: v for k, v in t.items() if k.startswith("sd.")})
+        with torch.no_grad():
+            # recorded on another host: fp32 summation order may differ in the last bits (~1e-6 at |y| ~ 3), not beyond
+            torch.testing.assert_close(b(t["x"]), t["y"], rtol=1e-5, atol=1e-5)
+        return
     spec = importlib.util.spec_from_file_location("ref_resampler", REF)
     ref = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(ref)
-    kw = dict(dim=64, depth=1, dim_head=32, heads=2, num_queries=8, embedding_dim=48, output_dim=96, ff_mult=2)
     torch.manual_seed(0)
-    a, b = ref.Resampler(**kw).eval(), Resampler(**kw).eval()
+    a = ref.Resampler(**kw).eval()
     b.load_state_dict(a.state_dict())
     x = torch.randn(3, 21, 48)
     with torch.no_grad():

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Round-end evidence (tools/gpu_final.sh TAG, e.g. r06_final): build, full GPU test suite, smoke(), the bench line as the driver runs it (with its own PMC traffic leg; the summary is
+# Round-end evidence (tools/gpu_final.sh TAG, e.g. r06_final): build, full GPU test suite, smoke(), the bench line with every leg (--full: its own PMC traffic leg; the summary is
 # also written to profiles-ready JSON), other configurations, rocprofv3 kernel traces of the timed hipGraph loop (two-stream and serial).
 cd "$(dirname "$0")/.." || exit 1
 R=$PWD; O=$R/gpurun_out; mkdir -p $O
@@ -11,10 +11,10 @@ timeout 1500 python -m pytest tests -m gpu -q --tb=short -p no:cacheprovider --d
 cp $O/fullsize_parity.json $O/${TAG}_fullsize_parity.json 2>/dev/null
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/${TAG}_smoke.log 2>&1; echo "smoke rc=$?"; tail -2 $O/${TAG}_smoke.log | cut -c1-400
 t0=$(date +%s)
-timeout 900 python bench.py --steps 10 --warmup 3 --pmc-out $O/${TAG}_pmc_traffic.json > $O/${TAG}_bench_clean.json 2> $O/${TAG}_bench_clean.err; echo "bench rc=$? in $(( $(date +%s) - t0 )) s"; cut -c1-1200 $O/${TAG}_bench_clean.json
+timeout 900 python bench.py --full --steps 10 --warmup 3 --pmc-out $O/${TAG}_pmc_traffic.json > $O/${TAG}_bench_clean.json 2> $O/${TAG}_bench_clean.err; echo "bench rc=$? in $(( $(date +%s) - t0 )) s"; cut -c1-1200 $O/${TAG}_bench_clean.json
 timeout 300 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-roofline --no-pmc --no-fp16-leg > $O/${TAG}_bench_2.json 2>/dev/null; cut -c1-160 $O/${TAG}_bench_2.json
-timeout 600 python bench.py --height 1536 --width 1024 --denoise-steps 50 --batch 1 --steps 2 --no-cpu-baseline --no-roofline --no-pmc > $O/${TAG}_bench_cfg4.json 2> $O/${TAG}_bench_cfg4.err; echo "bench cfg4 rc=$?"; cut -c1-160 $O/${TAG}_bench_cfg4.json
-timeout 600 python bench.py --batch 4 --steps 2 --no-cpu-baseline --no-roofline --no-pmc > $O/${TAG}_bench_b4.json 2> $O/${TAG}_bench_b4.err; echo "bench B=4 rc=$?"; cut -c1-160 $O/${TAG}_bench_b4.json
+timeout 600 python bench.py --full --height 1536 --width 1024 --denoise-steps 50 --batch 1 --steps 2 --no-cpu-baseline --no-roofline --no-pmc > $O/${TAG}_bench_cfg4.json 2> $O/${TAG}_bench_cfg4.err; echo "bench cfg4 rc=$?"; cut -c1-160 $O/${TAG}_bench_cfg4.json
+timeout 600 python bench.py --full --batch 4 --steps 2 --no-cpu-baseline --no-roofline --no-pmc > $O/${TAG}_bench_b4.json 2> $O/${TAG}_bench_b4.err; echo "bench B=4 rc=$?"; cut -c1-160 $O/${TAG}_bench_b4.json
 cd /tmp
 for mode in default serial; do
   extra=""; [ $mode = serial ] && extra="--no-overlap"
