@@ -26,6 +26,7 @@ import torch
 
 from .. import ffi
 from ..clip import HipCLIPText, HipCLIPVision
+from ..garment_cache import GarmentCache
 from ..pipeline import TryonEngine
 from .modules import params_version
 from .scheduler import DDIMScheduler, DDPMScheduler
@@ -335,6 +336,35 @@ class StableDiffusionXLInpaintPipeline:
             self._engine_key = key
         return self._engine
 
+    def _scheduler_kind(self):
+        kind = {DDPMScheduler: "ddpm", DDIMScheduler: "ddim"}.get(type(self.scheduler))
+        if kind is None:
+            kind = {"DDPMScheduler": "ddpm", "DDIMScheduler": "ddim"}.get(type(self.scheduler).__name__)
+        if kind is None:
+            raise NotImplementedError(f"scheduler {type(self.scheduler).__name__}: the fused step kernel implements DDPM and DDIM(eta=0)")
+        return kind
+
+    # ------------------------------------------------------------------------------------------ the garment, once
+    @torch.no_grad()
+    def encode_garment(self, cloth, text_embeds_cloth, num_inference_steps, height, width, strength=1.0, generator=None):
+        """Encode G garments once for many calls: -> GarmentCache, to be passed AS `cloth=` to __call__ (whose `text_embeds_cloth` may then
+        be None) with the same scheduler, num_inference_steps, height and width; any strength whose timesteps are among this one's (a cache
+        made with strength=1.0 serves every strength).  The batch of a cached call may hold P = m * G persons: person i wears garment i % G.
+        The reference has no counterpart (it runs GarmentNet in every step of every call, tryon_pipeline.py:1781-1787).
+
+        RNG: the one draw made here is the cloth posterior sample ([G,4,h,w] fp32, from `generator`).  In __call__ the cloth posterior draw
+        is the call's third draw from `generator` (latents, masked-image posterior, [pose: global generator], cloth, then
+        the DDPM step noise); a call on a cache STILL MAKES that draw and discards it, so every later draw -- the DDPM step noise -- and
+        the generator's final state are those of an uncached call with the same generator."""
+        eng = self.hip_engine()
+        clo = _to_tensor_image(cloth, "cloth")
+        if tuple(clo.shape[-2:]) != (height, width):
+            raise ValueError(f"`cloth` is {tuple(clo.shape[-2:])} but (height, width) = {(height, width)}")
+        h, w = height // self.vae_scale_factor, width // self.vae_scale_factor
+        n_cloth = _randn((clo.shape[0], 4, h, w), generator, eng.device, torch.float32)
+        return eng.encode_garment(cloth=clo, text_embeds_cloth=text_embeds_cloth, noise_cloth=n_cloth, num_inference_steps=num_inference_steps,
+                                  scheduler=self._scheduler_kind(), strength=strength, height=height, width=width)
+
     # ------------------------------------------------------------------------------------------ the call
     @torch.no_grad()
     def __call__(self, prompt=None, prompt_2=None, image=None, mask_image=None, masked_image_latents=None, height=None,
@@ -370,9 +400,10 @@ class StableDiffusionXLInpaintPipeline:
             raise ValueError("`image` input cannot be undefined.")
         if mask_image is None:
             raise ValueError("`mask_image` input cannot be undefined.")
+        cached = isinstance(cloth, GarmentCache)            # encode_garment()'s result passed as `cloth=`: the caption went into it
         for name, val in (("cloth", cloth), ("pose_img", pose_img), ("text_embeds_cloth", text_embeds_cloth),
                           ("ip_adapter_image", ip_adapter_image)):
-            if val is None:
+            if val is None and not (cached and name == "text_embeds_cloth"):
                 raise ValueError(f"`{name}` is required by the try-on pipeline (inference.py:397-414)")
 
         height = height or self.unet.config.sample_size * self.vae_scale_factor                  # :1486-1487
@@ -388,11 +419,7 @@ class StableDiffusionXLInpaintPipeline:
         if n_exec < 1:                                      # :1568-1572
             raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of pipeline"
                              f"steps is {n_exec} which is < 1 and not appropriate for this pipeline.")
-        kind = {DDPMScheduler: "ddpm", DDIMScheduler: "ddim"}.get(type(self.scheduler))
-        if kind is None:
-            kind = {"DDPMScheduler": "ddpm", "DDIMScheduler": "ddim"}.get(type(self.scheduler).__name__)
-        if kind is None:
-            raise NotImplementedError(f"scheduler {type(self.scheduler).__name__}: the fused step kernel implements DDPM and DDIM(eta=0)")
+        kind = self._scheduler_kind()
         if kind == "ddim" and eta != 0.0:
             raise NotImplementedError("DDIM with eta != 0")
 
@@ -411,9 +438,9 @@ class StableDiffusionXLInpaintPipeline:
         if msk.shape[1] != 1:
             msk = msk.mean(dim=1, keepdim=True)                                                  # do_convert_grayscale
         pose = _to_tensor_image(pose_img, "pose_img")
-        clo = _to_tensor_image(cloth, "cloth")
+        clo = cloth if cached else _to_tensor_image(cloth, "cloth")
         B = img.shape[0]
-        for name, t in (("pose_img", pose), ("cloth", clo)):                                     # encoded as they are (:1644-1654): no resize there
+        for name, t in (("pose_img", pose),) + ((("cloth", clo),) if not cached else ()):        # encoded as they are (:1644-1654): no resize there
             if tuple(t.shape[-2:]) != (height, width):
                 raise ValueError(f"`{name}` is {tuple(t.shape[-2:])} but (height, width) = {(height, width)}: the reference encodes it as it "
                                  "is and fails when its latents are concatenated with the image's")
@@ -433,6 +460,8 @@ class StableDiffusionXLInpaintPipeline:
         n_lat = latents.to(device).float() if latents is not None else _randn(shape, generator, device, prompt_embeds.dtype)
         n_masked, n_pose, n_cloth = (_randn(shape, generator, device, torch.float32), _randn(shape, None, device, torch.float32),
                                      _randn(shape, generator, device, torch.float32))
+        if cached:                                          # drawn all the same, so that every later draw is the uncached call's; not used
+            n_cloth = None
         steps_noise = None
         if kind == "ddpm":
             steps_noise = torch.stack([_randn(shape, generator, device, eng.dtype) for _ in range(n_exec)])

@@ -31,6 +31,7 @@ struct AttnParams {
     int nqb, chunk, parts;
     int pp_flags; float pp_thr;
     int q_prescaled;
+    int seg_nb[2];                                      // batch elements a segment holds (idmvton_attn_fwd_shared); 0 = one per query batch from seg_b0 on
 };
 
 #define NEG_BIG (-1.0e30f)
@@ -161,6 +162,7 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_kernel(const AttnParams p) {
     const int nt0 = pres0 ? (p.nk[0] + 63) >> 6 : 0;
     const int nt1 = pres1 ? (p.nk[1] + 63) >> 6 : 0;
     const int nt = nt0 + nt1;
+    const int bsg0 = seg_batch(b, p.seg_b0[0], p.seg_nb[0]), bsg1 = seg_batch(b, p.seg_b0[1], p.seg_nb[1]);   // per workgroup, scalar
 
     // ---- loader ----
     const int lrow = lane >> 3, lslot = lane & 7;
@@ -168,7 +170,7 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_kernel(const AttnParams p) {
         const int sg = t < nt0 ? 0 : 1;
         const int kt = sg ? t - nt0 : t;
         const int nk = p.nk[sg];
-        const int bsg = b - p.seg_b0[sg];
+        const int bsg = sg ? bsg1 : bsg0;
         char* dst = tile + wave * (IPW * 1024);
 #pragma unroll
         for (int i = 0; i < IPW; ++i) {
@@ -428,7 +430,7 @@ __global__ __launch_bounds__(512, DEEP ? 2 : 4) void attn_pp_kernel(const AttnPa
     const int lim_x = is_k ? 8 : 32;
 #pragma unroll
     for (int sg = 0; sg < 2; ++sg) {
-        const size_t bsg = (size_t)(b - p.seg_b0[sg] > 0 ? b - p.seg_b0[sg] : 0);
+        const size_t bsg = (size_t)seg_batch(b, p.seg_b0[sg], p.seg_nb[sg]);
         tstep[sg] = is_k ? (uint32_t)(64 * p.ldk[sg] * 2) : 128u;
 #pragma unroll
         for (int i = 0; i < IPW; ++i) {
@@ -744,7 +746,7 @@ __global__ __launch_bounds__(512, 2) void attn_pf_kernel(const AttnParams p) {
     const int lim_x = is_k ? 8 : 32;
 #pragma unroll
     for (int sg = 0; sg < 2; ++sg) {
-        const size_t bsg = (size_t)(b - p.seg_b0[sg] > 0 ? b - p.seg_b0[sg] : 0);
+        const size_t bsg = (size_t)seg_batch(b, p.seg_b0[sg], p.seg_nb[sg]);
         tstep[sg] = is_k ? (uint32_t)(64 * p.ldk[sg] * 2) : 128u;
 #pragma unroll
         for (int i = 0; i < IPW; ++i) {
@@ -1044,8 +1046,9 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_sp_kernel(const AttnParams p)
     // per-lane byte offsets of this wave's IPW DMA rows inside segment sg (tile 0).  Only the CURRENT segment's set lives in registers; it is
     // recomputed at the segment switch.  lane_lim(i): the smallest key index piece i fetches (only a segment's partial last tile needs it).
     uint32_t rb[IPW];
+    const int bsg0 = seg_batch(b, p.seg_b0[0], p.seg_nb[0]), bsg1 = seg_batch(b, p.seg_b0[1], p.seg_nb[1]);   // per workgroup, scalar
     auto seg_base = [&](int sg) {
-        const size_t bsg = (size_t)(b - p.seg_b0[sg] > 0 ? b - p.seg_b0[sg] : 0);
+        const size_t bsg = (size_t)(sg ? bsg1 : bsg0);
 #pragma unroll
         for (int i = 0; i < IPW; ++i) {
             const int R = ((wave * IPW + i) & 7) * 8 + lrow;
@@ -1406,7 +1409,9 @@ static int launch_attn(AttnParams& p, int tune, hipStream_t st) {
     return IDMVTON_OK;
 }
 
-extern "C" int idmvton_attn_fwd(const idmvton_attn_args* a, void* stream) {
+// One implementation behind both entry points.  seg_nb[s] > 0: segment s holds seg_nb[s] batch elements and query batch b >= seg_b0[s] reads
+// element (b - seg_b0[s]) % seg_nb[s] (one garment's K / V^T shared by several persons); 0: one element per query batch from seg_b0[s] on.
+static int attn_fwd_impl(const idmvton_attn_args* a, const int32_t* seg_nb, void* stream) {
     CHECK_ARG(a != nullptr, IDMVTON_E_ARG, "attn_fwd: null args");
     CHECK_ARG(a->dtype == IDMVTON_F16 || a->dtype == IDMVTON_BF16, IDMVTON_E_DTYPE, "attn_fwd: dtype %d", a->dtype);
     CHECK_ARG(a->mode == IDMVTON_ATTN_SELF || a->mode == IDMVTON_ATTN_CROSS, IDMVTON_E_ARG, "attn_fwd: mode %d", a->mode);
@@ -1427,20 +1432,33 @@ extern "C" int idmvton_attn_fwd(const idmvton_attn_args* a, void* stream) {
         const int ss = s < a->nseg ? s : 0;
         CHECK_ARG(a->k[ss] && a->vt[ss] && a->nk[ss] > 0 && a->seg_b0[ss] >= 0 && a->seg_b0[ss] <= a->B,
                   IDMVTON_E_SHAPE, "attn_fwd: seg %d nk=%d b0=%d", ss, a->nk[ss], a->seg_b0[ss]);
+        CHECK_ARG(seg_nb[ss] >= 0 && seg_nb[ss] <= a->B - a->seg_b0[ss], IDMVTON_E_SHAPE,
+                  "attn_fwd_shared: seg %d seg_nb=%d outside [0, B - seg_b0 = %d]", ss, seg_nb[ss], a->B - a->seg_b0[ss]);
+        CHECK_ARG(a->mode != IDMVTON_ATTN_CROSS || seg_nb[ss] == 0, IDMVTON_E_ARG, "attn_fwd_shared: CROSS mode takes seg_nb = {0, 0} (seg %d: %d)", ss, seg_nb[ss]);
         const int krows = a->k_rows[ss] > 0 ? a->k_rows[ss] : a->nk[ss];
         CHECK_ARG(krows >= a->nk[ss], IDMVTON_E_SHAPE, "attn_fwd: seg %d k_rows=%d < nk", ss, krows);
         CHECK_ARG(a->ldk[ss] % 8 == 0 && a->ldvt[ss] % 16 == 0 && a->ldvt[ss] >= ((a->nk[ss] + 15) & ~15) && a->ldk[ss] >= a->heads * 64 &&
                   ((uintptr_t)a->k[ss] & 15) == 0 && ((uintptr_t)a->vt[ss] & 15) == 0, IDMVTON_E_ALIGN,
                   "attn_fwd: seg %d ldk=%d ldvt=%d (V^T is read in key order: ldvt %% 16 == 0, ldvt >= roundup16(nk))", ss, a->ldk[ss], a->ldvt[ss]);
-        const int nb = a->B - a->seg_b0[ss];
+        const int nb = seg_nb[ss] > 0 ? seg_nb[ss] : a->B - a->seg_b0[ss];   // batch elements the segment holds: the bound of every K / V^T read
         const uint64_t kb = (uint64_t)nb * krows * a->ldk[ss] * 2, vb = (uint64_t)nb * a->heads * 64 * a->ldvt[ss] * 2;
         CHECK_ARG(kb < 0x80000000ull && vb < 0x80000000ull, IDMVTON_E_SHAPE, "attn_fwd: seg %d K/V^T >= 2 GiB", ss);
         p.k[s] = a->k[ss]; p.ldk[s] = a->ldk[ss]; p.kbytes[s] = (uint32_t)kb;
         p.vt[s] = a->vt[ss]; p.ldvt[s] = a->ldvt[ss]; p.vtbytes[s] = (uint32_t)vb;
-        p.nk[s] = a->nk[ss]; p.krows[s] = krows; p.seg_b0[s] = a->seg_b0[ss];
+        p.nk[s] = a->nk[ss]; p.krows[s] = krows; p.seg_b0[s] = a->seg_b0[ss]; p.seg_nb[s] = seg_nb[ss];
     }
     hipStream_t st = (hipStream_t)stream;
     if (a->dtype == IDMVTON_BF16)
         return a->mode == IDMVTON_ATTN_SELF ? launch_attn<bf16_t, IDMVTON_ATTN_SELF>(p, a->tune, st) : launch_attn<bf16_t, IDMVTON_ATTN_CROSS>(p, a->tune, st);
     return a->mode == IDMVTON_ATTN_SELF ? launch_attn<f16_t, IDMVTON_ATTN_SELF>(p, a->tune, st) : launch_attn<f16_t, IDMVTON_ATTN_CROSS>(p, a->tune, st);
+}
+
+extern "C" int idmvton_attn_fwd(const idmvton_attn_args* a, void* stream) {
+    static const int32_t none[2] = {0, 0};
+    return attn_fwd_impl(a, none, stream);
+}
+
+extern "C" int idmvton_attn_fwd_shared(const idmvton_attn_args* a, const int32_t seg_nb[2], void* stream) {
+    CHECK_ARG(seg_nb != nullptr, IDMVTON_E_ARG, "attn_fwd_shared: null seg_nb");
+    return attn_fwd_impl(a, seg_nb, stream);
 }

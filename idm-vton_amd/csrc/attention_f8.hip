@@ -33,6 +33,7 @@ struct AttnF8Params {
     int nk[2]; int krows[2]; int seg_b0[2];
     int sc_qk, sc_v;                                   // E8M0 bytes (127 + exponent), replicated in all four bytes
     int nqb;
+    int seg_nb[2];                                     // batch elements a segment holds (idmvton_attn_f8_shared); 0 = one per query batch from seg_b0 on
 };
 
 #define NEG_BIG_F8 (-1.0e30f)
@@ -64,6 +65,7 @@ __global__ __launch_bounds__(256) void attn_f8_kernel(const AttnF8Params p) {
     const int nt0 = pres0 ? (p.nk[0] + 63) >> 6 : 0;
     const int nt1 = pres1 ? (p.nk[1] + 63) >> 6 : 0;
     const int nt = nt0 + nt1;
+    const int bsg0 = seg_batch(b, p.seg_b0[0], p.seg_nb[0]), bsg1 = seg_batch(b, p.seg_b0[1], p.seg_nb[1]);   // per workgroup, scalar
 
     f32x16 oacc[2];
 #pragma unroll
@@ -82,7 +84,7 @@ __global__ __launch_bounds__(256) void attn_f8_kernel(const AttnF8Params p) {
     auto load_tile = [&](int t, i32x8 (&kk)[2], i32x8 (&vv)[2]) {
         const int sg = t < nt0 ? 0 : 1;
         const int kt = sg ? t - nt0 : t;
-        const int bsg = b - p.seg_b0[sg];
+        const int bsg = sg ? bsg1 : bsg0;
         const uint8_t* kp = p.k[sg] + (size_t)bsg * p.krows[sg] * p.ldk[sg] + h * 64 + 32 * u;
         const uint8_t* vp = p.vt[sg] + ((size_t)bsg * p.heads * 64 + h * 64) * p.ldvt[sg] + kt * 64 + 32 * u;
 #pragma unroll
@@ -171,7 +173,9 @@ __global__ __launch_bounds__(256) void attn_f8_kernel(const AttnF8Params p) {
     }
 }
 
-extern "C" int idmvton_attn_f8(const idmvton_attn_f8_args* a, void* stream) {
+// One implementation behind both entry points; seg_nb as in idmvton_attn_fwd_shared.  This kernel reads K / V^T through plain pointers, so the
+// seg_nb bound checked here is what keeps every read inside the caller's seg_nb-element tensors.
+static int attn_f8_impl(const idmvton_attn_f8_args* a, const int32_t* seg_nb, void* stream) {
     CHECK_ARG(a != nullptr, IDMVTON_E_ARG, "attn_f8: null args");
     CHECK_ARG(a->out_dtype == IDMVTON_F16 || a->out_dtype == IDMVTON_BF16, IDMVTON_E_DTYPE, "attn_f8: out_dtype %d", a->out_dtype);
     CHECK_ARG(a->B > 0 && a->heads > 0 && a->Nq > 0 && a->nseg >= 1 && a->nseg <= 2, IDMVTON_E_SHAPE, "attn_f8: B=%d heads=%d Nq=%d nseg=%d", a->B, a->heads, a->Nq, a->nseg);
@@ -183,12 +187,14 @@ extern "C" int idmvton_attn_f8(const idmvton_attn_f8_args* a, void* stream) {
     for (int s = 0; s < 2; ++s) {
         const int ss = s < a->nseg ? s : 0;
         CHECK_ARG(a->k8[ss] && a->vt8[ss] && a->nk[ss] > 0 && a->seg_b0[ss] >= 0 && a->seg_b0[ss] <= a->B, IDMVTON_E_SHAPE, "attn_f8: seg %d", ss);
+        CHECK_ARG(seg_nb[ss] >= 0 && seg_nb[ss] <= a->B - a->seg_b0[ss], IDMVTON_E_SHAPE,
+                  "attn_f8_shared: seg %d seg_nb=%d outside [0, B - seg_b0 = %d]", ss, seg_nb[ss], a->B - a->seg_b0[ss]);
         const int krows = a->k_rows[ss] > 0 ? a->k_rows[ss] : a->nk[ss];
         CHECK_ARG(krows >= a->nk[ss] && a->ldk[ss] % 16 == 0 && a->ldk[ss] >= a->heads * 64 && a->ldvt[ss] % 64 == 0 && a->ldvt[ss] >= ((a->nk[ss] + 63) & ~63) &&
                   ((uintptr_t)a->k8[ss] & 15) == 0 && ((uintptr_t)a->vt8[ss] & 15) == 0, IDMVTON_E_ALIGN,
                   "attn_f8: seg %d ldk=%d ldvt=%d (V^T rows hold whole 64-key tiles: ldvt %% 64 == 0, ldvt >= roundup64(nk), zero-filled beyond nk)", ss, a->ldk[ss], a->ldvt[ss]);
         p.k[s] = (const uint8_t*)a->k8[ss]; p.ldk[s] = a->ldk[ss]; p.vt[s] = (const uint8_t*)a->vt8[ss]; p.ldvt[s] = a->ldvt[ss];
-        p.nk[s] = a->nk[ss]; p.krows[s] = krows; p.seg_b0[s] = a->seg_b0[ss];
+        p.nk[s] = a->nk[ss]; p.krows[s] = krows; p.seg_b0[s] = a->seg_b0[ss]; p.seg_nb[s] = seg_nb[ss];
     }
     auto rep = [](int e) { const int b = (127 + e) & 0xff; return b | (b << 8) | (b << 16) | (b << 24); };
     p.sc_qk = rep(a->qk_scale_exp);
@@ -199,6 +205,16 @@ extern "C" int idmvton_attn_f8(const idmvton_attn_f8_args* a, void* stream) {
     else hipLaunchKernelGGL((attn_f8_kernel<f16_t>), grid, block, 0, (hipStream_t)stream, p);
     CHECK_LAUNCH("attn_f8");
     return IDMVTON_OK;
+}
+
+extern "C" int idmvton_attn_f8(const idmvton_attn_f8_args* a, void* stream) {
+    static const int32_t none[2] = {0, 0};
+    return attn_f8_impl(a, none, stream);
+}
+
+extern "C" int idmvton_attn_f8_shared(const idmvton_attn_f8_args* a, const int32_t seg_nb[2], void* stream) {
+    CHECK_ARG(seg_nb != nullptr, IDMVTON_E_ARG, "attn_f8_shared: null seg_nb");
+    return attn_f8_impl(a, seg_nb, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -39,6 +39,16 @@ template <> struct VT<f16_t> {
 // Wave-uniform value the compiler can prove uniform (needed for M0 / SGPR operands).
 __device__ __forceinline__ int uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }
 
+// Batch element of a key segment that query batch b reads (attention kernels): (b - b0) % nb; nb == 0 means one element per query batch from b0
+// on (no wrap).  b comes from the block id, so this is scalar code, evaluated once per workgroup; the division exists on the nb > 1 path only.
+__device__ __forceinline__ int seg_batch(int b, int b0, int nb) {
+    int d = b - b0;
+    d = d > 0 ? d : 0;
+    if (nb == 1) d = 0;
+    else if (nb > 1) d = (int)((unsigned)d % (unsigned)nb);
+    return d;
+}
+
 // 16-byte LDS-DMA: every lane supplies a byte offset into the buffer `rs`; lane l's 16 bytes land at
 // lds_base + 16*l (lds_base must be wave-uniform).  Out-of-range offsets (>= num_records) read as zero.
 __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rs, void* lds_base, uint32_t voff) {

@@ -111,7 +111,8 @@ SYMBOLS = ["idmvton_last_error", "idmvton_abi_version", "idmvton_sizeof", "idmvt
            "idmvton_layernorm", "idmvton_groupnorm", "idmvton_pack_input", "idmvton_cfg_step", "idmvton_layout",
            "idmvton_vae_sample", "idmvton_softmax_rows", "idmvton_probe_mfma", "idmvton_groupnorm_stats_doubles",
            "idmvton_attn_small", "idmvton_rccl_unique_id", "idmvton_rccl_comm_init", "idmvton_rccl_bcast_arena",
-           "idmvton_rccl_comm_destroy", "idmvton_attn_f8", "idmvton_quant_f8", "idmvton_split"]
+           "idmvton_rccl_comm_destroy", "idmvton_attn_f8", "idmvton_quant_f8", "idmvton_split", "idmvton_attn_fwd_shared",
+           "idmvton_attn_f8_shared"]
 
 _lib = None
 
@@ -148,6 +149,9 @@ def lib():
               "idmvton_attn_small", "idmvton_attn_f8", "idmvton_quant_f8", "idmvton_split"):
         getattr(L, s).argtypes = [vp, vp]
         getattr(L, s).restype = C.c_int
+    for s in ("idmvton_attn_fwd_shared", "idmvton_attn_f8_shared"):          # (args*, const int32_t seg_nb[2], stream)
+        getattr(L, s).argtypes = [vp, C.POINTER(i32), vp]
+        getattr(L, s).restype = C.c_int
     L.idmvton_probe_mfma.argtypes = [C.c_int, vp, vp, vp, vp]
     L.idmvton_groupnorm_stats_doubles.argtypes = [C.c_int] * 4
     L.idmvton_groupnorm_stats_doubles.restype = C.c_int
@@ -165,5 +169,14 @@ def call(fn_name, args, stream):
     """Invoke an `int f(const args*, void* stream)` entry point; raise RuntimeError with the library's message."""
     L = lib()
     rc = getattr(L, fn_name)(C.byref(args), C.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError(f"{fn_name} failed ({rc}): {L.idmvton_last_error().decode()}")
+
+
+def call_shared(fn_name, args, seg_nb, stream):
+    """Invoke an `int f(const args*, const int32_t seg_nb[2], void* stream)` entry point (the shared-segment attention launches)."""
+    L = lib()
+    nb = (i32 * 2)(*seg_nb)
+    rc = getattr(L, fn_name)(C.byref(args), nb, C.c_void_p(stream))
     if rc != 0:
         raise RuntimeError(f"{fn_name} failed ({rc}): {L.idmvton_last_error().decode()}")

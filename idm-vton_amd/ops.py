@@ -30,13 +30,15 @@ def _stream():
 PROFILE = None
 
 
-def _call(fn_name, args, flops=0.0, bytes_=0.0):
+def _call(fn_name, args, flops=0.0, bytes_=0.0, seg_nb=None):
+    """seg_nb: the shared-segment attention entry points' extra argument (fn_name is then idmvton_attn_*_shared)."""
+    launch = (lambda: ffi.call(fn_name, args, _stream())) if seg_nb is None else (lambda: ffi.call_shared(fn_name, args, seg_nb, _stream()))
     if PROFILE is None:
-        ffi.call(fn_name, args, _stream())
+        launch()
         return
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    ffi.call(fn_name, args, _stream())
+    launch()
     e1.record()
     PROFILE.append((fn_name, e0, e1, flops, bytes_))
 
@@ -220,7 +222,9 @@ QSCALE = 0.125 * 1.4426950408889634          # softmax_scale(d=64) * log2(e): wh
 
 
 def attention(q, out, segs, heads, *, mode=ffi.ATTN_SELF, ip_scale=1.0, B=None, Nq=None, ldq=None, ldo=None, tune=0, q_prescaled=False):
-    """q/out: [B][Nq][>=heads*64] views; segs: list of dict(k=, vt=, nk=, ldk=, ldvt=, k_rows=, b0=)."""
+    """q/out: [B][Nq][>=heads*64] views; segs: list of dict(k=, vt=, nk=, ldk=, ldvt=, k_rows=, b0=[, nb=]).
+    nb (absent or 0: one K / V^T element per query batch from b0 on): the segment holds nb elements and batch b reads (b - b0) % nb -- a shared
+    garment segment, launched through idmvton_attn_fwd_shared.  The tune-table key does not carry nb: same kernel choice as the materialised launch."""
     a = ffi.AttnArgs()
     a.dtype, a.mode = _dt(q), mode
     a.B = q.shape[0] if B is None else B
@@ -246,8 +250,15 @@ def attention(q, out, segs, heads, *, mode=ffi.ATTN_SELF, ip_scale=1.0, B=None, 
     fl = 0.0
     for s in segs:
         fl += 4.0 * (a.B - s.get("b0", 0)) * heads * a.Nq * s["nk"] * 64
-    _call("idmvton_attn_fwd", a, flops=fl, bytes_=2.0 * a.B * a.Nq * heads * 64 * q.element_size())
+    nb = _seg_nb(segs)
+    _call("idmvton_attn_fwd_shared" if nb else "idmvton_attn_fwd", a, flops=fl, bytes_=2.0 * a.B * a.Nq * heads * 64 * q.element_size(), seg_nb=nb)
     return out
+
+
+def _seg_nb(segs):
+    """None when no segment is shared (the old entry point is called), else the two seg_nb values."""
+    nb = [int(s.get("nb", 0) or 0) for s in segs] + [0] * (2 - len(segs))
+    return nb if any(nb) else None
 
 
 def quant_f8(src, scale, mode=0, out=None):
@@ -265,7 +276,8 @@ def quant_f8(src, scale, mode=0, out=None):
 
 
 def attention_f8(q8, out, segs, heads, *, qk_scale_exp, v_scale_exp, B, Nq, ldq=None, ldo=None):
-    """fp8 self-attention (csrc/attention_f8.hip).  q8: uint8 [B*Nq][>= heads*64]; segs: list of dict(k8=, vt8=, nk=, ldk=, ldvt=, k_rows=, b0=)."""
+    """fp8 self-attention (csrc/attention_f8.hip).  q8: uint8 [B*Nq][>= heads*64]; segs: list of dict(k8=, vt8=, nk=, ldk=, ldvt=, k_rows=, b0=[, nb=]);
+    nb as in attention() (idmvton_attn_f8_shared)."""
     a = ffi.AttnF8Args()
     a.out_dtype, a.B, a.heads, a.Nq = _dt(out), B, heads, Nq
     a.q8, a.ldq = _ptr(q8), (q8.stride(-2) if ldq is None else ldq)
@@ -278,7 +290,8 @@ def attention_f8(q8, out, segs, heads, *, qk_scale_exp, v_scale_exp, B, Nq, ldq=
         a.nk[i], a.k_rows[i], a.seg_b0[i] = s["nk"], s.get("k_rows", 0), s.get("b0", 0)
         fl += 4.0 * (B - s.get("b0", 0)) * heads * Nq * s["nk"] * 64
     a.qk_scale_exp, a.v_scale_exp = qk_scale_exp, v_scale_exp
-    _call("idmvton_attn_f8", a, flops=fl, bytes_=float(B * Nq * heads * 64 * (1 + out.element_size())))
+    nb = _seg_nb(segs)
+    _call("idmvton_attn_f8_shared" if nb else "idmvton_attn_f8", a, flops=fl, bytes_=float(B * Nq * heads * 64 * (1 + out.element_size())), seg_nb=nb)
     return out
 
 

@@ -14,21 +14,34 @@ that GarmentNet batch plus the TryonNet steps that consume its features.  Blocks
 timesteps -- because only the first block's GarmentNet batch cannot hide behind TryonNet work (nothing runs before it): with a
 one-timestep first block 7.5 ms of a call are exposed instead of the 45 ms of a six-timestep batch, and each later batch is
 shorter than the TryonNet steps of the block before it.  Every batch runs at its exact size (no padded timesteps).
+
+The same fact across calls: `encode_garment` runs the garment side alone (cloth VAE encode, GarmentNet batches in the same block schedule,
+the K / V^T projections) and returns a GarmentCache; `prepare(cloth=<GarmentCache>)` then builds a call with no garment work at all, for
+P persons on G cached garments (P % G == 0; the attention kernels read garment i % G for person i through a shared key segment).
 """
 import torch
 
 from . import ops
+from .garment_cache import GarmentCache
 from .scheduler import StepScheduler
 
 
 def _copy_state(dst, src):
     """Copy every tensor the captured step reads (latents, conditioning, K/V^T caches) into the graph's buffers."""
-    for k in ("latents", "cond", "cloth", "cloth_k"):
+    cached = src.get("gcache") is not None               # a GarmentCache call has no garment-side tensors
+    for k in ("latents", "cond") if cached else ("latents", "cond", "cloth", "cloth_k"):
         dst[k].copy_(src[k])
-    for ck in ("ctx_t", "ctx_g", "ctx_gk"):
+    for ck in ("ctx_t",) if cached else ("ctx_t", "ctx_g", "ctx_gk"):
         for p, ent in src[ck]["kv"].items():
             for name, t in ent.items():
                 dst[ck]["kv"][p][name].copy_(t)
+
+
+def _is_attn1_kv(key):
+    return ".attn1.to_k." in key or ".attn1.to_v." in key
+
+
+_CACHED = object()          # stands in for the GarmentCache in a persistent graph state (only "is there one" is asked of it)
 
 
 class TryonEngine:
@@ -40,6 +53,94 @@ class TryonEngine:
         self._side = None
         self.garment_steps = 6                               # timesteps per GarmentNet batch (see the module docstring)
         self.ramp = True                                     # first blocks of 1, 2, 4 timesteps
+        # garment_batches: GarmentNet batches launched or replayed by this engine (a call on a GarmentCache adds none); garment_set_copies: blocks
+        # of cached K / V^T copied into a persistent set by the graph forms
+        self.stats = dict(garment_batches=0, garment_set_copies=0)
+        self._weights_id = None
+
+    # -------------------------------------------------------------------------------------------- shared by prepare / encode_garment
+    @staticmethod
+    def _timesteps(scheduler, num_inference_steps, strength):
+        sched = StepScheduler(scheduler)
+        timesteps = sched.set_timesteps(num_inference_steps)                               # :1561
+        init_t = min(int(num_inference_steps * strength), num_inference_steps)             # get_timesteps :987-995
+        timesteps = timesteps[max(num_inference_steps - init_t, 0):]
+        if len(timesteps) < 1:                                                             # :1568-1572
+            raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of pipeline"
+                             f"steps is {len(timesteps)} which is < 1 and not appropriate for this pipeline.")
+        return sched, timesteps
+
+    def _block_schedule(self, n):
+        """-> (k, [(first step, steps)]): block sizes ramp 1, 2, 4, k, k, ... (module docstring)."""
+        k = max(1, min(self.garment_steps, n))
+        sizes, s0 = [], 0
+        for c in (1, 2, 4):
+            if c < k and s0 + c <= n and self.ramp:
+                sizes.append(c); s0 += c
+        while s0 < n:
+            sizes.append(min(k, n - s0)); s0 += sizes[-1]
+        blocks, s0 = [], 0
+        for c in sizes:
+            blocks.append((s0, c)); s0 += c
+        return k, blocks
+
+    def _garment_inputs(self, cloth_lat, text_embeds_cloth, timesteps, B):
+        """GarmentNet's inputs for B garments over the call's timesteps, batched per block: batch index = j*B + b (timestep-major);
+        temb_gk rows beyond a block's own c*B are never read."""
+        dev, dt = self.device, self.dtype
+        cloth_nhwc = ops.to_nhwc(cloth_lat, dt, cpad=self.unet_encoder.cin_pad)
+        ctx_g = self.unet_encoder.encode_context(text_embeds_cloth.to(dev))
+        temb_g = self.unet_encoder.time_embeddings(timesteps, B)
+        n = len(timesteps)
+        k, blocks = self._block_schedule(n)
+        tidx = torch.tensor([[min(s0 + j, n - 1) for j in range(k)] for s0, _ in blocks], device=dev)
+        temb_gk = temb_g[tidx].reshape(len(blocks), k * B, -1).contiguous()
+        cloth_k = cloth_nhwc.repeat(k, 1, 1).contiguous()
+        ctx_gk = ctx_g if k == 1 else self.unet_encoder.encode_context(text_embeds_cloth.to(dev).repeat(k, 1, 1))
+        return dict(cloth=cloth_nhwc, ctx_g=ctx_g, temb_g=temb_g, k=k, blocks=blocks, temb_gk=temb_gk, cloth_k=cloth_k, ctx_gk=ctx_gk)
+
+    def weights_identity(self):
+        """What a GarmentCache depends on besides its inputs: every GarmentNet weight, and TryonNet's attn1.to_k / to_v (the projections of
+        project_garment_kv), as stored (dtype included)."""
+        if self._weights_id is None:
+            self._weights_id = self.unet_encoder.weights_id() + ":" + self.unet.weights_id(_is_attn1_kv)
+        return self._weights_id
+
+    # -------------------------------------------------------------------------------------------- the garment side, once
+    @torch.no_grad()
+    def encode_garment(self, *, cloth, text_embeds_cloth, noise_cloth, num_inference_steps, scheduler="ddpm", strength=1.0,
+                       height=None, width=None):
+        """The garment side of a call for G = cloth.shape[0] garments, computed once: -> GarmentCache for `prepare(cloth=<it>)`.
+        cloth in [-1,1] [G,3,H,W]; noise_cloth: the posterior draw of the cloth encode, [G,4,h,w] fp32 (noise['cloth'] of an uncached call).
+        Runs what the loop runs for the garment side -- cloth VAE encode, encode_context, time_embeddings, and per block the GarmentNet batch
+        + project_garment_kv -- IN THE SAME BLOCK SCHEDULE (1, 2, 4, k, k, ...) and at the same batch sizes as an uncached call with G
+        persons and this num_inference_steps / strength, so every launch is the launch that call makes and the cached K / V^T are its bits.
+        For the same reason the cloth goes through the VAE encoder in the third slot of a 3G-image pass, where an uncached call encodes it
+        (prepare: [masked image | pose | cloth]): per image the arithmetic does not depend on the batch, but which GEMM tile runs may."""
+        dev = self.device
+        f32 = lambda t: t.to(dev, torch.float32).contiguous()
+        cloth, nz = f32(cloth), f32(noise_cloth)
+        G = cloth.shape[0]
+        H = height or cloth.shape[-2]
+        W = width or cloth.shape[-1]
+        if H % 8 or W % 8:
+            raise ValueError(f"`height` and `width` have to be divisible by 8 but are {H} and {W}.")
+        h, w = H // 8, W // 8
+        _, timesteps = self._timesteps(scheduler, num_inference_steps, strength)
+        cloth_lat = self.vae.encode_sample(torch.cat([cloth, cloth, cloth]), torch.cat([nz, nz, nz]))[2 * G:]
+        gs = dict(B=G, h=h, w=w, **self._garment_inputs(cloth_lat, text_embeds_cloth, timesteps, G))
+        n, k = len(timesteps), gs["k"]
+        if (G, h, w, k) not in self._set_shapes:
+            self._new_set(gs)                                # shape discovery (one GarmentNet batch, dropped)
+        fs, ks = self._set_shapes[(G, h, w, k)]
+        feats = [torch.empty(sh, dtype=self.dtype, device=dev) for sh in fs]
+        kv = [(torch.empty((a[0] // k * n,) + tuple(a[1:]), dtype=d, device=dev), torch.empty((n * G,) + tuple(b[1:]), dtype=d, device=dev))
+              for a, b, d in ks]
+        for bi, (s0, c) in enumerate(gs["blocks"]):          # each block's projections land in the cache's own rows
+            views = [(kk[s0 * (kk.shape[0] // n):], vv[s0 * G:]) for kk, vv in kv]
+            self._garment_side(gs, gs["temb_gk"][bi], dict(feats=feats, kv=views), c)
+        return GarmentCache(G=G, timesteps=timesteps, h=h, w=w, dtype=self.dtype, attn_fp8=self.unet.attn_fp8, f8_exp=self.unet.f8_exp,
+                            weights_id=self.weights_identity(), kv=kv)
 
     # -------------------------------------------------------------------------------------------- preparation
     @torch.no_grad()
@@ -53,10 +154,19 @@ class TryonEngine:
         strength < 1 (:987-995, 883-893): the last int(n*strength) timesteps, starting from add_noise(encode(image), noise, t_0).
         guidance_scale <= 1 (:440-442: no classifier-free guidance): the reference runs the conditional branch alone; here the
         batched step runs with guidance 1 -- u + 1*(t - u) = t to one fp32 rounding -- so negative_* may be None and
-        ip_hidden_states / image_embeds may hold the B conditional rows only."""
+        ip_hidden_states / image_embeds may hold the B conditional rows only.
+        cloth = a GarmentCache (encode_garment) of G garments: no garment work in this call -- no cloth encode, no GarmentNet inputs;
+        text_embeds_cloth and noise['cloth'] may be None.  B = image.shape[0] persons, B % G == 0, person i wears garment i % G.  A cache
+        that does not cover the call (timestep, resolution, dtype mode, weights, B % G) raises ValueError before anything is launched."""
         dev, dt = self.device, self.dtype
         f32 = lambda t: t.to(dev, torch.float32).contiguous()
-        image, mask_image, pose_img, cloth = f32(image), f32(mask_image), f32(pose_img), f32(cloth)
+        gcache = cloth if isinstance(cloth, GarmentCache) else None
+        if gcache is not None:
+            gidx = gcache.check(timesteps=self._timesteps(scheduler, num_inference_steps, strength)[1],
+                                h=(height or image.shape[-2]) // 8, w=(width or image.shape[-1]) // 8, dtype=dt, attn_fp8=self.unet.attn_fp8,
+                                f8_exp=self.unet.f8_exp, weights_id=self.weights_identity(), persons=image.shape[0])
+        image, mask_image, pose_img = f32(image), f32(mask_image), f32(pose_img)
+        cloth = f32(cloth) if gcache is None else None
         B = image.shape[0]
         H = height or image.shape[-2]
         W = width or image.shape[-1]
@@ -70,13 +180,7 @@ class TryonEngine:
             raise ValueError("strength < 1 starts from add_noise(encode(image)): pass the posterior draw of the init-image encode as "
                              "noise['image'] (the reference's first random draw, tryon_pipeline.py:883-889), or set noise['latents_given'] "
                              "when noise['latents'] already is the start (the reference's `latents=` argument)")
-        sched = StepScheduler(scheduler)
-        timesteps = sched.set_timesteps(num_inference_steps)                               # :1561
-        init_t = min(int(num_inference_steps * strength), num_inference_steps)             # get_timesteps :987-995
-        timesteps = timesteps[max(num_inference_steps - init_t, 0):]
-        if len(timesteps) < 1:                                                             # :1568-1572
-            raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of pipeline"
-                             f"steps is {len(timesteps)} which is < 1 and not appropriate for this pipeline.")
+        sched, timesteps = self._timesteps(scheduler, num_inference_steps, strength)
         if guidance_scale <= 1:                                                            # no CFG: see the docstring
             guidance_scale = 1.0
             if negative_prompt_embeds is None:
@@ -101,13 +205,16 @@ class TryonEngine:
         # the three VAE encodes of the call (:964 masked image, :1644-1647 pose, :1654 cloth) as ONE encoder pass over 3B images: per
         # image the arithmetic is unchanged (GroupNorm / attention are per image), the convolution GEMMs see 3x the rows and the
         # launch count of the encoder is paid once
-        enc = self.vae.encode_sample(torch.cat([masked_image, pose_img, cloth]),
-                                     torch.cat([f32(noise["masked"]), f32(noise["pose"]), f32(noise["cloth"])]))
-        masked_lat, pose_lat, cloth_lat = enc[:B], enc[B:2 * B], enc[2 * B:]
+        if gcache is None:
+            enc = self.vae.encode_sample(torch.cat([masked_image, pose_img, cloth]),
+                                         torch.cat([f32(noise["masked"]), f32(noise["pose"]), f32(noise["cloth"])]))
+            masked_lat, pose_lat, cloth_lat = enc[:B], enc[B:2 * B], enc[2 * B:]
+        else:                                                # the garment is already encoded: the pass is over 2B images
+            enc = self.vae.encode_sample(torch.cat([masked_image, pose_img]), torch.cat([f32(noise["masked"]), f32(noise["pose"])]))
+            masked_lat, pose_lat, cloth_lat = enc[:B], enc[B:], None
         # step-invariant 9 conditioning channels of the 13-channel input, NHWC, both CFG halves (:955,977,1649-1652,1777)
         cond = torch.cat([mask_l, masked_lat, pose_lat], dim=1).permute(0, 2, 3, 1).reshape(B, h * w, 9)
         cond = torch.cat([cond, cond], dim=0).to(dt).contiguous()
-        cloth_nhwc = ops.to_nhwc(cloth_lat, dt, cpad=self.unet_encoder.cin_pad)
 
         pe = torch.cat([negative_prompt_embeds, prompt_embeds], dim=0).to(dev)             # :1710
         add_text = torch.cat([negative_pooled_prompt_embeds, pooled_prompt_embeds], dim=0).to(dev)   # :1711
@@ -115,31 +222,18 @@ class TryonEngine:
         if image_embeds is None:
             image_embeds = self.resampler(ip_hidden_states.to(dev))                        # :1726 (encoder_hid_proj)
         ctx_t = self.unet.encode_context(pe, image_embeds)
-        ctx_g = self.unet_encoder.encode_context(text_embeds_cloth.to(dev))
         temb_t = self.unet.time_embeddings(timesteps, 2 * B, dict(text_embeds=add_text, time_ids=time_ids))
-        temb_g = self.unet_encoder.time_embeddings(timesteps, B)
-        # GarmentNet over consecutive timesteps per batch: batch index = j*B + b (timestep-major).  Block sizes ramp 1, 2, 4, k, k, ...
-        # (module docstring); temb_gk rows beyond a block's own c*B are never read
-        n = len(timesteps)
-        k = max(1, min(self.garment_steps, n))
-        sizes, s0 = [], 0
-        for c in (1, 2, 4):
-            if c < k and s0 + c <= n and self.ramp:
-                sizes.append(c); s0 += c
-        while s0 < n:
-            sizes.append(min(k, n - s0)); s0 += sizes[-1]
-        blocks, s0 = [], 0
-        for c in sizes:
-            blocks.append((s0, c)); s0 += c
-        tidx = torch.tensor([[min(s0 + j, n - 1) for j in range(k)] for s0, _ in blocks], device=dev)
-        temb_gk = temb_g[tidx].reshape(len(blocks), k * B, -1).contiguous()
-        cloth_k = cloth_nhwc.repeat(k, 1, 1).contiguous()
-        ctx_gk = ctx_g if k == 1 else self.unet_encoder.encode_context(text_embeds_cloth.to(dev).repeat(k, 1, 1))
+        if gcache is None:
+            # GarmentNet over consecutive timesteps per batch, blocks of 1, 2, 4, k, k, ... timesteps
+            garm = self._garment_inputs(cloth_lat, text_embeds_cloth, timesteps, B)
+        else:                                                # the same blocks drive the loop; their garment side is a read of the cache
+            k, blocks = self._block_schedule(len(timesteps))
+            garm = dict(cloth=None, ctx_g=None, temb_g=None, k=k, blocks=blocks, temb_gk=None, cloth_k=None, ctx_gk=None,
+                        gcache=gcache, gidx=gidx, G=gcache.G)
         coef = torch.tensor([list(sched.coeffs(t)) + [guidance_scale] for t in timesteps], dtype=torch.float32, device=dev)
         steps_noise = f32(noise["steps"]) if noise.get("steps") is not None and scheduler == "ddpm" else None
-        return dict(B=B, h=h, w=w, timesteps=timesteps, latents=latents.contiguous(), cond=cond, cloth=cloth_nhwc,
-                    ctx_t=ctx_t, ctx_g=ctx_g, temb_t=temb_t, temb_g=temb_g, coef=coef, steps_noise=steps_noise,
-                    k=k, blocks=blocks, temb_gk=temb_gk, cloth_k=cloth_k, ctx_gk=ctx_gk,
+        return dict(B=B, h=h, w=w, timesteps=timesteps, latents=latents.contiguous(), cond=cond,
+                    ctx_t=ctx_t, temb_t=temb_t, coef=coef, steps_noise=steps_noise, **garm,
                     x_in=torch.empty(2 * B, h * w, self.unet.cin_pad, dtype=dt, device=dev),
                     trace=dict(masked_lat=masked_lat, pose_lat=pose_lat, cloth_lat=cloth_lat, image_embeds=image_embeds))
 
@@ -160,15 +254,41 @@ class TryonEngine:
     def _garment_side(self, st, temb_gk, fset, c=None):
         B, h, w = st["B"], st["h"], st["w"]
         c = st["k"] if c is None else c                      # timesteps in this batch (the set's buffers hold up to st["k"])
+        self.stats["garment_batches"] += 1
         _, feats = self.unet_encoder.forward(st["cloth_k"][:c * B], temb_gk[:c * B], st["ctx_gk"], c * B, h, w, feats_buf=fset["feats"])   # :1787
         self.unet.project_garment_kv(feats, out=fset["kv"])
 
     def _tryon_main(self, st, temb_t, coef, noise, kv_j):
         B, h, w = st["B"], st["h"], st["w"]
         ops.pack_input(st["latents"], st["cond"], st["x_in"])                              # :1769,1777
-        eps, _ = self.unet.forward(st["x_in"], temb_t, st["ctx_t"], 2 * B, h, w, garment_kv=kv_j)        # :1796-1808
+        if st.get("gcache") is None:
+            eps, _ = self.unet.forward(st["x_in"], temb_t, st["ctx_t"], 2 * B, h, w, garment_kv=kv_j)    # :1796-1808
+        else:                                                # kv_j holds G garments for the B persons (a shared segment when G < B)
+            eps, _ = self.unet.forward(st["x_in"], temb_t, st["ctx_t"], 2 * B, h, w, garment_kv=kv_j, garment_persons=B)
         ops.cfg_step(eps, st["latents"], noise, coef)                                      # :1814-1823
         return eps
+
+    def _cached_set(self, st):
+        """GarmentCache calls, graph forms: a persistent (K, V^T) set for up to k timesteps of the cache's G garments, shaped like the cache's
+        own tensors (no features: GarmentNet does not run), + per-timestep views."""
+        gc, k = st["gcache"], st["k"]
+        n, G = len(gc.timesteps), gc.G
+        kv = [(torch.empty((kk.shape[0] // n * k,) + tuple(kk.shape[1:]), dtype=kk.dtype, device=kk.device),
+               torch.empty((k * G,) + tuple(vv.shape[1:]), dtype=vv.dtype, device=vv.device)) for kk, vv in gc.kv]
+        per_step = [[(kk[j * (kk.shape[0] // k):(j + 1) * (kk.shape[0] // k)], vv[j * G:(j + 1) * G]) for kk, vv in kv] for j in range(k)]
+        return dict(feats=[], kv=kv, step=per_step)
+
+    def _fill_set(self, st, fset, s0, c):
+        """Steps s0 .. s0 + c - 1 of the call: their cached K / V^T -> the first c timestep slots of a persistent set (current stream).  The
+        call's timesteps are consecutive cache entries unless the scheduler says otherwise: one copy per tensor then, else one per timestep."""
+        gc, idx = st["gcache"], st["gidx"][s0:s0 + c]
+        self.stats["garment_set_copies"] += 1
+        runs = [(0, idx[0], c)] if idx == list(range(idx[0], idx[0] + c)) else [(j, i, 1) for j, i in enumerate(idx)]
+        for j0, i0, cc in runs:
+            for (dk, dv), (sk, sv) in zip(fset["kv"], gc.run(i0, cc)):
+                r = sk.shape[0] // cc
+                dk[j0 * r:(j0 + cc) * r].copy_(sk)
+                dv[j0 * gc.G:(j0 + cc) * gc.G].copy_(sv)
 
     def _new_set(self, st, like=None, run=True):
         """A persistent {70 features, 70 (K, V^T)} set for up to k timesteps + per-timestep views of its K / V^T.  The tensor shapes
@@ -198,14 +318,16 @@ class TryonEngine:
         """on_step(i, t, latents) runs after step i on the live latents (it may rewrite them in place); a true return value ends the loop
         (the reference's per-step callbacks and `interrupt`, tryon_pipeline.py:1766-1767,1840-1863: host code between two steps, which
         only this un-captured form can run)."""
-        fset = None
+        fset, gc = None, st.get("gcache")
         for bi, (s0, c) in enumerate(st["blocks"]):
-            if fset is None:
-                fset = self._new_set(st)
-            self._garment_side(st, st["temb_gk"][bi], fset, c)
+            if gc is None:
+                if fset is None:
+                    fset = self._new_set(st)
+                self._garment_side(st, st["temb_gk"][bi], fset, c)
             for j in range(c):
                 i = s0 + j
-                self._tryon_main(st, st["temb_t"][i], st["coef"][i], self._noise(st, i), fset["step"][j])
+                # (GarmentCache call: TryonNet reads this timestep's views of the cache directly)
+                self._tryon_main(st, st["temb_t"][i], st["coef"][i], self._noise(st, i), fset["step"][j] if gc is None else gc.step(st["gidx"][i]))
                 if trace is not None:
                     trace.setdefault("step_latents", []).append(st["latents"].clone())
                 if on_step is not None and on_step(i, int(st["timesteps"][i]), st["latents"]):
@@ -213,6 +335,8 @@ class TryonEngine:
         return st["latents"]
 
     def _denoise_overlap_eager(self, st, trace=None):
+        if st.get("gcache") is not None:                     # nothing to overlap: the garment side is a read of the cache
+            return self._denoise_serial_eager(st, trace)
         main = torch.cuda.current_stream()
         if self._side is None:
             self._side = torch.cuda.Stream()
@@ -252,22 +376,30 @@ class TryonEngine:
         Captures use capture_error_mode="thread_local": with torch.distributed / RCCL initialised a watchdog thread polls events,
         which the default global mode would treat as a capture violation."""
         has_noise = st["steps_noise"] is not None
-        key = (st["B"], st["h"], st["w"], st["k"], has_noise)
+        gc = st.get("gcache")
+        key = (st["B"], st["h"], st["w"], st["k"], has_noise) + (() if gc is None else ("cached", gc.G))
         if key in self._graphs:
             return self._graphs[key]
-        tt, cf, tgk = st["temb_t"][0].clone(), st["coef"][0].clone(), st["temb_gk"][0].clone()
+        tt, cf, tgk = st["temb_t"][0].clone(), st["coef"][0].clone(), (st["temb_gk"][0].clone() if gc is None else None)
         nz = st["steps_noise"][0].clone() if has_noise else None
         saved = st["latents"].clone()
         warm = torch.cuda.Stream()
         warm.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(warm):                                # warm-up off the default stream (allocator, lazy init)
-            s0set = self._new_set(st)
-            sets = [s0set, self._new_set(st, like=s0set)]
-            self._garment_side(st, tgk, sets[1])
+            if gc is None:
+                s0set = self._new_set(st)
+                sets = [s0set, self._new_set(st, like=s0set)]
+                self._garment_side(st, tgk, sets[1])
+            else:                                            # the two sets hold cache entries; the first block's fill stands in for a warm-up batch
+                sets = [self._cached_set(st), self._cached_set(st)]
+                self._fill_set(st, sets[0], *st["blocks"][0])
             self._tryon_main(st, tt, cf, nz, sets[0]["step"][0])
         torch.cuda.current_stream().wait_stream(warm)
         torch.cuda.synchronize()
         st["latents"].copy_(saved)
+        if gc is not None:                                   # the persistent state must not keep the first call's cache (GBs) alive
+            st = {kk: vv for kk, vv in st.items() if kk not in ("gcache", "gidx")}
+            st["gcache"] = _CACHED                           # (what _tryon_main / _copy_state look at)
         G = dict(st=st, tt=tt, cf=cf, nz=nz, tgk=tgk, sets=sets, graphs={}, side=torch.cuda.Stream(),
                  ready=[torch.cuda.Event(), torch.cuda.Event()], free=[torch.cuda.Event(), torch.cuda.Event()],
                  # graphs that replay one after another on ONE stream may share a memory pool: all TryonNet graphs (main stream), all
@@ -287,6 +419,7 @@ class TryonEngine:
         with torch.cuda.graph(g, pool=G["pools"][kind], capture_error_mode="thread_local"):
             if kind == "garm":                                   # j = timesteps in the batch
                 self._garment_side(st, G["tgk"], G["sets"][par], j)
+                self.stats["garment_batches"] -= 1               # captured, not run: replays are counted
             else:
                 self._tryon_main(st, G["tt"], G["cf"], G["nz"], G["sets"][par]["step"][j])
         st["latents"].copy_(keep)                                    # capture does not execute, but keep the state explicit
@@ -296,14 +429,15 @@ class TryonEngine:
     def _denoise_graph(self, st, overlap, trace=None):
         G = self._graph_state(st)
         sst = G["st"]
-        if sst is not st:
+        if sst["latents"] is not st["latents"]:
             _copy_state(sst, st)                                                           # new call -> persistent buffers
+        cached = st.get("gcache") is not None
         blocks, nb, k = st["blocks"], len(st["blocks"]), st["k"]
         # capture everything this call needs before the loop (a capture must not interleave with work in flight on the side stream)
         for p in ((0, 1) if overlap and nb > 1 else (0,)):
             for j in range(k):
                 self._graph(G, "tryon", p, j)
-        for bi, (_, c) in enumerate(blocks):                          # one GarmentNet graph per (set, batch size)
+        for bi, (_, c) in enumerate(blocks if not cached else ()):    # one GarmentNet graph per (set, batch size)
             self._graph(G, "garm", (bi & 1) if overlap else 0, c)
         main, side = torch.cuda.current_stream(), G["side"]
         ready, free = G["ready"], G["free"]
@@ -318,14 +452,22 @@ class TryonEngine:
                 if trace is not None:
                     trace.setdefault("step_latents", []).append(sst["latents"].clone())
 
+        def garment_block(bi, p):
+            """Block bi's garment K / V^T into set p on the current stream: the GarmentNet graph, or -- GarmentCache call -- a copy of the
+            block's timesteps out of the cache (same place in the stream / event order)."""
+            if cached:
+                self._fill_set(st, G["sets"][p], *blocks[bi])
+                return
+            G["tgk"].copy_(st["temb_gk"][bi])
+            self.stats["garment_batches"] += 1
+            G["graphs"][("garm", p, blocks[bi][1])].replay()
+
         if not overlap:
             for bi, (s0, c) in enumerate(blocks):
-                G["tgk"].copy_(st["temb_gk"][bi])
-                G["graphs"][("garm", 0, c)].replay()
+                garment_block(bi, 0)
                 tryon_block(s0, c, 0)
             return sst["latents"]
-        G["tgk"].copy_(st["temb_gk"][0])
-        G["graphs"][("garm", 0, blocks[0][1])].replay()               # block 0's features, on the main stream
+        garment_block(0, 0)                                           # block 0's features, on the main stream
         side.wait_stream(main)
         for bi, (s0, c) in enumerate(blocks):
             cur, nxt = bi & 1, (bi + 1) & 1
@@ -333,8 +475,7 @@ class TryonEngine:
                 with torch.cuda.stream(side):
                     if bi >= 1:
                         side.wait_event(free[nxt])                   # TryonNet block bi-1 is done reading set nxt
-                    G["tgk"].copy_(st["temb_gk"][bi + 1])
-                    G["graphs"][("garm", nxt, blocks[bi + 1][1])].replay()
+                    garment_block(bi + 1, nxt)
                     ready[nxt].record(side)
             if bi >= 1:
                 main.wait_event(ready[cur])

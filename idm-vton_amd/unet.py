@@ -276,18 +276,22 @@ class HipUNet:
                 vtg = torch.empty(Bg, C, N, dtype=torch.uint8 if f8 else dt, device=dev)
                 ops.linear(g.reshape(Bg * N, C), blk["qkv"][C:], out=kg, vt=vtg, vt_n0=C, vt_tokens=N, **f8kw)
             garment["idx"] += 1
-            segs.append(dict(k=kg, vt=vtg, nk=nk, ldk=C, ldvt=N, k_rows=N, b0=B - Bg))
+            P = garment.get("persons") or Bg                    # conditional batches (GarmentCache calls: P persons, Bg = G garments)
+            gseg = dict(k=kg, vt=vtg, nk=nk, ldk=C, ldvt=N, k_rows=N, b0=B - P)
+            if Bg < P:                                           # a shared segment: conditional row i reads garment i % G
+                gseg["nb"] = Bg
+            segs.append(gseg)
         att = torch.empty(M, C, dtype=dt, device=dev)
         if self.attn_fp8:
             segs8 = []
             for sg in segs:
                 Bs = sg["vt"].shape[0]
                 if sg["k"].dtype == torch.uint8:                                            # written as e4m3 by its projection
-                    segs8.append(dict(k8=sg["k"], vt8=sg["vt"], nk=nk, ldk=sg["ldk"], ldvt=N, k_rows=N, b0=sg.get("b0", 0)))
+                    segs8.append(dict(k8=sg["k"], vt8=sg["vt"], nk=nk, ldk=sg["ldk"], ldvt=N, k_rows=N, b0=sg.get("b0", 0), nb=sg.get("nb", 0)))
                     continue
                 k8 = ops.quant_f8(sg["k"], 2.0 ** ek)                                   # [Bs*N][C] (row stride ldk)
                 vt8 = ops.quant_f8(sg["vt"].reshape(Bs * C, N), 2.0 ** ev, mode=1)      # 16-bit key order -> fp8 slot order
-                segs8.append(dict(k8=k8, vt8=vt8, nk=nk, ldk=C, ldvt=vt8.shape[1], k_rows=N, b0=sg.get("b0", 0)))
+                segs8.append(dict(k8=k8, vt8=vt8, nk=nk, ldk=C, ldvt=vt8.shape[1], k_rows=N, b0=sg.get("b0", 0), nb=sg.get("nb", 0)))
             if f8:
                 q8, ldq8 = qk, 2 * C
             else:
@@ -382,13 +386,25 @@ class HipUNet:
             res.append((kg, vtg))
         return res
 
+    def weights_id(self, select=None):
+        """Identity of this weight set (or of the tensors whose state-dict key satisfies `select`) in its storage dtype: see
+        garment_cache.weights_fingerprint.  Computed once per selection and kept."""
+        from .garment_cache import weights_fingerprint
+        ids = self.__dict__.setdefault("_weights_ids", {})
+        key = getattr(select, "__name__", None) if select is not None else "all"
+        if key not in ids:
+            ids[key] = weights_fingerprint({k: v for k, v in self.sd.items() if select is None or select(k)})
+        return ids[key]
+
     # ------------------------------------------------------------------------------------------------ forward
-    def forward(self, x, temb, ctx, B, H, W, garment_feats=None, garment_kv=None, feats_buf=None):
+    def forward(self, x, temb, ctx, B, H, W, garment_feats=None, garment_kv=None, feats_buf=None, garment_persons=None):
         """x: NHWC [B][H*W][cin_pad] (channels >= in_channels zero); temb: [B][sum Cout] (time_embeddings()[step]);
         ctx: encode_context(); garment_feats: list of [Bg][N][C] (Bg <= B; batches < B-Bg see all-zero features).
+        garment_persons = P (with garment_kv of G = Bg garments, P % G == 0): the last P batches are conditional and row i of them reads garment
+        i % G through a shared attention segment (GarmentCache calls); None: P = Bg, one garment entry per conditional batch.
         Returns (noise NHWC [B][H*W][n_out] for TryonNet | None, exported features for GarmentNet)."""
         topo = self.topo
-        garment = dict(feats=garment_feats, kv=garment_kv, feats_buf=feats_buf, idx=0)
+        garment = dict(feats=garment_feats, kv=garment_kv, feats_buf=feats_buf, idx=0, persons=garment_persons)
         feats = []
         stop = None if self.tryon else self.num_features()
         h, _, _ = self._conv3(x, self.conv_in, B, H, W)

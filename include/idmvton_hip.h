@@ -177,6 +177,11 @@ typedef struct {
                                     applies it in fp32 in the projection epilogue, same single rounding as an unscaled q) */
 } idmvton_attn_args;
 int idmvton_attn_fwd(const idmvton_attn_args* a, void* stream);
+/* The same launch with a SHARED (broadcast) key segment: segment s holds seg_nb[s] batch elements ([seg_nb][k_rows][ldk] / [seg_nb][heads*64][ldvt])
+ * and query batch b >= seg_b0[s] reads element (b - seg_b0[s]) % seg_nb[s] -- one garment's K / V^T serves every person it is tried on instead of
+ * one copy per person.  seg_nb[s] == 0 is idmvton_attn_fwd's rule (B - seg_b0[s] elements, no wrap); idmvton_attn_fwd IS this call with {0, 0}.
+ * Which batches skip a segment (b < seg_b0[s]) does not change.  Needs 0 <= seg_nb[s] <= B - seg_b0[s]; mode CROSS takes {0, 0} only. */
+int idmvton_attn_fwd_shared(const idmvton_attn_args* a, const int32_t seg_nb[2], void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * idmvton_attn_f8 / idmvton_quant_f8 : the fp8 (OCP e4m3) variant of the self-attention above, on the block-scaled MFMA
@@ -204,6 +209,7 @@ typedef struct {
     int32_t qk_scale_exp; int32_t v_scale_exp;
 } idmvton_attn_f8_args;
 int idmvton_attn_f8(const idmvton_attn_f8_args* a, void* stream);
+int idmvton_attn_f8_shared(const idmvton_attn_f8_args* a, const int32_t seg_nb[2], void* stream);   /* seg_nb: as idmvton_attn_fwd_shared */
 typedef struct {
     int32_t dtype; int32_t mode; int32_t rows, cols;
     const void* src; int32_t lds;
