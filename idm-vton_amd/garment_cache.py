@@ -14,6 +14,27 @@ tensors (tests/test_garment_cache_cpu.py).
 import torch
 
 
+def timestep_run(kv, n, G, i0, c=1):
+    """THE layout rule, in one place: views of entries i0 .. i0 + c - 1 of a timestep-major (K, V^T) list that holds n timesteps of G
+    elements -- K rows [i0 * r, (i0 + c) * r) with r = rows // n, V^T elements [i0 * G, (i0 + c) * G).  The cache itself, the engine's
+    persistent sets and the rows encode_garment projects into are all cut with it."""
+    out = []
+    for k, vt in kv:
+        r = k.shape[0] // n                              # K rows per timestep: G * N_f
+        out.append((k[i0 * r:(i0 + c) * r], vt[i0 * G:(i0 + c) * G]))
+    return out
+
+
+def alloc_kv(shapes, n, m, device):
+    """An uninitialised timestep-major (K, V^T) list for m timesteps, from the [(K shape, V^T shape, dtype)] of one that holds n."""
+    return [(torch.empty((a[0] // n * m,) + tuple(a[1:]), dtype=d, device=device), torch.empty((b[0] // n * m,) + tuple(b[1:]), dtype=d, device=device))
+            for a, b, d in shapes]
+
+
+def kv_shapes(kv):
+    return [(tuple(k.shape), tuple(vt.shape), k.dtype) for k, vt in kv]
+
+
 class GarmentCache:
     def __init__(self, *, G, timesteps, h, w, dtype, attn_fp8, f8_exp, weights_id, kv):
         self.G = int(G)
@@ -67,11 +88,7 @@ class GarmentCache:
         n, G = len(self.timesteps), self.G
         if not 0 <= i0 <= i0 + c <= n:
             raise IndexError(f"GarmentCache entries [{i0}, {i0 + c}) of {n}")
-        out = []
-        for k, vt in self.kv:
-            r = k.shape[0] // n                          # K rows per timestep: G * N_f
-            out.append((k[i0 * r:(i0 + c) * r], vt[i0 * G:(i0 + c) * G]))
-        return out
+        return timestep_run(self.kv, n, G, i0, c)
 
     def step(self, i):
         return self.run(i, 1)

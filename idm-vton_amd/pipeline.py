@@ -18,30 +18,72 @@ shorter than the TryonNet steps of the block before it.  Every batch runs at its
 The same fact across calls: `encode_garment` runs the garment side alone (cloth VAE encode, GarmentNet batches in the same block schedule,
 the K / V^T projections) and returns a GarmentCache; `prepare(cloth=<GarmentCache>)` then builds a call with no garment work at all, for
 P persons on G cached garments (P % G == 0; the attention kernels read garment i % G for person i through a shared key segment).
+
+Structure of the loop.  The block order -- serial, or two streams with two alternating sets and two events per set -- is written once,
+in `drive_blocks`, which knows nothing of graphs or caches (tests/test_loop_schedule_cpu.py checks its waits on stand-in streams).  An
+execution form is the pair of callables it hands over:
+
+                   garment(bi, p)                                    one TryonNet step (i = timestep, j = slot in set p)
+    eager, live    _garment_side into set p                          _tryon_main on set p's views of slot j
+    eager, cache   nothing to launch                                 _tryon_main on the cache's own views of entry gidx[i]
+    graph, live    copy temb_gk[bi], replay ('garm', p, c)           copy tt / cf / nz, replay ('tryon', p, j)
+    graph, cache   _fill_set: the block's cache entries -> set p     as graph, live
+
+`denoise` asks once whether the call is live or on a cache, wraps the step in the per-step hooks (`trace`, `on_step`) and drives the
+blocks.  The K / V^T layout of sets and cache (timestep-major) has one owner, garment_cache.timestep_run.
 """
 import torch
 
 from . import ops
-from .garment_cache import GarmentCache
+from .garment_cache import GarmentCache, alloc_kv, kv_shapes, timestep_run
 from .scheduler import StepScheduler
 
 
-def _copy_state(dst, src):
-    """Copy every tensor the captured step reads (latents, conditioning, K/V^T caches) into the graph's buffers."""
-    cached = src.get("gcache") is not None               # a GarmentCache call has no garment-side tensors
-    for k in ("latents", "cond") if cached else ("latents", "cond", "cloth", "cloth_k"):
-        dst[k].copy_(src[k])
-    for ck in ("ctx_t",) if cached else ("ctx_t", "ctx_g", "ctx_gk"):
-        for p, ent in src[ck]["kv"].items():
-            for name, t in ent.items():
-                dst[ck]["kv"][p][name].copy_(t)
+def drive_blocks(blocks, garment, tryon, main=None, side=None, ready=None, free=None):
+    """The block loop, written once for every execution form.  garment(bi, p): put block bi's garment K / V^T into set p, on the current
+    stream; tryon(bi, p): run the TryonNet steps of block bi against set p.  It knows nothing of graphs or caches.
+    Serial order (no side stream): garment(bi, 0); tryon(bi, 0) per block, and a true return of tryon ends the loop (the per-step hook).
+    Two-stream order (main = the current stream, side, two `ready` and two `free` events): block 0's garment work runs on main -- nothing
+    to hide behind --, block bi+1's on side while TryonNet runs block bi on main; sets alternate by block parity.  ready[p]: set p is
+    written (side -> main); free[p]: TryonNet is done reading set p (main -> side, before the block after next overwrites it)."""
+    if side is None:
+        for bi in range(len(blocks)):
+            garment(bi, 0)
+            if tryon(bi, 0):
+                return
+        return
+    garment(0, 0)
+    side.wait_stream(main)                                   # prepare()'s tensors and set 0 are complete
+    for bi in range(len(blocks)):
+        cur, nxt = bi & 1, (bi + 1) & 1
+        if bi + 1 < len(blocks):
+            with torch.cuda.stream(side):
+                if bi >= 1:
+                    side.wait_event(free[nxt])               # TryonNet block bi-1 is done reading set nxt
+                garment(bi + 1, nxt)
+                ready[nxt].record(side)
+        if bi >= 1:
+            main.wait_event(ready[cur])
+        tryon(bi, cur)
+        free[cur].record(main)
+    main.wait_stream(side)
+
+
+def _copy_state(G, st):
+    """A new call's tensors -> the persistent buffers of a graph state, for every tensor the state owns and a captured graph reads (a
+    GarmentCache state has no garment-side tensors)."""
+    for name in ("latents", "cond", "cloth_k"):
+        if name in G:
+            G[name].copy_(st[name])
+    for name in ("ctx_t", "ctx_gk"):
+        if name in G:
+            for p, ent in st[name]["kv"].items():
+                for kind, t in ent.items():
+                    G[name]["kv"][p][kind].copy_(t)
 
 
 def _is_attn1_kv(key):
     return ".attn1.to_k." in key or ".attn1.to_v." in key
-
-
-_CACHED = object()          # stands in for the GarmentCache in a persistent graph state (only "is there one" is asked of it)
 
 
 class TryonEngine:
@@ -130,15 +172,11 @@ class TryonEngine:
         cloth_lat = self.vae.encode_sample(torch.cat([cloth, cloth, cloth]), torch.cat([nz, nz, nz]))[2 * G:]
         gs = dict(B=G, h=h, w=w, **self._garment_inputs(cloth_lat, text_embeds_cloth, timesteps, G))
         n, k = len(timesteps), gs["k"]
-        if (G, h, w, k) not in self._set_shapes:
-            self._new_set(gs)                                # shape discovery (one GarmentNet batch, dropped)
-        fs, ks = self._set_shapes[(G, h, w, k)]
+        fs, ks = self._discover_set_shapes(gs)
         feats = [torch.empty(sh, dtype=self.dtype, device=dev) for sh in fs]
-        kv = [(torch.empty((a[0] // k * n,) + tuple(a[1:]), dtype=d, device=dev), torch.empty((n * G,) + tuple(b[1:]), dtype=d, device=dev))
-              for a, b, d in ks]
+        kv = alloc_kv(ks, k, n, dev)
         for bi, (s0, c) in enumerate(gs["blocks"]):          # each block's projections land in the cache's own rows
-            views = [(kk[s0 * (kk.shape[0] // n):], vv[s0 * G:]) for kk, vv in kv]
-            self._garment_side(gs, gs["temb_gk"][bi], dict(feats=feats, kv=views), c)
+            self._garment_side(gs, gs["temb_gk"][bi], dict(feats=feats, kv=timestep_run(kv, n, G, s0, c)), c)
         return GarmentCache(G=G, timesteps=timesteps, h=h, w=w, dtype=self.dtype, attn_fp8=self.unet.attn_fp8, f8_exp=self.unet.f8_exp,
                             weights_id=self.weights_identity(), kv=kv)
 
@@ -225,11 +263,11 @@ class TryonEngine:
         temb_t = self.unet.time_embeddings(timesteps, 2 * B, dict(text_embeds=add_text, time_ids=time_ids))
         if gcache is None:
             # GarmentNet over consecutive timesteps per batch, blocks of 1, 2, 4, k, k, ... timesteps
-            garm = self._garment_inputs(cloth_lat, text_embeds_cloth, timesteps, B)
+            garm = dict(self._garment_inputs(cloth_lat, text_embeds_cloth, timesteps, B), gcache=None, gidx=None, garment_persons=None)
         else:                                                # the same blocks drive the loop; their garment side is a read of the cache
             k, blocks = self._block_schedule(len(timesteps))
             garm = dict(cloth=None, ctx_g=None, temb_g=None, k=k, blocks=blocks, temb_gk=None, cloth_k=None, ctx_gk=None,
-                        gcache=gcache, gidx=gidx, G=gcache.G)
+                        gcache=gcache, gidx=gidx, garment_persons=B)
         coef = torch.tensor([list(sched.coeffs(t)) + [guidance_scale] for t in timesteps], dtype=torch.float32, device=dev)
         steps_noise = f32(noise["steps"]) if noise.get("steps") is not None and scheduler == "ddpm" else None
         return dict(B=B, h=h, w=w, timesteps=timesteps, latents=latents.contiguous(), cond=cond,
@@ -237,20 +275,10 @@ class TryonEngine:
                     x_in=torch.empty(2 * B, h * w, self.unet.cin_pad, dtype=dt, device=dev),
                     trace=dict(masked_lat=masked_lat, pose_lat=pose_lat, cloth_lat=cloth_lat, image_embeds=image_embeds))
 
-    # -------------------------------------------------------------------------------------------- one step
-    def _step(self, st, temb_t, temb_g, coef, noise):
-        """One loop iteration in the reference's own order (tryon_pipeline.py:1765-1866: GarmentNet for THIS timestep, then
-        TryonNet) on the current stream.  Debugging aid (tools/gpu_debug.py); the loop itself runs in blocks, below."""
-        B, h, w = st["B"], st["h"], st["w"]
-        ops.pack_input(st["latents"], st["cond"], st["x_in"])                              # :1769,1777
-        _, feats = self.unet_encoder.forward(st["cloth"], temb_g, st["ctx_g"], B, h, w)    # :1787
-        eps, _ = self.unet.forward(st["x_in"], temb_t, st["ctx_t"], 2 * B, h, w, garment_feats=feats)   # :1796-1808
-        ops.cfg_step(eps, st["latents"], noise, coef)                                      # :1814-1823
-        return eps
-
     # ---- blocks: one GarmentNet batch over k timesteps + the k TryonNet steps that consume it ------------------------------
     # The GarmentNet batch of block b+1 -- and the attn1 K / V^T projections of its features with TryonNet's weights -- can run on a
-    # second HIP stream while TryonNet runs the steps of block b.  Two feature sets alternate; there is no other coupling.
+    # second HIP stream while TryonNet runs the steps of block b (drive_blocks).  Two feature sets alternate; there is no other coupling.
+    # `st` below is a call's state (prepare) or a persistent graph state (_graph_state): both carry the keys these two read.
     def _garment_side(self, st, temb_gk, fset, c=None):
         B, h, w = st["B"], st["h"], st["w"]
         c = st["k"] if c is None else c                      # timesteps in this batch (the set's buffers hold up to st["k"])
@@ -261,22 +289,35 @@ class TryonEngine:
     def _tryon_main(self, st, temb_t, coef, noise, kv_j):
         B, h, w = st["B"], st["h"], st["w"]
         ops.pack_input(st["latents"], st["cond"], st["x_in"])                              # :1769,1777
-        if st.get("gcache") is None:
-            eps, _ = self.unet.forward(st["x_in"], temb_t, st["ctx_t"], 2 * B, h, w, garment_kv=kv_j)    # :1796-1808
-        else:                                                # kv_j holds G garments for the B persons (a shared segment when G < B)
-            eps, _ = self.unet.forward(st["x_in"], temb_t, st["ctx_t"], 2 * B, h, w, garment_kv=kv_j, garment_persons=B)
+        # garment_persons: None = one garment entry per conditional batch (unet.forward's default); B on a GarmentCache call, where kv_j
+        # holds G garments for the B persons (a shared segment when G < B)
+        eps, _ = self.unet.forward(st["x_in"], temb_t, st["ctx_t"], 2 * B, h, w, garment_kv=kv_j, garment_persons=st["garment_persons"])    # :1796-1808
         ops.cfg_step(eps, st["latents"], noise, coef)                                      # :1814-1823
         return eps
 
-    def _cached_set(self, st):
-        """GarmentCache calls, graph forms: a persistent (K, V^T) set for up to k timesteps of the cache's G garments, shaped like the cache's
-        own tensors (no features: GarmentNet does not run), + per-timestep views."""
-        gc, k = st["gcache"], st["k"]
-        n, G = len(gc.timesteps), gc.G
-        kv = [(torch.empty((kk.shape[0] // n * k,) + tuple(kk.shape[1:]), dtype=kk.dtype, device=kk.device),
-               torch.empty((k * G,) + tuple(vv.shape[1:]), dtype=vv.dtype, device=vv.device)) for kk, vv in gc.kv]
-        per_step = [[(kk[j * (kk.shape[0] // k):(j + 1) * (kk.shape[0] // k)], vv[j * G:(j + 1) * G]) for kk, vv in kv] for j in range(k)]
-        return dict(feats=[], kv=kv, step=per_step)
+    def _discover_set_shapes(self, st):
+        """-> (feature shapes, (K, V^T) shapes) of a GarmentNet batch over k timesteps, learnt once per (B, h, w, k) by running one (its
+        outputs are dropped; not counted in stats)."""
+        B, h, w, k = st["B"], st["h"], st["w"], st["k"]
+        key = (B, h, w, k)
+        if key not in self._set_shapes:
+            _, feats = self.unet_encoder.forward(st["cloth_k"], st["temb_gk"][0], st["ctx_gk"], k * B, h, w)
+            kv = self.unet.project_garment_kv(feats)         # (dtype uint8 = e4m3: attn_fp8)
+            self._set_shapes[key] = ([tuple(f.shape) for f in feats], kv_shapes(kv))
+        return self._set_shapes[key]
+
+    def _alloc_set(self, feat_shapes, shapes, n, k, G):
+        """A persistent {features, (K, V^T)} set for up to k timesteps of G garments + per-timestep views of its K / V^T, uninitialised;
+        `shapes` are those of a (K, V^T) list that holds n timesteps."""
+        kv = alloc_kv(shapes, n, k, self.device)
+        return dict(feats=[torch.empty(sh, dtype=self.dtype, device=self.device) for sh in feat_shapes], kv=kv,
+                    step=[timestep_run(kv, k, G, j) for j in range(k)])
+
+    def _new_set(self, st):
+        """The set of a live call: 70 features and 70 (K, V^T) of a GarmentNet batch over st["k"] timesteps.  A plain allocation:
+        _garment_side fills it."""
+        fs, ks = self._discover_set_shapes(st)
+        return self._alloc_set(fs, ks, st["k"], st["k"], st["B"])
 
     def _fill_set(self, st, fset, s0, c):
         """Steps s0 .. s0 + c - 1 of the call: their cached K / V^T -> the first c timestep slots of a persistent set (current stream).  The
@@ -285,126 +326,71 @@ class TryonEngine:
         self.stats["garment_set_copies"] += 1
         runs = [(0, idx[0], c)] if idx == list(range(idx[0], idx[0] + c)) else [(j, i, 1) for j, i in enumerate(idx)]
         for j0, i0, cc in runs:
-            for (dk, dv), (sk, sv) in zip(fset["kv"], gc.run(i0, cc)):
-                r = sk.shape[0] // cc
-                dk[j0 * r:(j0 + cc) * r].copy_(sk)
-                dv[j0 * gc.G:(j0 + cc) * gc.G].copy_(sv)
-
-    def _new_set(self, st, like=None, run=True):
-        """A persistent {70 features, 70 (K, V^T)} set for up to k timesteps + per-timestep views of its K / V^T.  The tensor shapes
-        are discovered once per (B, h, w, k) by running a GarmentNet batch (cached); after that a set is a plain allocation."""
-        B, h, w, k = st["B"], st["h"], st["w"], st["k"]
-        key = (B, h, w, k)
-        if like is None and key not in self._set_shapes:
-            _, feats = self.unet_encoder.forward(st["cloth_k"], st["temb_gk"][0], st["ctx_gk"], k * B, h, w)
-            kv = self.unet.project_garment_kv(feats)
-            self._set_shapes[key] = ([tuple(f.shape) for f in feats], [(tuple(kk.shape), tuple(vv.shape), kk.dtype) for kk, vv in kv])
-        elif like is None:
-            fs, ks = self._set_shapes[key]
-            feats = [torch.empty(sh, dtype=self.dtype, device=self.device) for sh in fs]
-            kv = [(torch.empty(a, dtype=d, device=self.device), torch.empty(b, dtype=d, device=self.device)) for a, b, d in ks]   # d: uint8 = e4m3 (attn_fp8)
-        else:
-            feats = [torch.empty_like(f) for f in like["feats"]]
-            kv = [(torch.empty_like(kk), torch.empty_like(vv)) for kk, vv in like["kv"]]
-        per_step = []
-        for j in range(k):
-            per_step.append([(kk[j * B * (kk.shape[0] // (k * B)):(j + 1) * B * (kk.shape[0] // (k * B))], vv[j * B:(j + 1) * B]) for kk, vv in kv])
-        return dict(feats=feats, kv=kv, step=per_step)
+            for (dk, dv), (sk, sv) in zip(timestep_run(fset["kv"], st["k"], gc.G, j0, cc), gc.run(i0, cc)):
+                dk.copy_(sk)
+                dv.copy_(sv)
 
     def _noise(self, st, i):
         return st["steps_noise"][i] if st["steps_noise"] is not None else None
 
-    def _denoise_serial_eager(self, st, trace=None, on_step=None):
-        """on_step(i, t, latents) runs after step i on the live latents (it may rewrite them in place); a true return value ends the loop
-        (the reference's per-step callbacks and `interrupt`, tryon_pipeline.py:1766-1767,1840-1863: host code between two steps, which
-        only this un-captured form can run)."""
-        fset, gc = None, st.get("gcache")
-        for bi, (s0, c) in enumerate(st["blocks"]):
-            if gc is None:
-                if fset is None:
-                    fset = self._new_set(st)
-                self._garment_side(st, st["temb_gk"][bi], fset, c)
-            for j in range(c):
-                i = s0 + j
-                # (GarmentCache call: TryonNet reads this timestep's views of the cache directly)
-                self._tryon_main(st, st["temb_t"][i], st["coef"][i], self._noise(st, i), fset["step"][j] if gc is None else gc.step(st["gidx"][i]))
-                if trace is not None:
-                    trace.setdefault("step_latents", []).append(st["latents"].clone())
-                if on_step is not None and on_step(i, int(st["timesteps"][i]), st["latents"]):
-                    return st["latents"]
-        return st["latents"]
-
-    def _denoise_overlap_eager(self, st, trace=None):
-        if st.get("gcache") is not None:                     # nothing to overlap: the garment side is a read of the cache
-            return self._denoise_serial_eager(st, trace)
-        main = torch.cuda.current_stream()
+    # ---- the execution forms: each hands drive_blocks its two callables ----------------------------------------------------
+    # -> (garment(bi, p), step(i, j, p), the latents the steps update, (side stream, ready, free) | None = serial order).
+    # `live` (denoise: GarmentNet runs in this call / its K, V^T are read from st["gcache"]) picks one row of each form's table.
+    def _eager_form(self, st, live, overlap):
+        blocks = st["blocks"]
+        if live:
+            sets = [self._new_set(st) for _ in range(2 if overlap else 1)]
+            garment = lambda bi, p: self._garment_side(st, st["temb_gk"][bi], sets[p], blocks[bi][1])
+            kv = lambda i, j, p: sets[p]["step"][j]
+        else:                                                # nothing to launch, so nothing to overlap: TryonNet reads the cache's own views
+            overlap = False
+            garment = lambda bi, p: None
+            kv = lambda i, j, p: st["gcache"].step(st["gidx"][i])
+        step = lambda i, j, p: self._tryon_main(st, st["temb_t"][i], st["coef"][i], self._noise(st, i), kv(i, j, p))
+        if not overlap:
+            return garment, step, st["latents"], None
         if self._side is None:
             self._side = torch.cuda.Stream()
-        side = self._side
-        s0set = self._new_set(st)
-        sets = [s0set, self._new_set(st, like=s0set)]
-        ready = [torch.cuda.Event(), torch.cuda.Event()]
-        free = [torch.cuda.Event(), torch.cuda.Event()]
-        self._garment_side(st, st["temb_gk"][0], sets[0], st["blocks"][0][1])      # block 0's batch: nothing to hide behind
-        side.wait_stream(main)                                       # prepare()'s tensors and set 0 are complete
-        nb = len(st["blocks"])
-        for bi, (s0, c) in enumerate(st["blocks"]):
-            cur, nxt = bi & 1, (bi + 1) & 1
-            if bi + 1 < nb:
-                with torch.cuda.stream(side):
-                    if bi >= 1:
-                        side.wait_event(free[nxt])                   # TryonNet block bi-1 is done reading set nxt
-                    self._garment_side(st, st["temb_gk"][bi + 1], sets[nxt], st["blocks"][bi + 1][1])
-                    ready[nxt].record(side)
-            if bi >= 1:
-                main.wait_event(ready[cur])
-            for j in range(c):
-                i = s0 + j
-                self._tryon_main(st, st["temb_t"][i], st["coef"][i], self._noise(st, i), sets[cur]["step"][j])
-                if trace is not None:
-                    trace.setdefault("step_latents", []).append(st["latents"].clone())
-            free[cur].record(main)
-        main.wait_stream(side)
-        return st["latents"]
+        ready, free = [torch.cuda.Event(), torch.cuda.Event()], [torch.cuda.Event(), torch.cuda.Event()]
+        return garment, step, st["latents"], (self._side, ready, free)
 
-    def _graph_state(self, st):
-        """Persistent buffers + captured graphs for one shape.  The graphs are SMALL: ('garm', p, c) = the GarmentNet batch into feature
-        set p, ('tryon', p, j) = one TryonNet step on timestep slice j of set p (2 + 2k graphs, captured on first use).  The loop
-        replays them like the eager form launches kernels -- GarmentNet graphs on the side stream, TryonNet graphs on the main stream,
-        two events per set -- so the overlap form has no fork/join inside a graph and a replay never queues more than one step.
-        (One graph per 6-step block, GarmentNet as a parallel branch, measured 1.2 % slower than eager launch; this form matches it.)
+    def _graph_state(self, st, live):
+        """Persistent buffers + captured graphs for one shape; it owns exactly what a captured graph reads or writes (latents, cond, x_in, the
+        ctx_t K / V^T and, live, cloth_k and the ctx_gk K / V^T: the first call's tensors, adopted; the two sets; tt / cf / nz / tgk) and
+        the scalars B, h, w, k, garment_persons -- nothing else of a call, so no GarmentCache and no time-embedding table stays alive here.
+        The graphs are SMALL: ('garm', p, c) = the GarmentNet batch into feature set p, ('tryon', p, j) = one TryonNet step on timestep
+        slice j of set p (2 + 2k graphs, captured on first use).  The loop replays them like the eager form launches kernels -- GarmentNet
+        graphs on the side stream, TryonNet graphs on the main stream, two events per set -- so the overlap form has no fork/join inside a
+        graph and a replay never queues more than one step.  (One graph per 6-step block, GarmentNet as a parallel branch, measured 1.2 %
+        slower than eager launch; this form matches it.)  On a GarmentCache call the sets hold cache entries and there are no 'garm' graphs.
         Captures use capture_error_mode="thread_local": with torch.distributed / RCCL initialised a watchdog thread polls events,
         which the default global mode would treat as a capture violation."""
         has_noise = st["steps_noise"] is not None
-        gc = st.get("gcache")
-        key = (st["B"], st["h"], st["w"], st["k"], has_noise) + (() if gc is None else ("cached", gc.G))
+        key = (st["B"], st["h"], st["w"], st["k"], has_noise) + (() if live else ("cached", st["gcache"].G))
         if key in self._graphs:
             return self._graphs[key]
-        tt, cf, tgk = st["temb_t"][0].clone(), st["coef"][0].clone(), (st["temb_gk"][0].clone() if gc is None else None)
-        nz = st["steps_noise"][0].clone() if has_noise else None
+        G = {name: st[name] for name in ("B", "h", "w", "k", "garment_persons", "latents", "cond", "x_in", "ctx_t")}
+        G.update(tt=st["temb_t"][0].clone(), cf=st["coef"][0].clone(), nz=st["steps_noise"][0].clone() if has_noise else None, graphs={},
+                 side=torch.cuda.Stream(), ready=[torch.cuda.Event(), torch.cuda.Event()], free=[torch.cuda.Event(), torch.cuda.Event()],
+                 # graphs that replay one after another on ONE stream may share a memory pool: all TryonNet graphs (main stream), all
+                 # GarmentNet graphs (side stream)
+                 pools=dict(tryon=torch.cuda.graph_pool_handle(), garm=torch.cuda.graph_pool_handle()))
         saved = st["latents"].clone()
         warm = torch.cuda.Stream()
         warm.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(warm):                                # warm-up off the default stream (allocator, lazy init)
-            if gc is None:
-                s0set = self._new_set(st)
-                sets = [s0set, self._new_set(st, like=s0set)]
-                self._garment_side(st, tgk, sets[1])
-            else:                                            # the two sets hold cache entries; the first block's fill stands in for a warm-up batch
-                sets = [self._cached_set(st), self._cached_set(st)]
-                self._fill_set(st, sets[0], *st["blocks"][0])
-            self._tryon_main(st, tt, cf, nz, sets[0]["step"][0])
+            if live:
+                G.update(cloth_k=st["cloth_k"], ctx_gk=st["ctx_gk"], tgk=st["temb_gk"][0].clone())
+                G["sets"] = [self._new_set(st), self._new_set(st)]
+                self._garment_side(G, G["tgk"], G["sets"][0])
+            else:                                            # the first block's fill stands in for a warm-up batch
+                gc = st["gcache"]
+                G["sets"] = [self._alloc_set((), kv_shapes(gc.kv), len(gc.timesteps), st["k"], gc.G) for _ in range(2)]
+                self._fill_set(st, G["sets"][0], *st["blocks"][0])
+            self._tryon_main(G, G["tt"], G["cf"], G["nz"], G["sets"][0]["step"][0])
         torch.cuda.current_stream().wait_stream(warm)
         torch.cuda.synchronize()
         st["latents"].copy_(saved)
-        if gc is not None:                                   # the persistent state must not keep the first call's cache (GBs) alive
-            st = {kk: vv for kk, vv in st.items() if kk not in ("gcache", "gidx")}
-            st["gcache"] = _CACHED                           # (what _tryon_main / _copy_state look at)
-        G = dict(st=st, tt=tt, cf=cf, nz=nz, tgk=tgk, sets=sets, graphs={}, side=torch.cuda.Stream(),
-                 ready=[torch.cuda.Event(), torch.cuda.Event()], free=[torch.cuda.Event(), torch.cuda.Event()],
-                 # graphs that replay one after another on ONE stream may share a memory pool: all TryonNet graphs (main stream), all
-                 # GarmentNet graphs (side stream)
-                 pools=dict(tryon=torch.cuda.graph_pool_handle(), garm=torch.cuda.graph_pool_handle()))
         self._graphs[key] = G
         return G
 
@@ -412,87 +398,76 @@ class TryonEngine:
         gk = (kind, par, j)
         if gk in G["graphs"]:
             return G["graphs"][gk]
-        st = G["st"]
-        keep = st["latents"].clone()
+        keep = G["latents"].clone()
         torch.cuda.synchronize()                                     # nothing of this engine in flight while a capture starts
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, pool=G["pools"][kind], capture_error_mode="thread_local"):
             if kind == "garm":                                   # j = timesteps in the batch
-                self._garment_side(st, G["tgk"], G["sets"][par], j)
+                self._garment_side(G, G["tgk"], G["sets"][par], j)
                 self.stats["garment_batches"] -= 1               # captured, not run: replays are counted
             else:
-                self._tryon_main(st, G["tt"], G["cf"], G["nz"], G["sets"][par]["step"][j])
-        st["latents"].copy_(keep)                                    # capture does not execute, but keep the state explicit
+                self._tryon_main(G, G["tt"], G["cf"], G["nz"], G["sets"][par]["step"][j])
+        G["latents"].copy_(keep)                                     # capture does not execute, but keep the state explicit
         G["graphs"][gk] = g
         return g
 
-    def _denoise_graph(self, st, overlap, trace=None):
-        G = self._graph_state(st)
-        sst = G["st"]
-        if sst["latents"] is not st["latents"]:
-            _copy_state(sst, st)                                                           # new call -> persistent buffers
-        cached = st.get("gcache") is not None
-        blocks, nb, k = st["blocks"], len(st["blocks"]), st["k"]
+    def _graph_form(self, st, live, overlap):
+        G = self._graph_state(st, live)
+        if G["latents"] is not st["latents"]:
+            _copy_state(G, st)                                                             # new call -> persistent buffers
+        blocks, graphs = st["blocks"], G["graphs"]
         # capture everything this call needs before the loop (a capture must not interleave with work in flight on the side stream)
-        for p in ((0, 1) if overlap and nb > 1 else (0,)):
-            for j in range(k):
+        for p in ((0, 1) if overlap and len(blocks) > 1 else (0,)):
+            for j in range(st["k"]):
                 self._graph(G, "tryon", p, j)
-        for bi, (_, c) in enumerate(blocks if not cached else ()):    # one GarmentNet graph per (set, batch size)
-            self._graph(G, "garm", (bi & 1) if overlap else 0, c)
-        main, side = torch.cuda.current_stream(), G["side"]
-        ready, free = G["ready"], G["free"]
+        if live:
+            for bi, (_, c) in enumerate(blocks):                 # one GarmentNet graph per (set, batch size)
+                self._graph(G, "garm", (bi & 1) if overlap else 0, c)
 
-        def tryon_block(s0, c, p):
-            for j in range(c):
-                i = s0 + j
-                G["tt"].copy_(st["temb_t"][i]); G["cf"].copy_(st["coef"][i])
-                if G["nz"] is not None:
-                    G["nz"].copy_(st["steps_noise"][i])
-                G["graphs"][("tryon", p, j)].replay()
-                if trace is not None:
-                    trace.setdefault("step_latents", []).append(sst["latents"].clone())
+            def garment(bi, p):
+                G["tgk"].copy_(st["temb_gk"][bi])
+                self.stats["garment_batches"] += 1
+                graphs[("garm", p, blocks[bi][1])].replay()
+        else:                                                # in the GarmentNet graph's place in the stream / event order: a copy out of the cache
+            garment = lambda bi, p: self._fill_set(st, G["sets"][p], *blocks[bi])
+        tt, cf, nz = G["tt"], G["cf"], G["nz"]
 
-        def garment_block(bi, p):
-            """Block bi's garment K / V^T into set p on the current stream: the GarmentNet graph, or -- GarmentCache call -- a copy of the
-            block's timesteps out of the cache (same place in the stream / event order)."""
-            if cached:
-                self._fill_set(st, G["sets"][p], *blocks[bi])
-                return
-            G["tgk"].copy_(st["temb_gk"][bi])
-            self.stats["garment_batches"] += 1
-            G["graphs"][("garm", p, blocks[bi][1])].replay()
+        def step(i, j, p):
+            tt.copy_(st["temb_t"][i]); cf.copy_(st["coef"][i])
+            if nz is not None:
+                nz.copy_(st["steps_noise"][i])
+            graphs[("tryon", p, j)].replay()
 
-        if not overlap:
-            for bi, (s0, c) in enumerate(blocks):
-                garment_block(bi, 0)
-                tryon_block(s0, c, 0)
-            return sst["latents"]
-        garment_block(0, 0)                                           # block 0's features, on the main stream
-        side.wait_stream(main)
-        for bi, (s0, c) in enumerate(blocks):
-            cur, nxt = bi & 1, (bi + 1) & 1
-            if bi + 1 < nb:
-                with torch.cuda.stream(side):
-                    if bi >= 1:
-                        side.wait_event(free[nxt])                   # TryonNet block bi-1 is done reading set nxt
-                    garment_block(bi + 1, nxt)
-                    ready[nxt].record(side)
-            if bi >= 1:
-                main.wait_event(ready[cur])
-            tryon_block(s0, c, cur)
-            free[cur].record(main)
-        main.wait_stream(side)
-        return sst["latents"]
+        return garment, step, G["latents"], (G["side"], G["ready"], G["free"]) if overlap else None
 
     @torch.no_grad()
     def denoise(self, st, use_graph=False, trace=None, overlap=False, on_step=None):
-        """The loop.  Four execution forms with bit-identical results: {serial, two-stream overlap} x {eager, hipGraph replay}; a per-step
-        host hook (`on_step`) selects the serial eager form."""
+        """The loop.  Four execution forms with bit-identical results: {serial, two-stream overlap} x {eager, hipGraph replay}, each on a live
+        GarmentNet or on a GarmentCache.  on_step(i, t, latents) runs after step i on the live latents (it may rewrite them in place); a true
+        return value ends the loop (the reference's per-step callbacks and `interrupt`, tryon_pipeline.py:1766-1767,1840-1863: host code
+        between two steps, which only the un-captured serial form can run, so it selects that form).  trace["step_latents"] receives a copy
+        of the latents after every step.  Graph forms return their persistent latents buffer, eager forms st["latents"]."""
         if on_step is not None:
-            return self._denoise_serial_eager(st, trace, on_step)
-        if use_graph:
-            return self._denoise_graph(st, overlap, trace)
-        return self._denoise_overlap_eager(st, trace) if overlap else self._denoise_serial_eager(st, trace)
+            use_graph = overlap = False
+        live = st["gcache"] is None                          # the one place a call chooses where its garment K / V^T come from
+        garment, step, latents, sync = (self._graph_form if use_graph else self._eager_form)(st, live, overlap)
+        blocks = st["blocks"]
+
+        def tryon(bi, p):
+            s0, c = blocks[bi]
+            for j in range(c):
+                i = s0 + j
+                step(i, j, p)
+                if trace is not None:
+                    trace.setdefault("step_latents", []).append(latents.clone())
+                if on_step is not None and on_step(i, int(st["timesteps"][i]), latents):
+                    return True
+
+        if sync is None:
+            drive_blocks(blocks, garment, tryon)
+        else:
+            drive_blocks(blocks, garment, tryon, torch.cuda.current_stream(), *sync)
+        return latents
 
     @torch.no_grad()
     def decode(self, latents):

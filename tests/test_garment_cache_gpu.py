@@ -279,6 +279,28 @@ def test_a_call_on_a_cache_runs_no_garmentnet_batch_and_a_wrong_cache_is_refused
         eng2.prepare(**ckw)
 
 
+def test_captured_graphs_do_not_keep_a_cache_alive():
+    """The persistent graph state owns its buffers and nothing of a call: once the caller drops a GarmentCache (gigabytes at full size) it
+    is freed although the engine and the graphs captured on that call live on, and the next cache runs through the same graphs."""
+    import gc
+    import weakref
+    steps = 3
+    eng, inp, _ = _engine(torch.float16, 2, steps)
+    call = lambda c: dict(num_inference_steps=steps, guidance_scale=2.0, scheduler="ddpm",
+                          **{**inp, "cloth": c, "text_embeds_cloth": None, "noise": {**inp["noise"], "cloth": None}})
+    cache = eng.encode_garment(num_inference_steps=steps, **_garment_kw(inp))
+    st = eng.prepare(**call(cache))
+    first = eng.denoise(st, **FORMS["graph_overlap"]).clone()
+    ref = weakref.ref(cache)
+    del cache, st
+    gc.collect()
+    assert ref() is None, "the engine's graph state still refers to the first call's GarmentCache"
+    cache = eng.encode_garment(num_inference_steps=steps, **_garment_kw(inp))
+    again = eng.denoise(eng.prepare(**call(cache)), **FORMS["graph_overlap"]).clone()
+    serial = eng.denoise(eng.prepare(**call(cache)), **FORMS["serial_eager"]).clone()
+    assert torch.isfinite(serial).all() and torch.equal(again, serial) and torch.equal(first, serial)
+
+
 # ------------------------------------------------------------------------------------------------------------------ boundary
 class _FakeCLIPVision(torch.nn.Module):
     """Stand-in for CLIPVisionModelWithProjection: deterministic 257-token hidden states from the pixels."""

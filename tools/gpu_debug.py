@@ -14,6 +14,18 @@ def rel(a, b):
     return ((a - b).abs().max() / b.abs().max().clamp_min(1e-20)).item()
 
 
+def one_step(engine, st, temb_t, temb_g, coef, noise):
+    """One loop iteration in the reference's own order (tryon_pipeline.py:1765-1866: GarmentNet for THIS timestep, then TryonNet) on the
+    current stream; the engine's loop itself runs in blocks."""
+    from idm_vton_amd import ops
+    B, h, w = st["B"], st["h"], st["w"]
+    ops.pack_input(st["latents"], st["cond"], st["x_in"])                              # :1769,1777
+    _, feats = engine.unet_encoder.forward(st["cloth"], temb_g, st["ctx_g"], B, h, w)    # :1787
+    eps, _ = engine.unet.forward(st["x_in"], temb_t, st["ctx_t"], 2 * B, h, w, garment_feats=feats)   # :1796-1808
+    ops.cfg_step(eps, st["latents"], noise, coef)                                      # :1814-1823
+    return eps
+
+
 @torch.no_grad()
 def part_a():
     from idm_vton_amd.pipeline import TryonEngine
@@ -38,21 +50,21 @@ def part_a():
     # localise at step 0 / 1: features, garment K/V, TryonNet eps
     st = fresh()
     h, w = st["h"], st["w"]
+    from idm_vton_amd import ops
+    fset = eng._new_set(st)
     for i in (0, 1):
+        # one timestep, once through freshly allocated outputs and once through the loop's own path into a persistent set (batch of 1)
         _, feats = eng.unet_encoder.forward(st["cloth"], st["temb_g"][i], st["ctx_g"], B, h, w)
-        sets = eng._feature_sets(st, st["temb_g"][i])
-        fe = max(rel(a, b) for a, b in zip(sets[0]["feats"], feats))
-        eng._garment_side(st, st["temb_g"][i], sets[1])
-        fb = max(rel(a, b) for a, b in zip(sets[1]["feats"], feats))
+        eng._garment_side(st, st["temb_g"][i], fset, 1)
+        fb = max(rel(a[:B], b) for a, b in zip(fset["feats"], feats))
         kv_ref = eng.unet.project_garment_kv(feats)
-        ke = max(max(rel(a[0], b[0]), rel(a[1], b[1])) for a, b in zip(sets[1]["kv"], kv_ref))
-        lat0 = st["latents"].clone()
-        from idm_vton_amd import ops
+        kv_set = fset["step"][0]
+        ke = max(max(rel(a[0], b[0]), rel(a[1], b[1])) for a, b in zip(kv_set, kv_ref))
         ops.pack_input(st["latents"], st["cond"], st["x_in"])
         e1, _ = eng.unet.forward(st["x_in"], st["temb_t"][i], st["ctx_t"], 2 * B, h, w, garment_feats=feats)
-        e2, _ = eng.unet.forward(st["x_in"], st["temb_t"][i], st["ctx_t"], 2 * B, h, w, garment_kv=sets[1]["kv"])
+        e2, _ = eng.unet.forward(st["x_in"], st["temb_t"][i], st["ctx_t"], 2 * B, h, w, garment_kv=kv_set)
         e3, _ = eng.unet.forward(st["x_in"], st["temb_t"][i], st["ctx_t"], 2 * B, h, w, garment_feats=feats)
-        print(f"A4 step {i}: feats(alloc) {fe:.2e} feats(buf) {fb:.2e} kv {ke:.2e} eps kv-vs-feats {rel(e2, e1):.2e} "
+        print(f"A4 step {i}: feats(buf) {fb:.2e} kv {ke:.2e} eps kv-vs-feats {rel(e2, e1):.2e} "
               f"eps feats-vs-feats {rel(e3, e1):.2e}", flush=True)
 
 
@@ -68,14 +80,14 @@ def part_b():
           "cloth finite", torch.isfinite(st["cloth"].float()).all().item(), flush=True)
     for i in range(30):
         saved = st["latents"].clone()
-        eps = engine._step(st, st["temb_t"][i], st["temb_g"][i], st["coef"][i], None)
+        eps = one_step(engine, st, st["temb_t"][i], st["temb_g"][i], st["coef"][i], None)
         lat = st["latents"]
         fin = bool(torch.isfinite(lat).all().item())
         print(f"B step {i:2d}: eps absmax {eps[..., :4].float().abs().max().item():.4g} latents absmax {lat.abs().max().item():.4g} finite {fin}", flush=True)
         if not fin:
             st["latents"].copy_(saved)
             ops.RECORD = []
-            engine._step(st, st["temb_t"][i], st["temb_g"][i], st["coef"][i], None)
+            one_step(engine, st, st["temb_t"][i], st["temb_g"][i], st["coef"][i], None)
             rec, ops.RECORD = ops.RECORD, None
             torch.cuda.synchronize()
             for j, (kind, key, a, keep) in enumerate(rec):

@@ -72,7 +72,10 @@ def main():
         st = engine.prepare(num_inference_steps=30, guidance_scale=2.0, scheduler="ddim", **inp)
         n_prep = len(ops.RECORD)
         k = st["k"]                                      # one block of the loop: GarmentNet over k timesteps + k TryonNet steps
+        rec, ops.RECORD = ops.RECORD, None               # (the set's shape discovery may run a GarmentNet batch: not part of the block)
         fset = engine._new_set(st)
+        ops.RECORD = rec
+        engine._garment_side(st, st["temb_gk"][0], fset, k)
         for j in range(k):
             engine._tryon_main(st, st["temb_t"][j], st["coef"][j], None, fset["step"][j])
         n_step = len(ops.RECORD)
