@@ -344,24 +344,31 @@ class StableDiffusionXLInpaintPipeline:
             raise NotImplementedError(f"scheduler {type(self.scheduler).__name__}: the fused step kernel implements DDPM and DDIM(eta=0)")
         return kind
 
+    def _cloth_latent_hw(self, clo):
+        """Latent (gh, gw) of a cloth image, which is encoded at its own size (:1654: no resize)."""
+        Hg, Wg = clo.shape[-2:]
+        if Hg % self.vae_scale_factor or Wg % self.vae_scale_factor:
+            raise ValueError(f"`cloth` height and width have to be divisible by {self.vae_scale_factor} but are {Hg} and {Wg}.")
+        return Hg // self.vae_scale_factor, Wg // self.vae_scale_factor
+
     # ------------------------------------------------------------------------------------------ the garment, once
     @torch.no_grad()
     def encode_garment(self, cloth, text_embeds_cloth, num_inference_steps, height, width, strength=1.0, generator=None):
         """Encode G garments once for many calls: -> GarmentCache, to be passed AS `cloth=` to __call__ (whose `text_embeds_cloth` may then
         be None) with the same scheduler, num_inference_steps, height and width; any strength whose timesteps are among this one's (a cache
         made with strength=1.0 serves every strength).  The batch of a cached call may hold P = m * G persons: person i wears garment i % G.
+        `cloth` may have any size divisible by 8, as in the reference (it encodes the cloth as it is, :1654, and the garment tokens meet the
+        person's along the token axis only): the garment runs at its own size; `height` / `width` are the PERSON size of the calls the cache
+        is declared for (GarmentCache.for_person_size declares it for another).  Image quality at other garment sizes is not evaluated.
         The reference has no counterpart (it runs GarmentNet in every step of every call, tryon_pipeline.py:1781-1787).
 
-        RNG: the one draw made here is the cloth posterior sample ([G,4,h,w] fp32, from `generator`).  In __call__ the cloth posterior draw
+        RNG: the one draw made here is the cloth posterior sample ([G,4,gh,gw] fp32 -- the garment latent's shape --, from `generator`).  In __call__ the cloth posterior draw
         is the call's third draw from `generator` (latents, masked-image posterior, [pose: global generator], cloth, then
         the DDPM step noise); a call on a cache STILL MAKES that draw and discards it, so every later draw -- the DDPM step noise -- and
         the generator's final state are those of an uncached call with the same generator."""
         eng = self.hip_engine()
         clo = _to_tensor_image(cloth, "cloth")
-        if tuple(clo.shape[-2:]) != (height, width):
-            raise ValueError(f"`cloth` is {tuple(clo.shape[-2:])} but (height, width) = {(height, width)}")
-        h, w = height // self.vae_scale_factor, width // self.vae_scale_factor
-        n_cloth = _randn((clo.shape[0], 4, h, w), generator, eng.device, torch.float32)
+        n_cloth = _randn((clo.shape[0], 4) + self._cloth_latent_hw(clo), generator, eng.device, torch.float32)
         return eng.encode_garment(cloth=clo, text_embeds_cloth=text_embeds_cloth, noise_cloth=n_cloth, num_inference_steps=num_inference_steps,
                                   scheduler=self._scheduler_kind(), strength=strength, height=height, width=width)
 
@@ -440,10 +447,13 @@ class StableDiffusionXLInpaintPipeline:
         pose = _to_tensor_image(pose_img, "pose_img")
         clo = cloth if cached else _to_tensor_image(cloth, "cloth")
         B = img.shape[0]
-        for name, t in (("pose_img", pose),) + ((("cloth", clo),) if not cached else ()):        # encoded as they are (:1644-1654): no resize there
-            if tuple(t.shape[-2:]) != (height, width):
-                raise ValueError(f"`{name}` is {tuple(t.shape[-2:])} but (height, width) = {(height, width)}: the reference encodes it as it "
-                                 "is and fails when its latents are concatenated with the image's")
+        # both are encoded as they are (:1644-1654: no resize there).  The pose latents are concatenated with the image's along channels
+        # (:1777), so pose_img must have the call's size; the cloth only meets the person along the token axis (attentionhacked_tryon.py:334)
+        # and may have any size divisible by 8
+        if tuple(pose.shape[-2:]) != (height, width):
+            raise ValueError(f"`pose_img` is {tuple(pose.shape[-2:])} but (height, width) = {(height, width)}: the reference encodes it as it "
+                             "is and fails when its latents are concatenated with the image's along channels")
+        cloth_hw = (clo.gh, clo.gw) if cached else self._cloth_latent_hw(clo)
         if img.min() < 0:
             raise ValueError("`image` is expected in [0, 1] (inference.py:408 passes (image + 1) / 2)")
         h, w = height // self.vae_scale_factor, width // self.vae_scale_factor
@@ -459,7 +469,7 @@ class StableDiffusionXLInpaintPipeline:
         n_img = _randn(shape, generator, device, torch.float32) if (strength != 1.0 and latents is None) else None
         n_lat = latents.to(device).float() if latents is not None else _randn(shape, generator, device, prompt_embeds.dtype)
         n_masked, n_pose, n_cloth = (_randn(shape, generator, device, torch.float32), _randn(shape, None, device, torch.float32),
-                                     _randn(shape, generator, device, torch.float32))
+                                     _randn((B, 4) + cloth_hw, generator, device, torch.float32))        # the garment latent's shape
         if cached:                                          # drawn all the same, so that every later draw is the uncached call's; not used
             n_cloth = None
         steps_noise = None

@@ -10,6 +10,12 @@ self-attention takes its operands straight from the projection), timestep-major:
 and V^T elements [i * G, (i + 1) * G).  A run of consecutive timesteps is therefore one contiguous slice of each tensor -- the shape of the
 engine's persistent feature sets, so a block of timesteps moves into a set with one copy per tensor.  Plain torch, no kernels: usable on CPU
 tensors (tests/test_garment_cache_cpu.py).
+
+Two sizes: (h, w) is the PERSON latent size a cache is declared for -- what `check` holds a call to -- and (gh, gw) the garment's own latent
+size, which fixes N_f (feature f has feature_tokens(gh, gw)[f] real tokens in round16 rows).  The K / V^T depend on the second alone, so
+`for_person_size` re-declares a cache for another person size on the same tensors.  Size: with N1 / N2 the token rows at the two attention
+levels of the SDXL topology (10 features of 640 channels, 60 of 1280), an entry is (10 * N1 * 640 + 60 * N2 * 1280) * 2 tensors * 2 bytes per
+garment and timestep (tests/test_garment_size_cpu.py).
 """
 import torch
 
@@ -36,10 +42,11 @@ def kv_shapes(kv):
 
 
 class GarmentCache:
-    def __init__(self, *, G, timesteps, h, w, dtype, attn_fp8, f8_exp, weights_id, kv):
+    def __init__(self, *, G, timesteps, h, w, dtype, attn_fp8, f8_exp, weights_id, kv, gh=None, gw=None):
         self.G = int(G)
         self.timesteps = [int(t) for t in timesteps]
         self.h, self.w = int(h), int(w)
+        self.gh, self.gw = int(h if gh is None else gh), int(w if gw is None else gw)    # the garment's own latent size (default: the person's)
         self.dtype = dtype
         self.attn_fp8 = bool(attn_fp8)
         self.f8_exp = tuple(int(e) for e in f8_exp)
@@ -58,8 +65,21 @@ class GarmentCache:
         return sum(k.numel() * k.element_size() + vt.numel() * vt.element_size() for k, vt in self.kv)
 
     def __repr__(self):
-        return (f"GarmentCache(G={self.G}, steps={len(self.timesteps)}, latent={self.h}x{self.w}, dtype={self.dtype}, attn_fp8={self.attn_fp8}, "
-                f"{self.nbytes / 2 ** 20:.1f} MiB)")
+        garment = f", garment latent={self.gh}x{self.gw}" if (self.gh, self.gw) != (self.h, self.w) else ""
+        return (f"GarmentCache(G={self.G}, steps={len(self.timesteps)}, latent={self.h}x{self.w}{garment}, dtype={self.dtype}, "
+                f"attn_fp8={self.attn_fp8}, {self.nbytes / 2 ** 20:.1f} MiB)")
+
+    def _like(self, **kw):
+        args = dict(G=self.G, timesteps=self.timesteps, h=self.h, w=self.w, gh=self.gh, gw=self.gw, dtype=self.dtype, attn_fp8=self.attn_fp8,
+                    f8_exp=self.f8_exp, weights_id=self.weights_id, kv=self.kv)
+        args.update(kw)
+        return GarmentCache(**args)
+
+    def for_person_size(self, h, w):
+        """The same cache -- the same tensors, no copy -- declared for calls at person latent size (h, w).  The garment K / V^T are made from
+        the cloth alone (GarmentNet at (gh, gw), TryonNet's attn1 to_k / to_v) and do not depend on the person's resolution, so one encoded
+        garment serves e.g. 768x1024 and 1024x1536 calls; `check` stays strict, this is the explicit opt-in."""
+        return self._like(h=h, w=w)
 
     def check(self, *, timesteps, h, w, dtype, attn_fp8, f8_exp, weights_id, persons):
         """The cache entry (timestep index) of every timestep of a call, looked up BY VALUE -- a cache built for n steps serves strength < 1
@@ -103,8 +123,7 @@ class GarmentCache:
             kk = k.reshape(n, 1, r, k.shape[1]).expand(n, times, r, k.shape[1]).reshape(n * times * r, k.shape[1]).contiguous()
             vv = vt.reshape(n, 1, G, *vt.shape[1:]).expand(n, times, G, *vt.shape[1:]).reshape(n * times * G, *vt.shape[1:]).contiguous()
             kv.append((kk, vv))
-        return GarmentCache(G=G * times, timesteps=self.timesteps, h=self.h, w=self.w, dtype=self.dtype, attn_fp8=self.attn_fp8,
-                            f8_exp=self.f8_exp, weights_id=self.weights_id, kv=kv)
+        return self._like(G=G * times, kv=kv)
 
 
 def weights_fingerprint(named_tensors):

@@ -141,6 +141,26 @@ class TryonEngine:
         ctx_gk = ctx_g if k == 1 else self.unet_encoder.encode_context(text_embeds_cloth.to(dev).repeat(k, 1, 1))
         return dict(cloth=cloth_nhwc, ctx_g=ctx_g, temb_g=temb_g, k=k, blocks=blocks, temb_gk=temb_gk, cloth_k=cloth_k, ctx_gk=ctx_gk)
 
+    @staticmethod
+    def _garment_latent_size(cloth):
+        """The garment runs at the cloth image's own size (the reference encodes it as it is, tryon_pipeline.py:1654, and its tokens meet the
+        person's only along the token axis, attentionhacked_tryon.py:334): -> latent (gh, gw)."""
+        Hg, Wg = cloth.shape[-2:]
+        if Hg % 8 or Wg % 8:
+            raise ValueError(f"`cloth` height and width have to be divisible by 8 but are {Hg} and {Wg}.")
+        return Hg // 8, Wg // 8
+
+    @staticmethod
+    def _set_key(st):
+        """What the shapes of a persistent garment set depend on: garments, the garment's latent size, timesteps per batch."""
+        return (st["B"], st["gh"], st["gw"], st["k"])
+
+    @staticmethod
+    def _graph_key(st, live):
+        """One persistent graph state per shape of a call: persons, person latent size, garment latent size, block size, step noise, and on a
+        GarmentCache its garment count."""
+        return (st["B"], st["h"], st["w"], st["gh"], st["gw"], st["k"], st["steps_noise"] is not None) + (() if live else ("cached", st["gcache"].G))
+
     def weights_identity(self):
         """What a GarmentCache depends on besides its inputs: every GarmentNet weight, and TryonNet's attn1.to_k / to_v (the projections of
         project_garment_kv), as stored (dtype included)."""
@@ -153,31 +173,39 @@ class TryonEngine:
     def encode_garment(self, *, cloth, text_embeds_cloth, noise_cloth, num_inference_steps, scheduler="ddpm", strength=1.0,
                        height=None, width=None):
         """The garment side of a call for G = cloth.shape[0] garments, computed once: -> GarmentCache for `prepare(cloth=<it>)`.
-        cloth in [-1,1] [G,3,H,W]; noise_cloth: the posterior draw of the cloth encode, [G,4,h,w] fp32 (noise['cloth'] of an uncached call).
+        cloth in [-1,1] [G,3,Hg,Wg], any size divisible by 8: the garment runs at its own latent (gh, gw) = (Hg / 8, Wg / 8); noise_cloth: the
+        posterior draw of the cloth encode, [G,4,gh,gw] fp32 (noise['cloth'] of an uncached call).  height / width: the PERSON size the cache is
+        declared for (default: the cloth's); GarmentCache.for_person_size re-declares it, the K / V^T do not depend on it.
         Runs what the loop runs for the garment side -- cloth VAE encode, encode_context, time_embeddings, and per block the GarmentNet batch
         + project_garment_kv -- IN THE SAME BLOCK SCHEDULE (1, 2, 4, k, k, ...) and at the same batch sizes as an uncached call with G
         persons and this num_inference_steps / strength, so every launch is the launch that call makes and the cached K / V^T are its bits.
-        For the same reason the cloth goes through the VAE encoder in the third slot of a 3G-image pass, where an uncached call encodes it
-        (prepare: [masked image | pose | cloth]): per image the arithmetic does not depend on the batch, but which GEMM tile runs may."""
+        For the same reason a cloth of the person's size goes through the VAE encoder in the third slot of a 3G-image pass, where an uncached
+        call encodes it (prepare: [masked image | pose | cloth]): per image the arithmetic does not depend on the batch, but which GEMM tile
+        runs may.  A cloth of another size has a pass of its own there, and here."""
         dev = self.device
         f32 = lambda t: t.to(dev, torch.float32).contiguous()
         cloth, nz = f32(cloth), f32(noise_cloth)
         G = cloth.shape[0]
-        H = height or cloth.shape[-2]
-        W = width or cloth.shape[-1]
+        Hg, Wg = cloth.shape[-2:]
+        H = height or Hg
+        W = width or Wg
         if H % 8 or W % 8:
             raise ValueError(f"`height` and `width` have to be divisible by 8 but are {H} and {W}.")
+        gh, gw = self._garment_latent_size(cloth)
         h, w = H // 8, W // 8
         _, timesteps = self._timesteps(scheduler, num_inference_steps, strength)
-        cloth_lat = self.vae.encode_sample(torch.cat([cloth, cloth, cloth]), torch.cat([nz, nz, nz]))[2 * G:]
-        gs = dict(B=G, h=h, w=w, **self._garment_inputs(cloth_lat, text_embeds_cloth, timesteps, G))
+        if (Hg, Wg) == (H, W):
+            cloth_lat = self.vae.encode_sample(torch.cat([cloth, cloth, cloth]), torch.cat([nz, nz, nz]))[2 * G:]
+        else:
+            cloth_lat = self.vae.encode_sample(cloth, nz)
+        gs = dict(B=G, gh=gh, gw=gw, **self._garment_inputs(cloth_lat, text_embeds_cloth, timesteps, G))
         n, k = len(timesteps), gs["k"]
         fs, ks = self._discover_set_shapes(gs)
         feats = [torch.empty(sh, dtype=self.dtype, device=dev) for sh in fs]
         kv = alloc_kv(ks, k, n, dev)
         for bi, (s0, c) in enumerate(gs["blocks"]):          # each block's projections land in the cache's own rows
             self._garment_side(gs, gs["temb_gk"][bi], dict(feats=feats, kv=timestep_run(kv, n, G, s0, c)), c)
-        return GarmentCache(G=G, timesteps=timesteps, h=h, w=w, dtype=self.dtype, attn_fp8=self.unet.attn_fp8, f8_exp=self.unet.f8_exp,
+        return GarmentCache(G=G, timesteps=timesteps, h=h, w=w, gh=gh, gw=gw, dtype=self.dtype, attn_fp8=self.unet.attn_fp8, f8_exp=self.unet.f8_exp,
                             weights_id=self.weights_identity(), kv=kv)
 
     # -------------------------------------------------------------------------------------------- preparation
@@ -187,8 +215,11 @@ class TryonEngine:
                 ip_hidden_states=None, image_embeds=None, scheduler="ddpm", height=None, width=None, strength=1.0,
                 image_dtype=None):
         """Everything before the loop (tryon_pipeline.py:1495-1762).  image in [0,1]; pose_img / cloth in [-1,1];
-        noise: dict(latents, masked, pose, cloth [B,4,h,w] fp32; steps [n,B,4,h,w] fp32 or None; image [B,4,h,w] when strength < 1)
-        -- RNG order SURVEY A.4.
+        noise: dict(latents, masked, pose [B,4,h,w] fp32; cloth [B,4,gh,gw] fp32; steps [n,B,4,h,w] fp32 or None; image [B,4,h,w] when
+        strength < 1) -- RNG order SURVEY A.4.
+        cloth: [B,3,Hg,Wg] of any size divisible by 8 -- the garment runs at its own latent (gh, gw) = (Hg / 8, Wg / 8), as in the reference,
+        which encodes the cloth as it is (:1654) and joins its tokens to the person's along the token axis only.  What another garment size
+        does to image quality is not evaluated here (no trained weights): the engine runs what the reference runs.
         strength < 1 (:987-995, 883-893): the last int(n*strength) timesteps, starting from add_noise(encode(image), noise, t_0).
         guidance_scale <= 1 (:440-442: no classifier-free guidance): the reference runs the conditional branch alone; here the
         batched step runs with guidance 1 -- u + 1*(t - u) = t to one fp32 rounding -- so negative_* may be None and
@@ -209,6 +240,7 @@ class TryonEngine:
         H = height or image.shape[-2]
         W = width or image.shape[-1]
         h, w = H // 8, W // 8
+        gh, gw = self._garment_latent_size(cloth) if gcache is None else (gcache.gh, gcache.gw)
         # any H x W divisible by 8 (the reference's own check, tryon_pipeline.py check_inputs): odd latent levels go through `upsample_size`
         # (unet.py: _conv3 out_hw), token counts that are not a multiple of 16 are padded inside each Transformer2DModel (unet.py: _transformer)
         if H % 8 or W % 8:
@@ -243,13 +275,15 @@ class TryonEngine:
         # the three VAE encodes of the call (:964 masked image, :1644-1647 pose, :1654 cloth) as ONE encoder pass over 3B images: per
         # image the arithmetic is unchanged (GroupNorm / attention are per image), the convolution GEMMs see 3x the rows and the
         # launch count of the encoder is paid once
-        if gcache is None:
+        if gcache is None and tuple(cloth.shape[-2:]) == (H, W):
             enc = self.vae.encode_sample(torch.cat([masked_image, pose_img, cloth]),
                                          torch.cat([f32(noise["masked"]), f32(noise["pose"]), f32(noise["cloth"])]))
             masked_lat, pose_lat, cloth_lat = enc[:B], enc[B:2 * B], enc[2 * B:]
-        else:                                                # the garment is already encoded: the pass is over 2B images
+        else:                                                # the pass is over 2B images: the garment is already encoded (a cache) ...
             enc = self.vae.encode_sample(torch.cat([masked_image, pose_img]), torch.cat([f32(noise["masked"]), f32(noise["pose"])]))
             masked_lat, pose_lat, cloth_lat = enc[:B], enc[B:], None
+            if gcache is None:                               # ... or has a size of its own, and a pass of its own
+                cloth_lat = self.vae.encode_sample(cloth, f32(noise["cloth"]))
         # step-invariant 9 conditioning channels of the 13-channel input, NHWC, both CFG halves (:955,977,1649-1652,1777)
         cond = torch.cat([mask_l, masked_lat, pose_lat], dim=1).permute(0, 2, 3, 1).reshape(B, h * w, 9)
         cond = torch.cat([cond, cond], dim=0).to(dt).contiguous()
@@ -270,7 +304,7 @@ class TryonEngine:
                         gcache=gcache, gidx=gidx, garment_persons=B)
         coef = torch.tensor([list(sched.coeffs(t)) + [guidance_scale] for t in timesteps], dtype=torch.float32, device=dev)
         steps_noise = f32(noise["steps"]) if noise.get("steps") is not None and scheduler == "ddpm" else None
-        return dict(B=B, h=h, w=w, timesteps=timesteps, latents=latents.contiguous(), cond=cond,
+        return dict(B=B, h=h, w=w, gh=gh, gw=gw, timesteps=timesteps, latents=latents.contiguous(), cond=cond,
                     ctx_t=ctx_t, temb_t=temb_t, coef=coef, steps_noise=steps_noise, **garm,
                     x_in=torch.empty(2 * B, h * w, self.unet.cin_pad, dtype=dt, device=dev),
                     trace=dict(masked_lat=masked_lat, pose_lat=pose_lat, cloth_lat=cloth_lat, image_embeds=image_embeds))
@@ -280,7 +314,7 @@ class TryonEngine:
     # second HIP stream while TryonNet runs the steps of block b (drive_blocks).  Two feature sets alternate; there is no other coupling.
     # `st` below is a call's state (prepare) or a persistent graph state (_graph_state): both carry the keys these two read.
     def _garment_side(self, st, temb_gk, fset, c=None):
-        B, h, w = st["B"], st["h"], st["w"]
+        B, h, w = st["B"], st["gh"], st["gw"]                # GarmentNet runs at the garment's own latent size
         c = st["k"] if c is None else c                      # timesteps in this batch (the set's buffers hold up to st["k"])
         self.stats["garment_batches"] += 1
         _, feats = self.unet_encoder.forward(st["cloth_k"][:c * B], temb_gk[:c * B], st["ctx_gk"], c * B, h, w, feats_buf=fset["feats"])   # :1787
@@ -291,15 +325,16 @@ class TryonEngine:
         ops.pack_input(st["latents"], st["cond"], st["x_in"])                              # :1769,1777
         # garment_persons: None = one garment entry per conditional batch (unet.forward's default); B on a GarmentCache call, where kv_j
         # holds G garments for the B persons (a shared segment when G < B)
-        eps, _ = self.unet.forward(st["x_in"], temb_t, st["ctx_t"], 2 * B, h, w, garment_kv=kv_j, garment_persons=st["garment_persons"])    # :1796-1808
+        eps, _ = self.unet.forward(st["x_in"], temb_t, st["ctx_t"], 2 * B, h, w, garment_kv=kv_j, garment_persons=st["garment_persons"],
+                                   garment_hw=(st["gh"], st["gw"]))                        # :1796-1808
         ops.cfg_step(eps, st["latents"], noise, coef)                                      # :1814-1823
         return eps
 
     def _discover_set_shapes(self, st):
-        """-> (feature shapes, (K, V^T) shapes) of a GarmentNet batch over k timesteps, learnt once per (B, h, w, k) by running one (its
+        """-> (feature shapes, (K, V^T) shapes) of a GarmentNet batch over k timesteps, learnt once per (B, gh, gw, k) by running one (its
         outputs are dropped; not counted in stats)."""
-        B, h, w, k = st["B"], st["h"], st["w"], st["k"]
-        key = (B, h, w, k)
+        B, h, w, k = st["B"], st["gh"], st["gw"], st["k"]
+        key = self._set_key(st)
         if key not in self._set_shapes:
             _, feats = self.unet_encoder.forward(st["cloth_k"], st["temb_gk"][0], st["ctx_gk"], k * B, h, w)
             kv = self.unet.project_garment_kv(feats)         # (dtype uint8 = e4m3: attn_fp8)
@@ -357,7 +392,7 @@ class TryonEngine:
     def _graph_state(self, st, live):
         """Persistent buffers + captured graphs for one shape; it owns exactly what a captured graph reads or writes (latents, cond, x_in, the
         ctx_t K / V^T and, live, cloth_k and the ctx_gk K / V^T: the first call's tensors, adopted; the two sets; tt / cf / nz / tgk) and
-        the scalars B, h, w, k, garment_persons -- nothing else of a call, so no GarmentCache and no time-embedding table stays alive here.
+        the scalars B, h, w, gh, gw, k, garment_persons -- nothing else of a call, so no GarmentCache and no time-embedding table stays alive here.
         The graphs are SMALL: ('garm', p, c) = the GarmentNet batch into feature set p, ('tryon', p, j) = one TryonNet step on timestep
         slice j of set p (2 + 2k graphs, captured on first use).  The loop replays them like the eager form launches kernels -- GarmentNet
         graphs on the side stream, TryonNet graphs on the main stream, two events per set -- so the overlap form has no fork/join inside a
@@ -366,10 +401,10 @@ class TryonEngine:
         Captures use capture_error_mode="thread_local": with torch.distributed / RCCL initialised a watchdog thread polls events,
         which the default global mode would treat as a capture violation."""
         has_noise = st["steps_noise"] is not None
-        key = (st["B"], st["h"], st["w"], st["k"], has_noise) + (() if live else ("cached", st["gcache"].G))
+        key = self._graph_key(st, live)                      # garment size included: calls with different garment sizes share nothing here
         if key in self._graphs:
             return self._graphs[key]
-        G = {name: st[name] for name in ("B", "h", "w", "k", "garment_persons", "latents", "cond", "x_in", "ctx_t")}
+        G = {name: st[name] for name in ("B", "h", "w", "gh", "gw", "k", "garment_persons", "latents", "cond", "x_in", "ctx_t")}
         G.update(tt=st["temb_t"][0].clone(), cf=st["coef"][0].clone(), nz=st["steps_noise"][0].clone() if has_noise else None, graphs={},
                  side=torch.cuda.Stream(), ready=[torch.cuda.Event(), torch.cuda.Event()], free=[torch.cuda.Event(), torch.cuda.Event()],
                  # graphs that replay one after another on ONE stream may share a memory pool: all TryonNet graphs (main stream), all

@@ -262,36 +262,48 @@ class HipUNet:
         ops.linear(n1, blk["qkv"], out=qk, vt=vt, vt_n0=2 * C, vt_tokens=N, colscale_n=C, colscale=qcs, **f8kw)
         segs = [dict(k=qk[:, C:], vt=vt, nk=nk, ldk=2 * C, ldvt=N, k_rows=N)]
         if self.tryon:
+            # the garment segment has its own geometry (attentionhacked_tryon.py:334 joins the two along the token axis only): gnk real tokens
+            # in Ng = round16(gnk) rows per garment, whatever the person's N
+            gnk = garment["nk"][garment["idx"]] if garment.get("nk") is not None else None
             if garment.get("kv") is not None:                   # K / V^T of the garment tokens projected ahead of time
                 kg, vtg = garment["kv"][garment["idx"]]         # (project_garment_kv, on the GarmentNet stream)
-                Bg = vtg.shape[0]
+                Bg, Ng = vtg.shape[0], vtg.shape[2]
+                if gnk is None:
+                    if Ng != N:
+                        raise ValueError(f"garment K / V^T of {Ng} token rows against {N} own rows: pass garment_hw (the garment's latent size)")
+                    gnk = nk
             else:
-                g = garment["feats"][garment["idx"]]            # [Bg][N][C] (or [Bg][nk][C]: reference-shaped features of a padded size)
+                g = garment["feats"][garment["idx"]]            # [Bg][Ng][C] of any Ng (or [Bg][gnk][C]: reference-shaped features of a padded size)
                 Bg = g.shape[0]
-                if g.shape[1] != N:
-                    gp = torch.zeros(Bg, N, C, dtype=dt, device=dev)
+                if gnk is None:                                  # engine-shaped rows of the person's size, else the rows are the real tokens
+                    gnk = nk if g.shape[1] == N else g.shape[1]
+                Ng = ops.round16(gnk)
+                if g.shape[1] != Ng:
+                    gp = torch.zeros(Bg, Ng, C, dtype=dt, device=dev)
                     gp[:, :g.shape[1]] = g
                     g = gp
-                kg = torch.empty(Bg * N, C, dtype=torch.uint8 if f8 else dt, device=dev)
-                vtg = torch.empty(Bg, C, N, dtype=torch.uint8 if f8 else dt, device=dev)
-                ops.linear(g.reshape(Bg * N, C), blk["qkv"][C:], out=kg, vt=vtg, vt_n0=C, vt_tokens=N, **f8kw)
+                f8g = self._f8_fused(Ng)
+                kg = torch.empty(Bg * Ng, C, dtype=torch.uint8 if f8g else dt, device=dev)
+                vtg = torch.empty(Bg, C, Ng, dtype=torch.uint8 if f8g else dt, device=dev)
+                ops.linear(g.reshape(Bg * Ng, C), blk["qkv"][C:], out=kg, vt=vtg, vt_n0=C, vt_tokens=Ng,
+                           **(dict(f8=(2.0 ** ek, 2.0 ** ev)) if f8g else {}))
             garment["idx"] += 1
             P = garment.get("persons") or Bg                    # conditional batches (GarmentCache calls: P persons, Bg = G garments)
-            gseg = dict(k=kg, vt=vtg, nk=nk, ldk=C, ldvt=N, k_rows=N, b0=B - P)
+            gseg = dict(k=kg, vt=vtg, nk=gnk, ldk=C, ldvt=Ng, k_rows=Ng, b0=B - P)
             if Bg < P:                                           # a shared segment: conditional row i reads garment i % G
                 gseg["nb"] = Bg
             segs.append(gseg)
         att = torch.empty(M, C, dtype=dt, device=dev)
         if self.attn_fp8:
             segs8 = []
-            for sg in segs:
-                Bs = sg["vt"].shape[0]
+            for sg in segs:                                      # each segment with its own token rows: e4m3 from its projection, or quantised here
+                Bs, Ns = sg["vt"].shape[0], sg["k_rows"]
                 if sg["k"].dtype == torch.uint8:                                            # written as e4m3 by its projection
-                    segs8.append(dict(k8=sg["k"], vt8=sg["vt"], nk=nk, ldk=sg["ldk"], ldvt=N, k_rows=N, b0=sg.get("b0", 0), nb=sg.get("nb", 0)))
+                    segs8.append(dict(k8=sg["k"], vt8=sg["vt"], nk=sg["nk"], ldk=sg["ldk"], ldvt=sg["ldvt"], k_rows=Ns, b0=sg.get("b0", 0), nb=sg.get("nb", 0)))
                     continue
-                k8 = ops.quant_f8(sg["k"], 2.0 ** ek)                                   # [Bs*N][C] (row stride ldk)
-                vt8 = ops.quant_f8(sg["vt"].reshape(Bs * C, N), 2.0 ** ev, mode=1)      # 16-bit key order -> fp8 slot order
-                segs8.append(dict(k8=k8, vt8=vt8, nk=nk, ldk=C, ldvt=vt8.shape[1], k_rows=N, b0=sg.get("b0", 0), nb=sg.get("nb", 0)))
+                k8 = ops.quant_f8(sg["k"], 2.0 ** ek)                                   # [Bs*Ns][C] (row stride ldk)
+                vt8 = ops.quant_f8(sg["vt"].reshape(Bs * C, Ns), 2.0 ** ev, mode=1)     # 16-bit key order -> fp8 slot order
+                segs8.append(dict(k8=k8, vt8=vt8, nk=sg["nk"], ldk=C, ldvt=vt8.shape[1], k_rows=Ns, b0=sg.get("b0", 0), nb=sg.get("nb", 0)))
             if f8:
                 q8, ldq8 = qk, 2 * C
             else:
@@ -397,14 +409,18 @@ class HipUNet:
         return ids[key]
 
     # ------------------------------------------------------------------------------------------------ forward
-    def forward(self, x, temb, ctx, B, H, W, garment_feats=None, garment_kv=None, feats_buf=None, garment_persons=None):
+    def forward(self, x, temb, ctx, B, H, W, garment_feats=None, garment_kv=None, feats_buf=None, garment_persons=None, garment_hw=None):
         """x: NHWC [B][H*W][cin_pad] (channels >= in_channels zero); temb: [B][sum Cout] (time_embeddings()[step]);
-        ctx: encode_context(); garment_feats: list of [Bg][N][C] (Bg <= B; batches < B-Bg see all-zero features).
+        ctx: encode_context(); garment_feats: list of [Bg][Ng][C] (Bg <= B; batches < B-Bg see all-zero features).
+        garment_hw = the garment's own latent (gh, gw) when it is not (H, W): its features have feature_tokens(gh, gw) real tokens per level
+        in round16 rows.  None: the person's size -- or, for garment_feats whose rows are neither N nor round16(N), the rows themselves
+        (reference-shaped features of a garment of another size).
         garment_persons = P (with garment_kv of G = Bg garments, P % G == 0): the last P batches are conditional and row i of them reads garment
         i % G through a shared attention segment (GarmentCache calls); None: P = Bg, one garment entry per conditional batch.
         Returns (noise NHWC [B][H*W][n_out] for TryonNet | None, exported features for GarmentNet)."""
         topo = self.topo
-        garment = dict(feats=garment_feats, kv=garment_kv, feats_buf=feats_buf, idx=0, persons=garment_persons)
+        garment = dict(feats=garment_feats, kv=garment_kv, feats_buf=feats_buf, idx=0, persons=garment_persons,
+                       nk=self.feature_tokens(*garment_hw) if garment_hw is not None and self.tryon else None)
         feats = []
         stop = None if self.tryon else self.num_features()
         h, _, _ = self._conv3(x, self.conv_in, B, H, W)

@@ -3,6 +3,8 @@
   (default)            cached vs uncached call at the configs[1] shape (768x1024, 30 steps, B = 2, bf16, hipGraph + two-stream overlap):
                        arms `uncached`, `cached_G2`, `cached_G1` interleaved over --rounds rounds of --calls timed calls each, one warm-up call
                        per arm discarded; images/s, loop ms/step, encode_garment time and cache.nbytes -> one JSON line
+  --cloth-size HxW     the same with a garment image of its own size (e.g. 512x384: a quarter of the tokens at every level, a quarter of the
+                       cache); the person stays 768x1024.  --arms picks a subset of the arms (an A/B against another tree: uncached only)
   --nbytes-only        only build the cache and print its size (with --attn-fp8: the e4m3 form)
   --attn               the self-attention launches on their own: the six CFG lines of profiles/r06_attention_sp_tuner_lines.txt through the OLD
                        entry point (IDMVTON_HIP_LIB selects the build: run once per build, interleaved, for an A/B), then shared vs materialised
@@ -27,27 +29,48 @@ DEV, DT = torch.device("cuda", 0), torch.bfloat16
 H, W, STEPS, B = 1024, 768, 30, 2
 
 
+def cloth_size(text):
+    hg, wg = (int(x) for x in text.lower().split("x"))
+    if hg % 8 or wg % 8 or hg < 8 or wg < 8:
+        raise argparse.ArgumentTypeError(f"--cloth-size {text}: height and width must be multiples of 8")
+    return hg, wg
+
+
+def with_cloth_of_size(inp, Hg, Wg, device=None):
+    """The call's inputs with a garment image of Hg x Wg and the posterior draw of its latent: the cloth fields of bench.synth_inputs at that
+    size (same per-image seeds), everything else untouched."""
+    g = bench.synth_inputs(inp["image"].shape[0], Hg, Wg, 1, device or inp["image"].device, first_image_index=0)
+    return {**inp, "cloth": g["cloth"], "noise": {**inp["noise"], "cloth": g["noise"]["cloth"]}}
+
+
 def call_arms(args):
     eng, _ = bench.build_engine(DT, DEV, 0, STEPS, attn_fp8=args.attn_fp8)
     inp = bench.synth_inputs(B, H, W, STEPS, DEV, first_image_index=0)
+    Hg, Wg = args.cloth_size or (H, W)
+    if (Hg, Wg) != (H, W):
+        inp = with_cloth_of_size(inp, Hg, Wg)
+    gh, gw = Hg // 8, Wg // 8
+    n1, n2 = ops.round16((gh + 1) // 2 * ((gw + 1) // 2)), ops.round16((gh + 3) // 4 * ((gw + 3) // 4))      # token rows at the two attention levels
+    want = [a for a in args.arms.split(",") if a]
     kw = dict(num_inference_steps=STEPS, guidance_scale=2.0, scheduler="ddim", use_graph=True, overlap=True)
-    garm = lambda G: dict(cloth=inp["cloth"][:G], text_embeds_cloth=inp["text_embeds_cloth"][:G], noise_cloth=inp["noise"]["cloth"][:G])
+    garm = lambda G: dict(cloth=inp["cloth"][:G], text_embeds_cloth=inp["text_embeds_cloth"][:G], noise_cloth=inp["noise"]["cloth"][:G],
+                          height=H, width=W)
     caches, enc_ms = {}, {}
-    for G in ((2,) if args.nbytes_only else (2, 1)):
+    for G in ((2,) if args.nbytes_only else tuple(g for g in (2, 1) if f"cached_G{g}" in want)):
         eng.encode_garment(num_inference_steps=STEPS, scheduler="ddim", **garm(G))          # warm-up (shape discovery, allocator)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         caches[G] = eng.encode_garment(num_inference_steps=STEPS, scheduler="ddim", **garm(G))
         torch.cuda.synchronize()
         enc_ms[G] = (time.perf_counter() - t0) * 1e3
-    res = {"shape": f"{W}x{H}, {STEPS} steps, B={B}, bf16{' + fp8 attention' if args.attn_fp8 else ''}",
+    res = {"shape": f"{W}x{H}, cloth {Wg}x{Hg}, {STEPS} steps, B={B}, bf16{' + fp8 attention' if args.attn_fp8 else ''}",
            "cache_nbytes": {f"G{G}": c.nbytes for G, c in caches.items()}, "encode_garment_ms": {f"G{G}": round(v, 1) for G, v in enc_ms.items()},
-           "derived_bytes_per_garment_16bit": (10 * 3072 * 640 + 60 * 768 * 1280) * 2 * 2 * STEPS}
+           "derived_bytes_per_garment_16bit": (10 * n1 * 640 + 60 * n2 * 1280) * 2 * 2 * STEPS}
     if args.nbytes_only:
         print(json.dumps(res))
         return
-    arms = {"uncached": inp, "cached_G2": {**inp, "cloth": caches[2], "text_embeds_cloth": None},
-            "cached_G1": {**inp, "cloth": caches[1], "text_embeds_cloth": None}}
+    arms = {"uncached": inp, **{f"cached_G{G}": {**inp, "cloth": c, "text_embeds_cloth": None} for G, c in caches.items()}}
+    arms = {a: arms[a] for a in want}
     outs, rows = {}, {a: [] for a in arms}
     for a, ai in arms.items():                            # warm-up: graph capture, discarded
         outs[a] = eng(**kw, **ai).clone()
@@ -69,7 +92,8 @@ def call_arms(args):
                            prepare_ms=[round(x["prepare_ms"], 1) for x in v]) for a, v in rows.items()}
     # same garment noise and same per-garment batches: the G = 2 cached call computes the uncached call's latents (its person-side VAE encodes
     # run at another batch size, so the images are compared, not asserted equal)
-    res["max_abs_image_diff_cached_G2_vs_uncached"] = (outs["cached_G2"].float() - outs["uncached"].float()).abs().max().item()
+    if "cached_G2" in outs and "uncached" in outs:
+        res["max_abs_image_diff_cached_G2_vs_uncached"] = (outs["cached_G2"].float() - outs["uncached"].float()).abs().max().item()
     res["garment_batches_total"] = eng.stats["garment_batches"]
     print(json.dumps(res))
 
@@ -148,6 +172,8 @@ if __name__ == "__main__":
     ap.add_argument("--calls", type=int, default=3)
     ap.add_argument("--attn-fp8", action="store_true")
     ap.add_argument("--nbytes-only", action="store_true")
+    ap.add_argument("--cloth-size", type=cloth_size, default=None, metavar="HxW", help="garment image size (default: the person's 1024x768)")
+    ap.add_argument("--arms", default="uncached,cached_G2,cached_G1", help="comma-separated subset of uncached, cached_G2, cached_G1")
     ap.add_argument("--attn", action="store_true")
     ap.add_argument("--old-only", action="store_true", help="--attn: only the old entry point's lines (A/B against a tree without the shared one)")
     ap.add_argument("--pmc-arm", choices=["shared", "mat"], default=None)

@@ -6,6 +6,10 @@ around each launch with L2/MALL flushed in between (weights are cold in the real
 writes the winners to gpurun_out/tune_gfx950.json (reviewed, then committed as idm-vton_amd/tune_gfx950.json).
 
   python tools/gpu_tune.py [--batch 2] [--height 1024 --width 768] [--iters 6]
+
+--cloth-size HxW: the call's garment image has its own size.  Only the launch signatures that call adds -- those neither a same-size call
+makes nor the committed table holds -- are tuned, and the written table is the committed one plus the new winners: existing keys stay as
+they are.
 """
 import argparse
 import json
@@ -52,6 +56,7 @@ def main():
     ap.add_argument("--merge", action="store_true", help="start from the committed table: signatures this run does not see keep their entries")
     ap.add_argument("--only-attn", action="store_true", help="tune the attention launches only; the GEMM half of the written table is the committed one")
     ap.add_argument("--warm-weights", action="store_true", help="touch the weights back into the cache before every timed launch (the pre-round-4 regime)")
+    ap.add_argument("--cloth-size", default=None, metavar="HxW", help="garment image size; tunes only the signatures this adds (see above)")
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "tune_gfx950.json"))
     args = ap.parse_args()
     import bench
@@ -67,28 +72,42 @@ def main():
         engine.garment_steps = args.garment_steps
         engine.ramp = False                              # one steady block of the chosen size
 
-    ops.RECORD = []
-    with torch.no_grad():
-        st = engine.prepare(num_inference_steps=30, guidance_scale=2.0, scheduler="ddim", **inp)
-        n_prep = len(ops.RECORD)
-        k = st["k"]                                      # one block of the loop: GarmentNet over k timesteps + k TryonNet steps
-        rec, ops.RECORD = ops.RECORD, None               # (the set's shape discovery may run a GarmentNet batch: not part of the block)
-        fset = engine._new_set(st)
-        ops.RECORD = rec
-        engine._garment_side(st, st["temb_gk"][0], fset, k)
-        for j in range(k):
-            engine._tryon_main(st, st["temb_t"][j], st["coef"][j], None, fset["step"][j])
-        n_step = len(ops.RECORD)
-        engine.decode(st["latents"])
-    rec, ops.RECORD = ops.RECORD, None
-    torch.cuda.synchronize()
+    def record(inp):
+        """-> (launches of one call: prepare + one block + decode, first / one-past-last index of the block, k)."""
+        ops.RECORD = []
+        with torch.no_grad():
+            st = engine.prepare(num_inference_steps=30, guidance_scale=2.0, scheduler="ddim", **inp)
+            n_prep = len(ops.RECORD)
+            k = st["k"]                                  # one block of the loop: GarmentNet over k timesteps + k TryonNet steps
+            rec, ops.RECORD = ops.RECORD, None           # (the set's shape discovery may run a GarmentNet batch: not part of the block)
+            fset = engine._new_set(st)
+            ops.RECORD = rec
+            engine._garment_side(st, st["temb_gk"][0], fset, k)
+            for j in range(k):
+                engine._tryon_main(st, st["temb_t"][j], st["coef"][j], None, fset["step"][j])
+            n_step = len(ops.RECORD)
+            engine.decode(st["latents"])
+        rec, ops.RECORD = ops.RECORD, None
+        torch.cuda.synchronize()
+        return rec, n_prep, n_step, k
+
+    known = set()
+    if args.cloth_size:
+        from tools.gpu_garment_cache import cloth_size, with_cloth_of_size
+        old = json.load(open(ops.TUNE_PATH))
+        known = {(kind, key) for kind, key, _, _ in record(inp)[0]} | {(kd[:4], key) for kd in ("gemm", "attn") for key in old.get(kd, {})}
+        inp = with_cloth_of_size(inp, *cloth_size(args.cloth_size))
+        args.merge = True
+    rec, n_prep, n_step, k = record(inp)
 
     uniq = {}
     for i, (kind, key, a, keep) in enumerate(rec):
+        if (kind, key) in known:
+            continue
         w = 30.0 / k if n_prep <= i < n_step else 1      # a block's launches run 30/k times per call
         u = uniq.setdefault((kind, key), dict(kind=kind, key=key, a=a, keep=keep, weight=0))
         u["weight"] += w
-    print(f"{len(rec)} launches recorded, {len(uniq)} unique signatures", flush=True)
+    print(f"{len(rec)} launches recorded, {len(uniq)} unique signatures" + (" that the garment size adds" if args.cloth_size else ""), flush=True)
 
     flush = torch.empty(640 << 20, dtype=torch.uint8, device=dev)
     stream = torch.cuda.current_stream().cuda_stream
