@@ -387,6 +387,8 @@ class StableDiffusionXLInpaintPipeline:
                  **kwargs):
         callback_steps = kwargs.pop("callback_steps", None)
         callback = kwargs.pop("callback", None)              # deprecated form, still honoured by the reference (:1855-1863)
+        # not in the reference's signature (a fixture pins the positional one): with cloth=<GarmentCache>, person i wears garment garment_index[i]
+        garment_index = kwargs.pop("garment_index", None)
         self._interrupt = False                              # :1519
         if callback_on_step_end is not None and any(k != "latents" for k in (callback_on_step_end_tensor_inputs or [])):
             raise NotImplementedError("callback_on_step_end_tensor_inputs other than 'latents': the text / image conditioning is projected once "
@@ -408,6 +410,8 @@ class StableDiffusionXLInpaintPipeline:
         if mask_image is None:
             raise ValueError("`mask_image` input cannot be undefined.")
         cached = isinstance(cloth, GarmentCache)            # encode_garment()'s result passed as `cloth=`: the caption went into it
+        if garment_index is not None and not cached:
+            raise ValueError("`garment_index` names garments of a GarmentCache: pass encode_garment()'s result as `cloth=`")
         for name, val in (("cloth", cloth), ("pose_img", pose_img), ("text_embeds_cloth", text_embeds_cloth),
                           ("ip_adapter_image", ip_adapter_image)):
             if val is None and not (cached and name == "text_embeds_cloth"):
@@ -484,6 +488,8 @@ class StableDiffusionXLInpaintPipeline:
                                latents_given=latents is not None),
                     num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, ip_hidden_states=image_states,
                     strength=strength, scheduler=kind, height=height, width=width)
+        if garment_index is not None:
+            call["garment_index"] = garment_index
         if isinstance(getattr(self, "trace_call", None), dict):    # test hook: what crossed the engine boundary (an oracle can replay it)
             self.trace_call.update(call)
         on_step = None

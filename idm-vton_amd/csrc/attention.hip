@@ -32,6 +32,7 @@ struct AttnParams {
     int pp_flags; float pp_thr;
     int q_prescaled;
     int seg_nb[2];                                      // batch elements a segment holds (idmvton_attn_fwd_shared); 0 = one per query batch from seg_b0 on
+    const int32_t* seg_ix[2];                           // idmvton_attn_fwd_indexed: device table, query batch b reads element seg_ix[s][b - seg_b0[s]]; NULL = the seg_nb rule
 };
 
 #define NEG_BIG (-1.0e30f)
@@ -162,7 +163,7 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_kernel(const AttnParams p) {
     const int nt0 = pres0 ? (p.nk[0] + 63) >> 6 : 0;
     const int nt1 = pres1 ? (p.nk[1] + 63) >> 6 : 0;
     const int nt = nt0 + nt1;
-    const int bsg0 = seg_batch(b, p.seg_b0[0], p.seg_nb[0]), bsg1 = seg_batch(b, p.seg_b0[1], p.seg_nb[1]);   // per workgroup, scalar
+    const int bsg0 = seg_batch_ix(b, p.seg_b0[0], p.seg_nb[0], p.seg_ix[0]), bsg1 = seg_batch_ix(b, p.seg_b0[1], p.seg_nb[1], p.seg_ix[1]);   // per workgroup, scalar
 
     // ---- loader ----
     const int lrow = lane >> 3, lslot = lane & 7;
@@ -430,7 +431,7 @@ __global__ __launch_bounds__(512, DEEP ? 2 : 4) void attn_pp_kernel(const AttnPa
     const int lim_x = is_k ? 8 : 32;
 #pragma unroll
     for (int sg = 0; sg < 2; ++sg) {
-        const size_t bsg = (size_t)seg_batch(b, p.seg_b0[sg], p.seg_nb[sg]);
+        const size_t bsg = (size_t)seg_batch_ix(b, p.seg_b0[sg], p.seg_nb[sg], p.seg_ix[sg]);
         tstep[sg] = is_k ? (uint32_t)(64 * p.ldk[sg] * 2) : 128u;
 #pragma unroll
         for (int i = 0; i < IPW; ++i) {
@@ -746,7 +747,7 @@ __global__ __launch_bounds__(512, 2) void attn_pf_kernel(const AttnParams p) {
     const int lim_x = is_k ? 8 : 32;
 #pragma unroll
     for (int sg = 0; sg < 2; ++sg) {
-        const size_t bsg = (size_t)seg_batch(b, p.seg_b0[sg], p.seg_nb[sg]);
+        const size_t bsg = (size_t)seg_batch_ix(b, p.seg_b0[sg], p.seg_nb[sg], p.seg_ix[sg]);
         tstep[sg] = is_k ? (uint32_t)(64 * p.ldk[sg] * 2) : 128u;
 #pragma unroll
         for (int i = 0; i < IPW; ++i) {
@@ -1046,7 +1047,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_sp_kernel(const AttnParams p)
     // per-lane byte offsets of this wave's IPW DMA rows inside segment sg (tile 0).  Only the CURRENT segment's set lives in registers; it is
     // recomputed at the segment switch.  lane_lim(i): the smallest key index piece i fetches (only a segment's partial last tile needs it).
     uint32_t rb[IPW];
-    const int bsg0 = seg_batch(b, p.seg_b0[0], p.seg_nb[0]), bsg1 = seg_batch(b, p.seg_b0[1], p.seg_nb[1]);   // per workgroup, scalar
+    const int bsg0 = seg_batch_ix(b, p.seg_b0[0], p.seg_nb[0], p.seg_ix[0]), bsg1 = seg_batch_ix(b, p.seg_b0[1], p.seg_nb[1], p.seg_ix[1]);   // per workgroup, scalar
     auto seg_base = [&](int sg) {
         const size_t bsg = (size_t)(sg ? bsg1 : bsg0);
 #pragma unroll
@@ -1411,7 +1412,10 @@ static int launch_attn(AttnParams& p, int tune, hipStream_t st) {
 
 // One implementation behind both entry points.  seg_nb[s] > 0: segment s holds seg_nb[s] batch elements and query batch b >= seg_b0[s] reads
 // element (b - seg_b0[s]) % seg_nb[s] (one garment's K / V^T shared by several persons); 0: one element per query batch from seg_b0[s] on.
-static int attn_fwd_impl(const idmvton_attn_args* a, const int32_t* seg_nb, void* stream) {
+// seg_index (idmvton_attn_fwd_indexed; NULL for the other two): seg_index[s] != NULL is a device table of B - seg_b0[s] int32, and query batch b
+// reads element seg_index[s][b - seg_b0[s]] of the seg_nb[s] >= 1 the segment holds (a pool may hold more elements than the batch has persons,
+// so seg_nb has no upper bound then).  The descriptor sizes stay seg_nb elements, and the kernels clamp the table's values to [0, seg_nb - 1].
+static int attn_fwd_impl(const idmvton_attn_args* a, const int32_t* seg_nb, const int32_t* const* seg_index, void* stream) {
     CHECK_ARG(a != nullptr, IDMVTON_E_ARG, "attn_fwd: null args");
     CHECK_ARG(a->dtype == IDMVTON_F16 || a->dtype == IDMVTON_BF16, IDMVTON_E_DTYPE, "attn_fwd: dtype %d", a->dtype);
     CHECK_ARG(a->mode == IDMVTON_ATTN_SELF || a->mode == IDMVTON_ATTN_CROSS, IDMVTON_E_ARG, "attn_fwd: mode %d", a->mode);
@@ -1432,6 +1436,13 @@ static int attn_fwd_impl(const idmvton_attn_args* a, const int32_t* seg_nb, void
         const int ss = s < a->nseg ? s : 0;
         CHECK_ARG(a->k[ss] && a->vt[ss] && a->nk[ss] > 0 && a->seg_b0[ss] >= 0 && a->seg_b0[ss] <= a->B,
                   IDMVTON_E_SHAPE, "attn_fwd: seg %d nk=%d b0=%d", ss, a->nk[ss], a->seg_b0[ss]);
+        const int32_t* ix = seg_index ? seg_index[ss] : nullptr;
+        if (ix) {
+            CHECK_ARG(a->mode != IDMVTON_ATTN_CROSS, IDMVTON_E_ARG, "attn_fwd_indexed: CROSS mode takes no table (seg %d)", ss);
+            CHECK_ARG(seg_nb[ss] >= 1 && a->seg_b0[ss] < a->B, IDMVTON_E_SHAPE,
+                      "attn_fwd_indexed: seg %d has a table: needs seg_nb >= 1 (%d) and seg_b0 < B (%d, %d)", ss, seg_nb[ss], a->seg_b0[ss], a->B);
+            CHECK_ARG(((uintptr_t)ix & 3) == 0, IDMVTON_E_ALIGN, "attn_fwd_indexed: seg %d table is not 4-byte aligned", ss);
+        } else
         CHECK_ARG(seg_nb[ss] >= 0 && seg_nb[ss] <= a->B - a->seg_b0[ss], IDMVTON_E_SHAPE,
                   "attn_fwd_shared: seg %d seg_nb=%d outside [0, B - seg_b0 = %d]", ss, seg_nb[ss], a->B - a->seg_b0[ss]);
         CHECK_ARG(a->mode != IDMVTON_ATTN_CROSS || seg_nb[ss] == 0, IDMVTON_E_ARG, "attn_fwd_shared: CROSS mode takes seg_nb = {0, 0} (seg %d: %d)", ss, seg_nb[ss]);
@@ -1445,7 +1456,7 @@ static int attn_fwd_impl(const idmvton_attn_args* a, const int32_t* seg_nb, void
         CHECK_ARG(kb < 0x80000000ull && vb < 0x80000000ull, IDMVTON_E_SHAPE, "attn_fwd: seg %d K/V^T >= 2 GiB", ss);
         p.k[s] = a->k[ss]; p.ldk[s] = a->ldk[ss]; p.kbytes[s] = (uint32_t)kb;
         p.vt[s] = a->vt[ss]; p.ldvt[s] = a->ldvt[ss]; p.vtbytes[s] = (uint32_t)vb;
-        p.nk[s] = a->nk[ss]; p.krows[s] = krows; p.seg_b0[s] = a->seg_b0[ss]; p.seg_nb[s] = seg_nb[ss];
+        p.nk[s] = a->nk[ss]; p.krows[s] = krows; p.seg_b0[s] = a->seg_b0[ss]; p.seg_nb[s] = seg_nb[ss]; p.seg_ix[s] = ix;
     }
     hipStream_t st = (hipStream_t)stream;
     if (a->dtype == IDMVTON_BF16)
@@ -1455,10 +1466,15 @@ static int attn_fwd_impl(const idmvton_attn_args* a, const int32_t* seg_nb, void
 
 extern "C" int idmvton_attn_fwd(const idmvton_attn_args* a, void* stream) {
     static const int32_t none[2] = {0, 0};
-    return attn_fwd_impl(a, none, stream);
+    return attn_fwd_impl(a, none, nullptr, stream);
 }
 
 extern "C" int idmvton_attn_fwd_shared(const idmvton_attn_args* a, const int32_t seg_nb[2], void* stream) {
     CHECK_ARG(seg_nb != nullptr, IDMVTON_E_ARG, "attn_fwd_shared: null seg_nb");
-    return attn_fwd_impl(a, seg_nb, stream);
+    return attn_fwd_impl(a, seg_nb, nullptr, stream);
+}
+
+extern "C" int idmvton_attn_fwd_indexed(const idmvton_attn_args* a, const int32_t seg_nb[2], const int32_t* const seg_index[2], void* stream) {
+    CHECK_ARG(seg_nb != nullptr && seg_index != nullptr, IDMVTON_E_ARG, "attn_fwd_indexed: null seg_nb / seg_index");
+    return attn_fwd_impl(a, seg_nb, seg_index, stream);
 }

@@ -34,6 +34,7 @@ struct AttnF8Params {
     int sc_qk, sc_v;                                   // E8M0 bytes (127 + exponent), replicated in all four bytes
     int nqb;
     int seg_nb[2];                                     // batch elements a segment holds (idmvton_attn_f8_shared); 0 = one per query batch from seg_b0 on
+    const int32_t* seg_ix[2];                          // idmvton_attn_f8_indexed: device table, query batch b reads element seg_ix[s][b - seg_b0[s]]; NULL = the seg_nb rule
 };
 
 #define NEG_BIG_F8 (-1.0e30f)
@@ -65,7 +66,7 @@ __global__ __launch_bounds__(256) void attn_f8_kernel(const AttnF8Params p) {
     const int nt0 = pres0 ? (p.nk[0] + 63) >> 6 : 0;
     const int nt1 = pres1 ? (p.nk[1] + 63) >> 6 : 0;
     const int nt = nt0 + nt1;
-    const int bsg0 = seg_batch(b, p.seg_b0[0], p.seg_nb[0]), bsg1 = seg_batch(b, p.seg_b0[1], p.seg_nb[1]);   // per workgroup, scalar
+    const int bsg0 = seg_batch_ix(b, p.seg_b0[0], p.seg_nb[0], p.seg_ix[0]), bsg1 = seg_batch_ix(b, p.seg_b0[1], p.seg_nb[1], p.seg_ix[1]);   // per workgroup, scalar
 
     f32x16 oacc[2];
 #pragma unroll
@@ -175,7 +176,8 @@ __global__ __launch_bounds__(256) void attn_f8_kernel(const AttnF8Params p) {
 
 // One implementation behind both entry points; seg_nb as in idmvton_attn_fwd_shared.  This kernel reads K / V^T through plain pointers, so the
 // seg_nb bound checked here is what keeps every read inside the caller's seg_nb-element tensors.
-static int attn_f8_impl(const idmvton_attn_f8_args* a, const int32_t* seg_nb, void* stream) {
+// seg_index as in idmvton_attn_fwd_indexed; with a table the kernel's clamp of its values to [0, seg_nb - 1] is that bound.
+static int attn_f8_impl(const idmvton_attn_f8_args* a, const int32_t* seg_nb, const int32_t* const* seg_index, void* stream) {
     CHECK_ARG(a != nullptr, IDMVTON_E_ARG, "attn_f8: null args");
     CHECK_ARG(a->out_dtype == IDMVTON_F16 || a->out_dtype == IDMVTON_BF16, IDMVTON_E_DTYPE, "attn_f8: out_dtype %d", a->out_dtype);
     CHECK_ARG(a->B > 0 && a->heads > 0 && a->Nq > 0 && a->nseg >= 1 && a->nseg <= 2, IDMVTON_E_SHAPE, "attn_f8: B=%d heads=%d Nq=%d nseg=%d", a->B, a->heads, a->Nq, a->nseg);
@@ -187,6 +189,12 @@ static int attn_f8_impl(const idmvton_attn_f8_args* a, const int32_t* seg_nb, vo
     for (int s = 0; s < 2; ++s) {
         const int ss = s < a->nseg ? s : 0;
         CHECK_ARG(a->k8[ss] && a->vt8[ss] && a->nk[ss] > 0 && a->seg_b0[ss] >= 0 && a->seg_b0[ss] <= a->B, IDMVTON_E_SHAPE, "attn_f8: seg %d", ss);
+        const int32_t* ix = seg_index ? seg_index[ss] : nullptr;
+        if (ix) {
+            CHECK_ARG(seg_nb[ss] >= 1 && a->seg_b0[ss] < a->B, IDMVTON_E_SHAPE,
+                      "attn_f8_indexed: seg %d has a table: needs seg_nb >= 1 (%d) and seg_b0 < B (%d, %d)", ss, seg_nb[ss], a->seg_b0[ss], a->B);
+            CHECK_ARG(((uintptr_t)ix & 3) == 0, IDMVTON_E_ALIGN, "attn_f8_indexed: seg %d table is not 4-byte aligned", ss);
+        } else
         CHECK_ARG(seg_nb[ss] >= 0 && seg_nb[ss] <= a->B - a->seg_b0[ss], IDMVTON_E_SHAPE,
                   "attn_f8_shared: seg %d seg_nb=%d outside [0, B - seg_b0 = %d]", ss, seg_nb[ss], a->B - a->seg_b0[ss]);
         const int krows = a->k_rows[ss] > 0 ? a->k_rows[ss] : a->nk[ss];
@@ -194,7 +202,7 @@ static int attn_f8_impl(const idmvton_attn_f8_args* a, const int32_t* seg_nb, vo
                   ((uintptr_t)a->k8[ss] & 15) == 0 && ((uintptr_t)a->vt8[ss] & 15) == 0, IDMVTON_E_ALIGN,
                   "attn_f8: seg %d ldk=%d ldvt=%d (V^T rows hold whole 64-key tiles: ldvt %% 64 == 0, ldvt >= roundup64(nk), zero-filled beyond nk)", ss, a->ldk[ss], a->ldvt[ss]);
         p.k[s] = (const uint8_t*)a->k8[ss]; p.ldk[s] = a->ldk[ss]; p.vt[s] = (const uint8_t*)a->vt8[ss]; p.ldvt[s] = a->ldvt[ss];
-        p.nk[s] = a->nk[ss]; p.krows[s] = krows; p.seg_b0[s] = a->seg_b0[ss]; p.seg_nb[s] = seg_nb[ss];
+        p.nk[s] = a->nk[ss]; p.krows[s] = krows; p.seg_b0[s] = a->seg_b0[ss]; p.seg_nb[s] = seg_nb[ss]; p.seg_ix[s] = ix;
     }
     auto rep = [](int e) { const int b = (127 + e) & 0xff; return b | (b << 8) | (b << 16) | (b << 24); };
     p.sc_qk = rep(a->qk_scale_exp);
@@ -209,12 +217,17 @@ static int attn_f8_impl(const idmvton_attn_f8_args* a, const int32_t* seg_nb, vo
 
 extern "C" int idmvton_attn_f8(const idmvton_attn_f8_args* a, void* stream) {
     static const int32_t none[2] = {0, 0};
-    return attn_f8_impl(a, none, stream);
+    return attn_f8_impl(a, none, nullptr, stream);
 }
 
 extern "C" int idmvton_attn_f8_shared(const idmvton_attn_f8_args* a, const int32_t seg_nb[2], void* stream) {
     CHECK_ARG(seg_nb != nullptr, IDMVTON_E_ARG, "attn_f8_shared: null seg_nb");
-    return attn_f8_impl(a, seg_nb, stream);
+    return attn_f8_impl(a, seg_nb, nullptr, stream);
+}
+
+extern "C" int idmvton_attn_f8_indexed(const idmvton_attn_f8_args* a, const int32_t seg_nb[2], const int32_t* const seg_index[2], void* stream) {
+    CHECK_ARG(seg_nb != nullptr && seg_index != nullptr, IDMVTON_E_ARG, "attn_f8_indexed: null seg_nb / seg_index");
+    return attn_f8_impl(a, seg_nb, seg_index, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -48,6 +48,15 @@ __device__ __forceinline__ int seg_batch(int b, int b0, int nb) {
     else if (nb > 1) d = (int)((unsigned)d % (unsigned)nb);
     return d;
 }
+// The same with an optional device table (the _indexed entry points): ix != nullptr -> element ix[b - b0] of the nb the segment holds, clamped to
+// [0, nb - 1] (for the fp8 kernel, which reads through plain pointers, this clamp is the only bound).  b, b0 and ix are workgroup-uniform, so
+// this is one scalar load per workgroup; a NULL table costs one scalar test and is seg_batch exactly.  Absent segments (b < b0) read no entry.
+__device__ __forceinline__ int seg_batch_ix(int b, int b0, int nb, const int32_t* ix) {
+    if (ix == nullptr || b < b0) return seg_batch(b, b0, nb);
+    int v = uniform(ix[b - b0]);
+    v = v < nb - 1 ? v : nb - 1;
+    return v > 0 ? v : 0;
+}
 
 // 16-byte LDS-DMA: every lane supplies a byte offset into the buffer `rs`; lane l's 16 bytes land at
 // lds_base + 16*l (lds_base must be wave-uniform).  Out-of-range offsets (>= num_records) read as zero.

@@ -13,7 +13,12 @@ tensors (tests/test_garment_cache_cpu.py).
 
 Two sizes: (h, w) is the PERSON latent size a cache is declared for -- what `check` holds a call to -- and (gh, gw) the garment's own latent
 size, which fixes N_f (feature f has feature_tokens(gh, gw)[f] real tokens in round16 rows).  The K / V^T depend on the second alone, so
-`for_person_size` re-declares a cache for another person size on the same tensors.  Size: with N1 / N2 the token rows at the two attention
+`for_person_size` re-declares a cache for another person size on the same tensors.
+
+A cache is also a POOL: with `garment_index` a call's person i wears garment garment_index[i] of the G (any P >= 1, values may repeat; the
+attention kernels read the slot from a device table), and `select` / `cat` / `put` / `to` / `save` / `load` are what a resident pool is built
+from -- `put` swaps one garment of a cache in place, so tensors, pointers and the engine's graph states stay valid.  GarmentPool keeps an LRU map
+key -> slot over one such cache.  Size: with N1 / N2 the token rows at the two attention
 levels of the SDXL topology (10 features of 640 channels, 60 of 1280), an entry is (10 * N1 * 640 + 60 * N2 * 1280) * 2 tensors * 2 bytes per
 garment and timestep (tests/test_garment_size_cpu.py).
 """
@@ -29,6 +34,23 @@ def timestep_run(kv, n, G, i0, c=1):
         r = k.shape[0] // n                              # K rows per timestep: G * N_f
         out.append((k[i0 * r:(i0 + c) * r], vt[i0 * G:(i0 + c) * G]))
     return out
+
+
+def slot_run(kv, n, G, i, g0, c=1):
+    """Views of garments g0 .. g0 + c - 1 of timestep entry i: timestep_run applied twice -- inside one timestep's views the G garments are
+    laid out as that rule lays out timesteps of one element each."""
+    return timestep_run(timestep_run(kv, n, G, i), G, 1, g0, c)
+
+
+def index_runs(ids):
+    """[3, 4, 5, 0, 1] -> [(0, 3, 3), (3, 0, 2)]: (destination slot, first source garment, count) of every run of consecutive garments."""
+    runs = []
+    for j, g in enumerate(ids):
+        if runs and runs[-1][1] + runs[-1][2] == g:
+            runs[-1] = (runs[-1][0], runs[-1][1], runs[-1][2] + 1)
+        else:
+            runs.append((j, g, 1))
+    return runs
 
 
 def alloc_kv(shapes, n, m, device):
@@ -81,9 +103,11 @@ class GarmentCache:
         garment serves e.g. 768x1024 and 1024x1536 calls; `check` stays strict, this is the explicit opt-in."""
         return self._like(h=h, w=w)
 
-    def check(self, *, timesteps, h, w, dtype, attn_fp8, f8_exp, weights_id, persons):
+    def check(self, *, timesteps, h, w, dtype, attn_fp8, f8_exp, weights_id, persons, garment_index=None):
         """The cache entry (timestep index) of every timestep of a call, looked up BY VALUE -- a cache built for n steps serves strength < 1
-        (the last int(n * strength) of the same timesteps).  ValueError naming the field on any mismatch."""
+        (the last int(n * strength) of the same timesteps).  ValueError naming the field on any mismatch.
+        garment_index (person i wears garment garment_index[i]): replaces the P % G rule by len == persons and 0 <= v < G, and the result is
+        the pair (cache entries, garment_index as a validated list of ints) -- what the engine needs of an indexed call."""
         if (int(h), int(w)) != (self.h, self.w):
             raise ValueError(f"GarmentCache resolution mismatch: built for latent (h, w) = ({self.h}, {self.w}), the call runs at ({h}, {w})")
         if dtype != self.dtype:
@@ -94,14 +118,31 @@ class GarmentCache:
             raise ValueError(f"GarmentCache f8_exp mismatch: built with exponents {self.f8_exp}, the engine uses {tuple(f8_exp)}")
         if weights_id != self.weights_id:
             raise ValueError(f"GarmentCache weights mismatch: built with weights {self.weights_id}, the engine holds {weights_id}")
-        if persons < 1 or persons % self.G:
+        ids = None
+        if garment_index is not None:
+            ids = self.garment_ids(garment_index, persons)
+        elif persons < 1 or persons % self.G:
             raise ValueError(f"GarmentCache persons mismatch: P = {persons} persons is not a multiple of G = {self.G} garments "
                              "(conditional row i reads garment i % G)")
         missing = [int(t) for t in timesteps if int(t) not in self._index]
         if missing:
             raise ValueError(f"GarmentCache timesteps mismatch: {missing} are not among the {len(self.timesteps)} cached timesteps "
                              f"{self.timesteps[:3]}..{self.timesteps[-1:]} (same scheduler and num_inference_steps as encode_garment?)")
-        return [self._index[int(t)] for t in timesteps]
+        entries = [self._index[int(t)] for t in timesteps]
+        return entries if ids is None else (entries, ids)
+
+    def garment_ids(self, garment_index, persons):
+        """garment_index as a list of `persons` ints in [0, G); ValueError naming the field otherwise."""
+        try:
+            ids = [int(v) for v in (garment_index.tolist() if isinstance(garment_index, torch.Tensor) else garment_index)]
+        except (TypeError, ValueError):
+            raise ValueError(f"GarmentCache garment_index mismatch: expected a sequence of {persons} ints, got {garment_index!r}") from None
+        if persons < 1 or len(ids) != persons:
+            raise ValueError(f"GarmentCache garment_index mismatch: {len(ids)} entries for P = {persons} persons (one garment per person)")
+        bad = [v for v in ids if not 0 <= v < self.G]
+        if bad:
+            raise ValueError(f"GarmentCache garment_index mismatch: {bad} outside [0, G = {self.G}) garments")
+        return ids
 
     def run(self, i0, c=1):
         """Views of the 70 (K, V^T) pairs of cache entries i0 .. i0 + c - 1 (what TryonNet's attn1 reads as its garment segment)."""
@@ -124,6 +165,211 @@ class GarmentCache:
             vv = vt.reshape(n, 1, G, *vt.shape[1:]).expand(n, times, G, *vt.shape[1:]).reshape(n * times * G, *vt.shape[1:]).contiguous()
             kv.append((kk, vv))
         return self._like(G=G * times, kv=kv)
+
+
+    # ---- the pool primitives --------------------------------------------------------------------------------------------
+    _FIELDS = ("timesteps", "h", "w", "gh", "gw", "dtype", "attn_fp8", "f8_exp", "weights_id")
+
+    def _agrees(self, other, what, devices=True):
+        """ValueError naming the first field in which `other` differs from this cache (G aside; devices=False: and where its tensors live)."""
+        for f in self._FIELDS:
+            if getattr(self, f) != getattr(other, f):
+                raise ValueError(f"GarmentCache {what}: {f} mismatch ({getattr(self, f)} against {getattr(other, f)})")
+        n = len(self.timesteps)
+        mine = [(k.shape[0] // (n * self.G),) + tuple(k.shape[1:]) + tuple(vt.shape[1:]) + (k.dtype, k.device.type if devices else None) for k, vt in self.kv]
+        theirs = [(k.shape[0] // (n * other.G),) + tuple(k.shape[1:]) + tuple(vt.shape[1:]) + (k.dtype, k.device.type if devices else None) for k, vt in other.kv]
+        if mine != theirs:
+            raise ValueError(f"GarmentCache {what}: kv mismatch (feature shapes, dtypes or devices differ)")
+
+    def _gather(self, sources):
+        """A new cache (a copy) whose garment j is garment g of cache c for (c, g) = sources[j]."""
+        n, U = len(self.timesteps), len(sources)
+        kv = alloc_kv(kv_shapes(timestep_run(self.kv, n, self.G, 0)), self.G, n * U, self.kv[0][0].device)
+        # consecutive garments of one source move as one run (index_runs, per stretch of one source)
+        runs, j = [], 0
+        while j < U:
+            e = j
+            while e < U and sources[e][0] is sources[j][0]:
+                e += 1
+            runs += [(j + d0, sources[j][0], g0, c) for d0, g0, c in index_runs([g for _, g in sources[j:e]])]
+            j = e
+        for i in range(n):
+            for j0, src, g0, c in runs:
+                for (dk, dv), (sk, sv) in zip(slot_run(kv, n, U, i, j0, c), slot_run(src.kv, n, src.G, i, g0, c)):
+                    dk.copy_(sk)
+                    dv.copy_(sv)
+        return self._like(G=U, kv=kv)
+
+    def select(self, ids):
+        """A new cache (a copy) of garments ids[0], ids[1], ... of this one, in that order; values may repeat."""
+        ids = self.garment_ids(ids, len(ids))
+        return self._gather([(self, g) for g in ids])
+
+    @staticmethod
+    def cat(caches):
+        """One cache of sum(G) garments (a copy) from caches that agree in every other field; ValueError naming the field otherwise."""
+        caches = list(caches)
+        if not caches:
+            raise ValueError("GarmentCache cat: no caches")
+        for c in caches[1:]:
+            caches[0]._agrees(c, "cat")
+        return caches[0]._gather([(c, g) for c in caches for g in range(c.G)])
+
+    def put(self, slot, other):
+        """Overwrite garment `slot` IN PLACE with the one garment of `other` (G = 1, every other field equal): the tensors, their pointers and
+        the engine's graph states stay valid -- how a resident pool swaps a garment.  `other` may live on another device (a garment spilled to
+        the host comes back without a temporary device copy).  Stream-ordered copies: calls already queued read the old garment, later ones
+        the new; only a pinned host source is copied asynchronously."""
+        if not 0 <= int(slot) < self.G:
+            raise ValueError(f"GarmentCache put: slot mismatch ({slot} outside [0, G = {self.G}))")
+        if other.G != 1:
+            raise ValueError(f"GarmentCache put: G mismatch (takes a cache of one garment, got G = {other.G})")
+        self._agrees(other, "put", devices=False)
+        n = len(self.timesteps)
+        for i in range(n):
+            for (dk, dv), (sk, sv) in zip(slot_run(self.kv, n, self.G, i, int(slot)), timestep_run(other.kv, n, 1, i)):
+                dk.copy_(sk, non_blocking=sk.is_cuda or sk.is_pinned())
+                dv.copy_(sv, non_blocking=sv.is_cuda or sv.is_pinned())
+        return self
+
+    def take(self, slot, device=None, pin_memory=False):
+        """A new G = 1 cache holding garment `slot` (a copy), on `device` (default: where the cache lives) -- copied slot view by slot view
+        straight into the destination (pin_memory: page-locked host tensors), with no intermediate copy on the source device.  Copies to the
+        host are complete when this returns."""
+        if not 0 <= int(slot) < self.G:
+            raise ValueError(f"GarmentCache take: slot mismatch ({slot} outside [0, G = {self.G}))")
+        n = len(self.timesteps)
+        device = self.kv[0][0].device if device is None else torch.device(device)
+        pin = bool(pin_memory) and device.type == "cpu"
+        kv = [(torch.empty((k.shape[0] // self.G,) + tuple(k.shape[1:]), dtype=k.dtype, device=device, pin_memory=pin),
+               torch.empty((vt.shape[0] // self.G,) + tuple(vt.shape[1:]), dtype=vt.dtype, device=device, pin_memory=pin)) for k, vt in self.kv]
+        for i in range(n):
+            for (dk, dv), (sk, sv) in zip(timestep_run(kv, n, 1, i), slot_run(self.kv, n, self.G, i, int(slot))):
+                dk.copy_(sk)
+                dv.copy_(sv)
+        return self._like(G=1, kv=kv)
+
+    def to(self, device, pin_memory=False):
+        """The same cache on another device (host offload and return): one copy per tensor; pin_memory: page-locked host tensors, so that
+        the way back is an asynchronous copy.  Copies TO the host are blocking -- the result is complete when this returns and may be read,
+        compared or saved at once; only pinned host -> device is queued asynchronously (stream-ordered before any later launch).  The same
+        device without pinning returns self."""
+        device = torch.device(device)
+        if not pin_memory and all(k.device == device for k, _ in self.kv):
+            return self
+
+        def move(t):
+            if pin_memory and device.type == "cpu":
+                out = torch.empty(t.shape, dtype=t.dtype, device="cpu", pin_memory=True)
+                out.copy_(t)
+                return out
+            return t.to(device, non_blocking=device.type != "cpu" and t.device.type == "cpu" and t.is_pinned())
+        return self._like(kv=[(move(k), move(vt)) for k, vt in self.kv])
+
+    FORMAT_VERSION = 1
+
+    def save(self, path):
+        """-> a safetensors file: tensors k.<f> / vt.<f> (e4m3 caches are uint8 bytes) and a metadata record (format version, G, timesteps, both
+        sizes, dtype, attn_fp8, f8_exp, weights_id)."""
+        import json
+        from safetensors.torch import save_file
+        tensors = {}
+        for f, (k, vt) in enumerate(self.kv):
+            tensors[f"k.{f:03d}"], tensors[f"vt.{f:03d}"] = k.detach().cpu().contiguous(), vt.detach().cpu().contiguous()
+        meta = dict(format="idmvton_garment_cache", version=self.FORMAT_VERSION, G=self.G, timesteps=self.timesteps, h=self.h, w=self.w, gh=self.gh,
+                    gw=self.gw, dtype=str(self.dtype), attn_fp8=self.attn_fp8, f8_exp=list(self.f8_exp), weights_id=self.weights_id, features=len(self.kv))
+        save_file(tensors, path, metadata={k: json.dumps(v) for k, v in meta.items()})
+
+    @staticmethod
+    def load(path, device="cpu"):
+        """The cache `save` wrote, on `device`.  What it was built for travels in the metadata, so `check` refuses it on any other engine with
+        the messages it has for a cache made in this process."""
+        import json
+        from safetensors import safe_open
+        with safe_open(path, framework="pt", device=str(device)) as f:
+            meta = {k: json.loads(v) for k, v in (f.metadata() or {}).items()}
+            if meta.get("format") != "idmvton_garment_cache" or meta.get("version") != GarmentCache.FORMAT_VERSION:
+                raise ValueError(f"GarmentCache load: {path} is not a garment cache of format version {GarmentCache.FORMAT_VERSION} "
+                                 f"(format={meta.get('format')!r}, version={meta.get('version')!r})")
+            kv = [(f.get_tensor(f"k.{i:03d}"), f.get_tensor(f"vt.{i:03d}")) for i in range(meta["features"])]
+        dtype = {str(d): d for d in (torch.float16, torch.bfloat16, torch.float32)}[meta["dtype"]]
+        return GarmentCache(G=meta["G"], timesteps=meta["timesteps"], h=meta["h"], w=meta["w"], gh=meta["gh"], gw=meta["gw"], dtype=dtype,
+                            attn_fp8=meta["attn_fp8"], f8_exp=meta["f8_exp"], weights_id=meta["weights_id"], kv=kv)
+
+
+class GarmentPool:
+    """A resident pool: one `capacity`-slot GarmentCache and an LRU map key -> slot.  `get(keys, encode)` returns the garment_index list of a
+    batch, after putting the garments the pool lacks into the least-recently-used slots that the batch does not itself need; evicted garments
+    optionally go to pinned host memory and come back from there instead of being encoded again: spill=True keeps EVERY garment ever evicted
+    (0.3-9.4 GB each at full size: unbounded), spill=<int> at most that many, dropping the one spilled longest ago; `drop(key)` frees one.
+    A slot's views are copied straight to and from the pinned tensors, with no temporary garment on the device.  Everything moves BEFORE the
+    call -- nothing is streamed during one -- and the pool's tensors never move, so an engine's graph states stay valid across swaps.
+        pool = GarmentPool(8, like=pipe.encode_garment(cloth=c0, ...))
+        out = pipe(cloth=pool.cache, garment_index=pool.get(["sku7", "sku7", "sku3"], encode=my_encode), ...)"""
+
+    def __init__(self, capacity, like, spill=False):
+        if like.G != 1:
+            raise ValueError(f"GarmentPool: `like` must hold one garment (G = {like.G})")
+        if capacity < 1:
+            raise ValueError(f"GarmentPool: capacity {capacity} < 1")
+        self.capacity, self.spill = int(capacity), bool(spill)
+        self.host_capacity = None if spill is True or not spill else int(spill)      # garments kept on the host; None: no bound
+        n = len(like.timesteps)
+        self.cache = like._like(G=self.capacity, kv=alloc_kv(kv_shapes(like.kv), 1, self.capacity, like.kv[0][0].device))
+        # alloc_kv scales the leading dimension of a list that holds n timesteps: [n * 1 ...] -> [n * capacity ...] is "capacity times as many"
+        assert all(vt.shape[0] == n * self.capacity for _, vt in self.cache.kv)
+        self._slot = {}                                      # key -> slot, in use order: the first key is the least recently used
+        self._free = list(range(self.capacity))
+        self.host = {}                                       # key -> spilled G = 1 cache in pinned host memory
+        self.stats = dict(hits=0, encoded=0, restored=0, evicted=0)
+
+    def __contains__(self, key):
+        return key in self._slot
+
+    def slots(self):
+        """{key: slot} of the resident garments, least recently used first."""
+        return dict(self._slot)
+
+    def get(self, keys, encode=None):
+        """-> the garment_index of a batch whose person i wears garment keys[i].  encode(key) -> a G = 1 GarmentCache like the pool's; it is
+        called once per distinct key that is neither resident nor spilled.  ValueError when the batch has more distinct garments than slots."""
+        keys = list(keys)
+        distinct = list(dict.fromkeys(keys))
+        if len(distinct) > self.capacity:
+            raise ValueError(f"GarmentPool: the batch names {len(distinct)} distinct garments, the pool has capacity {self.capacity}")
+        for key in distinct:
+            if key in self._slot:
+                self.stats["hits"] += 1
+                self._slot[key] = self._slot.pop(key)        # most recently used: to the end
+                continue
+            if key not in self.host and encode is None:      # before anything is evicted for it
+                raise KeyError(f"GarmentPool: {key!r} is not resident and no `encode` was given")
+            # the garment first: if encode raises (out of memory, say) no slot has left `_free` and nothing was evicted for it
+            restored = key in self.host
+            one = self.host[key] if restored else encode(key)
+            if self._free:
+                slot = self._free.pop(0)
+            else:                                            # the least recently used resident garment this batch does not name
+                victim = next(k for k in self._slot if k not in distinct)
+                slot = self._slot[victim]
+                if self.spill and victim not in self.host:
+                    self.host[victim] = self.cache.take(slot, "cpu", pin_memory=self.cache.kv[0][0].is_cuda)
+                    while self.host_capacity is not None and len(self.host) > self.host_capacity:
+                        del self.host[next(k for k in self.host if k != key)]      # spilled longest ago (never the one being restored)
+                del self._slot[victim]
+                self.stats["evicted"] += 1
+            try:
+                self.cache.put(slot, one)
+            except BaseException:
+                self._free.insert(0, slot)                   # the slot holds nothing valid, but it is not lost
+                raise
+            self._slot[key] = slot
+            self.stats["restored" if restored else "encoded"] += 1
+        return [self._slot[k] for k in keys]
+
+    def drop(self, key):
+        """Free the host copy of a spilled garment (a resident garment stays resident)."""
+        self.host.pop(key, None)
 
 
 def weights_fingerprint(named_tensors):

@@ -30,9 +30,15 @@ def _stream():
 PROFILE = None
 
 
-def _call(fn_name, args, flops=0.0, bytes_=0.0, seg_nb=None):
-    """seg_nb: the shared-segment attention entry points' extra argument (fn_name is then idmvton_attn_*_shared)."""
-    launch = (lambda: ffi.call(fn_name, args, _stream())) if seg_nb is None else (lambda: ffi.call_shared(fn_name, args, seg_nb, _stream()))
+def _call(fn_name, args, flops=0.0, bytes_=0.0, seg_nb=None, seg_index=None):
+    """seg_nb: the shared-segment attention entry points' extra argument (fn_name is then idmvton_attn_*_shared); seg_index: the indexed ones'
+    second extra argument, two device addresses (fn_name is then idmvton_attn_*_indexed)."""
+    if seg_index is not None:
+        launch = lambda: ffi.call_indexed(fn_name, args, seg_nb, seg_index, _stream())
+    elif seg_nb is not None:
+        launch = lambda: ffi.call_shared(fn_name, args, seg_nb, _stream())
+    else:
+        launch = lambda: ffi.call(fn_name, args, _stream())
     if PROFILE is None:
         launch()
         return
@@ -222,9 +228,11 @@ QSCALE = 0.125 * 1.4426950408889634          # softmax_scale(d=64) * log2(e): wh
 
 
 def attention(q, out, segs, heads, *, mode=ffi.ATTN_SELF, ip_scale=1.0, B=None, Nq=None, ldq=None, ldo=None, tune=0, q_prescaled=False):
-    """q/out: [B][Nq][>=heads*64] views; segs: list of dict(k=, vt=, nk=, ldk=, ldvt=, k_rows=, b0=[, nb=]).
+    """q/out: [B][Nq][>=heads*64] views; segs: list of dict(k=, vt=, nk=, ldk=, ldvt=, k_rows=, b0=[, nb=][, index=]).
     nb (absent or 0: one K / V^T element per query batch from b0 on): the segment holds nb elements and batch b reads (b - b0) % nb -- a shared
-    garment segment, launched through idmvton_attn_fwd_shared.  The tune-table key does not carry nb: same kernel choice as the materialised launch."""
+    garment segment, launched through idmvton_attn_fwd_shared.  index (with nb >= 1): an int32 device tensor of B - b0 entries, batch b reads
+    element index[b - b0] of the nb -- a pooled garment segment, launched through idmvton_attn_fwd_indexed.  The tune-table key carries neither
+    nb nor the index: same kernel choice as the materialised launch."""
     a = ffi.AttnArgs()
     a.dtype, a.mode = _dt(q), mode
     a.B = q.shape[0] if B is None else B
@@ -250,8 +258,9 @@ def attention(q, out, segs, heads, *, mode=ffi.ATTN_SELF, ip_scale=1.0, B=None, 
     fl = 0.0
     for s in segs:
         fl += 4.0 * (a.B - s.get("b0", 0)) * heads * a.Nq * s["nk"] * 64
-    nb = _seg_nb(segs)
-    _call("idmvton_attn_fwd_shared" if nb else "idmvton_attn_fwd", a, flops=fl, bytes_=2.0 * a.B * a.Nq * heads * 64 * q.element_size(), seg_nb=nb)
+    nb, ix = _seg_nb(segs), _seg_index(segs, a.B)
+    _call("idmvton_attn_fwd_indexed" if ix else "idmvton_attn_fwd_shared" if nb else "idmvton_attn_fwd", a, flops=fl,
+          bytes_=2.0 * a.B * a.Nq * heads * 64 * q.element_size(), seg_nb=nb or ([0, 0] if ix else None), seg_index=ix)
     return out
 
 
@@ -259,6 +268,21 @@ def _seg_nb(segs):
     """None when no segment is shared (the old entry point is called), else the two seg_nb values."""
     nb = [int(s.get("nb", 0) or 0) for s in segs] + [0] * (2 - len(segs))
     return nb if any(nb) else None
+
+
+def _seg_index(segs, B):
+    """None when no segment carries an index table (the other entry points are called), else the two device addresses (0 = no table)."""
+    ix = []
+    for s in segs:
+        t = s.get("index")
+        if t is not None:
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.numel() == B - s.get("b0", 0)):
+                raise ValueError(f"attention: a segment's index must be a contiguous int32 device tensor of B - b0 = {B - s.get('b0', 0)} entries")
+            if int(s.get("nb", 0) or 0) < 1:
+                raise ValueError("attention: a segment with index= needs nb= (the number of elements it holds)")
+        ix.append(0 if t is None else t.data_ptr())
+    ix += [0] * (2 - len(ix))
+    return ix if any(ix) else None
 
 
 def quant_f8(src, scale, mode=0, out=None):
@@ -276,8 +300,8 @@ def quant_f8(src, scale, mode=0, out=None):
 
 
 def attention_f8(q8, out, segs, heads, *, qk_scale_exp, v_scale_exp, B, Nq, ldq=None, ldo=None):
-    """fp8 self-attention (csrc/attention_f8.hip).  q8: uint8 [B*Nq][>= heads*64]; segs: list of dict(k8=, vt8=, nk=, ldk=, ldvt=, k_rows=, b0=[, nb=]);
-    nb as in attention() (idmvton_attn_f8_shared)."""
+    """fp8 self-attention (csrc/attention_f8.hip).  q8: uint8 [B*Nq][>= heads*64]; segs: list of dict(k8=, vt8=, nk=, ldk=, ldvt=, k_rows=, b0=[, nb=][, index=]);
+    nb / index as in attention() (idmvton_attn_f8_shared / idmvton_attn_f8_indexed)."""
     a = ffi.AttnF8Args()
     a.out_dtype, a.B, a.heads, a.Nq = _dt(out), B, heads, Nq
     a.q8, a.ldq = _ptr(q8), (q8.stride(-2) if ldq is None else ldq)
@@ -290,8 +314,9 @@ def attention_f8(q8, out, segs, heads, *, qk_scale_exp, v_scale_exp, B, Nq, ldq=
         a.nk[i], a.k_rows[i], a.seg_b0[i] = s["nk"], s.get("k_rows", 0), s.get("b0", 0)
         fl += 4.0 * (B - s.get("b0", 0)) * heads * Nq * s["nk"] * 64
     a.qk_scale_exp, a.v_scale_exp = qk_scale_exp, v_scale_exp
-    nb = _seg_nb(segs)
-    _call("idmvton_attn_f8_shared" if nb else "idmvton_attn_f8", a, flops=fl, bytes_=float(B * Nq * heads * 64 * (1 + out.element_size())), seg_nb=nb)
+    nb, ix = _seg_nb(segs), _seg_index(segs, B)
+    _call("idmvton_attn_f8_indexed" if ix else "idmvton_attn_f8_shared" if nb else "idmvton_attn_f8", a, flops=fl,
+          bytes_=float(B * Nq * heads * 64 * (1 + out.element_size())), seg_nb=nb or ([0, 0] if ix else None), seg_index=ix)
     return out
 
 

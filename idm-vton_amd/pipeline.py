@@ -17,7 +17,9 @@ shorter than the TryonNet steps of the block before it.  Every batch runs at its
 
 The same fact across calls: `encode_garment` runs the garment side alone (cloth VAE encode, GarmentNet batches in the same block schedule,
 the K / V^T projections) and returns a GarmentCache; `prepare(cloth=<GarmentCache>)` then builds a call with no garment work at all, for
-P persons on G cached garments (P % G == 0; the attention kernels read garment i % G for person i through a shared key segment).
+P persons on G cached garments (P % G == 0; the attention kernels read garment i % G for person i through a shared key segment) -- or, with
+`garment_index=[...]`, for any P >= 1 persons of whom person i wears garment garment_index[i] of the cache (the kernels read the garment's
+slot from a device table: an indexed key segment).
 
 Structure of the loop.  The block order -- serial, or two streams with two alternating sets and two events per set -- is written once,
 in `drive_blocks`, which knows nothing of graphs or caches (tests/test_loop_schedule_cpu.py checks its waits on stand-in streams).  An
@@ -28,6 +30,8 @@ execution form is the pair of callables it hands over:
     eager, cache   nothing to launch                                 _tryon_main on the cache's own views of entry gidx[i]
     graph, live    copy temb_gk[bi], replay ('garm', p, c)           copy tt / cf / nz, replay ('tryon', p, j)
     graph, cache   _fill_set: the block's cache entries -> set p     as graph, live
+With garment_index the two cache rows read through the table: eager on the cache's own views (nb = G, table = garment_index), graph on
+P-slot sets into which _fill_set gathers the U distinct garments of the call (table = person -> set slot, a persistent buffer of the state).
 
 `denoise` asks once whether the call is live or on a cache, wraps the step in the per-step hooks (`trace`, `on_step`) and drives the
 blocks.  The K / V^T layout of sets and cache (timestep-major) has one owner, garment_cache.timestep_run.
@@ -35,7 +39,7 @@ blocks.  The K / V^T layout of sets and cache (timestep-major) has one owner, ga
 import torch
 
 from . import ops
-from .garment_cache import GarmentCache, alloc_kv, kv_shapes, timestep_run
+from .garment_cache import GarmentCache, alloc_kv, index_runs, kv_shapes, slot_run, timestep_run
 from .scheduler import StepScheduler
 
 
@@ -72,8 +76,8 @@ def drive_blocks(blocks, garment, tryon, main=None, side=None, ready=None, free=
 def _copy_state(G, st):
     """A new call's tensors -> the persistent buffers of a graph state, for every tensor the state owns and a captured graph reads (a
     GarmentCache state has no garment-side tensors)."""
-    for name in ("latents", "cond", "cloth_k"):
-        if name in G:
+    for name in ("latents", "cond", "cloth_k", "gix"):
+        if G.get(name) is not None:
             G[name].copy_(st[name])
     for name in ("ctx_t", "ctx_gk"):
         if name in G:
@@ -158,8 +162,12 @@ class TryonEngine:
     @staticmethod
     def _graph_key(st, live):
         """One persistent graph state per shape of a call: persons, person latent size, garment latent size, block size, step noise, and on a
-        GarmentCache its garment count."""
-        return (st["B"], st["h"], st["w"], st["gh"], st["gw"], st["k"], st["steps_noise"] is not None) + (() if live else ("cached", st["gcache"].G))
+        GarmentCache its garment count -- or, with garment_index, nothing more: the sets of an indexed state have one slot per PERSON, so one
+        state serves every pool size and every assignment."""
+        if live:
+            return (st["B"], st["h"], st["w"], st["gh"], st["gw"], st["k"], st["steps_noise"] is not None)
+        return (st["B"], st["h"], st["w"], st["gh"], st["gw"], st["k"], st["steps_noise"] is not None, "cached",
+                "indexed" if st.get("gindex") is not None else st["gcache"].G)
 
     def weights_identity(self):
         """What a GarmentCache depends on besides its inputs: every GarmentNet weight, and TryonNet's attn1.to_k / to_v (the projections of
@@ -213,7 +221,7 @@ class TryonEngine:
     def prepare(self, *, image, mask_image, pose_img, cloth, prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds,
                 negative_pooled_prompt_embeds, text_embeds_cloth, noise, num_inference_steps, guidance_scale,
                 ip_hidden_states=None, image_embeds=None, scheduler="ddpm", height=None, width=None, strength=1.0,
-                image_dtype=None):
+                image_dtype=None, garment_index=None):
         """Everything before the loop (tryon_pipeline.py:1495-1762).  image in [0,1]; pose_img / cloth in [-1,1];
         noise: dict(latents, masked, pose [B,4,h,w] fp32; cloth [B,4,gh,gw] fp32; steps [n,B,4,h,w] fp32 or None; image [B,4,h,w] when
         strength < 1) -- RNG order SURVEY A.4.
@@ -226,14 +234,21 @@ class TryonEngine:
         ip_hidden_states / image_embeds may hold the B conditional rows only.
         cloth = a GarmentCache (encode_garment) of G garments: no garment work in this call -- no cloth encode, no GarmentNet inputs;
         text_embeds_cloth and noise['cloth'] may be None.  B = image.shape[0] persons, B % G == 0, person i wears garment i % G.  A cache
-        that does not cover the call (timestep, resolution, dtype mode, weights, B % G) raises ValueError before anything is launched."""
+        that does not cover the call (timestep, resolution, dtype mode, weights, B % G) raises ValueError before anything is launched.
+        garment_index (with a GarmentCache only): B ints in [0, G), person i wears garment garment_index[i] -- any B >= 1, values may repeat,
+        no B % G rule; the cache is a pool, and G may exceed B."""
         dev, dt = self.device, self.dtype
         f32 = lambda t: t.to(dev, torch.float32).contiguous()
         gcache = cloth if isinstance(cloth, GarmentCache) else None
+        if garment_index is not None and gcache is None:
+            raise ValueError("garment_index names garments of a GarmentCache: pass one as `cloth=` (a live call encodes one garment per person)")
+        gindex = None
         if gcache is not None:
             gidx = gcache.check(timesteps=self._timesteps(scheduler, num_inference_steps, strength)[1],
                                 h=(height or image.shape[-2]) // 8, w=(width or image.shape[-1]) // 8, dtype=dt, attn_fp8=self.unet.attn_fp8,
-                                f8_exp=self.unet.f8_exp, weights_id=self.weights_identity(), persons=image.shape[0])
+                                f8_exp=self.unet.f8_exp, weights_id=self.weights_identity(), persons=image.shape[0], garment_index=garment_index)
+            if garment_index is not None:
+                gidx, gindex = gidx
         image, mask_image, pose_img = f32(image), f32(mask_image), f32(pose_img)
         cloth = f32(cloth) if gcache is None else None
         B = image.shape[0]
@@ -297,11 +312,14 @@ class TryonEngine:
         temb_t = self.unet.time_embeddings(timesteps, 2 * B, dict(text_embeds=add_text, time_ids=time_ids))
         if gcache is None:
             # GarmentNet over consecutive timesteps per batch, blocks of 1, 2, 4, k, k, ... timesteps
-            garm = dict(self._garment_inputs(cloth_lat, text_embeds_cloth, timesteps, B), gcache=None, gidx=None, garment_persons=None)
+            garm = dict(self._garment_inputs(cloth_lat, text_embeds_cloth, timesteps, B), gcache=None, gidx=None, garment_persons=None,
+                        gindex=None, gix=None)
         else:                                                # the same blocks drive the loop; their garment side is a read of the cache
             k, blocks = self._block_schedule(len(timesteps))
             garm = dict(cloth=None, ctx_g=None, temb_g=None, k=k, blocks=blocks, temb_gk=None, cloth_k=None, ctx_gk=None,
-                        gcache=gcache, gidx=gidx, garment_persons=B)
+                        gcache=gcache, gidx=gidx, garment_persons=B, gindex=gindex,
+                        # the table the kernels read: person -> garment of the cache (a graph state keeps its own: person -> set slot)
+                        gix=torch.tensor(gindex, dtype=torch.int32, device=dev) if gindex is not None else None)
         coef = torch.tensor([list(sched.coeffs(t)) + [guidance_scale] for t in timesteps], dtype=torch.float32, device=dev)
         steps_noise = f32(noise["steps"]) if noise.get("steps") is not None and scheduler == "ddpm" else None
         return dict(B=B, h=h, w=w, gh=gh, gw=gw, timesteps=timesteps, latents=latents.contiguous(), cond=cond,
@@ -326,7 +344,7 @@ class TryonEngine:
         # garment_persons: None = one garment entry per conditional batch (unet.forward's default); B on a GarmentCache call, where kv_j
         # holds G garments for the B persons (a shared segment when G < B)
         eps, _ = self.unet.forward(st["x_in"], temb_t, st["ctx_t"], 2 * B, h, w, garment_kv=kv_j, garment_persons=st["garment_persons"],
-                                   garment_hw=(st["gh"], st["gw"]))                        # :1796-1808
+                                   garment_hw=(st["gh"], st["gw"]), garment_index=st.get("gix"))   # :1796-1808
         ops.cfg_step(eps, st["latents"], noise, coef)                                      # :1814-1823
         return eps
 
@@ -356,14 +374,34 @@ class TryonEngine:
 
     def _fill_set(self, st, fset, s0, c):
         """Steps s0 .. s0 + c - 1 of the call: their cached K / V^T -> the first c timestep slots of a persistent set (current stream).  The
-        call's timesteps are consecutive cache entries unless the scheduler says otherwise: one copy per tensor then, else one per timestep."""
+        call's timesteps are consecutive cache entries unless the scheduler says otherwise: one copy per tensor then, else one per timestep.
+        With garment_index: the U distinct garments the call uses, in first-use order, -> slots 0 .. U - 1 of each timestep slot of a P-slot
+        set (the state's table maps persons to those slots; no slot beyond U is ever indexed): per timestep one copy per tensor and run of
+        consecutive garments, so the bytes moved scale with what the call uses, not with the pool."""
         gc, idx = st["gcache"], st["gidx"][s0:s0 + c]
         self.stats["garment_set_copies"] += 1
+        if st["gindex"] is not None:
+            n, P = len(gc.timesteps), st["B"]
+            runs = index_runs(list(dict.fromkeys(st["gindex"])))
+            for j, i in enumerate(idx):
+                for d0, g0, cc in runs:
+                    for (dk, dv), (sk, sv) in zip(slot_run(fset["kv"], st["k"], P, j, d0, cc), slot_run(gc.kv, n, gc.G, i, g0, cc)):
+                        dk.copy_(sk)
+                        dv.copy_(sv)
+            return
         runs = [(0, idx[0], c)] if idx == list(range(idx[0], idx[0] + c)) else [(j, i, 1) for j, i in enumerate(idx)]
         for j0, i0, cc in runs:
             for (dk, dv), (sk, sv) in zip(timestep_run(fset["kv"], st["k"], gc.G, j0, cc), gc.run(i0, cc)):
                 dk.copy_(sk)
                 dv.copy_(sv)
+
+    def _slot_table(self, st):
+        """Graph forms with garment_index: person -> slot of the persistent sets, where _fill_set puts the call's distinct garments in
+        first-use order ([7, 7, 3, 9] -> [0, 0, 1, 2]); None without an index."""
+        if st["gindex"] is None:
+            return None
+        slot = {g: u for u, g in enumerate(dict.fromkeys(st["gindex"]))}
+        return torch.tensor([slot[g] for g in st["gindex"]], dtype=torch.int32, device=self.device)
 
     def _noise(self, st, i):
         return st["steps_noise"][i] if st["steps_noise"] is not None else None
@@ -405,6 +443,8 @@ class TryonEngine:
         if key in self._graphs:
             return self._graphs[key]
         G = {name: st[name] for name in ("B", "h", "w", "gh", "gw", "k", "garment_persons", "latents", "cond", "x_in", "ctx_t")}
+        # indexed: the table person -> set slot, a persistent buffer whose pointer the captured graphs hold; its contents are copied per call
+        G["gix"] = self._slot_table(st)
         G.update(tt=st["temb_t"][0].clone(), cf=st["coef"][0].clone(), nz=st["steps_noise"][0].clone() if has_noise else None, graphs={},
                  side=torch.cuda.Stream(), ready=[torch.cuda.Event(), torch.cuda.Event()], free=[torch.cuda.Event(), torch.cuda.Event()],
                  # graphs that replay one after another on ONE stream may share a memory pool: all TryonNet graphs (main stream), all
@@ -420,7 +460,12 @@ class TryonEngine:
                 self._garment_side(G, G["tgk"], G["sets"][0])
             else:                                            # the first block's fill stands in for a warm-up batch
                 gc = st["gcache"]
-                G["sets"] = [self._alloc_set((), kv_shapes(gc.kv), len(gc.timesteps), st["k"], gc.G) for _ in range(2)]
+                if st["gindex"] is None:
+                    slots, shapes = gc.G, kv_shapes(gc.kv)
+                else:                                        # one slot per person, whatever the pool holds
+                    slots = st["B"]
+                    shapes = [((a[0] // gc.G * slots,) + a[1:], (b[0] // gc.G * slots,) + b[1:], d) for a, b, d in kv_shapes(gc.kv)]
+                G["sets"] = [self._alloc_set((), shapes, len(gc.timesteps), st["k"], slots) for _ in range(2)]
                 self._fill_set(st, G["sets"][0], *st["blocks"][0])
             self._tryon_main(G, G["tt"], G["cf"], G["nz"], G["sets"][0]["step"][0])
         torch.cuda.current_stream().wait_stream(warm)
@@ -449,7 +494,7 @@ class TryonEngine:
     def _graph_form(self, st, live, overlap):
         G = self._graph_state(st, live)
         if G["latents"] is not st["latents"]:
-            _copy_state(G, st)                                                             # new call -> persistent buffers
+            _copy_state(G, dict(st, gix=self._slot_table(st)))                             # new call -> persistent buffers
         blocks, graphs = st["blocks"], G["graphs"]
         # capture everything this call needs before the loop (a capture must not interleave with work in flight on the side stream)
         for p in ((0, 1) if overlap and len(blocks) > 1 else (0,)):

@@ -288,9 +288,12 @@ class HipUNet:
                 ops.linear(g.reshape(Bg * Ng, C), blk["qkv"][C:], out=kg, vt=vtg, vt_n0=C, vt_tokens=Ng,
                            **(dict(f8=(2.0 ** ek, 2.0 ** ev)) if f8g else {}))
             garment["idx"] += 1
-            P = garment.get("persons") or Bg                    # conditional batches (GarmentCache calls: P persons, Bg = G garments)
+            gix = garment.get("index")
+            P = gix.numel() if gix is not None else garment.get("persons") or Bg   # conditional batches (GarmentCache calls: P persons, Bg = G garments)
             gseg = dict(k=kg, vt=vtg, nk=gnk, ldk=C, ldvt=Ng, k_rows=Ng, b0=B - P)
-            if Bg < P:                                           # a shared segment: conditional row i reads garment i % G
+            if gix is not None:                                  # a pooled segment: conditional row i reads garment index[i] of the Bg, whatever Bg is to P
+                gseg.update(nb=Bg, index=gix)
+            elif Bg < P:                                         # a shared segment: conditional row i reads garment i % G
                 gseg["nb"] = Bg
             segs.append(gseg)
         att = torch.empty(M, C, dtype=dt, device=dev)
@@ -299,11 +302,12 @@ class HipUNet:
             for sg in segs:                                      # each segment with its own token rows: e4m3 from its projection, or quantised here
                 Bs, Ns = sg["vt"].shape[0], sg["k_rows"]
                 if sg["k"].dtype == torch.uint8:                                            # written as e4m3 by its projection
-                    segs8.append(dict(k8=sg["k"], vt8=sg["vt"], nk=sg["nk"], ldk=sg["ldk"], ldvt=sg["ldvt"], k_rows=Ns, b0=sg.get("b0", 0), nb=sg.get("nb", 0)))
+                    segs8.append(dict(k8=sg["k"], vt8=sg["vt"], nk=sg["nk"], ldk=sg["ldk"], ldvt=sg["ldvt"], k_rows=Ns, b0=sg.get("b0", 0), nb=sg.get("nb", 0),
+                                      index=sg.get("index")))
                     continue
                 k8 = ops.quant_f8(sg["k"], 2.0 ** ek)                                   # [Bs*Ns][C] (row stride ldk)
                 vt8 = ops.quant_f8(sg["vt"].reshape(Bs * C, Ns), 2.0 ** ev, mode=1)     # 16-bit key order -> fp8 slot order
-                segs8.append(dict(k8=k8, vt8=vt8, nk=sg["nk"], ldk=C, ldvt=vt8.shape[1], k_rows=Ns, b0=sg.get("b0", 0), nb=sg.get("nb", 0)))
+                segs8.append(dict(k8=k8, vt8=vt8, nk=sg["nk"], ldk=C, ldvt=vt8.shape[1], k_rows=Ns, b0=sg.get("b0", 0), nb=sg.get("nb", 0), index=sg.get("index")))
             if f8:
                 q8, ldq8 = qk, 2 * C
             else:
@@ -409,7 +413,8 @@ class HipUNet:
         return ids[key]
 
     # ------------------------------------------------------------------------------------------------ forward
-    def forward(self, x, temb, ctx, B, H, W, garment_feats=None, garment_kv=None, feats_buf=None, garment_persons=None, garment_hw=None):
+    def forward(self, x, temb, ctx, B, H, W, garment_feats=None, garment_kv=None, feats_buf=None, garment_persons=None, garment_hw=None,
+                garment_index=None):
         """x: NHWC [B][H*W][cin_pad] (channels >= in_channels zero); temb: [B][sum Cout] (time_embeddings()[step]);
         ctx: encode_context(); garment_feats: list of [Bg][Ng][C] (Bg <= B; batches < B-Bg see all-zero features).
         garment_hw = the garment's own latent (gh, gw) when it is not (H, W): its features have feature_tokens(gh, gw) real tokens per level
@@ -417,9 +422,12 @@ class HipUNet:
         (reference-shaped features of a garment of another size).
         garment_persons = P (with garment_kv of G = Bg garments, P % G == 0): the last P batches are conditional and row i of them reads garment
         i % G through a shared attention segment (GarmentCache calls); None: P = Bg, one garment entry per conditional batch.
+        garment_index = an int32 device tensor of P entries (with garment_kv or garment_feats of any Bg >= 1 garments): the last P batches are
+        conditional and row i of them reads garment garment_index[i] through an indexed attention segment -- no relation between Bg and P, and
+        the table is read by the kernels, so a captured forward follows its contents.
         Returns (noise NHWC [B][H*W][n_out] for TryonNet | None, exported features for GarmentNet)."""
         topo = self.topo
-        garment = dict(feats=garment_feats, kv=garment_kv, feats_buf=feats_buf, idx=0, persons=garment_persons,
+        garment = dict(feats=garment_feats, kv=garment_kv, feats_buf=feats_buf, idx=0, persons=garment_persons, index=garment_index,
                        nk=self.feature_tokens(*garment_hw) if garment_hw is not None and self.tryon else None)
         feats = []
         stop = None if self.tryon else self.num_features()

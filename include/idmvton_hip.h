@@ -182,6 +182,12 @@ int idmvton_attn_fwd(const idmvton_attn_args* a, void* stream);
  * one copy per person.  seg_nb[s] == 0 is idmvton_attn_fwd's rule (B - seg_b0[s] elements, no wrap); idmvton_attn_fwd IS this call with {0, 0}.
  * Which batches skip a segment (b < seg_b0[s]) does not change.  Needs 0 <= seg_nb[s] <= B - seg_b0[s]; mode CROSS takes {0, 0} only. */
 int idmvton_attn_fwd_shared(const idmvton_attn_args* a, const int32_t seg_nb[2], void* stream);
+/* The same launch with an INDEXED key segment: seg_index[s] is NULL or a device pointer to B - seg_b0[s] int32 values, and query batch
+ * b >= seg_b0[s] reads element seg_index[s][b - seg_b0[s]] of the seg_nb[s] elements the segment holds -- any person of a batch reads any slot
+ * of a resident pool of garments.  The table is read when the kernel runs (one scalar load per workgroup), so a captured graph holds its
+ * pointer, not its values; values are clamped to [0, seg_nb[s] - 1] in the kernel.  A NULL table is idmvton_attn_fwd_shared's rule exactly;
+ * a non-NULL one needs seg_nb[s] >= 1 and seg_b0[s] < B, and seg_nb[s] may exceed B - seg_b0[s].  Mode CROSS takes no table. */
+int idmvton_attn_fwd_indexed(const idmvton_attn_args* a, const int32_t seg_nb[2], const int32_t* const seg_index[2], void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * idmvton_attn_f8 / idmvton_quant_f8 : the fp8 (OCP e4m3) variant of the self-attention above, on the block-scaled MFMA
@@ -210,6 +216,8 @@ typedef struct {
 } idmvton_attn_f8_args;
 int idmvton_attn_f8(const idmvton_attn_f8_args* a, void* stream);
 int idmvton_attn_f8_shared(const idmvton_attn_f8_args* a, const int32_t seg_nb[2], void* stream);   /* seg_nb: as idmvton_attn_fwd_shared */
+/* seg_nb / seg_index: as idmvton_attn_fwd_indexed.  This kernel reads through plain pointers: the clamp of the table's values is its bound. */
+int idmvton_attn_f8_indexed(const idmvton_attn_f8_args* a, const int32_t seg_nb[2], const int32_t* const seg_index[2], void* stream);
 typedef struct {
     int32_t dtype; int32_t mode; int32_t rows, cols;
     const void* src; int32_t lds;
