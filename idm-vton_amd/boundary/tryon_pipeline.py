@@ -372,6 +372,14 @@ class StableDiffusionXLInpaintPipeline:
         return eng.encode_garment(cloth=clo, text_embeds_cloth=text_embeds_cloth, noise_cloth=n_cloth, num_inference_steps=num_inference_steps,
                                   scheduler=self._scheduler_kind(), strength=strength, height=height, width=width)
 
+    def empty_garment_cache(self, garments, garment_height, garment_width, num_inference_steps, height=None, width=None, strength=1.0):
+        """A GarmentCache of `garments` uninitialised slots for garments of up to garment_height x garment_width, for `put` to fill with
+        encode_garment()'s results of that or any smaller size (GarmentPool(capacity, like=<this with garments=1>, mixed_sizes=True) does it
+        by key): one call -- `cloth=<the cache>, garment_index=[...]` -- then serves persons wearing garments of different sizes.  Same
+        scheduler, num_inference_steps, height and width as the calls it is for; nothing is encoded and no random number is drawn."""
+        return self.hip_engine().empty_garment_cache(garments, garment_height, garment_width, num_inference_steps, scheduler=self._scheduler_kind(),
+                                                     strength=strength, height=height, width=width)
+
     # ------------------------------------------------------------------------------------------ the call
     @torch.no_grad()
     def __call__(self, prompt=None, prompt_2=None, image=None, mask_image=None, masked_image_latents=None, height=None,

@@ -33,6 +33,7 @@ struct AttnParams {
     int q_prescaled;
     int seg_nb[2];                                      // batch elements a segment holds (idmvton_attn_fwd_shared); 0 = one per query batch from seg_b0 on
     const int32_t* seg_ix[2];                           // idmvton_attn_fwd_indexed: device table, query batch b reads element seg_ix[s][b - seg_b0[s]]; NULL = the seg_nb rule
+    const int32_t* seg_nkt[2];                          // idmvton_attn_fwd_ragged: device table of B key counts, query batch b has seg_nkt[s][b] keys of segment s; NULL = nk[s]
 };
 
 #define NEG_BIG (-1.0e30f)
@@ -160,8 +161,9 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_kernel(const AttnParams p) {
     // ---- which segments exist for this batch element (block-uniform) ----
     const bool pres0 = p.nseg > 0 && b >= p.seg_b0[0];
     const bool pres1 = p.nseg > 1 && b >= p.seg_b0[1];
-    const int nt0 = pres0 ? (p.nk[0] + 63) >> 6 : 0;
-    const int nt1 = pres1 ? (p.nk[1] + 63) >> 6 : 0;
+    const int nk0 = seg_keys(b, p.nk[0], p.seg_nkt[0]), nk1 = seg_keys(b, p.nk[1], p.seg_nkt[1]);   // this batch's key counts: per workgroup, scalar
+    const int nt0 = pres0 ? (nk0 + 63) >> 6 : 0;
+    const int nt1 = pres1 ? (nk1 + 63) >> 6 : 0;
     const int nt = nt0 + nt1;
     const int bsg0 = seg_batch_ix(b, p.seg_b0[0], p.seg_nb[0], p.seg_ix[0]), bsg1 = seg_batch_ix(b, p.seg_b0[1], p.seg_nb[1], p.seg_ix[1]);   // per workgroup, scalar
 
@@ -170,7 +172,7 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_kernel(const AttnParams p) {
     auto issue = [&](int t, char* tile) {
         const int sg = t < nt0 ? 0 : 1;
         const int kt = sg ? t - nt0 : t;
-        const int nk = p.nk[sg];
+        const int nk = sg ? nk1 : nk0;
         const int bsg = sg ? bsg1 : bsg0;
         char* dst = tile + wave * (IPW * 1024);
 #pragma unroll
@@ -213,8 +215,8 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_kernel(const AttnParams p) {
     if (MODE == IDMVTON_ATTN_SELF) {
         // closed form for absent (all-zero) segments: nk keys with logit 0, value 0
         int nz = 0;
-        if (p.nseg > 0 && !pres0) nz += p.nk[0];
-        if (p.nseg > 1 && !pres1) nz += p.nk[1];
+        if (p.nseg > 0 && !pres0) nz += nk0;
+        if (p.nseg > 1 && !pres1) nz += nk1;
         if (nz > 0) { m_run = 0.f; l_run = u == 0 ? (float)nz : 0.f; }
     }
 
@@ -257,7 +259,7 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_kernel(const AttnParams p) {
         const char* buf = sbuf + sub * 16384;
         const int sg = t < nt0 ? 0 : 1;
         const int kt = sg ? t - nt0 : t;
-        const int valid = p.nk[sg] - kt * 64;            // keys of this tile that exist (>= 64: all)
+        const int valid = (sg ? nk1 : nk0) - kt * 64;    // keys of this tile that exist (>= 64: all)
 
         // ---- S^T = K . Q^T ----
         f32x16 sacc[2];
@@ -414,8 +416,9 @@ __global__ __launch_bounds__(512, DEEP ? 2 : 4) void attn_pp_kernel(const AttnPa
     }
     const bool pres0 = p.nseg > 0 && b >= p.seg_b0[0];
     const bool pres1 = p.nseg > 1 && b >= p.seg_b0[1];
-    const int nt0 = pres0 ? (p.nk[0] + 63) >> 6 : 0;
-    const int nt1 = pres1 ? (p.nk[1] + 63) >> 6 : 0;
+    const int nk0 = seg_keys(b, p.nk[0], p.seg_nkt[0]), nk1 = seg_keys(b, p.nk[1], p.seg_nkt[1]);   // this batch's key counts: per workgroup, scalar
+    const int nt0 = pres0 ? (nk0 + 63) >> 6 : 0;
+    const int nt1 = pres1 ? (nk1 + 63) >> 6 : 0;
     const int nt = nt0 + nt1;
 
     // ---- loader: stage s = K(s) (DMA instructions j = 0..7: waves 0-3) | V^T(s-1) (j = 8..15: waves 4-7).  A wave loads
@@ -423,8 +426,8 @@ __global__ __launch_bounds__(512, DEEP ? 2 : 4) void attn_pp_kernel(const AttnPa
     // constants here and the in-loop issue is branch-free: offset = rowbase[seg][i] + kt * tstep[seg]; a chunk is fetched iff
     // its smallest key index lim[i] + 64 kt exists (< nk[seg]); everything else (tiles -1 and nt, key tails) reads zeros.
     const int lrow = lane >> 3, lslot = lane & 7;
-    const int nk0 = p.nk[0], nk1 = p.nk[1];             // in SGPRs: indexing p.nk[] by a loop value makes hipcc re-load it from the
-    const bool is_k = wave < 4;                          // kernarg segment (s_load + lgkmcnt(0)) in every phase
+    const bool is_k = wave < 4;                          // (nk0 / nk1 are locals, in SGPRs: indexing p.nk[] by a loop value makes hipcc re-load it
+                                                         // from the kernarg segment -- s_load + lgkmcnt(0) -- in every phase)
     const int t_shift = is_k ? 0 : 1;                    // this wave's tile of stage s is s - t_shift
     uint32_t rowbase[2][IPW], tstep[2];
     int lim0 = 0;                                        // lim of instruction 0; instruction 1's is lim0 ^ lim_x (one register less)
@@ -497,8 +500,8 @@ __global__ __launch_bounds__(512, DEEP ? 2 : 4) void attn_pp_kernel(const AttnPa
     float thr_cur = -3.0e38f, floor_cur = -3.0e38f;      // first tile: the branch below is always taken and delta = the row max
     {
         int nz = 0;
-        if (p.nseg > 0 && !pres0) nz += p.nk[0];
-        if (p.nseg > 1 && !pres1) nz += p.nk[1];
+        if (p.nseg > 0 && !pres0) nz += nk0;
+        if (p.nseg > 1 && !pres1) nz += nk1;
         if (nz > 0) {
             l_run = u == 0 ? (float)nz : 0.f; thr_cur = thr; floor_cur = 0.f;
             if constexpr (LSUM) {
@@ -733,13 +736,13 @@ __global__ __launch_bounds__(512, 2) void attn_pf_kernel(const AttnParams p) {
     }
     const bool pres0 = p.nseg > 0 && b >= p.seg_b0[0];
     const bool pres1 = p.nseg > 1 && b >= p.seg_b0[1];
-    const int nt0 = pres0 ? (p.nk[0] + 63) >> 6 : 0;
-    const int nt1 = pres1 ? (p.nk[1] + 63) >> 6 : 0;
+    const int nk0 = seg_keys(b, p.nk[0], p.seg_nkt[0]), nk1 = seg_keys(b, p.nk[1], p.seg_nkt[1]);   // this batch's key counts: per workgroup, scalar
+    const int nt0 = pres0 ? (nk0 + 63) >> 6 : 0;
+    const int nt1 = pres1 ? (nk1 + 63) >> 6 : 0;
     const int nt = nt0 + nt1;
 
     // ---- loader (as attn_pp_kernel): waves 0-3 fetch K(s), waves 4-7 V^T(s-1); per-lane constants, branch-free issue ----
     const int lrow = lane >> 3, lslot = lane & 7;
-    const int nk0 = p.nk[0], nk1 = p.nk[1];
     const bool is_k = wave < 4;
     const int t_shift = is_k ? 0 : 1;
     uint32_t rowbase[2][IPW], tstep[2];
@@ -799,8 +802,8 @@ __global__ __launch_bounds__(512, 2) void attn_pf_kernel(const AttnParams p) {
     float thr_cur = -3.0e38f, floor_cur = -3.0e38f;      // first tile: the max is forced to the tile's own row max (see attn_pp_kernel)
     {
         int nz = 0;
-        if (p.nseg > 0 && !pres0) nz += p.nk[0];
-        if (p.nseg > 1 && !pres1) nz += p.nk[1];
+        if (p.nseg > 0 && !pres0) nz += nk0;
+        if (p.nseg > 1 && !pres1) nz += nk1;
         if (nz > 0) {
             l_run = u == 0 ? (float)nz : 0.f; thr_cur = thr; floor_cur = 0.f;
             if constexpr (LSUM) {
@@ -1034,10 +1037,10 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_sp_kernel(const AttnParams p)
     }
     const bool pres0 = p.nseg > 0 && b >= p.seg_b0[0];
     const bool pres1 = p.nseg > 1 && b >= p.seg_b0[1];
-    const int nt0 = pres0 ? (p.nk[0] + 63) >> 6 : 0;
-    const int nt1 = pres1 ? (p.nk[1] + 63) >> 6 : 0;
+    const int nk0 = seg_keys(b, p.nk[0], p.seg_nkt[0]), nk1 = seg_keys(b, p.nk[1], p.seg_nkt[1]);   // this batch's key counts: per workgroup, scalar
+    const int nt0 = pres0 ? (nk0 + 63) >> 6 : 0;
+    const int nt1 = pres1 ? (nk1 + 63) >> 6 : 0;
     const int nt = nt0 + nt1;
-    const int nk0 = p.nk[0], nk1 = p.nk[1];
 
     // ---- loader: waves 0-3 fetch K(i), waves 4-7 V^T(i-2).  The stages are issued strictly in order, so the segment walk is running scalar
     // state: ld_t = tile of the next stage for this wave (negative: V^T's two-stage lag; >= nt: past the end -> zero fill), ld_off = byte
@@ -1415,7 +1418,10 @@ static int launch_attn(AttnParams& p, int tune, hipStream_t st) {
 // seg_index (idmvton_attn_fwd_indexed; NULL for the other two): seg_index[s] != NULL is a device table of B - seg_b0[s] int32, and query batch b
 // reads element seg_index[s][b - seg_b0[s]] of the seg_nb[s] >= 1 the segment holds (a pool may hold more elements than the batch has persons,
 // so seg_nb has no upper bound then).  The descriptor sizes stay seg_nb elements, and the kernels clamp the table's values to [0, seg_nb - 1].
-static int attn_fwd_impl(const idmvton_attn_args* a, const int32_t* seg_nb, const int32_t* const* seg_index, void* stream) {
+// seg_nk (idmvton_attn_fwd_ragged; NULL for the other three): seg_nk[s] != NULL is a device table of B int32 from batch 0 on, the keys segment s
+// has for each query batch (walk length and last-tile mask where the segment is present, the closed form's count where it is absent).  a->nk[s]
+// stays the capacity: every size and bound checked here uses it, and the kernels clamp the table's values to [1, nk[s]].
+static int attn_fwd_impl(const idmvton_attn_args* a, const int32_t* seg_nb, const int32_t* const* seg_index, const int32_t* const* seg_nk, void* stream) {
     CHECK_ARG(a != nullptr, IDMVTON_E_ARG, "attn_fwd: null args");
     CHECK_ARG(a->dtype == IDMVTON_F16 || a->dtype == IDMVTON_BF16, IDMVTON_E_DTYPE, "attn_fwd: dtype %d", a->dtype);
     CHECK_ARG(a->mode == IDMVTON_ATTN_SELF || a->mode == IDMVTON_ATTN_CROSS, IDMVTON_E_ARG, "attn_fwd: mode %d", a->mode);
@@ -1445,6 +1451,11 @@ static int attn_fwd_impl(const idmvton_attn_args* a, const int32_t* seg_nb, cons
         } else
         CHECK_ARG(seg_nb[ss] >= 0 && seg_nb[ss] <= a->B - a->seg_b0[ss], IDMVTON_E_SHAPE,
                   "attn_fwd_shared: seg %d seg_nb=%d outside [0, B - seg_b0 = %d]", ss, seg_nb[ss], a->B - a->seg_b0[ss]);
+        const int32_t* nkt = seg_nk && s < a->nseg ? seg_nk[s] : nullptr;
+        if (nkt) {
+            CHECK_ARG(a->mode != IDMVTON_ATTN_CROSS, IDMVTON_E_ARG, "attn_fwd_ragged: CROSS mode takes no table (seg %d)", ss);
+            CHECK_ARG(((uintptr_t)nkt & 3) == 0, IDMVTON_E_ALIGN, "attn_fwd_ragged: seg %d key-count table is not 4-byte aligned", ss);
+        }
         CHECK_ARG(a->mode != IDMVTON_ATTN_CROSS || seg_nb[ss] == 0, IDMVTON_E_ARG, "attn_fwd_shared: CROSS mode takes seg_nb = {0, 0} (seg %d: %d)", ss, seg_nb[ss]);
         const int krows = a->k_rows[ss] > 0 ? a->k_rows[ss] : a->nk[ss];
         CHECK_ARG(krows >= a->nk[ss], IDMVTON_E_SHAPE, "attn_fwd: seg %d k_rows=%d < nk", ss, krows);
@@ -1456,7 +1467,7 @@ static int attn_fwd_impl(const idmvton_attn_args* a, const int32_t* seg_nb, cons
         CHECK_ARG(kb < 0x80000000ull && vb < 0x80000000ull, IDMVTON_E_SHAPE, "attn_fwd: seg %d K/V^T >= 2 GiB", ss);
         p.k[s] = a->k[ss]; p.ldk[s] = a->ldk[ss]; p.kbytes[s] = (uint32_t)kb;
         p.vt[s] = a->vt[ss]; p.ldvt[s] = a->ldvt[ss]; p.vtbytes[s] = (uint32_t)vb;
-        p.nk[s] = a->nk[ss]; p.krows[s] = krows; p.seg_b0[s] = a->seg_b0[ss]; p.seg_nb[s] = seg_nb[ss]; p.seg_ix[s] = ix;
+        p.nk[s] = a->nk[ss]; p.krows[s] = krows; p.seg_b0[s] = a->seg_b0[ss]; p.seg_nb[s] = seg_nb[ss]; p.seg_ix[s] = ix; p.seg_nkt[s] = nkt;
     }
     hipStream_t st = (hipStream_t)stream;
     if (a->dtype == IDMVTON_BF16)
@@ -1466,15 +1477,21 @@ static int attn_fwd_impl(const idmvton_attn_args* a, const int32_t* seg_nb, cons
 
 extern "C" int idmvton_attn_fwd(const idmvton_attn_args* a, void* stream) {
     static const int32_t none[2] = {0, 0};
-    return attn_fwd_impl(a, none, nullptr, stream);
+    return attn_fwd_impl(a, none, nullptr, nullptr, stream);
 }
 
 extern "C" int idmvton_attn_fwd_shared(const idmvton_attn_args* a, const int32_t seg_nb[2], void* stream) {
     CHECK_ARG(seg_nb != nullptr, IDMVTON_E_ARG, "attn_fwd_shared: null seg_nb");
-    return attn_fwd_impl(a, seg_nb, nullptr, stream);
+    return attn_fwd_impl(a, seg_nb, nullptr, nullptr, stream);
 }
 
 extern "C" int idmvton_attn_fwd_indexed(const idmvton_attn_args* a, const int32_t seg_nb[2], const int32_t* const seg_index[2], void* stream) {
     CHECK_ARG(seg_nb != nullptr && seg_index != nullptr, IDMVTON_E_ARG, "attn_fwd_indexed: null seg_nb / seg_index");
-    return attn_fwd_impl(a, seg_nb, seg_index, stream);
+    return attn_fwd_impl(a, seg_nb, seg_index, nullptr, stream);
+}
+
+extern "C" int idmvton_attn_fwd_ragged(const idmvton_attn_args* a, const int32_t seg_nb[2], const int32_t* const seg_index[2],
+                                       const int32_t* const seg_nk[2], void* stream) {
+    CHECK_ARG(seg_nb != nullptr && seg_nk != nullptr, IDMVTON_E_ARG, "attn_fwd_ragged: null seg_nb / seg_nk");
+    return attn_fwd_impl(a, seg_nb, seg_index, seg_nk, stream);
 }

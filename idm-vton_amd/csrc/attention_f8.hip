@@ -35,6 +35,7 @@ struct AttnF8Params {
     int nqb;
     int seg_nb[2];                                     // batch elements a segment holds (idmvton_attn_f8_shared); 0 = one per query batch from seg_b0 on
     const int32_t* seg_ix[2];                          // idmvton_attn_f8_indexed: device table, query batch b reads element seg_ix[s][b - seg_b0[s]]; NULL = the seg_nb rule
+    const int32_t* seg_nkt[2];                         // idmvton_attn_f8_ragged: device table of B key counts, query batch b has seg_nkt[s][b] keys of segment s; NULL = nk[s]
 };
 
 #define NEG_BIG_F8 (-1.0e30f)
@@ -63,8 +64,9 @@ __global__ __launch_bounds__(256) void attn_f8_kernel(const AttnF8Params p) {
 
     const bool pres0 = p.nseg > 0 && b >= p.seg_b0[0];
     const bool pres1 = p.nseg > 1 && b >= p.seg_b0[1];
-    const int nt0 = pres0 ? (p.nk[0] + 63) >> 6 : 0;
-    const int nt1 = pres1 ? (p.nk[1] + 63) >> 6 : 0;
+    const int nk0 = seg_keys(b, p.nk[0], p.seg_nkt[0]), nk1 = seg_keys(b, p.nk[1], p.seg_nkt[1]);   // this batch's key counts: per workgroup, scalar
+    const int nt0 = pres0 ? (nk0 + 63) >> 6 : 0;
+    const int nt1 = pres1 ? (nk1 + 63) >> 6 : 0;
     const int nt = nt0 + nt1;
     const int bsg0 = seg_batch_ix(b, p.seg_b0[0], p.seg_nb[0], p.seg_ix[0]), bsg1 = seg_batch_ix(b, p.seg_b0[1], p.seg_nb[1], p.seg_ix[1]);   // per workgroup, scalar
 
@@ -76,8 +78,8 @@ __global__ __launch_bounds__(256) void attn_f8_kernel(const AttnF8Params p) {
     float m_run = NEG_BIG_F8, l_run = 0.f;             // l_run in units of 2^-8 (it sums the scaled probabilities)
     {
         int nz = 0;                                     // closed form for absent (all-zero) segments: nk keys, logit 0, value 0
-        if (p.nseg > 0 && !pres0) nz += p.nk[0];
-        if (p.nseg > 1 && !pres1) nz += p.nk[1];
+        if (p.nseg > 0 && !pres0) nz += nk0;
+        if (p.nseg > 1 && !pres1) nz += nk1;
         if (nz > 0) { m_run = 0.f; l_run = u == 0 ? 256.f * (float)nz : 0.f; }
     }
 
@@ -85,13 +87,13 @@ __global__ __launch_bounds__(256) void attn_f8_kernel(const AttnF8Params p) {
     auto load_tile = [&](int t, i32x8 (&kk)[2], i32x8 (&vv)[2]) {
         const int sg = t < nt0 ? 0 : 1;
         const int kt = sg ? t - nt0 : t;
-        const int bsg = sg ? bsg1 : bsg0;
+        const int bsg = sg ? bsg1 : bsg0, nk = sg ? nk1 : nk0;
         const uint8_t* kp = p.k[sg] + (size_t)bsg * p.krows[sg] * p.ldk[sg] + h * 64 + 32 * u;
         const uint8_t* vp = p.vt[sg] + ((size_t)bsg * p.heads * 64 + h * 64) * p.ldvt[sg] + kt * 64 + 32 * u;
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
             int key = kt * 64 + kb * 32 + l31;
-            key = key < p.nk[sg] ? key : p.nk[sg] - 1;            // masked below; V^T positions beyond nk are zero-filled
+            key = key < nk ? key : nk - 1;                        // masked below; V^T positions beyond nk are zero-filled
             kk[kb] = load32(kp + (size_t)key * p.ldk[sg]);
             vv[kb] = load32(vp + (size_t)(kb * 32 + l31) * p.ldvt[sg]);
         }
@@ -102,7 +104,7 @@ __global__ __launch_bounds__(256) void attn_f8_kernel(const AttnF8Params p) {
         if (t + 1 < nt) load_tile(t + 1, kn, vn);                 // next tile's fragments in flight behind this tile's math
         const int sg = t < nt0 ? 0 : 1;
         const int kt = sg ? t - nt0 : t;
-        const int valid = p.nk[sg] - kt * 64;
+        const int valid = (sg ? nk1 : nk0) - kt * 64;
         f32x16 sacc[2];
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
@@ -177,7 +179,8 @@ __global__ __launch_bounds__(256) void attn_f8_kernel(const AttnF8Params p) {
 // One implementation behind both entry points; seg_nb as in idmvton_attn_fwd_shared.  This kernel reads K / V^T through plain pointers, so the
 // seg_nb bound checked here is what keeps every read inside the caller's seg_nb-element tensors.
 // seg_index as in idmvton_attn_fwd_indexed; with a table the kernel's clamp of its values to [0, seg_nb - 1] is that bound.
-static int attn_f8_impl(const idmvton_attn_f8_args* a, const int32_t* seg_nb, const int32_t* const* seg_index, void* stream) {
+// seg_nk as in idmvton_attn_fwd_ragged; the kernel's clamp of its values to [1, nk] keeps the walk inside the k_rows / ldvt checked here.
+static int attn_f8_impl(const idmvton_attn_f8_args* a, const int32_t* seg_nb, const int32_t* const* seg_index, const int32_t* const* seg_nk, void* stream) {
     CHECK_ARG(a != nullptr, IDMVTON_E_ARG, "attn_f8: null args");
     CHECK_ARG(a->out_dtype == IDMVTON_F16 || a->out_dtype == IDMVTON_BF16, IDMVTON_E_DTYPE, "attn_f8: out_dtype %d", a->out_dtype);
     CHECK_ARG(a->B > 0 && a->heads > 0 && a->Nq > 0 && a->nseg >= 1 && a->nseg <= 2, IDMVTON_E_SHAPE, "attn_f8: B=%d heads=%d Nq=%d nseg=%d", a->B, a->heads, a->Nq, a->nseg);
@@ -197,12 +200,14 @@ static int attn_f8_impl(const idmvton_attn_f8_args* a, const int32_t* seg_nb, co
         } else
         CHECK_ARG(seg_nb[ss] >= 0 && seg_nb[ss] <= a->B - a->seg_b0[ss], IDMVTON_E_SHAPE,
                   "attn_f8_shared: seg %d seg_nb=%d outside [0, B - seg_b0 = %d]", ss, seg_nb[ss], a->B - a->seg_b0[ss]);
+        const int32_t* nkt = seg_nk && s < a->nseg ? seg_nk[s] : nullptr;
+        if (nkt) CHECK_ARG(((uintptr_t)nkt & 3) == 0, IDMVTON_E_ALIGN, "attn_f8_ragged: seg %d key-count table is not 4-byte aligned", ss);
         const int krows = a->k_rows[ss] > 0 ? a->k_rows[ss] : a->nk[ss];
         CHECK_ARG(krows >= a->nk[ss] && a->ldk[ss] % 16 == 0 && a->ldk[ss] >= a->heads * 64 && a->ldvt[ss] % 64 == 0 && a->ldvt[ss] >= ((a->nk[ss] + 63) & ~63) &&
                   ((uintptr_t)a->k8[ss] & 15) == 0 && ((uintptr_t)a->vt8[ss] & 15) == 0, IDMVTON_E_ALIGN,
                   "attn_f8: seg %d ldk=%d ldvt=%d (V^T rows hold whole 64-key tiles: ldvt %% 64 == 0, ldvt >= roundup64(nk), zero-filled beyond nk)", ss, a->ldk[ss], a->ldvt[ss]);
         p.k[s] = (const uint8_t*)a->k8[ss]; p.ldk[s] = a->ldk[ss]; p.vt[s] = (const uint8_t*)a->vt8[ss]; p.ldvt[s] = a->ldvt[ss];
-        p.nk[s] = a->nk[ss]; p.krows[s] = krows; p.seg_b0[s] = a->seg_b0[ss]; p.seg_nb[s] = seg_nb[ss]; p.seg_ix[s] = ix;
+        p.nk[s] = a->nk[ss]; p.krows[s] = krows; p.seg_b0[s] = a->seg_b0[ss]; p.seg_nb[s] = seg_nb[ss]; p.seg_ix[s] = ix; p.seg_nkt[s] = nkt;
     }
     auto rep = [](int e) { const int b = (127 + e) & 0xff; return b | (b << 8) | (b << 16) | (b << 24); };
     p.sc_qk = rep(a->qk_scale_exp);
@@ -217,17 +222,23 @@ static int attn_f8_impl(const idmvton_attn_f8_args* a, const int32_t* seg_nb, co
 
 extern "C" int idmvton_attn_f8(const idmvton_attn_f8_args* a, void* stream) {
     static const int32_t none[2] = {0, 0};
-    return attn_f8_impl(a, none, nullptr, stream);
+    return attn_f8_impl(a, none, nullptr, nullptr, stream);
 }
 
 extern "C" int idmvton_attn_f8_shared(const idmvton_attn_f8_args* a, const int32_t seg_nb[2], void* stream) {
     CHECK_ARG(seg_nb != nullptr, IDMVTON_E_ARG, "attn_f8_shared: null seg_nb");
-    return attn_f8_impl(a, seg_nb, nullptr, stream);
+    return attn_f8_impl(a, seg_nb, nullptr, nullptr, stream);
 }
 
 extern "C" int idmvton_attn_f8_indexed(const idmvton_attn_f8_args* a, const int32_t seg_nb[2], const int32_t* const seg_index[2], void* stream) {
     CHECK_ARG(seg_nb != nullptr && seg_index != nullptr, IDMVTON_E_ARG, "attn_f8_indexed: null seg_nb / seg_index");
-    return attn_f8_impl(a, seg_nb, seg_index, stream);
+    return attn_f8_impl(a, seg_nb, seg_index, nullptr, stream);
+}
+
+extern "C" int idmvton_attn_f8_ragged(const idmvton_attn_f8_args* a, const int32_t seg_nb[2], const int32_t* const seg_index[2],
+                                      const int32_t* const seg_nk[2], void* stream) {
+    CHECK_ARG(seg_nb != nullptr && seg_nk != nullptr, IDMVTON_E_ARG, "attn_f8_ragged: null seg_nb / seg_nk");
+    return attn_f8_impl(a, seg_nb, seg_index, seg_nk, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -58,6 +58,16 @@ __device__ __forceinline__ int seg_batch_ix(int b, int b0, int nb, const int32_t
     return v > 0 ? v : 0;
 }
 
+// Key count of a segment for query batch b (the _ragged entry points): nkt != nullptr -> nkt[b] (a table of B entries from batch 0 on, so the
+// CFG-unconditional rows, for which the segment is absent, find the count of their closed form there), clamped to [1, cap]; NULL -> cap, the
+// launch-wide nk.  One scalar load per workgroup, as seg_batch_ix; everything a kernel derives from a segment's key count derives from this.
+__device__ __forceinline__ int seg_keys(int b, int cap, const int32_t* nkt) {
+    if (nkt == nullptr) return cap;
+    int v = uniform(nkt[b]);
+    v = v < cap ? v : cap;
+    return v > 1 ? v : 1;
+}
+
 // 16-byte LDS-DMA: every lane supplies a byte offset into the buffer `rs`; lane l's 16 bytes land at
 // lds_base + 16*l (lds_base must be wave-uniform).  Out-of-range offsets (>= num_records) read as zero.
 __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rs, void* lds_base, uint32_t voff) {

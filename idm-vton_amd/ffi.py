@@ -112,7 +112,8 @@ SYMBOLS = ["idmvton_last_error", "idmvton_abi_version", "idmvton_sizeof", "idmvt
            "idmvton_vae_sample", "idmvton_softmax_rows", "idmvton_probe_mfma", "idmvton_groupnorm_stats_doubles",
            "idmvton_attn_small", "idmvton_rccl_unique_id", "idmvton_rccl_comm_init", "idmvton_rccl_bcast_arena",
            "idmvton_rccl_comm_destroy", "idmvton_attn_f8", "idmvton_quant_f8", "idmvton_split", "idmvton_attn_fwd_shared",
-           "idmvton_attn_f8_shared", "idmvton_attn_fwd_indexed", "idmvton_attn_f8_indexed"]
+           "idmvton_attn_f8_shared", "idmvton_attn_fwd_indexed", "idmvton_attn_f8_indexed",
+           "idmvton_attn_fwd_ragged", "idmvton_attn_f8_ragged"]
 
 _lib = None
 
@@ -155,6 +156,9 @@ def lib():
     for s in ("idmvton_attn_fwd_indexed", "idmvton_attn_f8_indexed"):        # (args*, const int32_t seg_nb[2], const int32_t* const seg_index[2], stream)
         getattr(L, s).argtypes = [vp, C.POINTER(i32), C.POINTER(vp), vp]
         getattr(L, s).restype = C.c_int
+    for s in ("idmvton_attn_fwd_ragged", "idmvton_attn_f8_ragged"):          # (args*, seg_nb[2], seg_index[2], const int32_t* const seg_nk[2], stream)
+        getattr(L, s).argtypes = [vp, C.POINTER(i32), C.POINTER(vp), C.POINTER(vp), vp]
+        getattr(L, s).restype = C.c_int
     L.idmvton_probe_mfma.argtypes = [C.c_int, vp, vp, vp, vp]
     L.idmvton_groupnorm_stats_doubles.argtypes = [C.c_int] * 4
     L.idmvton_groupnorm_stats_doubles.restype = C.c_int
@@ -192,5 +196,18 @@ def call_indexed(fn_name, args, seg_nb, seg_index, stream):
     nb = (i32 * 2)(*seg_nb)
     ix = (vp * 2)(*[int(x) if x else None for x in seg_index])
     rc = getattr(L, fn_name)(C.byref(args), nb, ix, C.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError(f"{fn_name} failed ({rc}): {L.idmvton_last_error().decode()}")
+
+
+def call_ragged(fn_name, args, seg_nb, seg_index, seg_nk, stream):
+    """Invoke an `int f(const args*, const int32_t seg_nb[2], const int32_t* const seg_index[2], const int32_t* const seg_nk[2], void* stream)`
+    entry point (the ragged-segment attention launches).  seg_index / seg_nk: two device addresses each, 0 / None = no table for that segment;
+    seg_index=None stands for no index table at all."""
+    L = lib()
+    nb = (i32 * 2)(*seg_nb)
+    ix = (vp * 2)(*[int(x) if x else None for x in (seg_index or (0, 0))])
+    nk = (vp * 2)(*[int(x) if x else None for x in seg_nk])
+    rc = getattr(L, fn_name)(C.byref(args), nb, ix, nk, C.c_void_p(stream))
     if rc != 0:
         raise RuntimeError(f"{fn_name} failed ({rc}): {L.idmvton_last_error().decode()}")

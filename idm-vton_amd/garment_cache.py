@@ -21,6 +21,13 @@ from -- `put` swaps one garment of a cache in place, so tensors, pointers and th
 key -> slot over one such cache.  Size: with N1 / N2 the token rows at the two attention
 levels of the SDXL topology (10 features of 640 channels, 60 of 1280), an entry is (10 * N1 * 640 + 60 * N2 * 1280) * 2 tensors * 2 bytes per
 garment and timestep (tests/test_garment_size_cpu.py).
+
+Mixed sizes: a cache that carries `sizes` -- one (gh, gw) per garment -- is SLOTTED: (gh, gw) is then the size its slots are laid out for, and
+the garment of slot g, of latent size sizes[g], fills the front of the slot: K rows [0, N'_f) and V^T positions [0, ld'_f) of every feature and
+timestep, with the rest of the V^T zero.  The attention kernels read each person's key count from a device table (the _ragged entry points),
+so persons of one call wear garments of different sizes and a person with a small garment walks only its own key tiles.  Slots are always
+16-bit: `put` widens an e4m3 feature (exactly: e4m3 times a power of two is a 16-bit number) and the fp8 attention quantises a slot per launch,
+which gives the projection's own bytes back.  `take` returns a garment at its own compact size.  A cache without `sizes` is what it always was.
 """
 import torch
 
@@ -63,8 +70,28 @@ def kv_shapes(kv):
     return [(tuple(k.shape), tuple(vt.shape), k.dtype) for k, vt in kv]
 
 
+def _f8_positions(ld):
+    """position -> position: where the 16-bit kernels' key-ordered V^T keeps the key that the fp8 kernel's slot-ordered V^T holds at each of
+    its ld positions (the inverse of idmvton_quant_f8 mode 1: position 64t + 32u + 16kb + 4g + j holds key 64t + 32kb + 8g + 4u + j, and the
+    16-bit order swaps bits 2 and 3 of the key)."""
+    pos = torch.arange(ld)
+    key = (pos & ~63) | (((pos >> 4) & 1) << 5) | (((pos >> 2) & 3) << 3) | (((pos >> 5) & 1) << 2) | (pos & 3)
+    return (key & ~12) | ((key & 4) << 1) | ((key & 8) >> 1)
+
+
+def widen_f8(k8, vt8, dtype, ek, ev):
+    """(K, V^T) of one feature as e4m3 bytes (the fp8 engine's fused projection: e4m3(x * 2^e), V^T in the fp8 kernel's slot order) -> the
+    16-bit pair that idmvton_quant_f8 turns back into those bytes: e4m3 has 4 significant bits and |e| is small, so x' = e4m3 * 2^-e is
+    exact in fp16 / bf16, and x' * 2^e rounds to the byte it came from."""
+    k = (k8.view(torch.float8_e4m3fn).to(torch.float32) * 2.0 ** -ek).to(dtype)
+    v = (vt8.view(torch.float8_e4m3fn).to(torch.float32) * 2.0 ** -ev).to(dtype)
+    vt = torch.empty_like(v)
+    vt[..., _f8_positions(v.shape[-1]).to(v.device)] = v
+    return k, vt
+
+
 class GarmentCache:
-    def __init__(self, *, G, timesteps, h, w, dtype, attn_fp8, f8_exp, weights_id, kv, gh=None, gw=None):
+    def __init__(self, *, G, timesteps, h, w, dtype, attn_fp8, f8_exp, weights_id, kv, gh=None, gw=None, sizes=None, rows=None):
         self.G = int(G)
         self.timesteps = [int(t) for t in timesteps]
         self.h, self.w = int(h), int(w)
@@ -78,6 +105,12 @@ class GarmentCache:
         n = len(self.timesteps)
         if n < 1 or self.G < 1 or len(self._index) != n:
             raise ValueError(f"GarmentCache: needs G >= 1 and distinct timesteps (G={self.G}, timesteps={self.timesteps})")
+        # sizes: None, or the latent (gh, gw) of the garment in every slot of a slotted cache (module docstring); rows: per slot the (K rows,
+        # V^T positions) per feature that garment fills -- what `take` cuts out -- or None for a slot that is filled to its end / never put
+        self.sizes = None if sizes is None else [(int(a), int(b)) for a, b in sizes]
+        self.rows = [None] * self.G if rows is None else [None if r is None else [(int(a), int(b)) for a, b in r] for r in rows]
+        if self.sizes is not None and len(self.sizes) != self.G or len(self.rows) != self.G:
+            raise ValueError(f"GarmentCache: sizes / rows need one entry per garment (G={self.G}, sizes={self.sizes})")
         for f, (k, vt) in enumerate(self.kv):
             if k.shape[0] % (n * self.G) or vt.shape[0] != n * self.G or k.dtype != vt.dtype:
                 raise ValueError(f"GarmentCache: feature {f} has K {tuple(k.shape)} / V^T {tuple(vt.shape)} for {n} timesteps x {self.G} garments")
@@ -88,12 +121,14 @@ class GarmentCache:
 
     def __repr__(self):
         garment = f", garment latent={self.gh}x{self.gw}" if (self.gh, self.gw) != (self.h, self.w) else ""
+        if self.sizes is not None:
+            garment = f", slots of {self.gh}x{self.gw} holding {sorted(set(self.sizes))}"
         return (f"GarmentCache(G={self.G}, steps={len(self.timesteps)}, latent={self.h}x{self.w}{garment}, dtype={self.dtype}, "
                 f"attn_fp8={self.attn_fp8}, {self.nbytes / 2 ** 20:.1f} MiB)")
 
     def _like(self, **kw):
         args = dict(G=self.G, timesteps=self.timesteps, h=self.h, w=self.w, gh=self.gh, gw=self.gw, dtype=self.dtype, attn_fp8=self.attn_fp8,
-                    f8_exp=self.f8_exp, weights_id=self.weights_id, kv=self.kv)
+                    f8_exp=self.f8_exp, weights_id=self.weights_id, kv=self.kv, sizes=self.sizes, rows=self.rows if self.sizes is not None else None)
         args.update(kw)
         return GarmentCache(**args)
 
@@ -101,7 +136,9 @@ class GarmentCache:
         """The same cache -- the same tensors, no copy -- declared for calls at person latent size (h, w).  The garment K / V^T are made from
         the cloth alone (GarmentNet at (gh, gw), TryonNet's attn1 to_k / to_v) and do not depend on the person's resolution, so one encoded
         garment serves e.g. 768x1024 and 1024x1536 calls; `check` stays strict, this is the explicit opt-in."""
-        return self._like(h=h, w=w)
+        c = self._like(h=h, w=w)
+        c.sizes, c.rows = self.sizes, self.rows          # shared like the tensors: a `put` through either is seen by both
+        return c
 
     def check(self, *, timesteps, h, w, dtype, attn_fp8, f8_exp, weights_id, persons, garment_index=None):
         """The cache entry (timestep index) of every timestep of a call, looked up BY VALUE -- a cache built for n steps serves strength < 1
@@ -144,6 +181,12 @@ class GarmentCache:
             raise ValueError(f"GarmentCache garment_index mismatch: {bad} outside [0, G = {self.G}) garments")
         return ids
 
+    def garment_sizes(self, garment_index, persons=None):
+        """The latent (gh, gw) of the garment each person wears, for a garment_index that `garment_ids` accepts: sizes[garment_index[i]] on a
+        slotted cache, the cache's one (gh, gw) otherwise."""
+        ids = self.garment_ids(garment_index, len(garment_index) if persons is None else persons)
+        return [self.sizes[g] if self.sizes is not None else (self.gh, self.gw) for g in ids]
+
     def run(self, i0, c=1):
         """Views of the 70 (K, V^T) pairs of cache entries i0 .. i0 + c - 1 (what TryonNet's attn1 reads as its garment segment)."""
         n, G = len(self.timesteps), self.G
@@ -164,7 +207,7 @@ class GarmentCache:
             kk = k.reshape(n, 1, r, k.shape[1]).expand(n, times, r, k.shape[1]).reshape(n * times * r, k.shape[1]).contiguous()
             vv = vt.reshape(n, 1, G, *vt.shape[1:]).expand(n, times, G, *vt.shape[1:]).reshape(n * times * G, *vt.shape[1:]).contiguous()
             kv.append((kk, vv))
-        return self._like(G=G * times, kv=kv)
+        return self._like(G=G * times, kv=kv, sizes=None if self.sizes is None else self.sizes * times, rows=self.rows * times)
 
 
     # ---- the pool primitives --------------------------------------------------------------------------------------------
@@ -198,7 +241,9 @@ class GarmentCache:
                 for (dk, dv), (sk, sv) in zip(slot_run(kv, n, U, i, j0, c), slot_run(src.kv, n, src.G, i, g0, c)):
                     dk.copy_(sk)
                     dv.copy_(sv)
-        return self._like(G=U, kv=kv)
+        slotted = any(c.sizes is not None for c, _ in sources)       # equal slot size (_agrees): whole slots moved, the sizes go along
+        return self._like(G=U, kv=kv, sizes=[c.sizes[g] if c.sizes is not None else (c.gh, c.gw) for c, g in sources] if slotted else None,
+                          rows=[c.rows[g] for c, g in sources] if slotted else None)
 
     def select(self, ids):
         """A new cache (a copy) of garments ids[0], ids[1], ... of this one, in that order; values may repeat."""
@@ -224,12 +269,52 @@ class GarmentCache:
             raise ValueError(f"GarmentCache put: slot mismatch ({slot} outside [0, G = {self.G}))")
         if other.G != 1:
             raise ValueError(f"GarmentCache put: G mismatch (takes a cache of one garment, got G = {other.G})")
+        if self.sizes is not None:
+            return self._put_slotted(int(slot), other)
         self._agrees(other, "put", devices=False)
         n = len(self.timesteps)
         for i in range(n):
             for (dk, dv), (sk, sv) in zip(slot_run(self.kv, n, self.G, i, int(slot)), timestep_run(other.kv, n, 1, i)):
                 dk.copy_(sk, non_blocking=sk.is_cuda or sk.is_pinned())
                 dv.copy_(sv, non_blocking=sv.is_cuda or sv.is_pinned())
+        return self
+
+    def _put_slotted(self, slot, other):
+        """`put` on a cache with `sizes`: the garment of `other` may be of another (smaller) size than the slots.  Every feature's K rows and
+        V^T positions must fit the slot's ("does not fit" otherwise, before any copy); they go to the front of the slot and the rest of the
+        slot's V^T is zero-filled -- the fp8 attention quantises whole slots and permutes inside 64-key tiles, so a stale value next to the
+        last real ones would meet a zero probability as NaN.  The K tail keeps what it held: no kernel reads a K row beyond a garment's count.
+        An e4m3 feature of `other` is widened (widen_f8): slots are 16-bit."""
+        for f in self._FIELDS:
+            if f not in ("gh", "gw") and getattr(self, f) != getattr(other, f):
+                raise ValueError(f"GarmentCache put: {f} mismatch ({getattr(self, f)} against {getattr(other, f)})")
+        n = len(self.timesteps)
+        size = other.sizes[0] if other.sizes is not None else (other.gh, other.gw)
+        if len(self.kv) != len(other.kv):
+            raise ValueError(f"GarmentCache put: does not fit ({len(other.kv)} features against {len(self.kv)})")
+        fill = []                                        # per feature: (K rows, V^T positions) the garment fills
+        for f, ((k, vt), (ok, ovt)) in enumerate(zip(self.kv, other.kv)):
+            N, Nf = k.shape[0] // (n * self.G), ok.shape[0] // n
+            if other.rows[0] is not None:
+                Nf, ldf = other.rows[0][f]
+            else:
+                ldf = ovt.shape[2]
+            ok_dtype = ok.dtype == k.dtype or (ok.dtype == torch.uint8 and self.attn_fp8 and k.dtype != torch.uint8)
+            if k.shape[1:] != ok.shape[1:] or vt.shape[1] != ovt.shape[1] or Nf > N or ldf > vt.shape[2] or not ok_dtype:
+                raise ValueError(f"GarmentCache put: does not fit (feature {f}: a garment of latent {size[0]}x{size[1]} has K rows {Nf} x {tuple(ok.shape[1:])} "
+                                 f"{ok.dtype} and V^T {ovt.shape[1]} x {ldf}, a slot of {self.gh}x{self.gw} holds {N} x {tuple(k.shape[1:])} {k.dtype} and "
+                                 f"{vt.shape[1]} x {vt.shape[2]})")
+            fill.append((Nf, ldf))
+        for i in range(n):
+            for (Nf, ldf), (dk, dv), (sk, sv) in zip(fill, slot_run(self.kv, n, self.G, i, slot), timestep_run(other.kv, n, 1, i)):
+                if sk.dtype != dk.dtype:
+                    sk, sv = widen_f8(sk, sv, dk.dtype, self.f8_exp[1], self.f8_exp[2])
+                nb = sk.is_cuda or sk.is_pinned()
+                dk[:Nf].copy_(sk[:Nf], non_blocking=nb)
+                dv[..., :ldf].copy_(sv[..., :ldf], non_blocking=nb)
+                dv[..., ldf:].zero_()
+        self.sizes[slot] = size
+        self.rows[slot] = None if all(a == k.shape[0] // (n * self.G) and b == vt.shape[2] for (a, b), (k, vt) in zip(fill, self.kv)) else fill
         return self
 
     def take(self, slot, device=None, pin_memory=False):
@@ -241,13 +326,17 @@ class GarmentCache:
         n = len(self.timesteps)
         device = self.kv[0][0].device if device is None else torch.device(device)
         pin = bool(pin_memory) and device.type == "cpu"
-        kv = [(torch.empty((k.shape[0] // self.G,) + tuple(k.shape[1:]), dtype=k.dtype, device=device, pin_memory=pin),
-               torch.empty((vt.shape[0] // self.G,) + tuple(vt.shape[1:]), dtype=vt.dtype, device=device, pin_memory=pin)) for k, vt in self.kv]
+        # a slotted cache gives the garment back at its own compact size: the rows / positions `put` filled
+        fill = self.rows[int(slot)] or [(k.shape[0] // (n * self.G), vt.shape[2]) for k, vt in self.kv]
+        kv = [(torch.empty((n * Nf,) + tuple(k.shape[1:]), dtype=k.dtype, device=device, pin_memory=pin),
+               torch.empty((n, vt.shape[1], ldf), dtype=vt.dtype, device=device, pin_memory=pin)) for (Nf, ldf), (k, vt) in zip(fill, self.kv)]
         for i in range(n):
-            for (dk, dv), (sk, sv) in zip(timestep_run(kv, n, 1, i), slot_run(self.kv, n, self.G, i, int(slot))):
-                dk.copy_(sk)
-                dv.copy_(sv)
-        return self._like(G=1, kv=kv)
+            for (Nf, ldf), (dk, dv), (sk, sv) in zip(fill, timestep_run(kv, n, 1, i), slot_run(self.kv, n, self.G, i, int(slot))):
+                dk.copy_(sk[:Nf])
+                dv.copy_(sv[..., :ldf])
+        if self.sizes is None:
+            return self._like(G=1, kv=kv)
+        return self._like(G=1, kv=kv, gh=self.sizes[int(slot)][0], gw=self.sizes[int(slot)][1], sizes=None, rows=None)
 
     def to(self, device, pin_memory=False):
         """The same cache on another device (host offload and return): one copy per tensor; pin_memory: page-locked host tensors, so that
@@ -270,7 +359,8 @@ class GarmentCache:
 
     def save(self, path):
         """-> a safetensors file: tensors k.<f> / vt.<f> (e4m3 caches are uint8 bytes) and a metadata record (format version, G, timesteps, both
-        sizes, dtype, attn_fp8, f8_exp, weights_id)."""
+        sizes, dtype, attn_fp8, f8_exp, weights_id).  A cache with `sizes` writes format version 2, which adds sizes and rows; one without
+        writes version 1 exactly as before."""
         import json
         from safetensors.torch import save_file
         tensors = {}
@@ -278,6 +368,8 @@ class GarmentCache:
             tensors[f"k.{f:03d}"], tensors[f"vt.{f:03d}"] = k.detach().cpu().contiguous(), vt.detach().cpu().contiguous()
         meta = dict(format="idmvton_garment_cache", version=self.FORMAT_VERSION, G=self.G, timesteps=self.timesteps, h=self.h, w=self.w, gh=self.gh,
                     gw=self.gw, dtype=str(self.dtype), attn_fp8=self.attn_fp8, f8_exp=list(self.f8_exp), weights_id=self.weights_id, features=len(self.kv))
+        if self.sizes is not None:
+            meta.update(version=2, sizes=[list(sz) for sz in self.sizes], rows=[None if r is None else [list(x) for x in r] for r in self.rows])
         save_file(tensors, path, metadata={k: json.dumps(v) for k, v in meta.items()})
 
     @staticmethod
@@ -288,13 +380,13 @@ class GarmentCache:
         from safetensors import safe_open
         with safe_open(path, framework="pt", device=str(device)) as f:
             meta = {k: json.loads(v) for k, v in (f.metadata() or {}).items()}
-            if meta.get("format") != "idmvton_garment_cache" or meta.get("version") != GarmentCache.FORMAT_VERSION:
+            if meta.get("format") != "idmvton_garment_cache" or meta.get("version") not in (GarmentCache.FORMAT_VERSION, 2):
                 raise ValueError(f"GarmentCache load: {path} is not a garment cache of format version {GarmentCache.FORMAT_VERSION} "
                                  f"(format={meta.get('format')!r}, version={meta.get('version')!r})")
             kv = [(f.get_tensor(f"k.{i:03d}"), f.get_tensor(f"vt.{i:03d}")) for i in range(meta["features"])]
         dtype = {str(d): d for d in (torch.float16, torch.bfloat16, torch.float32)}[meta["dtype"]]
         return GarmentCache(G=meta["G"], timesteps=meta["timesteps"], h=meta["h"], w=meta["w"], gh=meta["gh"], gw=meta["gw"], dtype=dtype,
-                            attn_fp8=meta["attn_fp8"], f8_exp=meta["f8_exp"], weights_id=meta["weights_id"], kv=kv)
+                            attn_fp8=meta["attn_fp8"], f8_exp=meta["f8_exp"], weights_id=meta["weights_id"], kv=kv, sizes=meta.get("sizes"), rows=meta.get("rows"))
 
 
 class GarmentPool:
@@ -302,12 +394,13 @@ class GarmentPool:
     batch, after putting the garments the pool lacks into the least-recently-used slots that the batch does not itself need; evicted garments
     optionally go to pinned host memory and come back from there instead of being encoded again: spill=True keeps EVERY garment ever evicted
     (0.3-9.4 GB each at full size: unbounded), spill=<int> at most that many, dropping the one spilled longest ago; `drop(key)` frees one.
-    A slot's views are copied straight to and from the pinned tensors, with no temporary garment on the device.  Everything moves BEFORE the
+    mixed_sizes=True: the pool's cache is slotted -- `like` fixes the slot size, any garment that fits goes in, and a spilled garment has its own
+    compact size on the host.  A slot's views are copied straight to and from the pinned tensors, with no temporary garment on the device.  Everything moves BEFORE the
     call -- nothing is streamed during one -- and the pool's tensors never move, so an engine's graph states stay valid across swaps.
         pool = GarmentPool(8, like=pipe.encode_garment(cloth=c0, ...))
         out = pipe(cloth=pool.cache, garment_index=pool.get(["sku7", "sku7", "sku3"], encode=my_encode), ...)"""
 
-    def __init__(self, capacity, like, spill=False):
+    def __init__(self, capacity, like, spill=False, mixed_sizes=False):
         if like.G != 1:
             raise ValueError(f"GarmentPool: `like` must hold one garment (G = {like.G})")
         if capacity < 1:
@@ -315,7 +408,14 @@ class GarmentPool:
         self.capacity, self.spill = int(capacity), bool(spill)
         self.host_capacity = None if spill is True or not spill else int(spill)      # garments kept on the host; None: no bound
         n = len(like.timesteps)
-        self.cache = like._like(G=self.capacity, kv=alloc_kv(kv_shapes(like.kv), 1, self.capacity, like.kv[0][0].device))
+        if mixed_sizes:
+            # a slotted cache (module docstring): `like` fixes the slot size, `get` accepts every garment that fits, host copies are compact.
+            # Slots are 16-bit, whatever `like` holds
+            shapes = [(a, b, like.dtype if d == torch.uint8 else d) for a, b, d in kv_shapes(like.kv)]
+            self.cache = like._like(G=self.capacity, kv=alloc_kv(shapes, 1, self.capacity, like.kv[0][0].device),
+                                    sizes=[(like.gh, like.gw)] * self.capacity, rows=None)
+        else:
+            self.cache = like._like(G=self.capacity, kv=alloc_kv(kv_shapes(like.kv), 1, self.capacity, like.kv[0][0].device), sizes=None, rows=None)
         # alloc_kv scales the leading dimension of a list that holds n timesteps: [n * 1 ...] -> [n * capacity ...] is "capacity times as many"
         assert all(vt.shape[0] == n * self.capacity for _, vt in self.cache.kv)
         self._slot = {}                                      # key -> slot, in use order: the first key is the least recently used

@@ -30,10 +30,13 @@ def _stream():
 PROFILE = None
 
 
-def _call(fn_name, args, flops=0.0, bytes_=0.0, seg_nb=None, seg_index=None):
+def _call(fn_name, args, flops=0.0, bytes_=0.0, seg_nb=None, seg_index=None, seg_nk=None):
     """seg_nb: the shared-segment attention entry points' extra argument (fn_name is then idmvton_attn_*_shared); seg_index: the indexed ones'
-    second extra argument, two device addresses (fn_name is then idmvton_attn_*_indexed)."""
-    if seg_index is not None:
+    second extra argument, two device addresses (fn_name is then idmvton_attn_*_indexed); seg_nk: the ragged ones' third, two device addresses
+    (fn_name is then idmvton_attn_*_ragged)."""
+    if seg_nk is not None:
+        launch = lambda: ffi.call_ragged(fn_name, args, seg_nb, seg_index, seg_nk, _stream())
+    elif seg_index is not None:
         launch = lambda: ffi.call_indexed(fn_name, args, seg_nb, seg_index, _stream())
     elif seg_nb is not None:
         launch = lambda: ffi.call_shared(fn_name, args, seg_nb, _stream())
@@ -228,11 +231,13 @@ QSCALE = 0.125 * 1.4426950408889634          # softmax_scale(d=64) * log2(e): wh
 
 
 def attention(q, out, segs, heads, *, mode=ffi.ATTN_SELF, ip_scale=1.0, B=None, Nq=None, ldq=None, ldo=None, tune=0, q_prescaled=False):
-    """q/out: [B][Nq][>=heads*64] views; segs: list of dict(k=, vt=, nk=, ldk=, ldvt=, k_rows=, b0=[, nb=][, index=]).
+    """q/out: [B][Nq][>=heads*64] views; segs: list of dict(k=, vt=, nk=, ldk=, ldvt=, k_rows=, b0=[, nb=][, index=][, nk_table=]).
     nb (absent or 0: one K / V^T element per query batch from b0 on): the segment holds nb elements and batch b reads (b - b0) % nb -- a shared
     garment segment, launched through idmvton_attn_fwd_shared.  index (with nb >= 1): an int32 device tensor of B - b0 entries, batch b reads
-    element index[b - b0] of the nb -- a pooled garment segment, launched through idmvton_attn_fwd_indexed.  The tune-table key carries neither
-    nb nor the index: same kernel choice as the materialised launch."""
+    element index[b - b0] of the nb -- a pooled garment segment, launched through idmvton_attn_fwd_indexed.  nk_table: an int32 device tensor of
+    B entries (from batch 0 on), batch b has nk_table[b] of the segment's nk keys -- a ragged segment (slots of nk keys, each garment at the
+    front of its own), launched through idmvton_attn_fwd_ragged; nk stays the capacity.  The tune-table key carries neither nb nor a table: same
+    kernel choice as the materialised launch (the FLOP count of a profile uses the capacity too)."""
     a = ffi.AttnArgs()
     a.dtype, a.mode = _dt(q), mode
     a.B = q.shape[0] if B is None else B
@@ -258,9 +263,9 @@ def attention(q, out, segs, heads, *, mode=ffi.ATTN_SELF, ip_scale=1.0, B=None, 
     fl = 0.0
     for s in segs:
         fl += 4.0 * (a.B - s.get("b0", 0)) * heads * a.Nq * s["nk"] * 64
-    nb, ix = _seg_nb(segs), _seg_index(segs, a.B)
-    _call("idmvton_attn_fwd_indexed" if ix else "idmvton_attn_fwd_shared" if nb else "idmvton_attn_fwd", a, flops=fl,
-          bytes_=2.0 * a.B * a.Nq * heads * 64 * q.element_size(), seg_nb=nb or ([0, 0] if ix else None), seg_index=ix)
+    nb, ix, nkt = _seg_nb(segs), _seg_index(segs, a.B), _seg_nk(segs, a.B)
+    _call("idmvton_attn_fwd_ragged" if nkt else "idmvton_attn_fwd_indexed" if ix else "idmvton_attn_fwd_shared" if nb else "idmvton_attn_fwd", a, flops=fl,
+          bytes_=2.0 * a.B * a.Nq * heads * 64 * q.element_size(), seg_nb=nb or ([0, 0] if ix or nkt else None), seg_index=ix, seg_nk=nkt)
     return out
 
 
@@ -285,6 +290,18 @@ def _seg_index(segs, B):
     return ix if any(ix) else None
 
 
+def _seg_nk(segs, B):
+    """None when no segment carries a key-count table (the other entry points are called), else the two device addresses (0 = no table)."""
+    nk = []
+    for s in segs:
+        t = s.get("nk_table")
+        if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.numel() == B):
+            raise ValueError(f"attention: a segment's nk_table must be a contiguous int32 device tensor of B = {B} entries")
+        nk.append(0 if t is None else t.data_ptr())
+    nk += [0] * (2 - len(nk))
+    return nk if any(nk) else None
+
+
 def quant_f8(src, scale, mode=0, out=None):
     """16-bit -> e4m3 bytes (torch.uint8) times `scale` (a power of two).  mode 0: src [rows][cols] (row stride src.stride(0)) ->
     [rows][cols]; mode 1: src = V^T [rows][N] in the 16-bit kernels' key order -> [rows][roundup64(N)] in the fp8 kernel's slot order."""
@@ -300,8 +317,8 @@ def quant_f8(src, scale, mode=0, out=None):
 
 
 def attention_f8(q8, out, segs, heads, *, qk_scale_exp, v_scale_exp, B, Nq, ldq=None, ldo=None):
-    """fp8 self-attention (csrc/attention_f8.hip).  q8: uint8 [B*Nq][>= heads*64]; segs: list of dict(k8=, vt8=, nk=, ldk=, ldvt=, k_rows=, b0=[, nb=][, index=]);
-    nb / index as in attention() (idmvton_attn_f8_shared / idmvton_attn_f8_indexed)."""
+    """fp8 self-attention (csrc/attention_f8.hip).  q8: uint8 [B*Nq][>= heads*64]; segs: list of dict(k8=, vt8=, nk=, ldk=, ldvt=, k_rows=, b0=[, nb=][, index=][, nk_table=]);
+    nb / index / nk_table as in attention() (idmvton_attn_f8_shared / idmvton_attn_f8_indexed / idmvton_attn_f8_ragged)."""
     a = ffi.AttnF8Args()
     a.out_dtype, a.B, a.heads, a.Nq = _dt(out), B, heads, Nq
     a.q8, a.ldq = _ptr(q8), (q8.stride(-2) if ldq is None else ldq)
@@ -314,9 +331,9 @@ def attention_f8(q8, out, segs, heads, *, qk_scale_exp, v_scale_exp, B, Nq, ldq=
         a.nk[i], a.k_rows[i], a.seg_b0[i] = s["nk"], s.get("k_rows", 0), s.get("b0", 0)
         fl += 4.0 * (B - s.get("b0", 0)) * heads * Nq * s["nk"] * 64
     a.qk_scale_exp, a.v_scale_exp = qk_scale_exp, v_scale_exp
-    nb, ix = _seg_nb(segs), _seg_index(segs, B)
-    _call("idmvton_attn_f8_indexed" if ix else "idmvton_attn_f8_shared" if nb else "idmvton_attn_f8", a, flops=fl,
-          bytes_=float(B * Nq * heads * 64 * (1 + out.element_size())), seg_nb=nb or ([0, 0] if ix else None), seg_index=ix)
+    nb, ix, nkt = _seg_nb(segs), _seg_index(segs, B), _seg_nk(segs, B)
+    _call("idmvton_attn_f8_ragged" if nkt else "idmvton_attn_f8_indexed" if ix else "idmvton_attn_f8_shared" if nb else "idmvton_attn_f8", a, flops=fl,
+          bytes_=float(B * Nq * heads * 64 * (1 + out.element_size())), seg_nb=nb or ([0, 0] if ix or nkt else None), seg_index=ix, seg_nk=nkt)
     return out
 
 

@@ -19,7 +19,9 @@ The same fact across calls: `encode_garment` runs the garment side alone (cloth 
 the K / V^T projections) and returns a GarmentCache; `prepare(cloth=<GarmentCache>)` then builds a call with no garment work at all, for
 P persons on G cached garments (P % G == 0; the attention kernels read garment i % G for person i through a shared key segment) -- or, with
 `garment_index=[...]`, for any P >= 1 persons of whom person i wears garment garment_index[i] of the cache (the kernels read the garment's
-slot from a device table: an indexed key segment).
+slot from a device table: an indexed key segment).  A cache with `sizes` (empty_garment_cache, GarmentPool(mixed_sizes=True)) holds garments
+of several sizes in slots of one size; `prepare` then adds the per-person key counts of every garment feature as a second device table (a
+ragged key segment), so one call -- and one graph state -- serves persons wearing garments of different sizes.
 
 Structure of the loop.  The block order -- serial, or two streams with two alternating sets and two events per set -- is written once,
 in `drive_blocks`, which knows nothing of graphs or caches (tests/test_loop_schedule_cpu.py checks its waits on stand-in streams).  An
@@ -76,7 +78,7 @@ def drive_blocks(blocks, garment, tryon, main=None, side=None, ready=None, free=
 def _copy_state(G, st):
     """A new call's tensors -> the persistent buffers of a graph state, for every tensor the state owns and a captured graph reads (a
     GarmentCache state has no garment-side tensors)."""
-    for name in ("latents", "cond", "cloth_k", "gix"):
+    for name in ("latents", "cond", "cloth_k", "gix", "gnk"):
         if G.get(name) is not None:
             G[name].copy_(st[name])
     for name in ("ctx_t", "ctx_gk"):
@@ -163,11 +165,12 @@ class TryonEngine:
     def _graph_key(st, live):
         """One persistent graph state per shape of a call: persons, person latent size, garment latent size, block size, step noise, and on a
         GarmentCache its garment count -- or, with garment_index, nothing more: the sets of an indexed state have one slot per PERSON, so one
-        state serves every pool size and every assignment."""
+        state serves every pool size and every assignment.  A cache with `sizes` adds "ragged" (its forwards read a key-count table that a plain
+        state's captures do not have); gh, gw are then the SLOT size, and the garments' own sizes are not in the key."""
         if live:
             return (st["B"], st["h"], st["w"], st["gh"], st["gw"], st["k"], st["steps_noise"] is not None)
         return (st["B"], st["h"], st["w"], st["gh"], st["gw"], st["k"], st["steps_noise"] is not None, "cached",
-                "indexed" if st.get("gindex") is not None else st["gcache"].G)
+                "indexed" if st.get("gindex") is not None else st["gcache"].G) + (("ragged",) if st.get("gnk") is not None else ())
 
     def weights_identity(self):
         """What a GarmentCache depends on besides its inputs: every GarmentNet weight, and TryonNet's attn1.to_k / to_v (the projections of
@@ -216,6 +219,29 @@ class TryonEngine:
         return GarmentCache(G=G, timesteps=timesteps, h=h, w=w, gh=gh, gw=gw, dtype=self.dtype, attn_fp8=self.unet.attn_fp8, f8_exp=self.unet.f8_exp,
                             weights_id=self.weights_identity(), kv=kv)
 
+    def empty_garment_cache(self, G, garment_height, garment_width, num_inference_steps, scheduler="ddpm", strength=1.0, height=None, width=None):
+        """A slotted GarmentCache (one with `sizes`) of G uninitialised slots laid out for garments of garment_height x garment_width: what
+        `put` fills with garments of that size or any smaller one, and what a GarmentPool(mixed_sizes=True) takes as `like` -- a pool for a
+        maximum garment size without encoding a garment of it.  Nothing is encoded and nothing is launched: feature f of a slot has
+        round16(feature_tokens(gh, gw)[f]) rows of TryonNet's attn1 width, 16-bit (an fp8 engine quantises a slot per launch).  height /
+        width: the PERSON size the cache is declared for (default: the garment's), as in encode_garment."""
+        if garment_height % 8 or garment_width % 8:
+            raise ValueError(f"`garment_height` and `garment_width` have to be divisible by 8 but are {garment_height} and {garment_width}.")
+        H, W = height or garment_height, width or garment_width
+        if H % 8 or W % 8:
+            raise ValueError(f"`height` and `width` have to be divisible by 8 but are {H} and {W}.")
+        if G < 1:
+            raise ValueError(f"empty_garment_cache: G = {G} < 1")
+        gh, gw = garment_height // 8, garment_width // 8
+        _, timesteps = self._timesteps(scheduler, num_inference_steps, strength)
+        n = len(timesteps)
+        kv = []
+        for blk, tokens in zip(self.unet.block_order, self.unet.feature_tokens(gh, gw)):
+            C, N = blk["qkv"].shape[1], ops.round16(tokens)
+            kv.append((torch.empty(n * G * N, C, dtype=self.dtype, device=self.device), torch.empty(n * G, C, N, dtype=self.dtype, device=self.device)))
+        return GarmentCache(G=G, timesteps=timesteps, h=H // 8, w=W // 8, gh=gh, gw=gw, dtype=self.dtype, attn_fp8=self.unet.attn_fp8,
+                            f8_exp=self.unet.f8_exp, weights_id=self.weights_identity(), kv=kv, sizes=[(gh, gw)] * G)
+
     # -------------------------------------------------------------------------------------------- preparation
     @torch.no_grad()
     def prepare(self, *, image, mask_image, pose_img, cloth, prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds,
@@ -236,13 +262,17 @@ class TryonEngine:
         text_embeds_cloth and noise['cloth'] may be None.  B = image.shape[0] persons, B % G == 0, person i wears garment i % G.  A cache
         that does not cover the call (timestep, resolution, dtype mode, weights, B % G) raises ValueError before anything is launched.
         garment_index (with a GarmentCache only): B ints in [0, G), person i wears garment garment_index[i] -- any B >= 1, values may repeat,
-        no B % G rule; the cache is a pool, and G may exceed B."""
+        no B % G rule; the cache is a pool, and G may exceed B.  A cache with `sizes` (garments of several sizes in slots of one size) needs
+        garment_index: which size a person's garment has follows from the slot it names."""
         dev, dt = self.device, self.dtype
         f32 = lambda t: t.to(dev, torch.float32).contiguous()
         gcache = cloth if isinstance(cloth, GarmentCache) else None
         if garment_index is not None and gcache is None:
             raise ValueError("garment_index names garments of a GarmentCache: pass one as `cloth=` (a live call encodes one garment per person)")
         gindex = None
+        if gcache is not None and gcache.sizes is not None and garment_index is None:
+            raise ValueError("a GarmentCache with `sizes` holds garments of several sizes: pass garment_index (person i wears garment "
+                             "garment_index[i]; the i % G rule of a plain cache does not apply)")
         if gcache is not None:
             gidx = gcache.check(timesteps=self._timesteps(scheduler, num_inference_steps, strength)[1],
                                 h=(height or image.shape[-2]) // 8, w=(width or image.shape[-1]) // 8, dtype=dt, attn_fp8=self.unet.attn_fp8,
@@ -313,13 +343,18 @@ class TryonEngine:
         if gcache is None:
             # GarmentNet over consecutive timesteps per batch, blocks of 1, 2, 4, k, k, ... timesteps
             garm = dict(self._garment_inputs(cloth_lat, text_embeds_cloth, timesteps, B), gcache=None, gidx=None, garment_persons=None,
-                        gindex=None, gix=None)
+                        gindex=None, gix=None, gnk=None)
         else:                                                # the same blocks drive the loop; their garment side is a read of the cache
             k, blocks = self._block_schedule(len(timesteps))
+            if gcache.sizes is not None:                     # [features][2B]: the real tokens of person b % B's garment, in both CFG halves
+                per = [self.unet.feature_tokens(*sz) for sz in gcache.garment_sizes(gindex)]
+                gnk = torch.tensor([[p[f] for p in per] * 2 for f in range(len(per[0]))], dtype=torch.int32, device=dev)
             garm = dict(cloth=None, ctx_g=None, temb_g=None, k=k, blocks=blocks, temb_gk=None, cloth_k=None, ctx_gk=None,
                         gcache=gcache, gidx=gidx, garment_persons=B, gindex=gindex,
                         # the table the kernels read: person -> garment of the cache (a graph state keeps its own: person -> set slot)
-                        gix=torch.tensor(gindex, dtype=torch.int32, device=dev) if gindex is not None else None)
+                        gix=torch.tensor(gindex, dtype=torch.int32, device=dev) if gindex is not None else None,
+                        # the second table, on a cache with sizes only: per garment feature the key count of every batch
+                        gnk=gnk if gcache.sizes is not None else None)
         coef = torch.tensor([list(sched.coeffs(t)) + [guidance_scale] for t in timesteps], dtype=torch.float32, device=dev)
         steps_noise = f32(noise["steps"]) if noise.get("steps") is not None and scheduler == "ddpm" else None
         return dict(B=B, h=h, w=w, gh=gh, gw=gw, timesteps=timesteps, latents=latents.contiguous(), cond=cond,
@@ -344,7 +379,7 @@ class TryonEngine:
         # garment_persons: None = one garment entry per conditional batch (unet.forward's default); B on a GarmentCache call, where kv_j
         # holds G garments for the B persons (a shared segment when G < B)
         eps, _ = self.unet.forward(st["x_in"], temb_t, st["ctx_t"], 2 * B, h, w, garment_kv=kv_j, garment_persons=st["garment_persons"],
-                                   garment_hw=(st["gh"], st["gw"]), garment_index=st.get("gix"))   # :1796-1808
+                                   garment_hw=(st["gh"], st["gw"]), garment_index=st.get("gix"), garment_nk=st.get("gnk"))   # :1796-1808
         ops.cfg_step(eps, st["latents"], noise, coef)                                      # :1814-1823
         return eps
 
@@ -445,6 +480,8 @@ class TryonEngine:
         G = {name: st[name] for name in ("B", "h", "w", "gh", "gw", "k", "garment_persons", "latents", "cond", "x_in", "ctx_t")}
         # indexed: the table person -> set slot, a persistent buffer whose pointer the captured graphs hold; its contents are copied per call
         G["gix"] = self._slot_table(st)
+        # ragged: the key-count table, persistent in the same way (the sets copy whole slots, so it is the call's own table)
+        G["gnk"] = st["gnk"].clone() if st.get("gnk") is not None else None
         G.update(tt=st["temb_t"][0].clone(), cf=st["coef"][0].clone(), nz=st["steps_noise"][0].clone() if has_noise else None, graphs={},
                  side=torch.cuda.Stream(), ready=[torch.cuda.Event(), torch.cuda.Event()], free=[torch.cuda.Event(), torch.cuda.Event()],
                  # graphs that replay one after another on ONE stream may share a memory pool: all TryonNet graphs (main stream), all

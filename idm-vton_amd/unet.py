@@ -295,6 +295,8 @@ class HipUNet:
                 gseg.update(nb=Bg, index=gix)
             elif Bg < P:                                         # a shared segment: conditional row i reads garment i % G
                 gseg["nb"] = Bg
+            if garment.get("nk_table") is not None:              # a ragged segment: batch b has nk_table[b] of the slot's gnk keys
+                gseg["nk_table"] = garment["nk_table"][garment["idx"] - 1]
             segs.append(gseg)
         att = torch.empty(M, C, dtype=dt, device=dev)
         if self.attn_fp8:
@@ -303,11 +305,12 @@ class HipUNet:
                 Bs, Ns = sg["vt"].shape[0], sg["k_rows"]
                 if sg["k"].dtype == torch.uint8:                                            # written as e4m3 by its projection
                     segs8.append(dict(k8=sg["k"], vt8=sg["vt"], nk=sg["nk"], ldk=sg["ldk"], ldvt=sg["ldvt"], k_rows=Ns, b0=sg.get("b0", 0), nb=sg.get("nb", 0),
-                                      index=sg.get("index")))
+                                      index=sg.get("index"), nk_table=sg.get("nk_table")))
                     continue
                 k8 = ops.quant_f8(sg["k"], 2.0 ** ek)                                   # [Bs*Ns][C] (row stride ldk)
-                vt8 = ops.quant_f8(sg["vt"].reshape(Bs * C, Ns), 2.0 ** ev, mode=1)     # 16-bit key order -> fp8 slot order
-                segs8.append(dict(k8=k8, vt8=vt8, nk=sg["nk"], ldk=C, ldvt=vt8.shape[1], k_rows=Ns, b0=sg.get("b0", 0), nb=sg.get("nb", 0), index=sg.get("index")))
+                vt8 = ops.quant_f8(sg["vt"].reshape(Bs * C, Ns), 2.0 ** ev, mode=1)     # 16-bit key order -> fp8 slot order (a ragged slot: whole)
+                segs8.append(dict(k8=k8, vt8=vt8, nk=sg["nk"], ldk=C, ldvt=vt8.shape[1], k_rows=Ns, b0=sg.get("b0", 0), nb=sg.get("nb", 0), index=sg.get("index"),
+                                  nk_table=sg.get("nk_table")))
             if f8:
                 q8, ldq8 = qk, 2 * C
             else:
@@ -414,7 +417,7 @@ class HipUNet:
 
     # ------------------------------------------------------------------------------------------------ forward
     def forward(self, x, temb, ctx, B, H, W, garment_feats=None, garment_kv=None, feats_buf=None, garment_persons=None, garment_hw=None,
-                garment_index=None):
+                garment_index=None, garment_nk=None):
         """x: NHWC [B][H*W][cin_pad] (channels >= in_channels zero); temb: [B][sum Cout] (time_embeddings()[step]);
         ctx: encode_context(); garment_feats: list of [Bg][Ng][C] (Bg <= B; batches < B-Bg see all-zero features).
         garment_hw = the garment's own latent (gh, gw) when it is not (H, W): its features have feature_tokens(gh, gw) real tokens per level
@@ -425,9 +428,12 @@ class HipUNet:
         garment_index = an int32 device tensor of P entries (with garment_kv or garment_feats of any Bg >= 1 garments): the last P batches are
         conditional and row i of them reads garment garment_index[i] through an indexed attention segment -- no relation between Bg and P, and
         the table is read by the kernels, so a captured forward follows its contents.
+        garment_nk = an int32 device tensor [features][B] (contiguous): row f holds, per batch, the real token count of garment feature f for
+        that batch -- garments of several sizes in slots of garment_hw's size (the rows of garment_kv / garment_feats), each at the front of
+        its slot.  Both CFG halves carry their person's count: an unconditional row counts the zero features of its own garment's shape.
         Returns (noise NHWC [B][H*W][n_out] for TryonNet | None, exported features for GarmentNet)."""
         topo = self.topo
-        garment = dict(feats=garment_feats, kv=garment_kv, feats_buf=feats_buf, idx=0, persons=garment_persons, index=garment_index,
+        garment = dict(feats=garment_feats, kv=garment_kv, feats_buf=feats_buf, idx=0, persons=garment_persons, index=garment_index, nk_table=garment_nk,
                        nk=self.feature_tokens(*garment_hw) if garment_hw is not None and self.tryon else None)
         feats = []
         stop = None if self.tryon else self.num_features()

@@ -188,6 +188,20 @@ int idmvton_attn_fwd_shared(const idmvton_attn_args* a, const int32_t seg_nb[2],
  * pointer, not its values; values are clamped to [0, seg_nb[s] - 1] in the kernel.  A NULL table is idmvton_attn_fwd_shared's rule exactly;
  * a non-NULL one needs seg_nb[s] >= 1 and seg_b0[s] < B, and seg_nb[s] may exceed B - seg_b0[s].  Mode CROSS takes no table. */
 int idmvton_attn_fwd_indexed(const idmvton_attn_args* a, const int32_t seg_nb[2], const int32_t* const seg_index[2], void* stream);
+/* The same launch with a RAGGED key segment: seg_nk[s] is NULL or a device pointer to B int32 values, one per query batch FROM BATCH 0 ON (not
+ * from seg_b0[s]), and query batch b has seg_nk[s][b] keys of segment s -- the elements of a segment are slots of nk[s] keys of which each
+ * garment fills its own front part.  Where the segment is present for b the value is the length of the walk and the bound of the last tile's
+ * mask; where it is absent (b < seg_b0[s]) it is the key count of the closed form, so an unconditional row counts the tokens of ITS person's
+ * garment.  a->nk[s] stays the capacity: k_rows, ldvt >= roundup16(nk), the descriptor sizes and the 2 GiB checks use it, the kernel choice and
+ * the grid are those of the launch without a table, and values are clamped to [1, nk[s]] in the kernel.  Read like seg_index (one scalar load
+ * per workgroup, when the kernel runs).  With a table, nothing the kernels read at or beyond these bounds reaches the result: K rows >= the
+ * batch's count are not fetched, and V^T positions >= roundup16(count) are not fetched (idmvton_attn_f8_ragged: K rows >= count are read as
+ * row count - 1 and masked, V^T positions >= roundup64(count) are not read); V^T positions from count to that bound must be finite (fp8: zero),
+ * as they must beyond nk without a table.  seg_index may be NULL (no index table for either segment), and either table of a segment may be NULL
+ * while the other is not; a NULL seg_nk[s] is nk[s] for every batch, i.e. idmvton_attn_fwd_indexed exactly.  seg_nb and seg_nk themselves must
+ * not be NULL.  Mode CROSS takes no table (IDMVTON_E_ARG); a table that is not 4-byte aligned is IDMVTON_E_ALIGN. */
+int idmvton_attn_fwd_ragged(const idmvton_attn_args* a, const int32_t seg_nb[2], const int32_t* const seg_index[2],
+                            const int32_t* const seg_nk[2], void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * idmvton_attn_f8 / idmvton_quant_f8 : the fp8 (OCP e4m3) variant of the self-attention above, on the block-scaled MFMA
@@ -218,6 +232,9 @@ int idmvton_attn_f8(const idmvton_attn_f8_args* a, void* stream);
 int idmvton_attn_f8_shared(const idmvton_attn_f8_args* a, const int32_t seg_nb[2], void* stream);   /* seg_nb: as idmvton_attn_fwd_shared */
 /* seg_nb / seg_index: as idmvton_attn_fwd_indexed.  This kernel reads through plain pointers: the clamp of the table's values is its bound. */
 int idmvton_attn_f8_indexed(const idmvton_attn_f8_args* a, const int32_t seg_nb[2], const int32_t* const seg_index[2], void* stream);
+/* seg_nk: as idmvton_attn_fwd_ragged, with this kernel's bounds (whole 64-key tiles of V^T up to roundup64(count), zero from count on). */
+int idmvton_attn_f8_ragged(const idmvton_attn_f8_args* a, const int32_t seg_nb[2], const int32_t* const seg_index[2],
+                           const int32_t* const seg_nk[2], void* stream);
 typedef struct {
     int32_t dtype; int32_t mode; int32_t rows, cols;
     const void* src; int32_t lds;
