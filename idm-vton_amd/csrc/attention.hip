@@ -1334,6 +1334,8 @@ static int launch_attn(AttnParams& p, int tune, hipStream_t st) {
         dim3 gridp;
         attn_grid(p, 256, gridp);
         if (MODE != IDMVTON_ATTN_SELF) return idmvton_set_error(IDMVTON_E_ARG, "attn_fwd: ablation kernels are SELF mode only");
+        if (nw != 8 || stg != 2)
+            return idmvton_set_error(IDMVTON_E_ARG, "attn_fwd: the ablation kernels are 8 waves, 2 stages (tune waves=%d stages=%d)", nw, stg);
         if (((tune >> 16) & 0xff) == 4) hipLaunchKernelGGL((attn_pp_kernel<T, 2, false, 1>), gridp, dim3(512), 0, st, p);
         else if (((tune >> 16) & 0xff) == 5) hipLaunchKernelGGL((attn_pp_kernel<T, 2, false, 2>), gridp, dim3(512), 0, st, p);
         else hipLaunchKernelGGL((attn_pp_kernel<T, 2, false, 3>), gridp, dim3(512), 0, st, p);
@@ -1343,6 +1345,8 @@ static int launch_attn(AttnParams& p, int tune, hipStream_t st) {
     if (((tune >> 16) & 0xff) == 7 || ((tune >> 16) & 0xff) == 8) {   // attn_pf_kernel: fragments prefetched a phase early (7: row sums on the matrix pipe)
         if (MODE != IDMVTON_ATTN_SELF || !p.q_prescaled)
             return idmvton_set_error(IDMVTON_E_ARG, "attn_fwd: the prefetch kernel needs SELF mode and a pre-multiplied q");
+        if (nw != 8 || stg != 3)                         // the one build there is: another word would run it under a name it does not have
+            return idmvton_set_error(IDMVTON_E_ARG, "attn_fwd: the prefetch kernel is 8 waves, 3 stages (tune waves=%d stages=%d)", nw, stg);
         static const float thr_tab[4] = {4.f, 0.f, 8.f, 2.f};
         p.pp_flags = 0;
         p.pp_thr = thr_tab[(tune >> 26) & 3];
@@ -1356,6 +1360,8 @@ static int launch_attn(AttnParams& p, int tune, hipStream_t st) {
     if (((tune >> 16) & 0xff) == 16) {   // attn_sp_kernel (software-pipelined, speculative exponentials, row-sum overflow test)
         if (MODE != IDMVTON_ATTN_SELF || !p.q_prescaled)
             return idmvton_set_error(IDMVTON_E_ARG, "attn_fwd: the software-pipelined kernel needs SELF mode and a pre-multiplied q");
+        if ((nw != 4 && nw != 8) || stg != 3)
+            return idmvton_set_error(IDMVTON_E_ARG, "attn_fwd: the software-pipelined kernel is 4 or 8 waves, 3 stages (tune waves=%d stages=%d)", nw, stg);
         static const float lim_tab[4] = {512.f, 32.f, 8192.f, 128.f};   // row-sum limits (tune bits 26-27): P <= limit while the max is kept
         p.pp_thr = lim_tab[(tune >> 26) & 3];
         dim3 gridp;

@@ -465,11 +465,14 @@ def softmax_rows(x, scale, n_valid=0):
     return x
 
 
-def softmax_rows_split(x, scale, dtype, n_valid=0):
+def softmax_rows_split(x, scale, dtype, n_valid=0, out=None):
     """softmax(scale * x) over the last dim of an fp32 2-D tensor -> the pair [rows][2n] = [hi | lo] of `dtype` (x is left as it is);
-    n_valid: over the first n_valid columns, the rest 0."""
+    n_valid: over the first n_valid columns, the rest 0.  out: a [rows][2n] tensor of `dtype` (row stride out.stride(0)) to write instead of a new one."""
     rows, n = x.shape
-    out = torch.empty((rows, 2 * n), dtype=dtype, device=x.device)
+    if out is None:
+        out = torch.empty((rows, 2 * n), dtype=dtype, device=x.device)
+    elif tuple(out.shape) != (rows, 2 * n) or out.dtype != dtype:
+        raise ValueError(f"softmax_rows_split(out=...): needs shape {(rows, 2 * n)} of {dtype}, got {tuple(out.shape)} of {out.dtype}")
     a = ffi.SoftmaxArgs()
     a.n_valid = n_valid
     a.dtype, a.rows, a.n, a.ld = _dt(out), rows, n, x.stride(0)
@@ -478,12 +481,16 @@ def softmax_rows_split(x, scale, dtype, n_valid=0):
     return out
 
 
-def split(x, dtype, mode=ffi.SPLIT_ACT):
+def split(x, dtype, mode=ffi.SPLIT_ACT, out=None):
     """fp32 [rows][cols] -> operand pairs of the split-precision GEMMs: SPLIT_ACT [rows][2 cols] = [hi | lo]; SPLIT_W3 [rows][3 cols] =
-    [hi | hi | lo]; SPLIT_W3T [cols][3 rows] = the W3 form of the transpose."""
+    [hi | hi | lo]; SPLIT_W3T [cols][3 rows] = the W3 form of the transpose.  out: a tensor of that shape and `dtype` (row stride out.stride(0))
+    to write instead of a new one."""
     rows, cols = x.shape
     shape = {ffi.SPLIT_ACT: (rows, 2 * cols), ffi.SPLIT_W3: (rows, 3 * cols), ffi.SPLIT_W3T: (cols, 3 * rows)}[mode]
-    out = torch.empty(shape, dtype=dtype, device=x.device)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=x.device)
+    elif tuple(out.shape) != shape or out.dtype != dtype:
+        raise ValueError(f"split(out=...): needs shape {shape} of {dtype}, got {tuple(out.shape)} of {out.dtype}")
     a = ffi.SplitArgs()
     a.dtype, a.mode, a.rows, a.cols = _dt(out), mode, rows, cols
     a.src, a.lds, a.dst, a.ldd = _ptr(x), x.stride(0), _ptr(out), out.stride(0)

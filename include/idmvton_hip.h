@@ -166,12 +166,18 @@ typedef struct {
                                     tile, stages 2 (two-buffer) | 3 | 4 (LDS ring), waves 2|4|8 (any mode).  kernel 2|3: the ping-pong kernel
                                     (SELF mode, 8 waves, stages 2|3; 2 = two workgroups per CU, 3 = one per CU with every fragment of a block
                                     prefetched); flags bit0 = pair waves (w, w^1) instead of (w, w+4), bit1 = no s_setprio, bits 2..3 =
-                                    deferred-rescale threshold selector {0: 4, 1: 0 (exact skip only), 2: 8, 3: 2} in log2 units.
-                                    kernel 7|8: the ping-pong kernel with each MFMA block's fragments read from LDS one phase early (3 stages;
-                                    7 = row sums on the matrix pipe); needs q_prescaled.  kernel 16: the software-pipelined kernel (every wave
+                                    deferred-rescale threshold selector {0: 4, 1: 0 (exact skip only), 2: 8, 3: 2} in log2 units.  The
+                                    stages byte sets the ring depth of kernel 3's deep build only, and that build needs q_prescaled:
+                                    kernel 2 with either stages value, and kernel 3 with a raw q, run the SAME two-stage 128-register
+                                    build (no error).  kernel 4|5|6: timing-only ablation builds of that two-stage build (8 waves, 2 stages,
+                                    SELF mode; their results are not attention).
+                                    kernel 7|8: the ping-pong kernel with each MFMA block's fragments read from LDS one phase early (8 waves,
+                                    3 stages; 7 = row sums on the matrix pipe); needs q_prescaled.  kernel 16: the software-pipelined kernel (every wave
                                     overlaps the exponentials of tile i-1 with the MFMAs of PV(i-2) and QK^T(i); exponentials are speculative
                                     and a row-sum bound replaces the row max), waves 8 | 4 = 256 | 128 query rows per workgroup, flags bits
-                                    2..3 = row-sum limit selector {0: 512, 1: 32, 2: 8192, 3: 128}; SELF mode, needs q_prescaled.  auto picks
+                                    2..3 = row-sum limit selector {0: 512, 1: 32, 2: 8192, 3: 128}, 3 stages; SELF mode, needs q_prescaled.
+                                    A kernel number not listed, and a (stages, waves) pair not listed for its kernel, is IDMVTON_E_ARG,
+                                    returned before anything is launched.  auto picks
                                     kernel 16 for SELF launches with a pre-multiplied q and >= 128 query rows */
     int32_t q_prescaled;         /* 1: q is already multiplied by softmax_scale * log2(e) = 0.125 * 1.4426950408889634 (gemm_conv's colscale
                                     applies it in fp32 in the projection epilogue, same single rounding as an unscaled q) */
@@ -215,7 +221,8 @@ int idmvton_attn_fwd_ragged(const idmvton_attn_args* a, const int32_t seg_nb[2],
  * qk_scale_exp = -(eq + ek), v_scale_exp = -ev: applied by the MFMA's E8M0 scale operands.  Output in out_dtype (f16 / bf16).
  * Accuracy: e4m3 carries 3 mantissa bits; on N(0,1) operands the output is within 6e-2 .. 1e-1 max-rel of fp32 SDPA on the unquantised
  * operands and 2e-2 of fp32 SDPA on the dequantised ones (tests/kernel_checks.py: check_attn_f8; stated tolerances 1.2e-1 / 3e-2).
- * idmvton_quant_f8: mode 0 rows (dst[r][c] = e4m3(src[r*lds + c] * scale), cols % 16 == 0), mode 1 the V^T re-order above;
+ * idmvton_quant_f8: mode 0 rows (dst[r][c] = e4m3(src[r*lds + c] * scale), cols % 16 == 0; bytes [cols, ldd) of a row are not written),
+ * mode 1 the V^T re-order above (ldd % 64 == 0, ldd >= roundup64(cols); the WHOLE row of ldd bytes is written, zero from key `cols` on);
  * saturating at +-448; lds in source elements, ldd in bytes.
  * ------------------------------------------------------------------------------------------------------------- */
 typedef struct {

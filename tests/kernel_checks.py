@@ -11,6 +11,8 @@ import os
 import torch
 import torch.nn.functional as F
 
+from tests.frames import Tight
+
 TOL = {torch.float16: 2e-3, torch.bfloat16: 1.6e-2}
 
 
@@ -24,6 +26,11 @@ def relerr(x, ref):
 def _r(*shape, dtype, dev, scale=1.0, seed=0):
     g = torch.Generator(device="cpu").manual_seed(seed + sum(shape) * 7919 % 100003)
     return (torch.randn(*shape, generator=g) * scale).to(dtype).to(dev)
+
+
+# Every check below takes its tensors from an allocation policy (tests/frames.py): `alloc=None` is Tight -- inputs as generated, outputs
+# torch.empty of the logical shape, zero padding: what this file always ran -- and tests/test_kernel_frames_gpu.py passes a Framed one
+# (every operand strided inside a NaN frame).  The reference arithmetic is the same lines either way.
 
 
 # ------------------------------------------------------------------------------------------------ MFMA layout probe
@@ -50,59 +57,64 @@ def _hint(variant, bn, bm):
 
 
 # ------------------------------------------------------------------------------------------------ GEMM / conv
-def check_linear(M, N, K, dtype, dev, bias=True, res=True, rowbias=False, tile_hint=0, seed=0):
+def check_linear(M, N, K, dtype, dev, bias=True, res=True, rowbias=False, tile_hint=0, seed=0, alloc=None, groups=None):
+    """groups: row groups of the rowbias (default 4 when M % 4 == 0, else 1); M % groups == 0."""
     from idm_vton_amd import ops
-    x = _r(M, K, dtype=dtype, dev=dev, seed=seed)
-    w = _r(N, K, dtype=dtype, dev=dev, scale=K ** -0.5, seed=seed + 1)
-    b = _r(N, dtype=dtype, dev=dev, seed=seed + 2) if bias else None
-    rs = _r(M, N, dtype=dtype, dev=dev, seed=seed + 3) if res else None
+    al = alloc or Tight()
+    x = al.inp("x", _r(M, K, dtype=dtype, dev=dev, seed=seed))
+    w = al.inp("w", _r(N, K, dtype=dtype, dev=dev, scale=K ** -0.5, seed=seed + 1), contig=True)
+    b = al.inp("bias", _r(N, dtype=dtype, dev=dev, seed=seed + 2), contig=True) if bias else None
+    rs = al.inp("res", _r(M, N, dtype=dtype, dev=dev, seed=seed + 3)) if res else None
     ref = x.float() @ w.float().t()
     if bias:
         ref = ref + b.float()
     kw = {}
     if rowbias:
-        G = 4 if M % 4 == 0 else 1
-        rb = _r(G, N, dtype=dtype, dev=dev, seed=seed + 4)
+        G = groups or (4 if M % 4 == 0 else 1)
+        rb = al.inp("rowbias", _r(G, N, dtype=dtype, dev=dev, seed=seed + 4))
         ref = ref + rb.float().repeat_interleave(M // G, dim=0)
-        kw = dict(rowbias=rb, rowbias_ld=N, rows_per_group=M // G)
+        kw = dict(rowbias=rb, rowbias_ld=rb.stride(0), rows_per_group=M // G)
     if res:
         ref = ref + rs.float()
-    out = ops.linear(x, w, bias=b, res=rs, tile_hint=tile_hint, **kw)
-    return relerr(out, ref)
+    out = ops.linear(x, w, bias=b, res=rs, out=al.out("out", (M, N), dtype, dev, own=True), tile_hint=tile_hint, **kw)
+    return relerr(al.done("out", out), ref)
 
 
-def check_geglu(M, C, dtype, dev, seed=0, tile_hint=0):
+def check_geglu(M, C, dtype, dev, seed=0, tile_hint=0, alloc=None):
     """GEGLU(x) = h * gelu(gate), [h | gate] = x W^T + b  (weights interleaved in 64-row blocks for the kernel)."""
     from idm_vton_amd import ops
     from idm_vton_amd.weights import interleave_geglu
+    al = alloc or Tight()
     inner = 4 * C
-    x = _r(M, C, dtype=dtype, dev=dev, seed=seed)
+    x = al.inp("x", _r(M, C, dtype=dtype, dev=dev, seed=seed))
     w = _r(2 * inner, C, dtype=dtype, dev=dev, scale=C ** -0.5, seed=seed + 1)
     b = _r(2 * inner, dtype=dtype, dev=dev, seed=seed + 2)
     y = x.float() @ w.float().t() + b.float()
     h, g = y.chunk(2, dim=-1)
     ref = h * F.gelu(g)
     wi, bi = interleave_geglu(w, b)
-    out = ops.linear(x, wi, bias=bi, geglu=True, tile_hint=tile_hint)
-    return relerr(out, ref)
+    wi, bi = al.inp("w", wi, contig=True), al.inp("bias", bi, contig=True)
+    out = ops.linear(x, wi, bias=bi, geglu=True, out=al.out("out", (M, inner), dtype, dev, own=True), tile_hint=tile_hint)
+    return relerr(al.done("out", out), ref)
 
 
-def check_vt(B, Ntok, C, dtype, dev, seed=0, tile_hint=0):
+def check_vt(B, Ntok, C, dtype, dev, seed=0, tile_hint=0, alloc=None):
     """Fused QKV-style projection: columns [0,2C) normal, columns [2C,3C) written transposed as V^T[b][c][tok]."""
     from idm_vton_amd import ops
+    al = alloc or Tight()
     M = B * Ntok
-    x = _r(M, C, dtype=dtype, dev=dev, seed=seed)
-    w = _r(3 * C, C, dtype=dtype, dev=dev, scale=C ** -0.5, seed=seed + 1)
+    x = al.inp("x", _r(M, C, dtype=dtype, dev=dev, seed=seed))
+    w = al.inp("w", _r(3 * C, C, dtype=dtype, dev=dev, scale=C ** -0.5, seed=seed + 1), contig=True)
     ref = x.float() @ w.float().t()
-    out = torch.zeros(M, 2 * C, dtype=dtype, device=dev)
-    vt = torch.zeros(B, C, Ntok, dtype=dtype, device=dev)
+    out = al.out("out", (M, 2 * C), dtype, dev, init=0.0)
+    vt = al.out("vt", (B, C, Ntok), dtype, dev, contig=True, init=0.0)            # V^T is contiguous by ABI: framed before and after
     vt_ref = ref[:, 2 * C:].reshape(B, Ntok, C).transpose(1, 2)
     ops.linear(x, w, out=out, vt=vt, vt_n0=2 * C, vt_tokens=Ntok, vt_perm=False, tile_hint=tile_hint)     # plain transpose
     e1 = relerr(out, ref[:, : 2 * C])
     e2 = relerr(vt, vt_ref)
     e3 = 0.0
     if Ntok % 16 == 0:                                   # attention key order (bits 2/3 of the token index swapped per 16)
-        vt2 = torch.zeros(B, C, Ntok, dtype=dtype, device=dev)
+        vt2 = al.out("vt_perm", (B, C, Ntok), dtype, dev, contig=True, init=0.0)
         ops.linear(x, w, out=out, vt=vt2, vt_n0=2 * C, vt_tokens=Ntok, tile_hint=tile_hint)
         e3 = relerr(vt2, ops.key_order(vt_ref))
         if not torch.equal(ops.key_order(vt2), vt):      # same values, only the position differs
@@ -114,27 +126,31 @@ def _nhwc(t):
     return t.permute(0, 2, 3, 1).contiguous()
 
 
-def check_conv_ups_odd(B, Cin, Cout, H, W, Ho, Wo, dtype, dev, seed=0):
+def check_conv_ups_odd(B, Cin, Cout, H, W, Ho, Wo, dtype, dev, seed=0, tile_hint=0, alloc=None):
     """Upsample2D with `upsample_size` (F.interpolate(size=(Ho, Wo)) nearest, Ho in {2H - 1, 2H}) + 3x3 conv, fused in the gather."""
     from idm_vton_amd import ops
     from idm_vton_amd.weights import conv_weight_nhwc
+    al = alloc or Tight()
     x = _r(B, H, W, Cin, dtype=dtype, dev=dev, seed=seed)
     w = _r(Cout, Cin, 3, 3, dtype=dtype, dev=dev, scale=(9 * Cin) ** -0.5, seed=seed + 1)
     b = _r(Cout, dtype=dtype, dev=dev, seed=seed + 2)
     up = F.interpolate(x.float().permute(0, 3, 1, 2), size=(Ho, Wo), mode="nearest")
     ref = F.conv2d(up, w.float(), b.float(), padding=1).permute(0, 2, 3, 1).reshape(B * Ho * Wo, Cout)
-    out = ops.gemm_conv(ops.conv_segs(x, 3, 1), conv_weight_nhwc(w), B * Ho * Wo, Ho=Ho, Wo=Wo, Hi=H, Wi=W, ups=True, bias=b)
-    return relerr(out, ref)
+    xt, c0 = al.chan("x", x)
+    out = ops.gemm_conv(ops.conv_segs(xt, 3, 1, coff=c0, length=Cin), al.inp("w", conv_weight_nhwc(w), contig=True), B * Ho * Wo, Ho=Ho, Wo=Wo, Hi=H, Wi=W,
+                        ups=True, bias=al.inp("bias", b, contig=True), out=al.out("out", (B * Ho * Wo, Cout), dtype, dev, own=True), tile_hint=tile_hint)
+    return relerr(al.done("out", out), ref)
 
 
 def check_conv(B, Cin, Cout, H, W, dtype, dev, k=3, stride=1, ups=False, split=0, shortcut=0, temb=False, res=False,
-               seed=0, tile_hint=0):
+               seed=0, tile_hint=0, alloc=None):
     """3x3 / 1x1 conv over NHWC with the fused extras of ResnetBlock2D:
     split>0  : input is cat([x1 (split ch), x2]) along C, never materialised (two pointers);
     shortcut : extra 1x1 conv of a second tensor (`shortcut` channels) fused as centre-tap K segments;
     temb     : + per-batch row vector; res: + residual; ups: nearest-2x upsample fused into the gather."""
     from idm_vton_amd import ops
     from idm_vton_amd.weights import conv_weight_nhwc
+    al = alloc or Tight()
     pad = (k - 1) // 2
     x = _r(B, Cin, H, W, dtype=dtype, dev=dev, seed=seed)
     w = _r(Cout, Cin, k, k, dtype=dtype, dev=dev, scale=(Cin * k * k) ** -0.5, seed=seed + 1)
@@ -144,45 +160,47 @@ def check_conv(B, Cin, Cout, H, W, dtype, dev, k=3, stride=1, ups=False, split=0
     Ho, Wo = ref.shape[-2:]
     xn = _nhwc(x)
     if split:
-        x1, x2 = xn[..., :split].contiguous(), xn[..., split:].contiguous()
+        (x1, c1), (x2, c2) = al.chan("x1", xn[..., :split].contiguous()), al.chan("x2", xn[..., split:].contiguous())
         segs = []
         for ky in range(k):
             for kx in range(k):
-                segs.append(ops.SegSpec(x1, 0, split, ky - pad, kx - pad))
-                segs.append(ops.SegSpec(x2, 0, Cin - split, ky - pad, kx - pad))
+                segs.append(ops.SegSpec(x1, c1, split, ky - pad, kx - pad))
+                segs.append(ops.SegSpec(x2, c2, Cin - split, ky - pad, kx - pad))
     else:
-        segs = ops.conv_segs(xn, k, pad)
+        xt, c0 = al.chan("x", xn)
+        segs = ops.conv_segs(xt, k, pad, coff=c0, length=Cin)
     wk = conv_weight_nhwc(w)
     kw = {}
     if shortcut:
         xs = _r(B, shortcut, Ho, Wo, dtype=dtype, dev=dev, seed=seed + 5)
         ws = _r(Cout, shortcut, 1, 1, dtype=dtype, dev=dev, scale=shortcut ** -0.5, seed=seed + 6)
         ref = ref + F.conv2d(xs.float(), ws.float())
-        xsn = _nhwc(xs)
-        segs.append(ops.SegSpec(xsn, 0, shortcut, 0, 0))
+        xsn, cs = al.chan("xs", _nhwc(xs))
+        segs.append(ops.SegSpec(xsn, cs, shortcut, 0, 0))
         wk = torch.cat([wk, ws.reshape(Cout, shortcut)], dim=1).contiguous()
         assert stride == 1 and not ups
     M = B * Ho * Wo
     if temb:
-        tb = _r(B, Cout, dtype=dtype, dev=dev, seed=seed + 3)
+        tb = al.inp("rowbias", _r(B, Cout, dtype=dtype, dev=dev, seed=seed + 3))
         ref = ref + tb.float()[:, :, None, None]
-        kw.update(rowbias=tb, rowbias_ld=Cout, rows_per_group=Ho * Wo)
+        kw.update(rowbias=tb, rowbias_ld=tb.stride(0), rows_per_group=Ho * Wo)
     if res:
         rs = _r(B, Cout, Ho, Wo, dtype=dtype, dev=dev, seed=seed + 4)
         ref = ref + rs.float()
-        kw.update(res=_nhwc(rs).reshape(M, Cout))
+        kw.update(res=al.inp("res", _nhwc(rs).reshape(M, Cout)))
     if len(segs) > 12:
         raise ValueError("too many segments for one launch")
-    out = ops.gemm_conv(segs, wk, M, Ho=Ho, Wo=Wo, Hi=H, Wi=W, stride=stride, ups=ups, bias=bias, tile_hint=tile_hint, **kw)
-    return relerr(out.reshape(B, Ho, Wo, Cout), _nhwc(ref))
+    out = ops.gemm_conv(segs, al.inp("w", wk, contig=True), M, Ho=Ho, Wo=Wo, Hi=H, Wi=W, stride=stride, ups=ups, bias=al.inp("bias", bias, contig=True),
+                        out=al.out("out", (M, Cout), dtype, dev, own=True), tile_hint=tile_hint, **kw)
+    return relerr(al.done("out", out).reshape(B, Ho, Wo, Cout), _nhwc(ref))
 
 
 # ------------------------------------------------------------------------------------------------ attention
-def _key_order_padded(v, nk):
-    """v [B][nk][C] -> (V^T [B][C][round16(nk)] in idmvton_attn_fwd's key order, padded keys zero; row length)."""
+def _key_order_padded(v, nk, pad=0.0, extra=0):
+    """v [B][nk][C] -> (V^T [B][C][round16(nk) + extra] in idmvton_attn_fwd's key order, the positions of keys >= nk holding `pad`; row length)."""
     from idm_vton_amd import ops
-    ld = ops.round16(nk)
-    vt = torch.zeros(v.shape[0], v.shape[2], ld, dtype=v.dtype, device=v.device)
+    ld = ops.round16(nk) + extra
+    vt = torch.full((v.shape[0], v.shape[2], ld), pad, dtype=v.dtype, device=v.device)
     vt[:, :, :nk] = v.transpose(1, 2)
     return ops.key_order(vt), ld
 
@@ -227,6 +245,116 @@ def check_attn_self(B, heads, N, dtype, dev, n_garm=0, b0=0, scale=1.0, seed=0, 
     return _run_attn(q, out, segs, heads, tune, prescaled, sp, kk, vv, ref)
 
 
+ENTRIES = ("plain", "shared", "indexed", "ragged")
+
+
+def _f8_slot_key(n, dev):
+    """Position -> key of idmvton_attn_f8's V^T slot order (include/idmvton_hip.h): position 64t + 32u + 16kb + 4g + j holds key 64t + 32kb + 8g + 4u + j."""
+    pos = torch.arange(n, device=dev)
+    return 64 * (pos // 64) + 32 * ((pos // 16) % 2) + 8 * ((pos // 4) % 4) + 4 * ((pos // 32) % 2) + pos % 4
+
+
+def check_attn_product(dtype, dev, tune=0, entry="plain", f8=False, alloc=None, B=3, heads=2, Nq=200, k_rows=208, n_garm=72, g_rows=80, b0=1, seed=0,
+                       nk_own=None):
+    """SELF attention in the launch geometry of unet.py's _block, which the checks above do not have: q and k are the column halves of ONE
+    [B * k_rows][2C] buffer (ldq = ldk = 2C), the own segment has nk = nk_own (default Nq) keys in k_rows >= nk rows per batch element, the garment segment its own
+    n_garm keys in g_rows rows from batch b0 on, and every V^T row is longer than round16(nk).  K rows nk..k_rows-1 hold what the policy puts
+    where the header says `masked` (zero / NaN), V^T positions of keys >= nk what it puts where the header says `finite` (zero / 1.0e4; the
+    e4m3 V^T tail inside the last 64-key tile stays zero: the header says zero there).
+    entry: plain (one garment element per conditional batch), shared (one element, every batch reads it), indexed (a pool of 4 slots, batches read
+    slots 2 and 0, ...; the slots nobody reads poisoned throughout), ragged (the same pool with slot lengths n, n/5, 5n/9, n: each batch has its
+    garment's count, the unconditional batches count their person's garment in the closed form; beyond a slot's length K is poisoned, V^T
+    holds the `finite` filler up to round16 / zero up to round64 (fp8) and is poisoned beyond).
+    f8: idmvton_attn_f8 on e4m3 bytes made by torch's own conversion (byte strides); returns (error against fp32 SDPA on the unquantised operands,
+    error against fp32 SDPA on the dequantised ones) -- the 1.2e-1 / 3e-2 bars of check_attn_f8 -- else the error against fp32 SDPA."""
+    from idm_vton_amd import ops
+    al = alloc or Tight()
+    C = heads * 64
+    pres = bool(tune) or f8                                                   # kernels 3, 7, 8, 16 need a pre-multiplied q; tune 0 runs the rule for a raw q
+    q = _r(B, Nq, C, dtype=dtype, dev=dev, seed=seed)
+    nk1 = Nq if nk_own is None else nk_own
+    k1, v1 = _r(B, nk1, C, dtype=dtype, dev=dev, seed=seed + 1), _r(B, nk1, C, dtype=dtype, dev=dev, seed=seed + 2)
+    qq = (q.float() * ops.QSCALE).to(dtype) if pres else q
+    nc = B - b0                                                               # conditional batches
+    G, idx = {"plain": (nc, list(range(nc))), "shared": (1, [0] * nc)}.get(entry, (4, [(2 - 2 * i) % 4 for i in range(nc)]))
+    lens = [n_garm, max(1, n_garm // 5), max(1, 5 * n_garm // 9), n_garm][:G] if entry == "ragged" else [n_garm] * G
+    k2, v2 = _r(G, n_garm, C, dtype=dtype, dev=dev, seed=seed + 3), _r(G, n_garm, C, dtype=dtype, dev=dev, seed=seed + 4)
+    per = [lens[idx[max(b - b0, 0) % nc]] for b in range(B)]                  # keys of the garment segment per query batch (absent: its person's)
+    eq, ek, ev = 2, 2, 2
+    e8 = lambda t, e: _e4m3(t.float().cpu() * 2.0 ** e).to(dev)
+    d8 = lambda u, e: _e4m3_to_f32(u.cpu()).to(dev) * 2.0 ** -e
+    st = torch.uint8 if f8 else dtype
+    enc = (lambda t, e: e8(t, e)) if f8 else (lambda t, e: t)
+    kfill = 0x7f if (f8 and al.framed) else (0 if f8 else al.k_pad)           # e4m3 NaN / zero bytes
+    # ---- q | k in one buffer ----
+    qk = torch.full((B * k_rows, 2 * C), kfill, dtype=st, device=dev)
+    qk[:B * Nq, :C] = enc(qq, eq).reshape(B * Nq, C)
+    qk.view(B, k_rows, 2 * C)[:, :nk1, C:] = enc(k1, ek)
+    qk = al.inp("qk", qk, contig=True)
+
+    def vt_of(v, n, lens_):
+        """[E][n][C] -> V^T [E][C][ld]: 16-bit key order, ld = round16(n) + 16, `finite` filler from each element's length on; fp8 slot order,
+        ld = round64(n) + 64, zero from the length to the end of its 64-key tile and the policy's poison in the 64 surplus positions."""
+        E = v.shape[0]
+        if not f8:
+            ld = ops.round16(n) + 16
+            vt = torch.full((E, C, ld), al.vt_pad, dtype=dtype, device=dev)
+            for e, L in enumerate(lens_):
+                vt[e, :, :L] = v[e, :L].transpose(0, 1)
+            vt = ops.key_order(vt)
+            for e, L in enumerate(lens_):
+                if L < n:
+                    al.poison(vt[e, :, ops.round16(L):ops.round16(n)])          # a ragged slot: not fetched beyond round16(count)
+            return vt
+        r64 = (n + 63) // 64 * 64
+        ld = r64 + 64
+        key = _f8_slot_key(ld, dev)
+        vt = torch.zeros(E, C, ld, dtype=torch.uint8, device=dev)
+        for e, L in enumerate(lens_):
+            vt[e][:, key < L] = e8(v[e], ev).transpose(0, 1)[:, key[key < L]]
+            al.poison(vt[e, :, (L + 63) // 64 * 64:])
+        return vt
+    vt1 = al.inp("vt", vt_of(v1, nk1, [nk1] * B), contig=True)
+    kg = torch.full((G, g_rows, C), kfill, dtype=st, device=dev)
+    for g, L in enumerate(lens):
+        kg[g, :L] = enc(k2[g, :L], ek)
+    vtg = vt_of(v2, n_garm, lens)
+    for g in range(G):
+        if g not in idx:                                                      # a slot of the pool no batch reads
+            al.poison(kg[g]), al.poison(vtg[g])
+    kg, vtg = al.inp("kg", kg, contig=f8), al.inp("vtg", vtg, contig=True)
+    kn, vn = ("k8", "vt8") if f8 else ("k", "vt")
+    own = {kn: qk[:, C:], vn: vt1, "nk": nk1, "ldk": 2 * C, "ldvt": vt1.stride(-2), "k_rows": k_rows}
+    gar = {kn: kg, vn: vtg, "nk": n_garm, "ldk": kg.stride(-2), "ldvt": vtg.stride(-2), "k_rows": g_rows, "b0": b0}
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=dev)
+    if entry != "plain":
+        gar["nb"] = G
+    if entry in ("indexed", "ragged"):
+        gar["index"] = i32(idx)
+    if entry == "ragged":
+        gar["nk_table"] = i32(per)
+    # ---- fp32 SDPA per batch on the keys each batch has ----
+    sp = lambda t: t.float().reshape(1, t.shape[0], heads, 64).transpose(1, 2)
+
+    def sdpa(qx, k1x, v1x, k2x, v2x):
+        o = []
+        for b in range(B):
+            L = per[b]
+            g = idx[b - b0] if b >= b0 else 0
+            kgb, vgb = (k2x[g, :L], v2x[g, :L]) if b >= b0 else (torch.zeros(L, C, device=dev), torch.zeros(L, C, device=dev))
+            kk, vv = torch.cat([sp(k1x[b]), sp(kgb)], dim=2), torch.cat([sp(v1x[b]), sp(vgb)], dim=2)
+            o.append(F.scaled_dot_product_attention(sp(qx[b]), kk, vv).transpose(1, 2).reshape(1, Nq, C))
+        return torch.cat(o)
+    ref = sdpa(qq.float() / ops.QSCALE if pres else q, k1, v1, k2, v2)
+    out = al.out("out", (B, Nq, C), dtype, dev)
+    if f8:
+        ops.attention_f8(qk, out, [own, gar], heads, qk_scale_exp=-(eq + ek), v_scale_exp=-ev, B=B, Nq=Nq, ldq=2 * C, ldo=out.stride(-2))
+        refq = sdpa(d8(e8(qq, eq), eq) / ops.QSCALE, d8(e8(k1, ek), ek), d8(e8(v1, ev), ev), d8(e8(k2, ek), ek), d8(e8(v2, ev), ev))
+        return relerr(out, sdpa(q, k1, v1, k2, v2)), relerr(out, refq)
+    ops.attention(qk, out, [own, gar], heads, B=B, Nq=Nq, ldq=2 * C, ldo=out.stride(-2), tune=tune, q_prescaled=pres)
+    return relerr(out, ref)
+
+
 def check_f8_out_320_refused(dtype, dev):
     """The 12-wave 320x192 tile carries only the plain 16-byte epilogue (csrc/gemm_conv.hip): asked to write e4m3 q | k | V^T it must fail
     loudly or run the launch on another tile bit-exactly -- never write something else.  0.0 = one of the two happened."""
@@ -266,28 +394,30 @@ def check_probe_mfma_f8(dev, scaled=False):
     return relerr(got, ref)
 
 
-def check_quant_f8(dtype, dev, seed=0):
+def check_quant_f8(dtype, dev, seed=0, alloc=None, vt_ldd=256):
     """idmvton_quant_f8 against torch's float8_e4m3fn conversion (bit-equal bytes): rows mode with a strided source, saturation at
-    +-448, and the V^T re-order (16-bit key order -> fp8 slot order, zero fill of the last partial 64-key tile)."""
+    +-448, and the V^T re-order (16-bit key order -> fp8 slot order, zero fill of the last partial 64-key tile).
+    vt_ldd: row length of the mode-1 destination (a multiple of 64, >= roundup64(N)): mode 1 writes the WHOLE row, zero from key N on."""
     from idm_vton_amd import ops
+    al = alloc or Tight()
     x = _r(200, 256, dtype=dtype, dev=dev, scale=3.0, seed=seed)
     x[0, :4] = torch.tensor([1000.0, -1000.0, 448.0, 0.0], dtype=dtype, device=dev)
-    src = x[:, 64:192]                                                       # strided view: lds = 256, cols = 128
-    got = ops.quant_f8(src, 4.0)
-    ok = torch.equal(got.cpu(), _e4m3(src.float().cpu() * 4.0))
+    src = al.inp("src", x[:, 64:192]) if al.framed else x[:, 64:192]         # strided view: lds = 256, cols = 128 (framed: lds = 128 + pad)
+    got = ops.quant_f8(src, 4.0, out=al.out("dst", (200, 128), torch.uint8, dev, own=True))
+    ok = torch.equal(al.done("dst", got).cpu(), _e4m3(src.float().cpu() * 4.0))
     N = 208                                                                  # 3 full tiles + 16 keys
     v = _r(5, N, dtype=dtype, dev=dev, scale=1.5, seed=seed + 1)            # plain V^T rows [row][key]
-    vt16 = ops.key_order(v)                                                  # what the 16-bit path stores
-    got2 = ops.quant_f8(vt16, 2.0, mode=1).cpu()
-    pos = torch.arange(256)
+    vt16 = al.inp("vt16", ops.key_order(v))                                  # what the 16-bit path stores
+    got2 = al.done("dst_vt", ops.quant_f8(vt16, 2.0, mode=1, out=al.out("dst_vt", (5, vt_ldd), torch.uint8, dev, contig=True, own=vt_ldd == 256))).cpu()
+    pos = torch.arange(vt_ldd)
     key = 64 * (pos // 64) + 32 * ((pos // 16) % 2) + 8 * ((pos // 4) % 4) + 4 * ((pos // 32) % 2) + pos % 4
-    vp = torch.zeros(5, 256)
+    vp = torch.zeros(5, vt_ldd)
     vp[:, key < N] = v.float().cpu()[:, key[key < N]]
-    ok = ok and got2.shape == (5, 256) and torch.equal(got2, _e4m3(vp * 2.0))
+    ok = ok and got2.shape == (5, vt_ldd) and torch.equal(got2, _e4m3(vp * 2.0))
     return 0.0 if ok else float("inf")
 
 
-def check_gemm_f8_out(dtype, dev, B=2, N=192, C=128, K=320, hint=0, seed=0, fused_attn=False):
+def check_gemm_f8_out(dtype, dev, B=2, N=192, C=128, K=320, hint=0, seed=0, fused_attn=False, alloc=None):
     """The QKV projection writing e4m3 operands itself (IDMVTON_IO_OUT_F8): q (softmax-scaled) | k into `out` bytes, V^T into the fp8
     kernel's slot order -- against the fp32 product of the same 16-bit operands, quantised by torch.  One e4m3 rounding of the kernel's fp32
     accumulator vs one of the reference's: they may land on neighbouring codes when the accumulators differ in their last bits, so the
@@ -295,12 +425,13 @@ def check_gemm_f8_out(dtype, dev, B=2, N=192, C=128, K=320, hint=0, seed=0, fuse
     accumulation-order slack.  fused_attn: also feed the bytes to idmvton_attn_f8 and return its error against the two-launch route
     (16-bit projection -> idmvton_quant_f8 -> idmvton_attn_f8) on the same inputs: both are e4m3 roundings of the same values."""
     from idm_vton_amd import ops
+    al = alloc or Tight()
     M = B * N
-    x = _r(M, K, dtype=dtype, dev=dev, scale=1.0, seed=seed)
-    w = _r(3 * C, K, dtype=dtype, dev=dev, scale=K ** -0.5, seed=seed + 1)
+    x = al.inp("x", _r(M, K, dtype=dtype, dev=dev, scale=1.0, seed=seed))
+    w = al.inp("w", _r(3 * C, K, dtype=dtype, dev=dev, scale=K ** -0.5, seed=seed + 1), contig=True)
     so, sv = 4.0, 2.0
-    qk8 = torch.empty(M, 2 * C, dtype=torch.uint8, device=dev)
-    vt8 = torch.empty(B, C, N, dtype=torch.uint8, device=dev)
+    qk8 = al.out("out", (M, 2 * C), torch.uint8, dev)                             # ldo in BYTES
+    vt8 = al.out("vt", (B, C, N), torch.uint8, dev, contig=True)
     ops.linear(x, w, out=qk8, vt=vt8, vt_n0=2 * C, vt_tokens=N, colscale_n=C, colscale=ops.QSCALE, f8=(so, sv), tile_hint=hint)
     y = x.float() @ w.float().t()
     ref_o = torch.cat([y[:, :C] * ops.QSCALE, y[:, C:2 * C]], 1) * so
@@ -466,52 +597,61 @@ def check_colscale(dtype, dev):
     return relerr(out, ref)
 
 
-def check_attn_cross(B, heads, N, dtype, dev, n_text=77, n_ip=16, ip_scale=1.0, seed=0, tune=0):
-    """IPAttnProcessor2_0 semantics: SDPA over text keys + ip_scale * SDPA over image keys."""
+def check_attn_cross(B, heads, N, dtype, dev, n_text=77, n_ip=16, ip_scale=1.0, seed=0, tune=0, k_rows=None, alloc=None):
+    """IPAttnProcessor2_0 semantics: SDPA over text keys + ip_scale * SDPA over image keys.  k_rows: rows per batch element of the two K tables
+    (default round16 of the key counts); rows nk.. hold the policy's filler for what the header calls masked."""
     from idm_vton_amd import ops
+    al = alloc or Tight()
     Cc = heads * 64
-    q = _r(B, N, Cc, dtype=dtype, dev=dev, seed=seed)
-    sp = lambda t: t.float().view(t.shape[0], t.shape[1], heads, 64).transpose(1, 2)
+    qv = _r(B, N, Cc, dtype=dtype, dev=dev, seed=seed)
+    q = al.inp("q", qv)
+    sp = lambda t: t.float().reshape(t.shape[0], t.shape[1], heads, 64).transpose(1, 2)
     segs, ref = [], 0
     for i, (nk, sc) in enumerate(((n_text, 1.0), (n_ip, ip_scale))):
         rows = (nk + 15) // 16 * 16
-        k = torch.zeros(B, rows, Cc, dtype=dtype, device=dev)
+        kr = rows if k_rows is None else k_rows[i]
+        k = torch.full((B, kr, Cc), al.k_pad, dtype=dtype, device=dev)
         k[:, :nk] = _r(B, nk, Cc, dtype=dtype, dev=dev, seed=seed + 10 + i)
         v = _r(B, nk, Cc, dtype=dtype, dev=dev, seed=seed + 20 + i)
-        vt, _ = _key_order_padded(v, nk)
-        segs.append(dict(k=k, vt=vt, nk=nk, ldk=Cc, ldvt=rows, k_rows=rows))
-        ref = ref + sc * F.scaled_dot_product_attention(sp(q), sp(k[:, :nk]), sp(v))
+        ref = ref + sc * F.scaled_dot_product_attention(sp(qv), sp(k[:, :nk]), sp(v))
+        vt, _ = _key_order_padded(v, nk, al.vt_pad, 16 if al.framed else 0)
+        k, vt = al.inp(f"k{i}", k), al.inp(f"vt{i}", vt, contig=True)
+        segs.append(dict(k=k, vt=vt, nk=nk, ldk=k.stride(-2), ldvt=vt.stride(-2), k_rows=kr))
     ref = ref.transpose(1, 2).reshape(B, N, Cc)
-    out = torch.empty(B, N, Cc, dtype=dtype, device=dev)
+    out = al.out("out", (B, N, Cc), dtype, dev)
     from idm_vton_amd import ffi
     ops.attention(q, out, segs, heads, mode=ffi.ATTN_CROSS, ip_scale=ip_scale, tune=tune)
     return relerr(out, ref)
 
 
-def check_xattn_fused(B, heads, N, K, dtype, dev, n_text=77, n_ip=16, ip_scale=1.0, tile_hint=0, seed=0):
+def check_xattn_fused(B, heads, N, K, dtype, dev, n_text=77, n_ip=16, ip_scale=1.0, tile_hint=0, seed=0, alloc=None):
     """attn2.to_q with the cross-attention as its epilogue (IDMVTON_EPI_XATTN) against fp32: q = x Wq^T, softmax(q k_t^T / 8) v_t + ip_scale *
     softmax(q k_i^T / 8) v_i per head; and against the two-launch form it replaces (same roundings: equal up to summation order)."""
     from idm_vton_amd import ffi, ops
+    al = alloc or Tight()
     C = heads * 64
     M = B * N
-    x = _r(M, K, dtype=dtype, dev=dev, seed=seed)
+    x = al.inp("x", _r(M, K, dtype=dtype, dev=dev, seed=seed))
     wq = _r(C, K, dtype=dtype, dev=dev, scale=K ** -0.5, seed=seed + 1)
     segs, refs = [], []
     q = (x.float() @ wq.float().t()).to(dtype).float().view(B, N, heads, 64).transpose(1, 2)          # q is rounded once to the storage type
     out_ref = torch.zeros(B, heads, N, 64, device=dev)
     for i, nk in enumerate([n_text] + ([n_ip] if n_ip else [])):
         rows = (nk + 31) // 32 * 32
-        k = torch.zeros(B, rows, C, dtype=dtype, device=dev)
+        k = torch.full((B, rows, C), al.k_pad, dtype=dtype, device=dev)      # rows nk..k_rows-1: masked (zero; NaN in a frame)
         k[:, :nk] = _r(B, nk, C, dtype=dtype, dev=dev, seed=seed + 2 + i)
         v = _r(B, nk, C, dtype=dtype, dev=dev, seed=seed + 5 + i)
-        vt = torch.zeros(B, C, rows, dtype=dtype, device=dev)
+        vt = torch.full((B, C, rows), al.vt_pad, dtype=dtype, device=dev)   # positions of keys >= nk: finite (zero; 1e4 in a frame)
         vt[:, :, :nk] = v.transpose(1, 2)
-        segs.append(dict(k=k, vt=ops.key_order(vt), nk=nk, ldk=C, ldvt=rows, k_rows=rows))
-        kk = k[:, :nk].float().view(B, nk, heads, 64).transpose(1, 2)
+        k, vt = al.inp(f"k{i}", k), al.inp(f"vt{i}", ops.key_order(vt))
+        segs.append(dict(k=k, vt=vt, nk=nk, ldk=k.stride(-2), ldvt=vt.stride(-2), k_rows=rows))
+        kk = k[:, :nk].float().reshape(B, nk, heads, 64).transpose(1, 2)
         vv = v.float().view(B, nk, heads, 64).transpose(1, 2)
         out_ref += (ip_scale if i == 1 else 1.0) * F.scaled_dot_product_attention(q, kk, vv)
     ref = out_ref.transpose(1, 2).reshape(M, C)
-    fused = ops.linear(x, ops.xattn_q_weight(wq), xattn=dict(segs=segs, tokens=N, ip_scale=ip_scale), tile_hint=tile_hint)
+    fused = ops.linear(x, al.inp("w", ops.xattn_q_weight(wq), contig=True), xattn=dict(segs=segs, tokens=N, ip_scale=ip_scale),
+                       out=al.out("out", (M, C), dtype, dev, own=True), tile_hint=tile_hint)
+    al.done("out", fused)
     q2 = ops.linear(x, wq)
     two = torch.empty(M, C, dtype=dtype, device=dev)
     if n_ip:
@@ -521,19 +661,21 @@ def check_xattn_fused(B, heads, N, K, dtype, dev, n_text=77, n_ip=16, ip_scale=1
     return max(relerr(fused, ref), relerr(fused, two.float()))
 
 
-def check_attn_small(B, heads, L, d, dtype, dev, causal, Lq=None, seed=0, scale=1.0):
+def check_attn_small(B, heads, L, d, dtype, dev, causal, Lq=None, seed=0, scale=1.0, alloc=None):
     """idmvton_attn_small (CLIP towers): fused-QKV layout, any even head_dim <= 128, optional causal mask."""
     from idm_vton_amd import ops
+    al = alloc or Tight()
     H, Lq = heads * d, (L if Lq is None else Lq)
-    qkv = _r(B, L, 3 * H, dtype=dtype, dev=dev, seed=seed, scale=scale)
-    q, k, v = qkv[:, L - Lq:, :H].contiguous(), qkv[:, :, H:2 * H], qkv[:, :, 2 * H:]
+    qkv = al.inp("qkv", _r(B, L, 3 * H, dtype=dtype, dev=dev, seed=seed, scale=scale))
+    q, k, v = al.inp("q", qkv[:, L - Lq:, :H].contiguous()), qkv[:, :, H:2 * H], qkv[:, :, 2 * H:]
     sp = lambda t: t.float().reshape(B, t.shape[1], heads, d).transpose(1, 2)
     mask = None
     if causal:
         mask = torch.ones(Lq, L, dtype=torch.bool, device=dev).tril(diagonal=L - Lq)
     ref = F.scaled_dot_product_attention(sp(q), sp(k), sp(v), attn_mask=mask).transpose(1, 2).reshape(B, Lq, H)
-    out = torch.empty(B, Lq, H, dtype=dtype, device=dev)
-    ops.attention_small(q, k, v, out, heads, d, scale=d ** -0.5, causal=causal, B=B, Lq=Lq, Lk=L, ldq=H, ldk=3 * H, ldv=3 * H, ldo=H)
+    out = al.out("out", (B, Lq, H), dtype, dev)
+    ops.attention_small(q, k, v, out, heads, d, scale=d ** -0.5, causal=causal, B=B, Lq=Lq, Lk=L, ldq=q.stride(-2), ldk=qkv.stride(-2), ldv=qkv.stride(-2),
+                        ldo=out.stride(-2))
     return relerr(out, ref)
 
 
@@ -547,59 +689,67 @@ def check_quickgelu(dtype, dev):
 
 
 # ------------------------------------------------------------------------------------------------ norms / elementwise
-def check_layernorm(rows, Cc, dtype, dev, seed=0):
+def check_layernorm(rows, Cc, dtype, dev, seed=0, x_f32=False, alloc=None):
+    """x_f32: x is the fp32 residual stream (values that 16 bits cannot hold)."""
     from idm_vton_amd import ops
-    x = _r(rows, Cc, dtype=dtype, dev=dev, scale=3.0, seed=seed) + 1.5
-    g = _r(Cc, dtype=dtype, dev=dev, seed=seed + 1)
-    b = _r(Cc, dtype=dtype, dev=dev, seed=seed + 2)
+    al = alloc or Tight()
+    x = al.inp("x", _r(rows, Cc, dtype=torch.float32 if x_f32 else dtype, dev=dev, scale=3.0, seed=seed) + 1.5)
+    g = al.inp("gamma", _r(Cc, dtype=dtype, dev=dev, seed=seed + 1), contig=True)
+    b = al.inp("beta", _r(Cc, dtype=dtype, dev=dev, seed=seed + 2), contig=True)
     ref = F.layer_norm(x.float(), (Cc,), g.float(), b.float(), 1e-5)
-    o2 = torch.empty_like(x)
-    out = ops.layernorm(x, g, b, 1e-5, out2=o2)
-    return max(relerr(out, ref), relerr(o2, ref))
+    o2 = al.out("y2", (rows, Cc), dtype, dev)
+    out = ops.layernorm(x, g, b, 1e-5, out=al.out("y", (rows, Cc), dtype, dev, own=True), out2=o2)
+    return max(relerr(al.done("y", out), ref), relerr(o2, ref))
 
 
-def check_stream_f32(M, N, K, dtype, dev, tile_hint=0, seed=0):
+def check_stream_f32(M, N, K, dtype, dev, tile_hint=0, seed=0, alloc=None):
     """The fp32 residual stream (gemm_conv io_flags, layernorm x_f32): fp32 res in / fp32 out, fp32 res in / 16-bit out, 16-bit
     res in / fp32 out, each against the fp32 reference with an fp32-ONLY tolerance where the output is fp32 (the only roundings left
     are the 16-bit operands, which the reference shares), then LayerNorm of the fp32 result."""
     from idm_vton_amd import ops
-    x = _r(M, K, dtype=dtype, dev=dev, seed=seed)
-    w = _r(N, K, dtype=dtype, dev=dev, scale=K ** -0.5, seed=seed + 1)
-    b = _r(N, dtype=dtype, dev=dev, seed=seed + 2)
-    r32 = _r(M, N, dtype=torch.float32, dev=dev, scale=3.0, seed=seed + 3)               # NOT representable in 16 bits
+    al = alloc or Tight()
+    x = al.inp("x", _r(M, K, dtype=dtype, dev=dev, seed=seed))
+    w = al.inp("w", _r(N, K, dtype=dtype, dev=dev, scale=K ** -0.5, seed=seed + 1), contig=True)
+    b = al.inp("bias", _r(N, dtype=dtype, dev=dev, seed=seed + 2), contig=True)
+    r32 = al.inp("res", _r(M, N, dtype=torch.float32, dev=dev, scale=3.0, seed=seed + 3))   # NOT representable in 16 bits
     ref = x.float() @ w.float().t() + b.float() + r32
-    o32 = ops.linear(x, w, bias=b, res=r32, out_f32=True, tile_hint=tile_hint)
-    assert o32.dtype == torch.float32
+    o32 = ops.linear(x, w, bias=b, res=r32, out=al.out("out", (M, N), torch.float32, dev, own=True), out_f32=True, tile_hint=tile_hint)
+    assert al.done("out", o32).dtype == torch.float32
     e = relerr(o32, ref) / 2e-5 * TOL[dtype]                                              # fp32 in, fp32 out: <= 2e-5, scaled to the caller's tolerance
-    o16 = ops.linear(x, w, bias=b, res=r32, tile_hint=tile_hint)
-    assert o16.dtype == dtype
+    o16 = ops.linear(x, w, bias=b, res=r32, out=al.out("out16", (M, N), dtype, dev, own=True), tile_hint=tile_hint)
+    assert al.done("out16", o16).dtype == dtype
     e = max(e, relerr(o16, ref))
-    r16 = r32.to(dtype)
-    o32b = ops.linear(x, w, bias=b, res=r16, out_f32=True, tile_hint=tile_hint)
+    r16 = al.inp("res16", r32.to(dtype))
+    o32b = ops.linear(x, w, bias=b, res=r16, out=al.out("out32_res16", (M, N), torch.float32, dev, own=True), out_f32=True, tile_hint=tile_hint)
+    al.done("out32_res16", o32b)
     e = max(e, relerr(o32b, x.float() @ w.float().t() + b.float() + r16.float()) / 2e-5 * TOL[dtype])
     g = _r(N, dtype=dtype, dev=dev, seed=seed + 4)
     bt = _r(N, dtype=dtype, dev=dev, seed=seed + 5)
     if N <= 2048:
-        y = ops.layernorm(o32, g, bt, 1e-5)
-        assert y.dtype == dtype
+        y = ops.layernorm(o32, g, bt, 1e-5, out=al.out("ln_y", (M, N), dtype, dev, own=True))
+        assert al.done("ln_y", y).dtype == dtype
         e = max(e, relerr(y, F.layer_norm(o32, (N,), g.float(), bt.float(), 1e-5)))
     return e
 
 
-def check_groupnorm(B, HW, Cc, dtype, dev, groups=32, silu=True, split=0, eps=1e-5, seed=0):
+def check_groupnorm(B, HW, Cc, dtype, dev, groups=32, silu=True, split=0, eps=1e-5, seed=0, alloc=None):
+    """x, x2, y are contiguous by ABI (a policy frames them before and after); `stats` is EXACTLY gn_stats_doubles long."""
     from idm_vton_amd import ops
+    al = alloc or Tight()
     x = _r(B, HW, Cc, dtype=dtype, dev=dev, scale=2.0, seed=seed) + 0.7
-    g = _r(Cc, dtype=dtype, dev=dev, seed=seed + 1)
-    b = _r(Cc, dtype=dtype, dev=dev, seed=seed + 2)
+    g = al.inp("gamma", _r(Cc, dtype=dtype, dev=dev, seed=seed + 1), contig=True)
+    b = al.inp("beta", _r(Cc, dtype=dtype, dev=dev, seed=seed + 2), contig=True)
     ref = F.group_norm(x.float().transpose(1, 2), groups, g.float(), b.float(), eps).transpose(1, 2)
     if silu:
         ref = F.silu(ref)
-    stats = torch.empty(ops.gn_stats_doubles(B, HW, Cc, groups), dtype=torch.float64, device=dev)
+    stats = al.out("stats", (ops.gn_stats_doubles(B, HW, Cc, groups),), torch.float64, dev, contig=True, scratch=True)
+    y = al.out("y", (B, HW, Cc), dtype, dev, contig=True, own=True)
     if split:
-        out = ops.groupnorm(x[..., :split].contiguous(), g, b, groups, eps, silu, stats, x2=x[..., split:].contiguous())
+        out = ops.groupnorm(al.inp("x", x[..., :split].contiguous(), contig=True), g, b, groups, eps, silu, stats,
+                            x2=al.inp("x2", x[..., split:].contiguous(), contig=True), out=y)
     else:
-        out = ops.groupnorm(x, g, b, groups, eps, silu, stats)
-    return relerr(out, ref)
+        out = ops.groupnorm(al.inp("x", x, contig=True), g, b, groups, eps, silu, stats, out=y)
+    return relerr(al.done("y", out), ref)
 
 
 def check_groupnorm_reproducible(B, HW, Cc, dtype, dev, groups=32):
@@ -614,6 +764,13 @@ def check_groupnorm_reproducible(B, HW, Cc, dtype, dev, groups=32):
 
 
 # ------------------------------------------------------------------------------------------------ split-precision (fp32-equivalent) VAE path
+def _poisoned_pad(al, n, C):
+    """A copy of the NHWC tensor n with the pad channels C.. holding the policy's poison (the to_nchw direction does not read them)."""
+    n = n.clone()
+    al.poison(n[..., C:])
+    return n
+
+
 def _relerr64(x, ref):
     x, ref = x.detach().double().cpu(), ref.detach().double().cpu()
     if not torch.isfinite(x).all():
@@ -621,14 +778,17 @@ def _relerr64(x, ref):
     return ((x - ref).abs().max() / ref.abs().max().clamp_min(1e-300)).item()
 
 
-def check_split(rows, cols, dev, mode, seed=0):
+def check_split(rows, cols, dev, mode, seed=0, alloc=None):
     """idmvton_split: hi = bf16(x), lo = bf16(x - hi) bit for bit, in the layout of each mode; hi + lo reproduces x to 2^-16."""
     from idm_vton_amd import ffi, ops
     g = torch.Generator(device="cpu").manual_seed(seed)
-    x = (torch.randn(rows, cols, generator=g) * torch.exp(4 * torch.randn(rows, 1, generator=g))).to(dev)      # rows spread over ~10 binades
+    al = alloc or Tight()
+    x = al.inp("src", (torch.randn(rows, cols, generator=g) * torch.exp(4 * torch.randn(rows, 1, generator=g))).to(dev))   # rows spread over ~10 binades
     hi = x.to(torch.bfloat16)
     lo = (x - hi.float()).to(torch.bfloat16)
-    out = ops.split(x, torch.bfloat16, mode)
+    shape = {ffi.SPLIT_ACT: (rows, 2 * cols), ffi.SPLIT_W3: (rows, 3 * cols), ffi.SPLIT_W3T: (cols, 3 * rows)}[mode]
+    out = ops.split(x, torch.bfloat16, mode, out=al.out("dst", shape, torch.bfloat16, dev, own=True))
+    al.done("dst", out)
     if mode == ffi.SPLIT_ACT:
         ref = torch.cat([hi, lo], 1)
     elif mode == ffi.SPLIT_W3:
@@ -639,26 +799,29 @@ def check_split(rows, cols, dev, mode, seed=0):
     return max(exact, _relerr64(hi.double() + lo.double(), x) / 256.0)            # second term: <= 2^-16 -> contributes <= 6e-8
 
 
-def check_gn_precise(B, HW, Cc, dev, groups=32, silu=True, seed=0):
+def check_gn_precise(B, HW, Cc, dev, groups=32, silu=True, seed=0, alloc=None):
     """GroupNorm in the split-precision form: fp32 in, fp32 affine, [hi | lo] out; hi + lo against an fp64 reference."""
     from idm_vton_amd import ops
-    x = _r(B, HW, Cc, dtype=torch.float32, dev=dev, scale=2.0, seed=seed) * 37.0 + 11.0
-    g = _r(Cc, dtype=torch.float32, dev=dev, seed=seed + 1)
-    b = _r(Cc, dtype=torch.float32, dev=dev, seed=seed + 2)
+    al = alloc or Tight()
+    x = al.inp("x", _r(B, HW, Cc, dtype=torch.float32, dev=dev, scale=2.0, seed=seed) * 37.0 + 11.0, contig=True)
+    g = al.inp("gamma", _r(Cc, dtype=torch.float32, dev=dev, seed=seed + 1), contig=True)
+    b = al.inp("beta", _r(Cc, dtype=torch.float32, dev=dev, seed=seed + 2), contig=True)
     ref = F.group_norm(x.double().transpose(1, 2), groups, g.double(), b.double(), 1e-6).transpose(1, 2)
     if silu:
         ref = F.silu(ref)
-    stats = torch.empty(ops.gn_stats_doubles(B, HW, Cc, groups), dtype=torch.float64, device=dev)
-    out = ops.groupnorm(x, g, b, groups, 1e-6, silu, stats, split_dtype=torch.bfloat16)
-    assert out.shape == (B, HW, 2 * Cc)
+    stats = al.out("stats", (ops.gn_stats_doubles(B, HW, Cc, groups),), torch.float64, dev, contig=True, scratch=True)
+    out = ops.groupnorm(x, g, b, groups, 1e-6, silu, stats, out=al.out("y", (B, HW, 2 * Cc), torch.bfloat16, dev, contig=True, own=True), split_dtype=torch.bfloat16)
+    assert al.done("y", out).shape == (B, HW, 2 * Cc)
     return _relerr64(out[..., :Cc].double() + out[..., Cc:].double(), ref)
 
 
-def check_softmax_split(rows, n, dev, seed=0, n_valid=0):
+def check_softmax_split(rows, n, dev, seed=0, n_valid=0, alloc=None):
     from idm_vton_amd import ops
-    x = _r(rows, n, dtype=torch.float32, dev=dev, scale=3.0, seed=seed)
+    al = alloc or Tight()
+    x = al.inp("x", _r(rows, n, dtype=torch.float32, dev=dev, scale=3.0, seed=seed))
     keep = x.clone()
-    out = ops.softmax_rows_split(x, 0.7, torch.bfloat16, n_valid=n_valid)
+    out = ops.softmax_rows_split(x, 0.7, torch.bfloat16, n_valid=n_valid, out=al.out("y", (rows, 2 * n), torch.bfloat16, dev, own=True))
+    al.done("y", out)
     nv = n_valid or n
     ref = torch.zeros(rows, n, dtype=torch.float64, device=dev)
     ref[:, :nv] = torch.softmax(0.7 * x[:, :nv].double(), dim=-1)
@@ -667,10 +830,10 @@ def check_softmax_split(rows, n, dev, seed=0, n_valid=0):
     return max(_relerr64(out[:, :n].double() + out[:, n:].double(), ref), tail)
 
 
-def check_softmax_rows(rows, n, dtype, dev, n_valid=0, seed=0):
-    """In-place row softmax (VAE mid-block attention, 16-bit path); n_valid: the padded-key form."""
+def check_softmax_rows(rows, n, dtype, dev, n_valid=0, seed=0, alloc=None):
+    """In-place row softmax (VAE mid-block attention, 16-bit path); n_valid: the padded-key form.  Columns [n, ld) are not the op's."""
     from idm_vton_amd import ops
-    x = _r(rows, n, dtype=dtype, dev=dev, scale=3.0, seed=seed)
+    x = (alloc or Tight()).inout("x", _r(rows, n, dtype=dtype, dev=dev, scale=3.0, seed=seed))
     nv = n_valid or n
     ref = torch.zeros(rows, n, dtype=torch.float32, device=dev)
     ref[:, :nv] = torch.softmax(0.7 * x[:, :nv].float(), dim=-1)
@@ -679,7 +842,7 @@ def check_softmax_rows(rows, n, dtype, dev, n_valid=0, seed=0):
     return max(relerr(x, ref), tail)
 
 
-def check_plin(M, N, K, dev, exact_w=False, res=True, seed=0):
+def check_plin(M, N, K, dev, exact_w=False, res=True, seed=0, alloc=None):
     """A Linear through the split-precision path (vae._PConv: [hi | lo] activations x [w_hi | w_hi][w_lo] weights, fp32 bias / residual /
     output) against fp64: fp32-equivalent (<= 2e-5 of the output range), where the 16-bit path gives 2e-3 / 1.6e-2."""
     from idm_vton_amd import ops
@@ -689,16 +852,19 @@ def check_plin(M, N, K, dev, exact_w=False, res=True, seed=0):
     if exact_w:
         w = w.to(torch.bfloat16).float()
     b = _r(N, dtype=torch.float32, dev=dev, seed=seed + 2)
-    rs = _r(M, N, dtype=torch.float32, dev=dev, seed=seed + 3) if res else None
+    al = alloc or Tight()
+    rs = al.inp("res", _r(M, N, dtype=torch.float32, dev=dev, seed=seed + 3)) if res else None
     cv = _PConv(w, b)
     assert cv.three == (not exact_w)
-    xp = ops.split(x, torch.bfloat16)
-    out = ops.gemm_conv(cv.segs(xp, 0), cv.w, M, bias=cv.b, res=rs, out_f32=True)
+    xp = al.inp("xp", ops.split(x, torch.bfloat16))
+    out = ops.gemm_conv(cv.segs(xp, 0), al.inp("w", cv.w, contig=True), M, bias=al.inp("bias", cv.b, contig=True), res=rs,
+                        out=al.out("out", (M, N), torch.float32, dev, own=True), out_f32=True)
+    al.done("out", out)
     ref = x.double() @ w.double().t() + b.double() + (rs.double() if res else 0.0)
     return _relerr64(out, ref)
 
 
-def check_pconv(B, Cin, Cout, H, W, dev, ups=False, shortcut=0, exact_w=False, seed=0):
+def check_pconv(B, Cin, Cout, H, W, dev, ups=False, shortcut=0, exact_w=False, seed=0, alloc=None):
     """3x3 conv (optionally fused nearest-2x, optionally a fused 1x1 shortcut on a second input) through the split-precision path vs fp64."""
     from idm_vton_amd import ops
     from idm_vton_amd.vae import _PConv
@@ -711,6 +877,7 @@ def check_pconv(B, Cin, Cout, H, W, dev, ups=False, shortcut=0, exact_w=False, s
     if ups:
         xin = F.interpolate(xin, scale_factor=2.0, mode="nearest")
     ref = F.conv2d(xin, w.double(), b.double(), padding=1)
+    al = alloc or Tight()
     sc, xs = None, None
     if shortcut:
         x2 = _r(B, H, W, shortcut, dtype=torch.float32, dev=dev, seed=seed + 3)
@@ -718,55 +885,72 @@ def check_pconv(B, Cin, Cout, H, W, dev, ups=False, shortcut=0, exact_w=False, s
         bs = _r(Cout, dtype=torch.float32, dev=dev, seed=seed + 5)
         ref = ref + F.conv2d(x2.double().permute(0, 3, 1, 2), ws.double(), bs.double())
         sc = (ws, bs)
-        xs = ops.split(x2.reshape(-1, shortcut), torch.bfloat16).view(B, H * W, 2 * shortcut)
+        xs = al.inp("xs", ops.split(x2.reshape(-1, shortcut), torch.bfloat16).view(B, H * W, 2 * shortcut))
     cv = _PConv(w, b, shortcut=sc)
-    xp = ops.split(x.reshape(-1, Cin), torch.bfloat16).view(B, H * W, 2 * Cin)
+    xp = al.inp("xp", ops.split(x.reshape(-1, Cin), torch.bfloat16).view(B, H * W, 2 * Cin))
     Ho, Wo = (2 * H, 2 * W) if ups else (H, W)
-    out = ops.gemm_conv(cv.segs(xp, 1, xs), cv.w, B * Ho * Wo, Ho=Ho, Wo=Wo, Hi=H, Wi=W, ups=ups, bias=cv.b, out_f32=True)
-    return _relerr64(out.view(B, Ho, Wo, Cout).permute(0, 3, 1, 2), ref)
+    out = ops.gemm_conv(cv.segs(xp, 1, xs), al.inp("w", cv.w, contig=True), B * Ho * Wo, Ho=Ho, Wo=Wo, Hi=H, Wi=W, ups=ups, bias=al.inp("bias", cv.b, contig=True),
+                        out=al.out("out", (B * Ho * Wo, Cout), torch.float32, dev, own=True), out_f32=True)
+    return _relerr64(al.done("out", out).reshape(B, Ho, Wo, Cout).permute(0, 3, 1, 2), ref)
 
 
-def check_layout_split(B, h, w, dev, seed=0):
+def check_layout_split(B, h, w, dev, seed=0, alloc=None):
     from idm_vton_amd import ops
-    src = _r(B, 4, h, w, dtype=torch.float32, dev=dev, seed=seed) * 5.0
-    n = ops.to_nhwc(src, torch.bfloat16, cpad=64, scale=2.0, shift=-1.0, split=True)                     # [B][hw][128]
+    al = alloc or Tight()
+    src = al.inp("nchw", _r(B, 4, h, w, dtype=torch.float32, dev=dev, seed=seed) * 5.0, contig=True)
+    n = ops.to_nhwc(src, torch.bfloat16, cpad=64, scale=2.0, shift=-1.0, split=True, out=al.out("nhwc_split", (B, h * w, 128), torch.bfloat16, dev, contig=True, own=True))   # [B][hw][128]
+    al.done("nhwc_split", n)
     v = (src * 2.0 - 1.0).permute(0, 2, 3, 1).reshape(B, h * w, 4)
     e1 = _relerr64(n[..., :4].double() + n[..., 64:68].double(), v)
     e2 = float(n[..., 4:64].abs().max() + n[..., 68:].abs().max())
-    img = _r(B, h * w, 8, dtype=torch.float32, dev=dev, seed=seed + 1)
-    back = ops.to_nchw(img, 3, (h, w), scale=0.5, shift=0.5)
-    e3 = _relerr64(back, (img[..., :3] * 0.5 + 0.5).reshape(B, h, w, 3).permute(0, 3, 1, 2))
+    img = al.inp("nhwc_f32", _poisoned_pad(al, _r(B, h * w, 8, dtype=torch.float32, dev=dev, seed=seed + 1), 3), contig=True)
+    back = ops.to_nchw(img, 3, (h, w), scale=0.5, shift=0.5, out=al.out("nchw_back", (B, 3, h, w), torch.float32, dev, contig=True, own=True))
+    e3 = _relerr64(al.done("nchw_back", back), (img[..., :3] * 0.5 + 0.5).reshape(B, h, w, 3).permute(0, 3, 1, 2))
     return max(e1, e2, e3)
 
 
-def check_elementwise(B, h, w, dtype, dev, seed=0):
+def check_elementwise(B, h, w, dtype, dev, seed=0, alloc=None, ldm=8, null_noise=False):
+    """pack_input, cfg_step, to_nhwc / to_nchw, vae_sample: every tensor contiguous by ABI (a policy frames them before and after); the
+    channels the header says are not read -- eps 4.., the NHWC source's pad channels, moments 8.. -- are the policy's poison.
+    null_noise: cfg_step without a noise term (a NULL pointer: the last step of a schedule)."""
     from idm_vton_amd import ops
+    al = alloc or Tight()
     hw = h * w
-    lat = _r(B, 4, h, w, dtype=torch.float32, dev=dev, seed=seed)
-    cond = _r(2 * B, hw, 9, dtype=dtype, dev=dev, seed=seed + 1)
-    out = torch.full((2 * B, hw, 64), 7.0, dtype=dtype, device=dev)
+    lat = al.inp("latents", _r(B, 4, h, w, dtype=torch.float32, dev=dev, seed=seed), contig=True)
+    cond = al.inp("cond", _r(2 * B, hw, 9, dtype=dtype, dev=dev, seed=seed + 1), contig=True)
+    out = al.out("packed", (2 * B, hw, 64), dtype, dev, contig=True, init=7.0)
     ops.pack_input(lat, cond, out)
     ln = lat.permute(0, 2, 3, 1).reshape(B, hw, 4).to(dtype)
     ref = torch.cat([torch.cat([ln, ln], 0), cond, torch.zeros(2 * B, hw, 51, dtype=dtype, device=dev)], dim=-1)
     e1 = (out.float() - ref.float()).abs().max().item()
     eps = _r(2 * B, hw, 64, dtype=dtype, dev=dev, seed=seed + 2)
-    noise = _r(B, 4, h, w, dtype=torch.float32, dev=dev, seed=seed + 3)
-    coef = torch.tensor([0.98, -0.03, 0.1, 2.0], dtype=torch.float32, device=dev)
+    al.poison(eps[..., 4:])                                                   # channels 0..3 used
+    eps = al.inp("eps", eps, contig=True)
+    noise = al.inp("noise", _r(B, 4, h, w, dtype=torch.float32, dev=dev, seed=seed + 3), contig=True)
+    coef = al.inp("coef", torch.tensor([0.98, -0.03, 0.1, 2.0], dtype=torch.float32, device=dev), contig=True)
     e = eps[..., :4].float().reshape(2, B, h, w, 4).permute(0, 1, 4, 2, 3)
     e = e[0] + 2.0 * (e[1] - e[0])
-    ref2 = 0.98 * lat - 0.03 * e + 0.1 * noise
-    lat2 = lat.clone()
-    ops.cfg_step(eps, lat2, noise, coef)
+    ref2 = 0.98 * lat - 0.03 * e + (0.0 if null_noise else 0.1 * noise)
+    lat2 = al.inout("latents_step", lat.clone(), contig=True)
+    ops.cfg_step(eps, lat2, None if null_noise else noise, coef)
     e2 = relerr(lat2, ref2)
-    src = _r(B, 3, h, w, dtype=torch.float32, dev=dev, seed=seed + 4)
-    n = ops.to_nhwc(src, dtype, cpad=64, scale=2.0, shift=-1.0)
-    back = ops.to_nchw(n, 3, (h, w), scale=0.5, shift=0.5)
-    e3 = (back - (src * 2 - 1).to(dtype).float() * 0.5 - 0.5).abs().max().item()
-    mom = _r(B, hw, 8, dtype=dtype, dev=dev, seed=seed + 5)
-    z = ops.vae_sample(mom, noise, 0.13025)
-    mm = mom.float().reshape(B, h, w, 8).permute(0, 3, 1, 2)
+    src = al.inp("nchw", _r(B, 3, h, w, dtype=torch.float32, dev=dev, seed=seed + 4), contig=True)
+    n = ops.to_nhwc(src, dtype, cpad=64, scale=2.0, shift=-1.0, out=al.out("nhwc", (B, hw, 64), dtype, dev, contig=True, own=True))
+    al.done("nhwc", n)
+    if al.framed:
+        e3z = float(n[..., 3:].float().abs().max())                          # the pad channels are written as zero
+        n = al.inp("nhwc_src", _poisoned_pad(al, n, 3), contig=True)
+    else:
+        e3z = 0.0
+    back = ops.to_nchw(n, 3, (h, w), scale=0.5, shift=0.5, out=al.out("nchw_back", (B, 3, h, w), torch.float32, dev, contig=True, own=True))
+    e3 = max(e3z, (al.done("nchw_back", back) - (src * 2 - 1).to(dtype).float() * 0.5 - 0.5).abs().max().item())
+    mom = _r(B, hw, ldm, dtype=dtype, dev=dev, seed=seed + 5)
+    al.poison(mom[..., 8:])                                                   # mean 0..3, logvar 4..7
+    mom = al.inp("moments", mom, contig=True)
+    z = ops.vae_sample(mom, noise, 0.13025, out=al.out("z", (B, 4, h, w), torch.float32, dev, contig=True, own=True))
+    mm = mom[..., :8].float().reshape(B, h, w, 8).permute(0, 3, 1, 2)
     refz = (mm[:, :4] + torch.exp(0.5 * mm[:, 4:].clamp(-30, 20)) * noise) * 0.13025
-    e4 = relerr(z, refz)
+    e4 = relerr(al.done("z", z), refz)
     return max(e1, e2, e3, e4)
 
 

@@ -73,6 +73,68 @@ def test_fp8_output_contract_is_checked_on_the_host():
         ffi.call("idmvton_gemm_conv", a, 0)
 
 
+def test_undefined_attention_tune_words_are_refused_on_the_host():
+    """idmvton_attn_args.tune = (flags << 24) | (kernel << 16) | (stages << 8) | waves: kernel 16 exists with 4 or 8 waves and 3 stages, kernels 7
+    and 8 with 8 waves and 3 stages, the timing-only kernels 4..6 with 8 waves and 2 stages.  Any other word for them used to run the nearest
+    build without a word; it is IDMVTON_E_ARG now, returned before anything is launched (the pointers below are never dereferenced) -- from
+    every entry point, in both storage types.  (What the header documents as running the same build without an error -- kernel 2 at either
+    stages value, kernel 3 with a raw q -- is not refused, and not claimed to be.)"""
+    import json
+    from idm_vton_amd import ffi
+
+    def args(tune, dtype=ffi.BF16, prescaled=1):
+        a = ffi.AttnArgs()
+        a.dtype, a.mode, a.B, a.heads, a.Nq = dtype, ffi.ATTN_SELF, 2, 2, 256
+        a.q, a.ldq, a.out, a.ldo, a.nseg = 0x10000, 128, 0x20000, 128, 1
+        a.k[0], a.vt[0], a.ldk[0], a.ldvt[0], a.nk[0] = 0x30000, 0x40000, 128, 256, 256
+        a.q_prescaled, a.tune = prescaled, tune
+        return a
+
+    word = lambda kern, stg, nw, flags=0: (flags << 24) | (kern << 16) | (stg << 8) | nw
+    undefined = [word(16, 3, 2), word(16, 3, 16), word(16, 3, 0), word(16, 2, 8), word(16, 4, 4), word(16, 0, 8), word(16, 2, 2), word(16, 3, 2, 4),
+                 word(7, 3, 4), word(7, 2, 8), word(7, 4, 8), word(7, 0, 0), word(8, 3, 4), word(8, 3, 2), word(8, 2, 8), word(8, 3, 16), word(8, 3, 4, 8),
+                 word(4, 3, 8), word(4, 2, 4), word(5, 0, 0), word(5, 2, 2), word(6, 4, 8), word(6, 3, 4)]
+    for tune in undefined:
+        kern = (tune >> 16) & 0xff
+        what = {16: "software-pipelined kernel is 4 or 8 waves, 3 stages", 7: "prefetch kernel is 8 waves, 3 stages", 8: "prefetch kernel is 8 waves, 3 stages"}.get(
+            kern, "ablation kernels are 8 waves, 2 stages")
+        for dtype in (ffi.F16, ffi.BF16):
+            with pytest.raises(RuntimeError, match=what):
+                ffi.call("idmvton_attn_fwd", args(tune, dtype), 0)
+        with pytest.raises(RuntimeError, match=what):
+            ffi.call_shared("idmvton_attn_fwd_shared", args(tune), [0, 0], 0)
+        with pytest.raises(RuntimeError, match=what):
+            ffi.call_indexed("idmvton_attn_fwd_indexed", args(tune), [0, 0], [0, 0], 0)
+        with pytest.raises(RuntimeError, match=what):
+            ffi.call_ragged("idmvton_attn_fwd_ragged", args(tune), [0, 0], [0, 0], [0, 0], 0)
+    # the older refusals keep their order: a raw q is named first, whatever the word
+    with pytest.raises(RuntimeError, match="needs SELF mode and a pre-multiplied q"):
+        ffi.call("idmvton_attn_fwd", args(word(16, 3, 2), prescaled=0), 0)
+    with pytest.raises(RuntimeError, match="unknown kernel selector"):
+        ffi.call("idmvton_attn_fwd", args(word(17, 3, 8)), 0)
+    with pytest.raises(RuntimeError, match="unsupported tune"):
+        ffi.call("idmvton_attn_fwd", args(word(0, 3, 16)), 0)
+    for tune in (word(2, 4, 8), word(2, 2, 4), word(3, 1, 8), word(3, 3, 2)):     # the ping-pong kernel's own, older refusal
+        with pytest.raises(RuntimeError, match="ping-pong kernel needs SELF mode, 8 waves, 2 or 3 stages"):
+            ffi.call("idmvton_attn_fwd", args(tune), 0)
+    for kern in (1, 9, 15, 32, 255):                                             # numbers the header does not list
+        with pytest.raises(RuntimeError, match="unknown kernel selector"):
+            ffi.call("idmvton_attn_fwd", args(word(kern, 3, 8)), 0)
+    # every word the suite's kernel list and the committed table spell is a defined one
+    from tests.test_garment_cache_gpu import TUNES
+
+    def defined(t):
+        kern, stg, nw = (t >> 16) & 0xff, (t >> 8) & 0xff, t & 0xff
+        return t == 0 or {0: nw in (2, 4, 8) and stg in (2, 3, 4), 2: nw == 8 and stg in (2, 3), 3: nw == 8 and stg in (2, 3),
+                          4: nw == 8 and stg == 2, 5: nw == 8 and stg == 2, 6: nw == 8 and stg == 2,
+                          7: nw == 8 and stg == 3, 8: nw == 8 and stg == 3, 16: nw in (4, 8) and stg == 3}.get(kern, False)
+    assert all(defined(t) and (t >> 16) & 0xff not in (4, 5, 6) for t in TUNES.values()), TUNES     # and none is a timing-only build
+    with open(os.path.join(ROOT, "idm-vton_amd", "tune_gfx950.json")) as f:
+        table = json.load(f).get("attn", {})
+    assert table and all(defined(int(t)) and (int(t) >> 16) & 0xff not in (4, 5, 6) for t in table.values()), [t for t in table.values() if not defined(int(t))]
+    assert not any(defined(t) for t in undefined)
+
+
 def test_fused_cross_attention_and_upsample_contracts_are_checked_on_the_host():
     """IDMVTON_EPI_XATTN (the cross-attention as attn2.to_q's epilogue) and `ups` with the skip tensor's size (diffusers' upsample_size): the shapes
     the kernels cannot serve are refused before any launch."""
