@@ -353,7 +353,7 @@ class StableDiffusionXLInpaintPipeline:
 
     # ------------------------------------------------------------------------------------------ the garment, once
     @torch.no_grad()
-    def encode_garment(self, cloth, text_embeds_cloth, num_inference_steps, height, width, strength=1.0, generator=None):
+    def encode_garment(self, cloth, text_embeds_cloth, num_inference_steps, height, width, strength=1.0, generator=None, storage="native"):
         """Encode G garments once for many calls: -> GarmentCache, to be passed AS `cloth=` to __call__ (whose `text_embeds_cloth` may then
         be None) with the same scheduler, num_inference_steps, height and width; any strength whose timesteps are among this one's (a cache
         made with strength=1.0 serves every strength).  The batch of a cached call may hold P = m * G persons: person i wears garment i % G.
@@ -361,6 +361,8 @@ class StableDiffusionXLInpaintPipeline:
         person's along the token axis only): the garment runs at its own size; `height` / `width` are the PERSON size of the calls the cache
         is declared for (GarmentCache.for_person_size declares it for another).  Image quality at other garment sizes is not evaluated.
         The reference has no counterpart (it runs GarmentNet in every step of every call, tryon_pipeline.py:1781-1787).
+        storage="e4m3": a packed cache (garment_cache.PackedGarmentCache) -- e4m3 bytes, half the resident memory, lossy for the garment keys
+        and values alone; passed as `cloth=` (and pooled, indexed, saved) like any other.
 
         RNG: the one draw made here is the cloth posterior sample ([G,4,gh,gw] fp32 -- the garment latent's shape --, from `generator`).  In __call__ the cloth posterior draw
         is the call's third draw from `generator` (latents, masked-image posterior, [pose: global generator], cloth, then
@@ -370,7 +372,7 @@ class StableDiffusionXLInpaintPipeline:
         clo = _to_tensor_image(cloth, "cloth")
         n_cloth = _randn((clo.shape[0], 4) + self._cloth_latent_hw(clo), generator, eng.device, torch.float32)
         return eng.encode_garment(cloth=clo, text_embeds_cloth=text_embeds_cloth, noise_cloth=n_cloth, num_inference_steps=num_inference_steps,
-                                  scheduler=self._scheduler_kind(), strength=strength, height=height, width=width)
+                                  scheduler=self._scheduler_kind(), strength=strength, height=height, width=width, storage=storage)
 
     def empty_garment_cache(self, garments, garment_height, garment_width, num_inference_steps, height=None, width=None, strength=1.0):
         """A GarmentCache of `garments` uninitialised slots for garments of up to garment_height x garment_width, for `put` to fill with

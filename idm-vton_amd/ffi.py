@@ -99,12 +99,21 @@ class SplitArgs(C.Structure):
     _fields_ = [("dtype", i32), ("mode", i32), ("rows", i32), ("cols", i32), ("src", vp), ("lds", i32), ("dst", vp), ("ldd", i32)]
 
 
+class KvUnpackDesc(C.Structure):
+    _fields_ = [("src", vp), ("dst", vp), ("exp", vp), ("rows", i32), ("cols", i32), ("lds", i32), ("ldd", i32)]
+
+
+class KvUnpackArgs(C.Structure):
+    _fields_ = [("dtype", i32), ("n", i32), ("desc", vp), ("max_chunks", i32)]
+
+
 STRUCTS = {"idmvton_seg": Seg, "idmvton_gemm_conv_args": GemmConvArgs, "idmvton_attn_args": AttnArgs,
            "idmvton_layernorm_args": LayerNormArgs, "idmvton_groupnorm_args": GroupNormArgs,
            "idmvton_pack_input_args": PackInputArgs, "idmvton_cfg_step_args": CfgStepArgs,
            "idmvton_layout_args": LayoutArgs, "idmvton_vae_sample_args": VaeSampleArgs, "idmvton_softmax_args": SoftmaxArgs,
            "idmvton_attn_small_args": AttnSmallArgs, "idmvton_attn_f8_args": AttnF8Args, "idmvton_quant_f8_args": QuantF8Args,
-           "idmvton_split_args": SplitArgs, "idmvton_xattn": XAttn}
+           "idmvton_split_args": SplitArgs, "idmvton_xattn": XAttn, "idmvton_kv_unpack_desc": KvUnpackDesc,
+           "idmvton_kv_unpack_args": KvUnpackArgs}
 
 # every symbol include/idmvton_hip.h declares
 SYMBOLS = ["idmvton_last_error", "idmvton_abi_version", "idmvton_sizeof", "idmvton_gemm_conv", "idmvton_attn_fwd",
@@ -113,7 +122,7 @@ SYMBOLS = ["idmvton_last_error", "idmvton_abi_version", "idmvton_sizeof", "idmvt
            "idmvton_attn_small", "idmvton_rccl_unique_id", "idmvton_rccl_comm_init", "idmvton_rccl_bcast_arena",
            "idmvton_rccl_comm_destroy", "idmvton_attn_f8", "idmvton_quant_f8", "idmvton_split", "idmvton_attn_fwd_shared",
            "idmvton_attn_f8_shared", "idmvton_attn_fwd_indexed", "idmvton_attn_f8_indexed",
-           "idmvton_attn_fwd_ragged", "idmvton_attn_f8_ragged"]
+           "idmvton_attn_fwd_ragged", "idmvton_attn_f8_ragged", "idmvton_kv_unpack"]
 
 _lib = None
 
@@ -159,6 +168,8 @@ def lib():
     for s in ("idmvton_attn_fwd_ragged", "idmvton_attn_f8_ragged"):          # (args*, seg_nb[2], seg_index[2], const int32_t* const seg_nk[2], stream)
         getattr(L, s).argtypes = [vp, C.POINTER(i32), C.POINTER(vp), C.POINTER(vp), vp]
         getattr(L, s).restype = C.c_int
+    L.idmvton_kv_unpack.argtypes = [vp, vp, vp]                               # (args*, const desc* host_desc, stream)
+    L.idmvton_kv_unpack.restype = C.c_int
     L.idmvton_probe_mfma.argtypes = [C.c_int, vp, vp, vp, vp]
     L.idmvton_groupnorm_stats_doubles.argtypes = [C.c_int] * 4
     L.idmvton_groupnorm_stats_doubles.restype = C.c_int
@@ -211,3 +222,12 @@ def call_ragged(fn_name, args, seg_nb, seg_index, seg_nk, stream):
     rc = getattr(L, fn_name)(C.byref(args), nb, ix, nk, C.c_void_p(stream))
     if rc != 0:
         raise RuntimeError(f"{fn_name} failed ({rc}): {L.idmvton_last_error().decode()}")
+
+
+def call_kv_unpack(args, host_desc, stream):
+    """Invoke idmvton_kv_unpack(const args*, const desc* host_desc, void* stream); host_desc: a ctypes array of KvUnpackDesc or the address of
+    one (what the library validates -- args.desc is its device copy)."""
+    L = lib()
+    rc = L.idmvton_kv_unpack(C.byref(args), host_desc if isinstance(host_desc, int) else C.cast(host_desc, vp), C.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError(f"idmvton_kv_unpack failed ({rc}): {L.idmvton_last_error().decode()}")

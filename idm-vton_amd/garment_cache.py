@@ -28,6 +28,11 @@ timestep, with the rest of the V^T zero.  The attention kernels read each person
 so persons of one call wear garments of different sizes and a person with a small garment walks only its own key tiles.  Slots are always
 16-bit: `put` widens an e4m3 feature (exactly: e4m3 times a power of two is a 16-bit number) and the fp8 attention quantises a slot per launch,
 which gives the projection's own bytes back.  `take` returns a garment at its own compact size.  A cache without `sizes` is what it always was.
+
+Packed storage: `pack()` gives a PackedGarmentCache -- the same tensors in the same layout as OCP e4m3 bytes (torch.uint8) plus one int32
+exponent per (garment, feature, K | V^T) in `exps` [G][F][2]: half the resident bytes.  pack_exponent / pack_values / unpack_values below ARE the
+format; the engine widens a block of timesteps into its 16-bit sets with one idmvton_kv_unpack launch, which matches them bit for bit.  Lossy
+and opt-in, for the garment segment alone; `dtype` stays the engine's 16-bit dtype and every primitive moves `exps` with the bytes.
 """
 import torch
 
@@ -90,7 +95,45 @@ def widen_f8(k8, vt8, dtype, ek, ev):
     return k, vt
 
 
+# ---- the packed format ---------------------------------------------------------------------------------------------------
+E4M3_MAX = 448.0
+PACK_EXP_MIN, PACK_EXP_MAX = -7, 15
+
+
+def pack_exponent(amax):
+    """amax (a tensor of largest |x|, any float dtype) -> int32 e = clamp(floor(log2(448 / amax)), -7, 15), and 0 where amax is 0.  No
+    division and no host sync: with amax = m * 2^x, m in [0.5, 1) (frexp), 448 / amax = (448 / m) * 2^-x and 448 / m lies in (448, 896], whose
+    log2 has floor 9 when m <= 0.875 (448 / 0.875 = 512) and 8 otherwise.  The bounds: 448 * 2^7 < 65504 (x' fits fp16) and 2^-9 * 2^-15 is
+    fp16's smallest subnormal (x' is exact in fp16 and bf16)."""
+    m, x = torch.frexp(amax.float())
+    e = torch.where(m <= 0.875, 9, 8) - x
+    return torch.where(amax > 0, e.clamp(PACK_EXP_MIN, PACK_EXP_MAX), 0).to(torch.int32)
+
+
+def _pow2(e):
+    """int tensor e in [-126, 127] -> float32 2^e, built from the exponent bits (exact on every device)."""
+    return ((e.to(torch.int32) + 127) << 23).view(torch.float32)
+
+
+def pack_values(x, e):
+    """x (16-bit or float), e (int tensor broadcastable to x) -> uint8 OCP e4m3fn bytes of clamp(x * 2^e, +-448), round to nearest even.
+    THE definition of the format, in plain torch (fp32 arithmetic: the product is exact)."""
+    return (x.float() * _pow2(e)).clamp(-E4M3_MAX, E4M3_MAX).to(torch.float8_e4m3fn).view(torch.uint8)
+
+
+def unpack_values(b, e, dtype):
+    """uint8 e4m3 bytes, e -> x' = e4m3(byte) * 2^-e in `dtype`: exact in fp16 and bf16 for e in [-7, 15]."""
+    return (b.view(torch.float8_e4m3fn).float() * _pow2(-e)).to(dtype)
+
+
+def _garment_major(t, n, G):
+    """A timestep-major tensor [n * G * r][...] as [n][G][r * ...]: one garment's elements of every timestep along dims 0 and 2."""
+    return t.reshape(n, G, -1)
+
+
 class GarmentCache:
+    packed = False                                       # PackedGarmentCache: True
+
     def __init__(self, *, G, timesteps, h, w, dtype, attn_fp8, f8_exp, weights_id, kv, gh=None, gw=None, sizes=None, rows=None):
         self.G = int(G)
         self.timesteps = [int(t) for t in timesteps]
@@ -126,11 +169,19 @@ class GarmentCache:
         return (f"GarmentCache(G={self.G}, steps={len(self.timesteps)}, latent={self.h}x{self.w}{garment}, dtype={self.dtype}, "
                 f"attn_fp8={self.attn_fp8}, {self.nbytes / 2 ** 20:.1f} MiB)")
 
-    def _like(self, **kw):
+    def _args(self, **kw):
         args = dict(G=self.G, timesteps=self.timesteps, h=self.h, w=self.w, gh=self.gh, gw=self.gw, dtype=self.dtype, attn_fp8=self.attn_fp8,
                     f8_exp=self.f8_exp, weights_id=self.weights_id, kv=self.kv, sizes=self.sizes, rows=self.rows if self.sizes is not None else None)
         args.update(kw)
-        return GarmentCache(**args)
+        return args
+
+    def _like(self, **kw):
+        return GarmentCache(**self._args(**kw))
+
+    def _carry(self, sources, device=None, pin_memory=False):
+        """Constructor arguments beyond kv that a copy made of garments sources = [(cache, garment)] needs: none here (PackedGarmentCache: the
+        exponents of those garments)."""
+        return {}
 
     def for_person_size(self, h, w):
         """The same cache -- the same tensors, no copy -- declared for calls at person latent size (h, w).  The garment K / V^T are made from
@@ -207,7 +258,8 @@ class GarmentCache:
             kk = k.reshape(n, 1, r, k.shape[1]).expand(n, times, r, k.shape[1]).reshape(n * times * r, k.shape[1]).contiguous()
             vv = vt.reshape(n, 1, G, *vt.shape[1:]).expand(n, times, G, *vt.shape[1:]).reshape(n * times * G, *vt.shape[1:]).contiguous()
             kv.append((kk, vv))
-        return self._like(G=G * times, kv=kv, sizes=None if self.sizes is None else self.sizes * times, rows=self.rows * times)
+        return self._like(G=G * times, kv=kv, sizes=None if self.sizes is None else self.sizes * times, rows=self.rows * times,
+                          **self._carry([(self, g) for _ in range(times) for g in range(G)]))
 
 
     # ---- the pool primitives --------------------------------------------------------------------------------------------
@@ -215,6 +267,8 @@ class GarmentCache:
 
     def _agrees(self, other, what, devices=True):
         """ValueError naming the first field in which `other` differs from this cache (G aside; devices=False: and where its tensors live)."""
+        if self.packed != other.packed:
+            raise ValueError(f"GarmentCache {what}: packed mismatch ({self.packed} against {other.packed}: pack() or unpack() one of them)")
         for f in self._FIELDS:
             if getattr(self, f) != getattr(other, f):
                 raise ValueError(f"GarmentCache {what}: {f} mismatch ({getattr(self, f)} against {getattr(other, f)})")
@@ -243,7 +297,7 @@ class GarmentCache:
                     dv.copy_(sv)
         slotted = any(c.sizes is not None for c, _ in sources)       # equal slot size (_agrees): whole slots moved, the sizes go along
         return self._like(G=U, kv=kv, sizes=[c.sizes[g] if c.sizes is not None else (c.gh, c.gw) for c, g in sources] if slotted else None,
-                          rows=[c.rows[g] for c, g in sources] if slotted else None)
+                          rows=[c.rows[g] for c, g in sources] if slotted else None, **self._carry(sources))
 
     def select(self, ids):
         """A new cache (a copy) of garments ids[0], ids[1], ... of this one, in that order; values may repeat."""
@@ -335,7 +389,7 @@ class GarmentCache:
                 dk.copy_(sk[:Nf])
                 dv.copy_(sv[..., :ldf])
         if self.sizes is None:
-            return self._like(G=1, kv=kv)
+            return self._like(G=1, kv=kv, **self._carry([(self, int(slot))], device, pin))
         return self._like(G=1, kv=kv, gh=self.sizes[int(slot)][0], gw=self.sizes[int(slot)][1], sizes=None, rows=None)
 
     def to(self, device, pin_memory=False):
@@ -360,7 +414,7 @@ class GarmentCache:
     def save(self, path):
         """-> a safetensors file: tensors k.<f> / vt.<f> (e4m3 caches are uint8 bytes) and a metadata record (format version, G, timesteps, both
         sizes, dtype, attn_fp8, f8_exp, weights_id).  A cache with `sizes` writes format version 2, which adds sizes and rows; one without
-        writes version 1 exactly as before."""
+        writes version 1 exactly as before.  A packed cache writes version 3: `packed: true` and the tensor `exps`."""
         import json
         from safetensors.torch import save_file
         tensors = {}
@@ -368,6 +422,9 @@ class GarmentCache:
             tensors[f"k.{f:03d}"], tensors[f"vt.{f:03d}"] = k.detach().cpu().contiguous(), vt.detach().cpu().contiguous()
         meta = dict(format="idmvton_garment_cache", version=self.FORMAT_VERSION, G=self.G, timesteps=self.timesteps, h=self.h, w=self.w, gh=self.gh,
                     gw=self.gw, dtype=str(self.dtype), attn_fp8=self.attn_fp8, f8_exp=list(self.f8_exp), weights_id=self.weights_id, features=len(self.kv))
+        if self.packed:                                  # version 3: e4m3 bytes + the exponents
+            meta.update(version=3, packed=True)
+            tensors["exps"] = self.exps.detach().cpu().contiguous()
         if self.sizes is not None:
             meta.update(version=2, sizes=[list(sz) for sz in self.sizes], rows=[None if r is None else [list(x) for x in r] for r in self.rows])
         save_file(tensors, path, metadata={k: json.dumps(v) for k, v in meta.items()})
@@ -380,13 +437,147 @@ class GarmentCache:
         from safetensors import safe_open
         with safe_open(path, framework="pt", device=str(device)) as f:
             meta = {k: json.loads(v) for k, v in (f.metadata() or {}).items()}
-            if meta.get("format") != "idmvton_garment_cache" or meta.get("version") not in (GarmentCache.FORMAT_VERSION, 2):
+            if meta.get("format") != "idmvton_garment_cache" or meta.get("version") not in (GarmentCache.FORMAT_VERSION, 2, 3):
                 raise ValueError(f"GarmentCache load: {path} is not a garment cache of format version {GarmentCache.FORMAT_VERSION} "
                                  f"(format={meta.get('format')!r}, version={meta.get('version')!r})")
             kv = [(f.get_tensor(f"k.{i:03d}"), f.get_tensor(f"vt.{i:03d}")) for i in range(meta["features"])]
+            exps = f.get_tensor("exps") if meta.get("packed") else None
         dtype = {str(d): d for d in (torch.float16, torch.bfloat16, torch.float32)}[meta["dtype"]]
-        return GarmentCache(G=meta["G"], timesteps=meta["timesteps"], h=meta["h"], w=meta["w"], gh=meta["gh"], gw=meta["gw"], dtype=dtype,
-                            attn_fp8=meta["attn_fp8"], f8_exp=meta["f8_exp"], weights_id=meta["weights_id"], kv=kv, sizes=meta.get("sizes"), rows=meta.get("rows"))
+        args = dict(G=meta["G"], timesteps=meta["timesteps"], h=meta["h"], w=meta["w"], gh=meta["gh"], gw=meta["gw"], dtype=dtype,
+                    attn_fp8=meta["attn_fp8"], f8_exp=meta["f8_exp"], weights_id=meta["weights_id"], kv=kv, sizes=meta.get("sizes"), rows=meta.get("rows"))
+        return PackedGarmentCache(exps=exps, **args) if exps is not None else GarmentCache(**args)
+
+    # ---- packed storage ---------------------------------------------------------------------------------------------------
+    def pack_exps(self):
+        """int32 [G][F][2] (0 = K, 1 = V^T): pack_exponent of the largest |x| of every garment's tensors over ALL timesteps, on the device the
+        cache lives on, without a host sync."""
+        n, G = len(self.timesteps), self.G
+        amax = [torch.stack([_garment_major(t, n, G).abs().amax(dim=(0, 2)).float() for t in kvf], dim=-1) for kvf in self.kv]   # F x [G][2]
+        return pack_exponent(torch.stack(amax, dim=1))
+
+    def pack(self, exps=None):
+        """-> PackedGarmentCache (a copy): every K / V^T as e4m3 bytes under one exponent per (garment, feature, tensor) -- half the bytes.
+        Lossy: |x' - x| <= 2^-4 |x| where |x| * 2^e >= 2^-6, <= 2^-10 * 2^-e below.  On the GPU the bytes come from idmvton_quant_f8 (mode 0,
+        bit-equal to the torch conversion) applied to x * 2^e.  ValueError for a cache with `sizes`, an attn_fp8 cache and a packed one."""
+        if self.packed:
+            raise ValueError("GarmentCache pack: the cache is already e4m3-packed")
+        if self.sizes is not None:
+            raise ValueError("GarmentCache pack: a cache with `sizes` (slotted / mixed_sizes) cannot be packed: its slots are 16-bit")
+        if self.attn_fp8:
+            raise ValueError("GarmentCache pack: an attn_fp8 cache cannot be packed: its features already are e4m3 operands of the fp8 attention")
+        n, G = len(self.timesteps), self.G
+        exps = self.pack_exps() if exps is None else exps
+        kv = []
+        for f, kvf in enumerate(self.kv):
+            kv.append(tuple(_pack_tensor(t, exps[:, f, j], n, G) for j, t in enumerate(kvf)))
+        return PackedGarmentCache(exps=exps, **self._args(kv=kv))
+
+
+def _pack_tensor(t, e, n, G):
+    """One timestep-major K / V^T tensor under its garments' exponents e [G] -> bytes of the same shape."""
+    if not t.is_cuda:
+        return pack_values(_garment_major(t, n, G), e.view(1, G, 1)).reshape(t.shape)
+    from . import ops                                    # the HIP conversion; x * 2^e in the 16-bit dtype is exact where the byte is not 0
+    scaled = (_garment_major(t, n, G) * _pow2(e).view(1, G, 1)).to(t.dtype).reshape(-1, t.shape[-1])
+    return ops.quant_f8(scaled, 1.0).reshape(t.shape)
+
+
+class PackedGarmentCache(GarmentCache):
+    """A GarmentCache whose K / V^T are e4m3 bytes (module docstring): kv tensors are torch.uint8 in the 16-bit layout, `exps` int32 [G][F][2]
+    on the same device.  `dtype` is the 16-bit dtype the engine widens into, attn_fp8 is False, `sizes` is None."""
+    packed = True
+
+    def __init__(self, *, exps=None, **kw):
+        super().__init__(**kw)
+        if self.sizes is not None or self.attn_fp8 or any(k.dtype != torch.uint8 for k, _ in self.kv):
+            raise ValueError("PackedGarmentCache: holds e4m3 bytes (torch.uint8) of a cache without `sizes` and without attn_fp8")
+        dev = self.kv[0][0].device
+        self.exps = torch.zeros(self.G, len(self.kv), 2, dtype=torch.int32, device=dev) if exps is None else exps
+        if tuple(self.exps.shape) != (self.G, len(self.kv), 2) or self.exps.dtype != torch.int32 or self.exps.device.type != dev.type:
+            raise ValueError(f"PackedGarmentCache: exps must be int32 [G = {self.G}][F = {len(self.kv)}][2] on {dev.type}, got "
+                             f"{self.exps.dtype} {tuple(self.exps.shape)} on {self.exps.device.type}")
+
+    @property
+    def nbytes(self):
+        return GarmentCache.nbytes.fget(self) + self.exps.numel() * self.exps.element_size()
+
+    def __repr__(self):
+        return "Packed" + super().__repr__()[:-1] + ", e4m3-packed)"
+
+    def _like(self, **kw):
+        """exps go with the tensors: shared when the tensors are (for_person_size), else the caller's (`_carry`) or zeros -- a pool's empty slots."""
+        args = self._args(**kw)
+        if "exps" not in kw and "kv" not in kw:
+            args["exps"] = self.exps
+        return PackedGarmentCache(**args)
+
+    def _carry(self, sources, device=None, pin_memory=False):
+        dev = self.exps.device if device is None else torch.device(device)
+        out = torch.empty((len(sources), len(self.kv), 2), dtype=torch.int32, device=dev, pin_memory=bool(pin_memory) and dev.type == "cpu")
+        for j, (c, g) in enumerate(sources):
+            out[j].copy_(c.exps[g])
+        return dict(exps=out)
+
+    def for_person_size(self, h, w):
+        return self._like(h=h, w=w)                      # the same tensors and the same exps
+
+    def put(self, slot, other):
+        """As GarmentCache.put, for a packed G = 1 cache (bytes and exponents copied in place) or a 16-bit one, which is packed first on the
+        device it lives on.  The exponents travel on the same stream as the bytes: calls already queued read the old garment whole."""
+        if not other.packed and other.G == 1 and 0 <= int(slot) < self.G:
+            other = other.pack()
+        super().put(slot, other)
+        src = other.exps[0]
+        self.exps[int(slot)].copy_(src, non_blocking=src.is_cuda or src.is_pinned())
+        return self
+
+    def to(self, device, pin_memory=False):
+        c = super().to(device, pin_memory)
+        if c is not self:
+            device = torch.device(device)
+            if pin_memory and device.type == "cpu":
+                c.exps = torch.empty(self.exps.shape, dtype=torch.int32, device="cpu", pin_memory=True)
+                c.exps.copy_(self.exps)
+            else:
+                c.exps = self.exps.to(device, non_blocking=device.type != "cpu" and self.exps.device.type == "cpu" and self.exps.is_pinned())
+        return c
+
+    def unpack(self):
+        """-> the 16-bit GarmentCache (a copy) of x' = e4m3(byte) * 2^-e: exactly what the engine's sets hold during a call on this cache (on
+        the GPU the same idmvton_kv_unpack kernel writes it)."""
+        n, G = len(self.timesteps), self.G
+        kv = alloc_kv([(a, b, self.dtype) for a, b, _ in kv_shapes(self.kv)], n, n, self.kv[0][0].device)
+        if self.kv[0][0].is_cuda:
+            from . import ops
+            ops.KvUnpackTable(fill_records(self.kv, n, G, kv, n, G, self.exps, list(range(n)), list(range(n)), list(range(G)), list(range(G))),
+                              self.kv[0][0].device).launch(self.dtype)
+        else:
+            for f, (src, dst) in enumerate(zip(self.kv, kv)):
+                for j in range(2):
+                    _garment_major(dst[j], n, G).copy_(unpack_values(_garment_major(src[j], n, G), self.exps[:, f, j].view(1, G, 1), self.dtype))
+        return GarmentCache(**self._args(kv=kv))
+
+
+def fill_records(src_kv, n, G, dst_kv, k, S, exps, entries, tslots, garments, gslots):
+    """The idmvton_kv_unpack descriptor records (ops.KvUnpackTable: int64 [N][5]) that widen, for every pair (entry i, timestep slot j) of
+    (entries, tslots) and every pair (garment g, garment slot u) of (garments, gslots), feature f's K and V^T of (i, g) of the packed list
+    src_kv (n timesteps of G) into (j, u) of the 16-bit list dst_kv (k timesteps of S): one record per (timestep, garment, feature, K | V^T),
+    in that order.  Pure address arithmetic on the one layout rule (timestep_run / slot_run): element (i, g) of a tensor starts
+    (i * G + g) * (elements per garment and timestep) after its base."""
+    I64 = torch.int64
+    F = len(src_kv)
+    cols = torch.tensor([[kk.shape[1], vt.shape[2]] for kk, vt in src_kv], dtype=I64)                     # [F][2]: K rows are C wide, V^T rows ld
+    rows = torch.tensor([[kk.shape[0] // (n * G), vt.shape[1]] for kk, vt in src_kv], dtype=I64)           # N_f K rows, C V^T rows
+    sbase = torch.tensor([[kk.data_ptr(), vt.data_ptr()] for kk, vt in src_kv], dtype=I64)
+    dbase = torch.tensor([[kk.data_ptr(), vt.data_ptr()] for kk, vt in dst_kv], dtype=I64)
+    esz = dst_kv[0][0].element_size()
+    unit = rows * cols                                                                                     # elements per (timestep, garment)
+    si = (torch.tensor(entries, dtype=I64).view(-1, 1) * G + torch.tensor(garments, dtype=I64).view(1, -1)).view(len(entries), len(garments), 1, 1)
+    di = (torch.tensor(tslots, dtype=I64).view(-1, 1) * S + torch.tensor(gslots, dtype=I64).view(1, -1)).view(len(tslots), len(gslots), 1, 1)
+    ex = exps.data_ptr() + 4 * ((torch.tensor(garments, dtype=I64).view(1, -1, 1, 1) * F + torch.arange(F, dtype=I64).view(1, 1, F, 1)) * 2
+                                + torch.arange(2, dtype=I64).view(1, 1, 1, 2))
+    from . import ops
+    return ops.kv_unpack_rows(sbase + si * unit, dbase + di * unit * esz, ex, rows, cols, cols, cols).reshape(-1, 5)
 
 
 class GarmentPool:
@@ -397,6 +588,8 @@ class GarmentPool:
     mixed_sizes=True: the pool's cache is slotted -- `like` fixes the slot size, any garment that fits goes in, and a spilled garment has its own
     compact size on the host.  A slot's views are copied straight to and from the pinned tensors, with no temporary garment on the device.  Everything moves BEFORE the
     call -- nothing is streamed during one -- and the pool's tensors never move, so an engine's graph states stay valid across swaps.
+    A packed `like` (PackedGarmentCache) makes a packed pool: resident and spilled garments are e4m3 bytes + exponents, half the device and
+    pinned host memory, and `encode` may return packed or 16-bit garments (the latter are packed on their way in); not with mixed_sizes.
         pool = GarmentPool(8, like=pipe.encode_garment(cloth=c0, ...))
         out = pipe(cloth=pool.cache, garment_index=pool.get(["sku7", "sku7", "sku3"], encode=my_encode), ...)"""
 

@@ -316,6 +316,69 @@ def quant_f8(src, scale, mode=0, out=None):
     return out
 
 
+KV_UNPACK_CHUNK = 1024                                   # 16-byte items one workgroup of idmvton_kv_unpack widens (csrc/kv_unpack.hip)
+KV_UNPACK_MAX_N = 65534                                  # descriptors per launch (grid.y; even: a slice of a table stays 16-byte aligned)
+
+
+class KvUnpackTable:
+    """The descriptor table of idmvton_kv_unpack: `host` -- int64 CPU tensor [n][5] whose rows ARE idmvton_kv_unpack_desc records (src, dst,
+    exp, rows | cols << 32, lds | ldd << 32: little-endian, 40 bytes) --, `dev` its device copy (one upload), and `items` the 16-byte items
+    of each run.  launch(dtype, first, count) widens descriptors [first, first + count) in one launch; `first` must be even (40-byte
+    records: the slice of the device copy has to start 16-byte aligned)."""
+
+    def __init__(self, host, device):
+        self.host = host.contiguous()
+        self.n = self.host.shape[0]
+        lo = lambda c: self.host[:, c] & 0xffffffff
+        self.items = lo(3) * ((self.host[:, 3] >> 32) >> 4)
+        self.dev = self.host.to(device)
+
+    def launch(self, dtype, first=0, count=None):
+        count = self.n - first if count is None else count
+        if first % 2 or first < 0 or count < 1 or first + count > self.n:
+            raise ValueError(f"kv_unpack: descriptors [{first}, {first + count}) of {self.n} (an even first index, at least one descriptor)")
+        for f0 in range(first, first + count, KV_UNPACK_MAX_N):
+            c = min(KV_UNPACK_MAX_N, first + count - f0)
+            a = ffi.KvUnpackArgs()
+            a.dtype, a.n, a.desc = _DT[dtype], c, self.dev.data_ptr() + 40 * f0
+            a.max_chunks = (int(self.items[f0:f0 + c].max()) + KV_UNPACK_CHUNK - 1) // KV_UNPACK_CHUNK
+            launch = lambda: ffi.call_kv_unpack(a, self.host.data_ptr() + 40 * f0, _stream())
+            if PROFILE is None:
+                launch()
+                continue
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            launch()
+            e1.record()
+            PROFILE.append(("idmvton_kv_unpack", e0, e1, 0.0, 48.0 * float(self.items[f0:f0 + c].sum())))
+
+
+def kv_unpack_rows(src, dst, exp, rows, cols, lds, ldd):
+    """int64 [..., 5] descriptor records from broadcastable int64 tensors / ints (addresses and sizes): see KvUnpackTable."""
+    t = lambda v: v if isinstance(v, torch.Tensor) else torch.tensor(v, dtype=torch.int64)
+    src, dst, exp, rows, cols, lds, ldd = torch.broadcast_tensors(*[t(v) for v in (src, dst, exp, rows, cols, lds, ldd)])
+    return torch.stack([src, dst, exp, rows | (cols << 32), lds | (ldd << 32)], dim=-1)
+
+
+def kv_unpack(descs, dtype, device=None):
+    """e4m3 bytes -> 16-bit, exactly: dst = dtype(e4m3(src) * 2^-e) for every run of `descs`, in one launch (idmvton_kv_unpack).  descs: a
+    KvUnpackTable (launched whole), or a list of (src, dst, exp) -- src a uint8 2-D tensor view (row stride src.stride(0) bytes), dst a 2-D
+    view of `dtype` and the same shape, exp a one-element int32 device tensor view -- from which the table is built, checked and uploaded.
+    -> the table."""
+    if not isinstance(descs, KvUnpackTable):
+        rec = []
+        for src, dst, exp in descs:
+            if src.dtype != torch.uint8 or dst.dtype != dtype or exp.dtype != torch.int32 or exp.numel() != 1 or src.dim() != 2 or src.shape != dst.shape or \
+                    src.stride(1) != 1 or dst.stride(1) != 1:
+                raise ValueError("kv_unpack: a run is (uint8 [rows][cols], %s [rows][cols], one int32), rows contiguous" % dtype)
+            rows, cols = src.shape
+            rec.append((_ptr(src), _ptr(dst), _ptr(exp), rows | (cols << 32), src.stride(0) | (dst.stride(0) << 32)))
+        device = descs[0][0].device if device is None else device
+        descs = KvUnpackTable(torch.tensor(rec, dtype=torch.int64).reshape(-1, 5), device)
+    descs.launch(dtype)
+    return descs
+
+
 def attention_f8(q8, out, segs, heads, *, qk_scale_exp, v_scale_exp, B, Nq, ldq=None, ldo=None):
     """fp8 self-attention (csrc/attention_f8.hip).  q8: uint8 [B*Nq][>= heads*64]; segs: list of dict(k8=, vt8=, nk=, ldk=, ldvt=, k_rows=, b0=[, nb=][, index=][, nk_table=]);
     nb / index / nk_table as in attention() (idmvton_attn_f8_shared / idmvton_attn_f8_indexed / idmvton_attn_f8_ragged)."""

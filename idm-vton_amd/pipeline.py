@@ -32,6 +32,9 @@ execution form is the pair of callables it hands over:
     eager, cache   nothing to launch                                 _tryon_main on the cache's own views of entry gidx[i]
     graph, live    copy temb_gk[bi], replay ('garm', p, c)           copy tt / cf / nz, replay ('tryon', p, j)
     graph, cache   _fill_set: the block's cache entries -> set p     as graph, live
+A PACKED cache (GarmentCache.pack, encode_garment(storage="e4m3")) holds e4m3 bytes that TryonNet cannot read, so all four forms go through 16-bit
+sets: `_packed_fill` widens a block's cache entries into set p with ONE idmvton_kv_unpack launch, from a descriptor table built and uploaded once
+per call; the eager forms then use sets too (one, or two with overlap), and with garment_index the P-slot sets and slot table of the graph forms.
 With garment_index the two cache rows read through the table: eager on the cache's own views (nb = G, table = garment_index), graph on
 P-slot sets into which _fill_set gathers the U distinct garments of the call (table = person -> set slot, a persistent buffer of the state).
 
@@ -41,7 +44,7 @@ blocks.  The K / V^T layout of sets and cache (timestep-major) has one owner, ga
 import torch
 
 from . import ops
-from .garment_cache import GarmentCache, alloc_kv, index_runs, kv_shapes, slot_run, timestep_run
+from .garment_cache import GarmentCache, PackedGarmentCache, alloc_kv, fill_records, index_runs, kv_shapes, slot_run, timestep_run
 from .scheduler import StepScheduler
 
 
@@ -102,7 +105,7 @@ class TryonEngine:
         self.garment_steps = 6                               # timesteps per GarmentNet batch (see the module docstring)
         self.ramp = True                                     # first blocks of 1, 2, 4 timesteps
         # garment_batches: GarmentNet batches launched or replayed by this engine (a call on a GarmentCache adds none); garment_set_copies: blocks
-        # of cached K / V^T copied into a persistent set by the graph forms
+        # of cached K / V^T copied into a persistent set by the graph forms (on a packed cache: widened into one, by every form)
         self.stats = dict(garment_batches=0, garment_set_copies=0)
         self._weights_id = None
 
@@ -182,8 +185,15 @@ class TryonEngine:
     # -------------------------------------------------------------------------------------------- the garment side, once
     @torch.no_grad()
     def encode_garment(self, *, cloth, text_embeds_cloth, noise_cloth, num_inference_steps, scheduler="ddpm", strength=1.0,
-                       height=None, width=None):
+                       height=None, width=None, storage="native"):
         """The garment side of a call for G = cloth.shape[0] garments, computed once: -> GarmentCache for `prepare(cloth=<it>)`.
+        storage="e4m3": -> a PackedGarmentCache (garment_cache.py: e4m3 bytes + one exponent per garment, feature and tensor), bit-equal to
+        encode_garment(storage="native").pack() without that cache ever being resident.  The exponent needs the largest |x| over ALL
+        timesteps, so the block schedule runs TWICE into one block-sized 16-bit set: the first pass keeps the running maxima only, the second
+        packs each block into the cache's bytes under the final exponents (the launches are deterministic: both passes produce the same
+        bits).  Peak device memory beyond the weights: the packed cache (half the native one) + ONE block of 16-bit K / V^T and features
+        (garment_steps of n timesteps: 6 / 30 of the native cache at the default schedule) + that block's bytes once more on their way
+        into the cache (half the block) + one fp32 copy of the largest single tensor of the block while it is scaled.  Costs a second run of the GarmentNet batches; encoding is not on a call's path.
         cloth in [-1,1] [G,3,Hg,Wg], any size divisible by 8: the garment runs at its own latent (gh, gw) = (Hg / 8, Wg / 8); noise_cloth: the
         posterior draw of the cloth encode, [G,4,gh,gw] fp32 (noise['cloth'] of an uncached call).  height / width: the PERSON size the cache is
         declared for (default: the cloth's); GarmentCache.for_person_size re-declares it, the K / V^T do not depend on it.
@@ -213,11 +223,42 @@ class TryonEngine:
         n, k = len(timesteps), gs["k"]
         fs, ks = self._discover_set_shapes(gs)
         feats = [torch.empty(sh, dtype=self.dtype, device=dev) for sh in fs]
+        if storage == "e4m3":
+            return self._encode_packed(gs, feats, ks, timesteps, h, w)
+        if storage != "native":
+            raise ValueError(f"encode_garment: storage={storage!r} (\"native\" or \"e4m3\")")
         kv = alloc_kv(ks, k, n, dev)
         for bi, (s0, c) in enumerate(gs["blocks"]):          # each block's projections land in the cache's own rows
             self._garment_side(gs, gs["temb_gk"][bi], dict(feats=feats, kv=timestep_run(kv, n, G, s0, c)), c)
         return GarmentCache(G=G, timesteps=timesteps, h=h, w=w, gh=gh, gw=gw, dtype=self.dtype, attn_fp8=self.unet.attn_fp8, f8_exp=self.unet.f8_exp,
                             weights_id=self.weights_identity(), kv=kv)
+
+    def _encode_packed(self, gs, feats, ks, timesteps, h, w):
+        """encode_garment(storage="e4m3") after the shared preamble: see its docstring."""
+        if self.unet.attn_fp8:
+            raise ValueError("encode_garment(storage=\"e4m3\"): an attn_fp8 engine's cache cannot be packed (its features already are e4m3 operands)")
+        G, n, k, dev = gs["B"], len(timesteps), gs["k"], self.device
+        blk = alloc_kv(ks, k, k, dev)                        # one block of 16-bit K / V^T, reused by every batch of both passes
+        meta = dict(G=G, timesteps=timesteps, h=h, w=w, gh=gs["gh"], gw=gs["gw"], dtype=self.dtype, attn_fp8=False, f8_exp=self.unet.f8_exp,
+                    weights_id=self.weights_identity())
+        amax = None
+        for bi, (s0, c) in enumerate(gs["blocks"]):          # pass 1: the largest |x| per (garment, feature, tensor), as exponents' input
+            self._garment_side(gs, gs["temb_gk"][bi], dict(feats=feats, kv=timestep_run(blk, k, G, 0, c)), c)
+            m = torch.stack([torch.stack([t.reshape(c, G, -1).abs().amax(dim=(0, 2)).float() for t in kvf], dim=-1)
+                             for kvf in timestep_run(blk, k, G, 0, c)], dim=1)
+            amax = m if amax is None else torch.maximum(amax, m)
+        from .garment_cache import pack_exponent
+        exps = pack_exponent(amax)                           # [G][F][2], on the device, no host sync
+        kv = alloc_kv([(a, b, torch.uint8) for a, b, _ in ks], k, n, dev)
+        for bi, (s0, c) in enumerate(gs["blocks"]):          # pass 2: the same batches, packed into the cache's own rows
+            views = timestep_run(blk, k, G, 0, c)
+            self._garment_side(gs, gs["temb_gk"][bi], dict(feats=feats, kv=views), c)
+            part = GarmentCache(**{**meta, "timesteps": timesteps[s0:s0 + c], "kv": views}).pack(exps)
+            for (dk, dv), (sk, sv) in zip(timestep_run(kv, n, G, s0, c), part.kv):
+                dk.copy_(sk)
+                dv.copy_(sv)
+        self.stats["garment_batches"] -= len(gs["blocks"])   # counted once: the batches of the cache
+        return PackedGarmentCache(exps=exps, kv=kv, **meta)
 
     def empty_garment_cache(self, G, garment_height, garment_width, num_inference_steps, scheduler="ddpm", strength=1.0, height=None, width=None):
         """A slotted GarmentCache (one with `sizes`) of G uninitialised slots laid out for garments of garment_height x garment_width: what
@@ -430,6 +471,39 @@ class TryonEngine:
                 dk.copy_(sk)
                 dv.copy_(sv)
 
+    @staticmethod
+    def _cache_set_shapes(st):
+        """-> (slots, shapes) of a persistent set for a call on a GarmentCache: one slot per garment of the cache -- or, with garment_index,
+        one per PERSON, whatever the pool holds --, (K, V^T) shapes of a list holding the cache's n timesteps, in the engine's 16-bit dtype
+        (a packed cache's bytes are widened on the way in)."""
+        gc = st["gcache"]
+        slots = gc.G if st["gindex"] is None else st["B"]
+        dt = lambda d: gc.dtype if gc.packed else d
+        return slots, [((a[0] // gc.G * slots,) + a[1:], (b[0] // gc.G * slots,) + b[1:], dt(d)) for a, b, d in kv_shapes(gc.kv)]
+
+    def _packed_fill(self, st, sets, blocks=None):
+        """-> garment(bi, p) of a call on a PACKED cache: block bi's cache entries widened into the first timestep slots of sets[p] by ONE
+        idmvton_kv_unpack launch on the current stream.  The gather is _fill_set's -- entries by value, consecutive or not; with
+        garment_index the U distinct garments in first-use order into slots 0 .. U - 1 of P-slot sets -- written as descriptors, one per
+        (timestep, garment, feature, K | V^T): cache, set and exponent addresses are all stable, so the table of every (set, step) is built on
+        the host and uploaded ONCE, here, and a block is a slice of it.  `blocks`: build for these block numbers only (the warm-up)."""
+        gc, k = st["gcache"], st["k"]
+        n = len(gc.timesteps)
+        garments = list(range(gc.G)) if st["gindex"] is None else list(dict.fromkeys(st["gindex"]))
+        S = gc.G if st["gindex"] is None else st["B"]
+        steps = [(s0 + j, j) for bi, (s0, c) in enumerate(st["blocks"]) if blocks is None or bi in blocks for j in range(c)]
+        first = {i: at for at, (i, _) in enumerate(steps)}   # step of the call -> its place in a set's part of the table
+        per = len(garments) * len(gc.kv) * 2                 # records per step: even, so every slice starts 16-byte aligned
+        rec = torch.cat([fill_records(gc.kv, n, gc.G, fs["kv"], k, S, gc.exps, [st["gidx"][i] for i, _ in steps], [j for _, j in steps], garments,
+                                      list(range(len(garments)))) for fs in sets])
+        table = ops.KvUnpackTable(rec, self.device)
+
+        def garment(bi, p):
+            s0, c = st["blocks"][bi]
+            self.stats["garment_set_copies"] += 1
+            table.launch(self.dtype, (p * len(steps) + first[s0]) * per, c * per)
+        return garment
+
     def _slot_table(self, st):
         """Graph forms with garment_index: person -> slot of the persistent sets, where _fill_set puts the call's distinct garments in
         first-use order ([7, 7, 3, 9] -> [0, 0, 1, 2]); None without an index."""
@@ -449,6 +523,12 @@ class TryonEngine:
         if live:
             sets = [self._new_set(st) for _ in range(2 if overlap else 1)]
             garment = lambda bi, p: self._garment_side(st, st["temb_gk"][bi], sets[p], blocks[bi][1])
+            kv = lambda i, j, p: sets[p]["step"][j]
+        elif st["gcache"].packed:                            # e4m3 bytes: TryonNet reads 16-bit sets, as the graph forms do (one, or two to overlap)
+            slots, shapes = self._cache_set_shapes(st)
+            sets = [self._alloc_set((), shapes, len(st["gcache"].timesteps), st["k"], slots) for _ in range(2 if overlap else 1)]
+            garment = self._packed_fill(st, sets)
+            st = dict(st, gix=self._slot_table(st))          # with garment_index: person -> set slot (the same tensors otherwise)
             kv = lambda i, j, p: sets[p]["step"][j]
         else:                                                # nothing to launch, so nothing to overlap: TryonNet reads the cache's own views
             overlap = False
@@ -497,13 +577,12 @@ class TryonEngine:
                 self._garment_side(G, G["tgk"], G["sets"][0])
             else:                                            # the first block's fill stands in for a warm-up batch
                 gc = st["gcache"]
-                if st["gindex"] is None:
-                    slots, shapes = gc.G, kv_shapes(gc.kv)
-                else:                                        # one slot per person, whatever the pool holds
-                    slots = st["B"]
-                    shapes = [((a[0] // gc.G * slots,) + a[1:], (b[0] // gc.G * slots,) + b[1:], d) for a, b, d in kv_shapes(gc.kv)]
+                slots, shapes = self._cache_set_shapes(st)   # (with an index: one slot per person, whatever the pool holds)
                 G["sets"] = [self._alloc_set((), shapes, len(gc.timesteps), st["k"], slots) for _ in range(2)]
-                self._fill_set(st, G["sets"][0], *st["blocks"][0])
+                if gc.packed:                                # (a table of block 0 alone: complete before the synchronize below)
+                    self._packed_fill(st, G["sets"][:1], blocks=(0,))(0, 0)
+                else:
+                    self._fill_set(st, G["sets"][0], *st["blocks"][0])
             self._tryon_main(G, G["tt"], G["cf"], G["nz"], G["sets"][0]["step"][0])
         torch.cuda.current_stream().wait_stream(warm)
         torch.cuda.synchronize()
@@ -545,6 +624,8 @@ class TryonEngine:
                 G["tgk"].copy_(st["temb_gk"][bi])
                 self.stats["garment_batches"] += 1
                 graphs[("garm", p, blocks[bi][1])].replay()
+        elif st["gcache"].packed:                            # in the same place: one launch that widens the block's bytes into set p
+            garment = self._packed_fill(st, G["sets"])
         else:                                                # in the GarmentNet graph's place in the stream / event order: a copy out of the cache
             garment = lambda bi, p: self._fill_set(st, G["sets"][p], *blocks[bi])
         tt, cf, nz = G["tt"], G["cf"], G["nz"]

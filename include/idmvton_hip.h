@@ -251,6 +251,30 @@ typedef struct {
 int idmvton_quant_f8(const idmvton_quant_f8_args* a, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * idmvton_kv_unpack : the packed garment cache (idm-vton_amd/garment_cache.py, PackedGarmentCache) -> 16-bit K / V^T.  ONE launch widens
+ * n independent strided 2-D runs: dst[r][c] = dtype(e4m3(src[r][c]) * 2^-*exp) for c < cols -- exact: an e4m3 value has 4 significant bits
+ * and *exp lies in [-7, 15] (a value outside is read as the nearer bound), so nothing is rounded.  Bytes [cols, lds) of a source row are not
+ * read, elements [cols, ldd) of a destination row are not written.  No reference counterpart (the reference recomputes the garment
+ * features in every step, src/tryon_pipeline.py:1781-1787).
+ * host_desc[0..n) is validated field by field before the launch (non-null pointers; src / dst 16-byte aligned; rows >= 1; cols >= 16,
+ * cols % 16 == 0; lds >= cols, lds % 16 == 0; ldd >= cols, ldd % 8 == 0; 1 <= n <= 65535; max_chunks == ceil(largest rows * cols / 16 /
+ * 1024): a workgroup widens 1024 16-byte items); the caller guarantees that a->desc is the uploaded copy of host_desc.
+ * Grid (max_chunks, n); plain vector stores.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    const void* src;            /* e4m3 bytes, row stride lds bytes */
+    void* dst;                  /* 16-bit, row stride ldd elements */
+    const int32_t* exp;         /* DEVICE int32: the run's exponent e (the bytes hold x * 2^e) */
+    int32_t rows, cols, lds, ldd;
+} idmvton_kv_unpack_desc;
+typedef struct {
+    int32_t dtype; int32_t n;
+    const idmvton_kv_unpack_desc* desc;   /* device copy of host_desc, 16-byte aligned */
+    int32_t max_chunks;
+} idmvton_kv_unpack_args;
+int idmvton_kv_unpack(const idmvton_kv_unpack_args* a, const idmvton_kv_unpack_desc* host_desc, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * idmvton_attn_small : softmax(scale * q k^T [+ causal mask]) v for the one-off conditioning encoders -- the CLIP text towers
  * (transformers CLIPTextModel / CLIPTextModelWithProjection as called at src/tryon_pipeline.py:511-743: 77 tokens, causal) and
  * the CLIP-H vision tower (:460-482: 257 tokens, head_dim 80).  Any even head_dim <= 128, Lk <= 1024, fp32 arithmetic; one wave
