@@ -100,7 +100,8 @@ typedef struct {
                                     of the BM field = placement form 0 | 1; bit 14 of it, tests only: 5 persistent workgroups) and 256x192 -- a PERSISTENT kernel:
                                     min(tiles, CUs) workgroups walk the tile raster.  Bit 15
                                     (0x8000) forces the 8-byte epilogue (measurement only; default: 16-byte accesses when every
-                                    epilogue operand is 16-byte aligned with strides / N multiples of 8).
+                                    epilogue operand that is present -- out, res, bias, rowbias -- is 16-byte aligned, and ldo, ldr, rowbias_ld,
+                                    N, the output's column count (N / 2 under GEGLU) and colscale_n are all multiples of 8).
                                     Filled from the per-shape tuning table (idm-vton_amd/tune_gfx950.json). */
     int32_t vt_perm;             /* 1: write vt in the attention kernel's KEY ORDER: inside every group of 16 tokens, bits 2 and 3 of
                                     the token index are swapped (position p holds token (p&~12)|((p&4)<<1)|((p&8)>>1)), which makes

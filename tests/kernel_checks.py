@@ -57,14 +57,31 @@ def _hint(variant, bn, bm):
 
 
 # ------------------------------------------------------------------------------------------------ GEMM / conv
-def check_linear(M, N, K, dtype, dev, bias=True, res=True, rowbias=False, tile_hint=0, seed=0, alloc=None, groups=None):
-    """groups: row groups of the rowbias (default 4 when M % 4 == 0, else 1); M % groups == 0."""
+def _act(y, act):
+    """The activation of the reference: erf GELU (F.gelu's default) or x * sigmoid(1.702 x)."""
+    if act == "gelu":
+        return F.gelu(y)
+    if act == "quick_gelu":
+        return y * torch.sigmoid(1.702 * y)
+    assert act is None, act
+    return y
+
+
+def check_linear(M, N, K, dtype, dev, bias=True, res=True, rowbias=False, tile_hint=0, seed=0, alloc=None, groups=None, act=None, colscale=None,
+                 out_f32=False):
+    """groups: row groups of the rowbias (default 4 when M % 4 == 0, else 1); M % groups == 0.
+    bias / res: True (the storage dtype), "f32" (IDMVTON_IO_BIAS_F32 / IDMVTON_IO_RES_F32) or False; act: None, "gelu" (erf) or "quick_gelu";
+    colscale = (n, s): columns [0, n) times s.  Reference order: bias -> rowbias -> colscale -> activation -> residual, all in fp32.
+    out_f32: fp32 output -- the only roundings left are those of the 16-bit operands, which the reference shares, so the error is returned by
+    check_stream_f32's rule, relerr / 2e-5 * TOL[dtype]: within the caller's TOL means within 2e-5 (a quick-GELU run for erf GELU lies 2.5e-3
+    away, the tanh form 6e-5: the 16-bit bars cannot tell them apart, this one does)."""
     from idm_vton_amd import ops
     al = alloc or Tight()
+    kind = lambda k: torch.float32 if k == "f32" else dtype
     x = al.inp("x", _r(M, K, dtype=dtype, dev=dev, seed=seed))
     w = al.inp("w", _r(N, K, dtype=dtype, dev=dev, scale=K ** -0.5, seed=seed + 1), contig=True)
-    b = al.inp("bias", _r(N, dtype=dtype, dev=dev, seed=seed + 2), contig=True) if bias else None
-    rs = al.inp("res", _r(M, N, dtype=dtype, dev=dev, seed=seed + 3)) if res else None
+    b = al.inp("bias", _r(N, dtype=kind(bias), dev=dev, seed=seed + 2), contig=True) if bias else None
+    rs = al.inp("res", _r(M, N, dtype=kind(res), dev=dev, seed=seed + 3)) if res else None
     ref = x.float() @ w.float().t()
     if bias:
         ref = ref + b.float()
@@ -74,10 +91,34 @@ def check_linear(M, N, K, dtype, dev, bias=True, res=True, rowbias=False, tile_h
         rb = al.inp("rowbias", _r(G, N, dtype=dtype, dev=dev, seed=seed + 4))
         ref = ref + rb.float().repeat_interleave(M // G, dim=0)
         kw = dict(rowbias=rb, rowbias_ld=rb.stride(0), rows_per_group=M // G)
+    if colscale:
+        ref = ref.clone()
+        ref[:, :colscale[0]] *= colscale[1]
+        kw.update(colscale_n=colscale[0], colscale=colscale[1])
+    if act:
+        ref = _act(ref, act)
+        kw[act] = True
     if res:
         ref = ref + rs.float()
-    out = ops.linear(x, w, bias=b, res=rs, out=al.out("out", (M, N), dtype, dev, own=True), tile_hint=tile_hint, **kw)
-    return relerr(al.done("out", out), ref)
+    out = ops.linear(x, w, bias=b, res=rs, out=al.out("out", (M, N), torch.float32 if out_f32 else dtype, dev, own=True), tile_hint=tile_hint,
+                     out_f32=out_f32, **kw)
+    e = relerr(al.done("out", out), ref)
+    if out_f32:
+        assert out.dtype == torch.float32
+        e = e / 2e-5 * TOL[dtype]
+    return e
+
+
+def check_epilogue_widths(dtype, dev, tile_hint, **kw):
+    """The 8-byte epilogue of a NAMED tile (bit 15 of its hint) against the 16-byte one of the same tile on the same values (a check_linear case
+    whose shape admits both): each within check_linear's bar, and the two outputs BIT-EQUAL -- both widths apply the same fp32 operations in the
+    same order to the same accumulators and round once (the 320-column tile hands the narrow launch to the 128x256 ring tile, which walks K in
+    the same 64-wide steps)."""
+    assert tile_hint and not tile_hint & 0x8000
+    wide, narrow = Tight(), Tight()
+    e_w = check_linear(dtype=dtype, dev=dev, tile_hint=tile_hint, alloc=wide, **kw)
+    e_n = check_linear(dtype=dtype, dev=dev, tile_hint=tile_hint | 0x8000, alloc=narrow, **kw)
+    return max(e_w, e_n) if torch.equal(wide.outs["out"], narrow.outs["out"]) else float("inf")
 
 
 def check_geglu(M, C, dtype, dev, seed=0, tile_hint=0, alloc=None):
@@ -98,28 +139,79 @@ def check_geglu(M, C, dtype, dev, seed=0, tile_hint=0, alloc=None):
     return relerr(al.done("out", out), ref)
 
 
-def check_vt(B, Ntok, C, dtype, dev, seed=0, tile_hint=0, alloc=None):
-    """Fused QKV-style projection: columns [0,2C) normal, columns [2C,3C) written transposed as V^T[b][c][tok]."""
+def check_vt(B, Ntok, C, dtype, dev, seed=0, tile_hint=0, alloc=None, bias=False, colscale=None, vt_n0_zero=False):
+    """Fused QKV-style projection: columns [0,2C) normal, columns [2C,3C) written transposed as V^T[b][c][tok].
+    bias: one bias vector over all 3C columns (the V^T branches add their own element of it); colscale = (n, s): the q columns [0, n) times s in
+    fp32 before the one rounding (the engine's QKV projection: n = C, s = softmax_scale * log2e), against the same fp32 product scaled;
+    vt_n0_zero: the 16-bit VAE mid-block's to_v -- N = C, vt_n0 = 0, every column goes to V^T, out = None, plain transpose only."""
     from idm_vton_amd import ops
     al = alloc or Tight()
     M = B * Ntok
+    Nw, n0 = (C, 0) if vt_n0_zero else (3 * C, 2 * C)
     x = al.inp("x", _r(M, C, dtype=dtype, dev=dev, seed=seed))
-    w = al.inp("w", _r(3 * C, C, dtype=dtype, dev=dev, scale=C ** -0.5, seed=seed + 1), contig=True)
+    w = al.inp("w", _r(Nw, C, dtype=dtype, dev=dev, scale=C ** -0.5, seed=seed + 1), contig=True)
     ref = x.float() @ w.float().t()
-    out = al.out("out", (M, 2 * C), dtype, dev, init=0.0)
+    kw = {}
+    if bias:
+        b = al.inp("bias", _r(Nw, dtype=dtype, dev=dev, seed=seed + 2), contig=True)
+        ref = ref + b.float()
+        kw["bias"] = b
+    if colscale:
+        assert colscale[0] <= n0
+        ref = ref.clone()
+        ref[:, :colscale[0]] *= colscale[1]
+        kw.update(colscale_n=colscale[0], colscale=colscale[1])
+    out = None if vt_n0_zero else al.out("out", (M, 2 * C), dtype, dev, init=0.0)
     vt = al.out("vt", (B, C, Ntok), dtype, dev, contig=True, init=0.0)            # V^T is contiguous by ABI: framed before and after
-    vt_ref = ref[:, 2 * C:].reshape(B, Ntok, C).transpose(1, 2)
-    ops.linear(x, w, out=out, vt=vt, vt_n0=2 * C, vt_tokens=Ntok, vt_perm=False, tile_hint=tile_hint)     # plain transpose
-    e1 = relerr(out, ref[:, : 2 * C])
+    vt_ref = ref[:, n0:].reshape(B, Ntok, C).transpose(1, 2)
+    ops.linear(x, w, out=out, vt=vt, vt_n0=n0, vt_tokens=Ntok, vt_perm=False, tile_hint=tile_hint, **kw)     # plain transpose
+    e1 = 0.0 if vt_n0_zero else relerr(out, ref[:, : 2 * C])
     e2 = relerr(vt, vt_ref)
     e3 = 0.0
-    if Ntok % 16 == 0:                                   # attention key order (bits 2/3 of the token index swapped per 16)
+    if Ntok % 16 == 0 and not vt_n0_zero:                # attention key order (bits 2/3 of the token index swapped per 16)
         vt2 = al.out("vt_perm", (B, C, Ntok), dtype, dev, contig=True, init=0.0)
-        ops.linear(x, w, out=out, vt=vt2, vt_n0=2 * C, vt_tokens=Ntok, tile_hint=tile_hint)
+        ops.linear(x, w, out=out, vt=vt2, vt_n0=2 * C, vt_tokens=Ntok, tile_hint=tile_hint, **kw)
         e3 = relerr(vt2, ops.key_order(vt_ref))
         if not torch.equal(ops.key_order(vt2), vt):      # same values, only the position differs
             e3 = float("inf")
     return max(e1, e2, e3)
+
+
+def check_row_repitch(B, N, Cin, Cout, dtype, dev, seed=0, tile_hint=0, alloc=None):
+    """The 1-D row re-pitch of unet.py's proj_in / proj_out when H*W is no multiple of 16: a Linear gathered as a 1x1 convolution between image
+    rows of different lengths (Ho = Hi = 1).
+    Pad:  Wo = round16(N), Wi = N, bias, 16-bit and fp32 output: rows < N of every image are the Linear; rows N.. read outside the image -- zeros
+          -- so they hold EXACTLY the bias, rounded to the output type (the finite filler the attention then masks as keys).
+    Crop: source [B][round16(N)][Cin] whose rows N.. hold the policy's poison (7.0 tight, NaN framed), Wo = N, Wi = round16(N), bias + residual:
+          the rows come back, the pad rows are never read."""
+    from idm_vton_amd import ops
+    al = alloc or Tight()
+    Np = ops.round16(N)
+    xv = _r(B, N, Cin, dtype=dtype, dev=dev, seed=seed)
+    x = al.inp("x", xv)
+    w = al.inp("w", _r(Cout, Cin, dtype=dtype, dev=dev, scale=Cin ** -0.5, seed=seed + 1), contig=True)
+    b = al.inp("bias", _r(Cout, dtype=dtype, dev=dev, seed=seed + 2), contig=True)
+    lin = xv.float().reshape(B * N, Cin) @ w.float().t() + b.float()
+    ref = b.float().expand(B, Np, Cout).clone()
+    ref[:, :N] = lin.view(B, N, Cout)
+    worst = 0.0
+    for name, f32 in (("pad16", False), ("pad32", True)):
+        odt = torch.float32 if f32 else dtype
+        o = ops.gemm_conv([ops.SegSpec(x, 0, Cin)], w, B * Np, Ho=1, Wo=Np, Hi=1, Wi=N, bias=b, out=al.out(name, (B * Np, Cout), odt, dev, own=True),
+                          out_f32=f32, tile_hint=tile_hint)
+        assert al.done(name, o).dtype == odt
+        e = relerr(o, ref.view(B * Np, Cout))
+        worst = max(worst, e / 2e-5 * TOL[dtype] if f32 else e)
+        if not torch.equal(o.reshape(B, Np, Cout)[:, N:].float(), b.float().expand(B, Np - N, Cout)):
+            worst = float("inf")
+    src = torch.full((B, Np, Cin), 7.0, dtype=dtype, device=dev)
+    src[:, :N] = xv
+    al.poison(src[:, N:])
+    src = al.inp("src", src)
+    rs = al.inp("res", _r(B * N, Cout, dtype=dtype, dev=dev, seed=seed + 3))
+    o = ops.gemm_conv([ops.SegSpec(src, 0, Cin)], w, B * N, Ho=1, Wo=N, Hi=1, Wi=Np, bias=b, res=rs, out=al.out("crop", (B * N, Cout), dtype, dev, own=True),
+                      tile_hint=tile_hint)
+    return max(worst, relerr(al.done("crop", o), lin + rs.float()))
 
 
 def _nhwc(t):
@@ -188,7 +280,7 @@ def check_conv(B, Cin, Cout, H, W, dtype, dev, k=3, stride=1, ups=False, split=0
         rs = _r(B, Cout, Ho, Wo, dtype=dtype, dev=dev, seed=seed + 4)
         ref = ref + rs.float()
         kw.update(res=al.inp("res", _nhwc(rs).reshape(M, Cout)))
-    if len(segs) > 12:
+    if len(segs) > 24:                                   # IDMVTON_MAX_SEG
         raise ValueError("too many segments for one launch")
     out = ops.gemm_conv(segs, al.inp("w", wk, contig=True), M, Ho=Ho, Wo=Wo, Hi=H, Wi=W, stride=stride, ups=ups, bias=al.inp("bias", bias, contig=True),
                         out=al.out("out", (M, Cout), dtype, dev, own=True), tile_hint=tile_hint, **kw)
@@ -255,7 +347,7 @@ def _f8_slot_key(n, dev):
 
 
 def check_attn_product(dtype, dev, tune=0, entry="plain", f8=False, alloc=None, B=3, heads=2, Nq=200, k_rows=208, n_garm=72, g_rows=80, b0=1, seed=0,
-                       nk_own=None):
+                       nk_own=None, prescaled=None):
     """SELF attention in the launch geometry of unet.py's _block, which the checks above do not have: q and k are the column halves of ONE
     [B * k_rows][2C] buffer (ldq = ldk = 2C), the own segment has nk = nk_own (default Nq) keys in k_rows >= nk rows per batch element, the garment segment its own
     n_garm keys in g_rows rows from batch b0 on, and every V^T row is longer than round16(nk).  K rows nk..k_rows-1 hold what the policy puts
@@ -266,11 +358,13 @@ def check_attn_product(dtype, dev, tune=0, entry="plain", f8=False, alloc=None, 
     garment's count, the unconditional batches count their person's garment in the closed form; beyond a slot's length K is poisoned, V^T
     holds the `finite` filler up to round16 / zero up to round64 (fp8) and is poisoned beyond).
     f8: idmvton_attn_f8 on e4m3 bytes made by torch's own conversion (byte strides); returns (error against fp32 SDPA on the unquantised operands,
-    error against fp32 SDPA on the dequantised ones) -- the 1.2e-1 / 3e-2 bars of check_attn_f8 -- else the error against fp32 SDPA."""
+    error against fp32 SDPA on the dequantised ones) -- the 1.2e-1 / 3e-2 bars of check_attn_f8 -- else the error against fp32 SDPA.
+    prescaled: None = a pre-multiplied q whenever a tune word is named (the engine's launches); False = a RAW q on a named kernel that accepts
+    one (kernels 0, 2 and 3; 3 then runs the build of 2) -- the Resampler's launch: Nq = 16 latent queries against nk_own = 257 keys."""
     from idm_vton_amd import ops
     al = alloc or Tight()
     C = heads * 64
-    pres = bool(tune) or f8                                                   # kernels 3, 7, 8, 16 need a pre-multiplied q; tune 0 runs the rule for a raw q
+    pres = (bool(tune) or f8) if prescaled is None else prescaled              # kernels 3, 7, 8, 16 need a pre-multiplied q; tune 0 runs the rule for a raw q
     q = _r(B, Nq, C, dtype=dtype, dev=dev, seed=seed)
     nk1 = Nq if nk_own is None else nk_own
     k1, v1 = _r(B, nk1, C, dtype=dtype, dev=dev, seed=seed + 1), _r(B, nk1, C, dtype=dtype, dev=dev, seed=seed + 2)
@@ -680,12 +774,17 @@ def check_attn_small(B, heads, L, d, dtype, dev, causal, Lq=None, seed=0, scale=
 
 
 def check_quickgelu(dtype, dev):
-    """quick_gelu epilogue (CLIP-L MLP): (x W^T + b) * sigmoid(1.702 (x W^T + b)), then + residual."""
+    """quick_gelu epilogue (CLIP-L MLP): (x W^T + b) * sigmoid(1.702 (x W^T + b)), then + residual -- in 16 bits, and with fp32 output by
+    check_stream_f32's rule (<= 2e-5, scaled to the caller's tolerance)."""
     from idm_vton_amd import ops
     M, N, K = 154, 3072, 768
     x, w, b = _r(M, K, dtype=dtype, dev=dev), _r(N, K, dtype=dtype, dev=dev, scale=2 * K ** -0.5, seed=1), _r(N, dtype=dtype, dev=dev, seed=2)
+    rs = _r(M, N, dtype=dtype, dev=dev, seed=3)
     pre = x.float() @ w.float().t() + b.float()
-    return relerr(ops.linear(x, w, bias=b, quick_gelu=True), pre * torch.sigmoid(1.702 * pre))
+    ref = pre * torch.sigmoid(1.702 * pre) + rs.float()
+    e16 = relerr(ops.linear(x, w, bias=b, res=rs, quick_gelu=True), ref)
+    e32 = relerr(ops.linear(x, w, bias=b, res=rs, quick_gelu=True, out_f32=True), ref)
+    return max(e16, e32 / 2e-5 * TOL[dtype])
 
 
 # ------------------------------------------------------------------------------------------------ norms / elementwise
@@ -842,9 +941,10 @@ def check_softmax_rows(rows, n, dtype, dev, n_valid=0, seed=0, alloc=None):
     return max(relerr(x, ref), tail)
 
 
-def check_plin(M, N, K, dev, exact_w=False, res=True, seed=0, alloc=None):
+def check_plin(M, N, K, dev, exact_w=False, res=True, seed=0, alloc=None, bias=True, colscale=None):
     """A Linear through the split-precision path (vae._PConv: [hi | lo] activations x [w_hi | w_hi][w_lo] weights, fp32 bias / residual /
-    output) against fp64: fp32-equivalent (<= 2e-5 of the output range), where the 16-bit path gives 2e-3 / 1.6e-2."""
+    output) against fp64: fp32-equivalent (<= 2e-5 of the output range), where the 16-bit path gives 2e-3 / 1.6e-2.
+    bias=False: no bias (the mid-block attention's logits and P.V products); colscale = (n, s): columns [0, n) times s after the bias (its to_q)."""
     from idm_vton_amd import ops
     from idm_vton_amd.vae import _PConv
     x = _r(M, K, dtype=torch.float32, dev=dev, seed=seed)
@@ -857,15 +957,20 @@ def check_plin(M, N, K, dev, exact_w=False, res=True, seed=0, alloc=None):
     cv = _PConv(w, b)
     assert cv.three == (not exact_w)
     xp = al.inp("xp", ops.split(x, torch.bfloat16))
-    out = ops.gemm_conv(cv.segs(xp, 0), al.inp("w", cv.w, contig=True), M, bias=al.inp("bias", cv.b, contig=True), res=rs,
-                        out=al.out("out", (M, N), torch.float32, dev, own=True), out_f32=True)
+    kw = dict(colscale_n=colscale[0], colscale=colscale[1]) if colscale else {}
+    out = ops.gemm_conv(cv.segs(xp, 0), al.inp("w", cv.w, contig=True), M, bias=al.inp("bias", cv.b, contig=True) if bias else None, res=rs,
+                        out=al.out("out", (M, N), torch.float32, dev, own=True), out_f32=True, **kw)
     al.done("out", out)
-    ref = x.double() @ w.double().t() + b.double() + (rs.double() if res else 0.0)
+    ref = x.double() @ w.double().t() + (b.double() if bias else 0.0)
+    if colscale:
+        ref[:, :colscale[0]] *= colscale[1]
+    ref = ref + (rs.double() if res else 0.0)
     return _relerr64(out, ref)
 
 
-def check_pconv(B, Cin, Cout, H, W, dev, ups=False, shortcut=0, exact_w=False, seed=0, alloc=None):
-    """3x3 conv (optionally fused nearest-2x, optionally a fused 1x1 shortcut on a second input) through the split-precision path vs fp64."""
+def check_pconv(B, Cin, Cout, H, W, dev, ups=False, shortcut=0, exact_w=False, seed=0, alloc=None, res=False):
+    """3x3 conv (optionally fused nearest-2x, optionally a fused 1x1 shortcut on a second input, optionally + an fp32 residual: conv2 of a
+    resnet whose channel count does not change) through the split-precision path vs fp64."""
     from idm_vton_amd import ops
     from idm_vton_amd.vae import _PConv
     x = _r(B, H, W, Cin, dtype=torch.float32, dev=dev, seed=seed)
@@ -889,8 +994,12 @@ def check_pconv(B, Cin, Cout, H, W, dev, ups=False, shortcut=0, exact_w=False, s
     cv = _PConv(w, b, shortcut=sc)
     xp = al.inp("xp", ops.split(x.reshape(-1, Cin), torch.bfloat16).view(B, H * W, 2 * Cin))
     Ho, Wo = (2 * H, 2 * W) if ups else (H, W)
+    rs = None
+    if res:
+        rs = al.inp("res", _r(B * Ho * Wo, Cout, dtype=torch.float32, dev=dev, seed=seed + 6))
+        ref = ref + rs.double().reshape(B, Ho, Wo, Cout).permute(0, 3, 1, 2)
     out = ops.gemm_conv(cv.segs(xp, 1, xs), al.inp("w", cv.w, contig=True), B * Ho * Wo, Ho=Ho, Wo=Wo, Hi=H, Wi=W, ups=ups, bias=al.inp("bias", cv.b, contig=True),
-                        out=al.out("out", (B * Ho * Wo, Cout), torch.float32, dev, own=True), out_f32=True)
+                        res=rs, out=al.out("out", (B * Ho * Wo, Cout), torch.float32, dev, own=True), out_f32=True)
     return _relerr64(al.done("out", out).reshape(B, Ho, Wo, Cout).permute(0, 3, 1, 2), ref)
 
 
@@ -975,6 +1084,18 @@ F8_OUT_TILES = (("auto", 0), ("r128x128", _hint(1, 128, 128)), ("r128x256", _hin
                # (the 320-column tile has no e4m3 / V^T epilogue: the library refuses or re-routes such a launch, see gemm_f8_out_320_tile_is_refused)
                ("w16_256x256", _hint(6, 256, 256)), ("w16_128x256", _hint(6, 128, 256)), ("p128x256", _hint(2, 128, 256)),
                ("v0_64x64", _hint(0, 64, 64)), ("r64x64", _hint(1, 64, 64)))
+
+
+# the three variant-0 hints, and every tile a launch form is checked on (the auto rule, variant 0, RING_TILES)
+V0_TILES = (((128 << 16) | 128, "v0_128x128"), ((128 << 16) | 64, "v0_128x64"), ((64 << 16) | 64, "v0_64x64"))
+FORM_TILES = ((0, "auto"),) + V0_TILES + RING_TILES
+QS = 0.125 * 1.4426950408889634                           # ops.QSCALE: what the engine's QKV projection multiplies the q columns by
+ACT_SHAPE = dict(M=515, N=328, K=192)                     # an M and an N tail on every tile, several tiles for the persistent-walk forms
+ACT_SHAPE_N4 = dict(M=203, N=132, K=64)                   # N % 8 == 4: the 8-byte epilogue by shape
+VT_SHAPE = dict(B=3, Ntok=80, C=128)                      # M = 240: a tail for every tile; vt_n0 = 256
+RESAMPLER_GEOMETRY = dict(B=3, heads=2, Nq=16, nk_own=257, k_rows=272, n_garm=16, g_rows=16, b0=0, entry="plain", prescaled=False)
+RAW_Q_TUNES = ((0, "auto"), (0x0204, "k0_2stage_4w"), (0x0304, "k0_ring3_4w"), (0x0208, "k0_2stage_8w"), ((2 << 16) | (2 << 8) | 8, "k2_pingpong"),
+               ((3 << 16) | (3 << 8) | 8, "k3_pingpong_deep"))
 
 
 def all_checks(dev="cuda"):
@@ -1119,6 +1240,46 @@ def all_checks(dev="cuda"):
         add("gemm_f8_out_feeds_attn_f8", lambda dt=dt: check_gemm_f8_out(dt, dev, B=2, N=256, C=128, K=256, fused_attn=True), 6e-2)
         add("linear_colscale", lambda dt=dt: check_colscale(dt, dev))
         add("linear_quickgelu", lambda dt=dt: check_quickgelu(dt, dev))
+        # ---- launch forms the product issues (tests/test_launch_forms_gpu.py holds the two sets against each other), on every tile ----
+        for hint, tag in FORM_TILES:
+            bn = (hint >> 16) & 0xfff
+            for act in ("gelu", "quick_gelu"):
+                # (a) exactness: fp32 output, 16-bit bias and residual, activation before the residual -- the 2e-5 rule of check_stream_f32 (the
+                #     returned error is scaled to TOL).  Measured on MI355X over every tile of FORM_TILES, tight and framed operands (bias + rowbias +
+                #     residual, 515x328x192): erf GELU 3.3e-7 (fp16 data) / 1.8e-7 (bf16 data), quick-GELU 3.0e-7 / 2.2e-7, against the 2e-5 bar; the
+                #     same launches with 16-bit output sit at 4.2e-4 / 2.3e-3, where quick-GELU for erf GELU (2.5e-3 .. 3.5e-3 away) would pass in bf16
+                add(f"act_{act}_res_f32out_515x328x192_{tag}", lambda dt=dt, hint=hint, act=act: check_linear(dtype=dt, dev=dev, act=act, out_f32=True, tile_hint=hint, **ACT_SHAPE))
+                # (b) the 8-byte epilogue: forced on the same tile (bit-equal to the 16-byte one), and by shape (N % 8 == 4)
+                if hint:
+                    add(f"act_{act}_res_narrow_equals_wide_515x328x192_{tag}", lambda dt=dt, hint=hint, act=act: check_epilogue_widths(dt, dev, hint, act=act, **ACT_SHAPE))
+                add(f"act_{act}_res_N132_203x132x64_{tag}", lambda dt=dt, hint=hint, act=act: check_linear(dtype=dt, dev=dev, act=act, tile_hint=hint, **ACT_SHAPE_N4))
+            if hint == 0 or 256 % bn == 0:               # vt_n0 = 2C = 256 must be a multiple of the tile's BN (the filter of the framed V^T test)
+                add(f"vt_bias_B3_N80_C128_{tag}", lambda dt=dt, hint=hint: check_vt(dtype=dt, dev=dev, tile_hint=hint, bias=True, **VT_SHAPE))
+                add(f"vt_colscale_B3_N80_C128_{tag}", lambda dt=dt, hint=hint: check_vt(dtype=dt, dev=dev, tile_hint=hint, colscale=(128, QS), **VT_SHAPE))
+                add(f"vt_bias_colscale_B3_N80_C128_{tag}", lambda dt=dt, hint=hint: check_vt(dtype=dt, dev=dev, tile_hint=hint, bias=True, colscale=(128, QS), **VT_SHAPE))
+                add(f"vt_colscale_n124_narrow_B3_N80_C128_{tag}", lambda dt=dt, hint=hint: check_vt(dtype=dt, dev=dev, tile_hint=hint, bias=True, colscale=(124, QS), **VT_SHAPE))
+            add(f"vt_only_bias_n0_zero_B3_N80_C128_{tag}", lambda dt=dt, hint=hint: check_vt(dtype=dt, dev=dev, tile_hint=hint, bias=True, vt_n0_zero=True, **VT_SHAPE))
+            # what the call sites really pass (tests/test_launch_forms_gpu.py names a form none of these covers): the towers' MLP has a bias and no
+            # residual, the Resampler's neither; its to_out a residual and no bias; the VAE's to_q a bias and colscale on every column; proj_in of
+            # the fp32 stream a bias, fp32 output and no residual
+            for act in ("gelu", "quick_gelu"):
+                add(f"act_{act}_bias_only_515x328x192_{tag}", lambda dt=dt, hint=hint, act=act: check_linear(dtype=dt, dev=dev, act=act, res=False, tile_hint=hint, **ACT_SHAPE))
+                add(f"act_{act}_bias_only_f32out_515x328x192_{tag}", lambda dt=dt, hint=hint, act=act: check_linear(dtype=dt, dev=dev, act=act, res=False, out_f32=True, tile_hint=hint, **ACT_SHAPE))
+            add(f"act_gelu_alone_515x328x192_{tag}", lambda dt=dt, hint=hint: check_linear(dtype=dt, dev=dev, act="gelu", bias=False, res=False, tile_hint=hint, **ACT_SHAPE))
+            add(f"linear_res_only_515x328x192_{tag}", lambda dt=dt, hint=hint: check_linear(dtype=dt, dev=dev, bias=False, tile_hint=hint, **ACT_SHAPE))
+            add(f"linear_bias_colscale_all_515x328x192_{tag}", lambda dt=dt, hint=hint: check_linear(dtype=dt, dev=dev, res=False, colscale=(328, 328 ** -0.5), tile_hint=hint, **ACT_SHAPE))
+            add(f"linear_bias_f32out_515x328x192_{tag}", lambda dt=dt, hint=hint: check_linear(dtype=dt, dev=dev, res=False, out_f32=True, tile_hint=hint, **ACT_SHAPE))
+            # convolutions as conv_in / conv_out / the up blocks issue them: a bias and nothing else; N = 4 (the 8-byte epilogue by shape); the fused
+            # shortcut without a time embedding; 3x3 over two pointers (18 segments) with one
+            add(f"conv3x3_bias_only_64_to_72_9x7_{tag}", lambda dt=dt, hint=hint: check_conv(2, 64, 72, 9, 7, dt, dev, tile_hint=hint))
+            add(f"conv3x3_N4_narrow_64_to_4_9x7_{tag}", lambda dt=dt, hint=hint: check_conv(2, 64, 4, 9, 7, dt, dev, tile_hint=hint))
+            add(f"conv3x3_shortcut_no_temb_64_to_72_9x7_{tag}", lambda dt=dt, hint=hint: check_conv(2, 64, 72, 9, 7, dt, dev, shortcut=64, tile_hint=hint))
+            add(f"conv3x3_two_pointers_temb_128_to_72_9x7_{tag}", lambda dt=dt, hint=hint: check_conv(2, 128, 72, 9, 7, dt, dev, split=64, temb=True, tile_hint=hint))
+            add(f"row_repitch_B3_N100_128_to_192_{tag}", lambda dt=dt, hint=hint: check_row_repitch(3, 100, 128, 192, dt, dev, tile_hint=hint))
+            add(f"row_repitch_B3_N63_64_to_72_{tag}", lambda dt=dt, hint=hint: check_row_repitch(3, 63, 64, 72, dt, dev, tile_hint=hint))
+        # the Resampler's attention: 16 raw latent queries against 257 keys in 272 rows plus the 16 latent keys, on every kernel that takes a raw q
+        for tn, tag in RAW_Q_TUNES:
+            add(f"attn_resampler_geometry_Nq16_nk257_{tag}", lambda dt=dt, tn=tn: check_attn_product(dt, dev, tune=tn, **RESAMPLER_GEOMETRY))
         add("attn_small_text_causal_77_d64", lambda dt=dt: check_attn_small(2, 12, 77, 64, dt, dev, True))
         add("attn_small_vision_257_d80", lambda dt=dt: check_attn_small(2, 16, 257, 80, dt, dev, False))
         add("attn_small_causal_offset_d32", lambda dt=dt: check_attn_small(3, 2, 100, 32, dt, dev, True, Lq=37))
@@ -1183,5 +1344,10 @@ def all_checks(dev="cuda"):
     P("pconv_256_to_128_shortcut", lambda: check_pconv(1, 128, 128, 16, 12, dev, shortcut=256), 2e-5)
     P("pconv_ups_128", lambda: check_pconv(2, 128, 128, 9, 7, dev, ups=True), 2e-5)
     P("pconv_exact_weights_shortcut", lambda: check_pconv(1, 128, 64, 8, 8, dev, shortcut=128, exact_w=True), 2e-5)
+    # the split-precision launch forms of the decoder's mid block and resnets the list above does not hold: to_q (colscale over every column, no
+    # residual), the bias-free logits / P.V products, conv2 with the fp32 residual
+    P("plin_colscale_q_768x512x512", lambda: check_plin(768, 512, 512, dev, res=False, colscale=(512, 512 ** -0.5)), 2e-5)
+    P("plin_no_bias_ragged_203x136x128", lambda: check_plin(203, 136, 128, dev, res=False, bias=False), 2e-5)
+    P("pconv_res_128_to_128_16x12", lambda: check_pconv(1, 128, 128, 16, 12, dev, res=True), 2e-5)
     P("layout_split_and_f32_nhwc", lambda: check_layout_split(2, 16, 12, dev), 2e-5)
     return out

@@ -104,6 +104,62 @@ def test_vt_projection_e4m3_out_strided(hint, dtype):
              C=128, K=192, hint=hint)
 
 
+ACTS = pytest.mark.parametrize("act", ["gelu", "quick_gelu"])
+
+
+@DTYPES
+@TILE
+@ACTS
+def test_activation_before_residual_out_res_rowbias_strided(act, hint, dtype):
+    """The erf-GELU / quick-GELU epilogues with every operand strided: 16-bit output at the LIN shape (bias, rowbias, activation, then the
+    residual), and fp32 output judged by the 2e-5 rule (check_linear scales it to TOL) -- the bar that tells the activations apart."""
+    pads = dict(x=64, out=8, res=16, rowbias=8)
+    run_both(kc.check_linear, kc.TOL[dtype], Framed(pads=pads), named=bool(hint), dtype=dtype, dev=DEV, tile_hint=hint, act=act, **LIN)
+    run_both(kc.check_linear, kc.TOL[dtype], Framed(pads=pads), named=bool(hint), dtype=dtype, dev=DEV, tile_hint=hint, act=act, out_f32=True, **LIN)
+
+
+@DTYPES
+@TILE
+@ACTS
+def test_activation_narrow_by_shape_N132(act, hint, dtype):
+    """N = 132 (N % 8 == 4): the 8-byte epilogue by shape, out at ldo = N + 4, res at ldr = N + 12."""
+    run_both(kc.check_linear, kc.TOL[dtype], Framed(pads=dict(x=8, out=4, res=12)), named=bool(hint), dtype=dtype, dev=DEV, tile_hint=hint, act=act,
+             **kc.ACT_SHAPE_N4)
+
+
+VT_FORMS = [("bias", dict(bias=True)), ("colscale", dict(colscale=(128, kc.QS))), ("bias_colscale", dict(bias=True, colscale=(128, kc.QS))),
+            ("colscale_n124_narrow", dict(bias=True, colscale=(124, kc.QS)))]
+
+
+@DTYPES
+@pytest.mark.parametrize("hint", [h for h, _ in TILES_A if h == 0 or 256 % BN(h) == 0], ids=[t for h, t in TILES_A if h == 0 or 256 % BN(h) == 0])
+@pytest.mark.parametrize("form", [f for _, f in VT_FORMS], ids=[n for n, _ in VT_FORMS])
+def test_vt_projection_with_bias_and_colscale(form, hint, dtype):
+    """The engine's QKV projection (colscale on the q columns, V^T in both orders) and the boundary's (a bias on top): out at ldo = 2C + 8, V^T
+    framed; colscale_n = C - 4 takes the 8-byte epilogue."""
+    run_both(kc.check_vt, kc.TOL[dtype], Framed(pads=dict(x=8, out=8)), equal=("out", "vt", "vt_perm"), named=bool(hint), dtype=dtype, dev=DEV,
+             tile_hint=hint, **kc.VT_SHAPE, **form)
+
+
+@DTYPES
+@TILE
+def test_vt_only_projection_with_bias(hint, dtype):
+    """vt_n0 = 0, out = NULL, plain transpose, bias: the 16-bit VAE mid-block's to_v.  V^T framed before and after."""
+    run_both(kc.check_vt, kc.TOL[dtype], Framed(pads=dict(x=8)), equal=("vt",), named=bool(hint), dtype=dtype, dev=DEV, tile_hint=hint, bias=True,
+             vt_n0_zero=True, **kc.VT_SHAPE)
+
+
+@DTYPES
+@TILE
+@pytest.mark.parametrize("shape", [(100, 128, 192), (63, 64, 72)], ids=["N100_128_to_192", "N63_64_to_72"])
+def test_row_repitch_pad_rows_hold_the_bias_crop_never_reads_them(shape, hint, dtype):
+    """proj_in / proj_out of a latent whose H*W is no multiple of 16: the padded rows read outside the image (they must hold exactly the bias), the
+    cropping launch reads a source whose pad rows are NaN; source, outputs and residual strided."""
+    N, Cin, Cout = shape
+    run_both(kc.check_row_repitch, kc.TOL[dtype], Framed(pads=dict(x=8, src=8, pad16=8, pad32=8, crop=8, res=16)), equal=("pad16", "pad32", "crop"),
+             named=bool(hint), B=3, N=N, Cin=Cin, Cout=Cout, dtype=dtype, dev=DEV, tile_hint=hint)
+
+
 CONVS = [("3x3", kc.check_conv, dict(B=2, Cin=128, Cout=136, H=9, W=7, temb=True)),
          ("3x3_s2", kc.check_conv, dict(B=2, Cin=128, Cout=192, H=17, W=13, stride=2)),
          ("3x3_ups", kc.check_conv, dict(B=2, Cin=128, Cout=128, H=9, W=7, ups=True)),
@@ -130,10 +186,11 @@ def test_fp32_stream_res_and_out_strided(hint, dtype):
 
 def test_split_precision_linear_and_conv_fp32_bias_in_a_frame():
     pads = dict(xp=16, xs=16, out=8, res=16)
-    for kw in (dict(M=1000, N=64, K=128), dict(M=203, N=136, K=64, exact_w=True), dict(M=200, N=72, K=128, res=False)):
+    for kw in (dict(M=1000, N=64, K=128), dict(M=203, N=136, K=64, exact_w=True), dict(M=200, N=72, K=128, res=False),
+               dict(M=203, N=136, K=64, res=False, colscale=(136, 136 ** -0.5)), dict(M=203, N=136, K=128, res=False, bias=False)):
         run_both(kc.check_plin, SPLIT_BAR, Framed(pads=pads), dev=DEV, **kw)
     for kw in (dict(B=1, Cin=128, Cout=128, H=16, W=12, shortcut=256), dict(B=2, Cin=128, Cout=136, H=9, W=7, ups=True),
-               dict(B=1, Cin=128, Cout=64, H=8, W=8, shortcut=128, exact_w=True)):
+               dict(B=1, Cin=128, Cout=64, H=8, W=8, shortcut=128, exact_w=True), dict(B=2, Cin=128, Cout=136, H=9, W=7, res=True)):
         run_both(kc.check_pconv, SPLIT_BAR, Framed(pads=pads), dev=DEV, **kw)
 
 
@@ -164,6 +221,18 @@ def test_self_attention_in_the_products_geometry(tune, entry, dtype, no_tune_tab
     """q | k column halves of one buffer (ldq = ldk = 2C), out at ldo = C + 8, own segment B = 3, 2 heads, 200 queries, nk = 200 of k_rows = 208,
     garment segment 72 keys of 80 rows from batch 1 on, ldvt > round16(nk); NaN key rows, 1.0e4 in V^T beyond nk; through every entry point."""
     run_both(kc.check_attn_product, kc.TOL[dtype], Framed(pads=dict(out=8, kg=8)), named=bool(TUNES[tune]), dtype=dtype, dev=DEV, tune=TUNES[tune], entry=entry)
+
+
+RAW_Q = [t for t in TUNES if ((TUNES[t] >> 16) & 0xff) not in (7, 8, 16)]       # kernels 7, 8 and 16 need a pre-multiplied q
+
+
+@DTYPES
+@pytest.mark.parametrize("tune", RAW_Q, ids=RAW_Q)
+def test_self_attention_in_the_resamplers_geometry(tune, dtype, no_tune_table):
+    """16 raw latent queries against 257 keys in 272 rows plus the 16 latent keys (Nq != round16(nk), q not pre-multiplied): key rows 257..271
+    NaN -- in the Resampler they hold the projection of zero rows through a LayerNorm: finite, non-zero --, V^T 1.0e4 beyond the keys."""
+    run_both(kc.check_attn_product, kc.TOL[dtype], Framed(pads=dict(out=8, kg=8)), named=bool(TUNES[tune]), dtype=dtype, dev=DEV, tune=TUNES[tune],
+             **kc.RESAMPLER_GEOMETRY)
 
 
 @DTYPES

@@ -24,6 +24,28 @@ def test_linear_any_shape(M, n4, k64, dt, bias, res, rowbias, hint):
     assert e <= kc.TOL[dt], (M, 4 * n4, 64 * k64, dt, hint, e)
 
 
+KIND = st.sampled_from(["none", "16", "f32"])
+
+
+@CFG
+@given(M=st.integers(1, 700), n4=st.integers(1, 120), k64=st.integers(1, 5), hint=TILES, dt=DT, act=st.sampled_from([None, "gelu", "quick_gelu"]), bias=KIND,
+       rowbias=st.booleans(), cs=st.integers(0, 120), res=KIND, out_f32=st.booleans(), narrow=st.booleans())
+def test_linear_epilogue_any_combination(M, n4, k64, hint, dt, act, bias, rowbias, cs, res, out_f32, narrow):
+    """The epilogue product on drawn shapes: activation x bias {none, 16, f32} x rowbias x colscale_n (any multiple of 4 up to N) x residual {none,
+    16, f32} x output {16, f32} x forced 8-byte width.  Every draw is made legal by REPAIR, so every example launches: an fp32 operand needs the
+    16-byte epilogue (the library refuses it otherwise), so N and colscale_n are rounded up to multiples of 8 and the forced width is cleared;
+    the forced width needs a named tile.  Bars: TOL, or the 2e-5 rule when the output is fp32 (check_linear scales it to TOL)."""
+    N, csn = 4 * n4, 4 * min(cs, n4)
+    if "f32" in (bias, res) or out_f32:
+        N, csn, narrow = (N + 7) // 8 * 8, (csn + 7) // 8 * 8, False
+    if narrow and hint:
+        hint |= 0x8000
+    kind = {"none": False, "16": True, "f32": "f32"}
+    e = kc.check_linear(M, N, 64 * k64, dt, DEV, bias=kind[bias], res=kind[res], rowbias=rowbias, groups=1, tile_hint=hint, act=act,
+                        colscale=(csn, 0.18) if csn else None, out_f32=out_f32)
+    assert e <= kc.TOL[dt], (M, N, 64 * k64, dt, hex(hint), act, bias, rowbias, csn, res, out_f32, e)
+
+
 @CFG
 @given(B=st.integers(1, 3), cin=st.sampled_from([64, 128, 192, 320]), co8=st.integers(1, 40), H=st.integers(1, 19), W=st.integers(1, 19),
        dt=DT, mode=st.sampled_from(["s1", "s2", "ups", "1x1"]), temb=st.booleans(), res=st.booleans())
