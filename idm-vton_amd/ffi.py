@@ -16,6 +16,7 @@ IO_RES_F32, IO_OUT_F32, IO_BIAS_F32, IO_OUT_F8 = 1, 2, 4, 8
 GN_X_F32, GN_Y_SPLIT, GN_AFFINE_F32 = 1, 2, 4
 LAYOUT_SPLIT, LAYOUT_NHWC_F32 = 1, 2
 SPLIT_ACT, SPLIT_W3, SPLIT_W3T = 0, 1, 2
+KVS_WIDEN_E4M3, KVS_COPY = 0, 1
 MAX_SEG = 24
 ABI_VERSION = 9
 
@@ -107,13 +108,21 @@ class KvUnpackArgs(C.Structure):
     _fields_ = [("dtype", i32), ("n", i32), ("desc", vp), ("max_chunks", i32)]
 
 
+class KvStreamDesc(KvUnpackDesc):                        # typedef idmvton_kv_unpack_desc idmvton_kv_stream_desc: one table builder serves both
+    pass
+
+
+class KvStreamArgs(C.Structure):
+    _fields_ = [("dtype", i32), ("mode", i32), ("n", i32), ("workgroups", i32), ("desc", vp), ("first", vp)]
+
+
 STRUCTS = {"idmvton_seg": Seg, "idmvton_gemm_conv_args": GemmConvArgs, "idmvton_attn_args": AttnArgs,
            "idmvton_layernorm_args": LayerNormArgs, "idmvton_groupnorm_args": GroupNormArgs,
            "idmvton_pack_input_args": PackInputArgs, "idmvton_cfg_step_args": CfgStepArgs,
            "idmvton_layout_args": LayoutArgs, "idmvton_vae_sample_args": VaeSampleArgs, "idmvton_softmax_args": SoftmaxArgs,
            "idmvton_attn_small_args": AttnSmallArgs, "idmvton_attn_f8_args": AttnF8Args, "idmvton_quant_f8_args": QuantF8Args,
            "idmvton_split_args": SplitArgs, "idmvton_xattn": XAttn, "idmvton_kv_unpack_desc": KvUnpackDesc,
-           "idmvton_kv_unpack_args": KvUnpackArgs}
+           "idmvton_kv_unpack_args": KvUnpackArgs, "idmvton_kv_stream_desc": KvStreamDesc, "idmvton_kv_stream_args": KvStreamArgs}
 
 # every symbol include/idmvton_hip.h declares
 SYMBOLS = ["idmvton_last_error", "idmvton_abi_version", "idmvton_sizeof", "idmvton_gemm_conv", "idmvton_attn_fwd",
@@ -122,7 +131,8 @@ SYMBOLS = ["idmvton_last_error", "idmvton_abi_version", "idmvton_sizeof", "idmvt
            "idmvton_attn_small", "idmvton_rccl_unique_id", "idmvton_rccl_comm_init", "idmvton_rccl_bcast_arena",
            "idmvton_rccl_comm_destroy", "idmvton_attn_f8", "idmvton_quant_f8", "idmvton_split", "idmvton_attn_fwd_shared",
            "idmvton_attn_f8_shared", "idmvton_attn_fwd_indexed", "idmvton_attn_f8_indexed",
-           "idmvton_attn_fwd_ragged", "idmvton_attn_f8_ragged", "idmvton_kv_unpack"]
+           "idmvton_attn_fwd_ragged", "idmvton_attn_f8_ragged", "idmvton_kv_unpack", "idmvton_kv_stream",
+           "idmvton_host_device_ptr"]
 
 _lib = None
 
@@ -170,6 +180,10 @@ def lib():
         getattr(L, s).restype = C.c_int
     L.idmvton_kv_unpack.argtypes = [vp, vp, vp]                               # (args*, const desc* host_desc, stream)
     L.idmvton_kv_unpack.restype = C.c_int
+    L.idmvton_kv_stream.argtypes = [vp, vp, vp, vp]                           # (args*, const desc* host_desc, const int32_t* host_first, stream)
+    L.idmvton_kv_stream.restype = C.c_int
+    L.idmvton_host_device_ptr.argtypes = [vp, C.POINTER(vp)]                  # (const void* host, void** dev)
+    L.idmvton_host_device_ptr.restype = C.c_int
     L.idmvton_probe_mfma.argtypes = [C.c_int, vp, vp, vp, vp]
     L.idmvton_groupnorm_stats_doubles.argtypes = [C.c_int] * 4
     L.idmvton_groupnorm_stats_doubles.restype = C.c_int
@@ -231,3 +245,24 @@ def call_kv_unpack(args, host_desc, stream):
     rc = L.idmvton_kv_unpack(C.byref(args), host_desc if isinstance(host_desc, int) else C.cast(host_desc, vp), C.c_void_p(stream))
     if rc != 0:
         raise RuntimeError(f"idmvton_kv_unpack failed ({rc}): {L.idmvton_last_error().decode()}")
+
+
+def call_kv_stream(args, host_desc, host_first, stream):
+    """Invoke idmvton_kv_stream(const args*, const desc* host_desc, const int32_t* host_first, void* stream); host_desc / host_first: ctypes
+    arrays or the addresses of such (what the library validates -- args.desc / args.first are their device copies)."""
+    L = lib()
+    p = lambda x: x if isinstance(x, int) else C.cast(x, vp)
+    rc = L.idmvton_kv_stream(C.byref(args), p(host_desc), p(host_first), C.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError(f"idmvton_kv_stream failed ({rc}): {L.idmvton_last_error().decode()}")
+
+
+def host_device_ptr(host):
+    """idmvton_host_device_ptr: the address under which the device reads the page-locked, mapped host address `host`; RuntimeError with the
+    library's message for any other address."""
+    L = lib()
+    dev = vp()
+    rc = L.idmvton_host_device_ptr(C.c_void_p(host), C.byref(dev))
+    if rc != 0:
+        raise RuntimeError(f"idmvton_host_device_ptr failed ({rc}): {L.idmvton_last_error().decode()}")
+    return int(dev.value)

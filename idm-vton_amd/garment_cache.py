@@ -33,6 +33,11 @@ Packed storage: `pack()` gives a PackedGarmentCache -- the same tensors in the s
 exponent per (garment, feature, K | V^T) in `exps` [G][F][2]: half the resident bytes.  pack_exponent / pack_values / unpack_values below ARE the
 format; the engine widens a block of timesteps into its 16-bit sets with one idmvton_kv_unpack launch, which matches them bit for bit.  Lossy
 and opt-in, for the garment segment alone; `dtype` stays the engine's 16-bit dtype and every primitive moves `exps` with the bytes.
+
+Host-resident: a cache whose tensors are CPU tensors (`to("cpu", pin_memory=True)`, GarmentPool(resident="host")) has `host_resident` true.
+The engine takes one that is PAGE-LOCKED as `cloth=`: every block of timesteps then goes from host memory straight into the 16-bit sets by
+one idmvton_kv_stream launch (pipeline.py, _stream_fill), so a catalogue is bounded by host RAM, not HBM.  Queued calls read such a cache
+by raw address, with no stream order to protect them: a `put` into it waits for the device first and copies blocking.
 """
 import torch
 
@@ -161,6 +166,21 @@ class GarmentCache:
     @property
     def nbytes(self):
         return sum(k.numel() * k.element_size() + vt.numel() * vt.element_size() for k, vt in self.kv)
+
+    @property
+    def host_resident(self):
+        """True when the tensors are CPU tensors (module docstring)."""
+        return not self.kv[0][0].is_cuda
+
+    def _put_mode(self):
+        """-> nb(source): may a `put` copy from `source` be queued?  Into a device cache: yes from the device or from pinned memory (stream
+        order protects queued calls).  Into a host-resident cache: never -- queued calls read it by raw address, so first everything queued
+        on the device finishes, then the copies block ("copies to the host are complete on return")."""
+        if not self.host_resident:
+            return lambda s: s.is_cuda or s.is_pinned()
+        if torch.cuda.is_available() and torch.cuda.is_initialized():
+            torch.cuda.synchronize()
+        return lambda s: False
 
     def __repr__(self):
         garment = f", garment latent={self.gh}x{self.gw}" if (self.gh, self.gw) != (self.h, self.w) else ""
@@ -318,7 +338,8 @@ class GarmentCache:
         """Overwrite garment `slot` IN PLACE with the one garment of `other` (G = 1, every other field equal): the tensors, their pointers and
         the engine's graph states stay valid -- how a resident pool swaps a garment.  `other` may live on another device (a garment spilled to
         the host comes back without a temporary device copy).  Stream-ordered copies: calls already queued read the old garment, later ones
-        the new; only a pinned host source is copied asynchronously."""
+        the new; only a pinned host source is copied asynchronously.  Into a HOST-RESIDENT cache: queued device work is waited for first and
+        the copies block (_put_mode), so calls already queued read the old garment and the new one is complete on return."""
         if not 0 <= int(slot) < self.G:
             raise ValueError(f"GarmentCache put: slot mismatch ({slot} outside [0, G = {self.G}))")
         if other.G != 1:
@@ -327,10 +348,11 @@ class GarmentCache:
             return self._put_slotted(int(slot), other)
         self._agrees(other, "put", devices=False)
         n = len(self.timesteps)
+        nb = self._put_mode()
         for i in range(n):
             for (dk, dv), (sk, sv) in zip(slot_run(self.kv, n, self.G, i, int(slot)), timestep_run(other.kv, n, 1, i)):
-                dk.copy_(sk, non_blocking=sk.is_cuda or sk.is_pinned())
-                dv.copy_(sv, non_blocking=sv.is_cuda or sv.is_pinned())
+                dk.copy_(sk, non_blocking=nb(sk))
+                dv.copy_(sv, non_blocking=nb(sv))
         return self
 
     def _put_slotted(self, slot, other):
@@ -528,7 +550,7 @@ class PackedGarmentCache(GarmentCache):
             other = other.pack()
         super().put(slot, other)
         src = other.exps[0]
-        self.exps[int(slot)].copy_(src, non_blocking=src.is_cuda or src.is_pinned())
+        self.exps[int(slot)].copy_(src, non_blocking=not self.host_resident and (src.is_cuda or src.is_pinned()))
         return self
 
     def to(self, device, pin_memory=False):
@@ -558,25 +580,33 @@ class PackedGarmentCache(GarmentCache):
         return GarmentCache(**self._args(kv=kv))
 
 
-def fill_records(src_kv, n, G, dst_kv, k, S, exps, entries, tslots, garments, gslots):
-    """The idmvton_kv_unpack descriptor records (ops.KvUnpackTable: int64 [N][5]) that widen, for every pair (entry i, timestep slot j) of
-    (entries, tslots) and every pair (garment g, garment slot u) of (garments, gslots), feature f's K and V^T of (i, g) of the packed list
-    src_kv (n timesteps of G) into (j, u) of the 16-bit list dst_kv (k timesteps of S): one record per (timestep, garment, feature, K | V^T),
-    in that order.  Pure address arithmetic on the one layout rule (timestep_run / slot_run): element (i, g) of a tensor starts
-    (i * G + g) * (elements per garment and timestep) after its base."""
+def fill_records(src_kv, n, G, dst_kv, k, S, exps, entries, tslots, garments, gslots, address=None):
+    """The idmvton_kv_unpack / idmvton_kv_stream descriptor records (ops.KvUnpackTable, ops.KvStreamTable: int64 [N][5]) that move, for every
+    pair (entry i, timestep slot j) of (entries, tslots) and every pair (garment g, garment slot u) of (garments, gslots), feature f's K and
+    V^T of (i, g) of the list src_kv (n timesteps of G) into (j, u) of the 16-bit list dst_kv (k timesteps of S): one record per (timestep,
+    garment, feature, K | V^T), in that order.  Pure address arithmetic on the one layout rule (timestep_run / slot_run): element (i, g) of a
+    tensor starts (i * G + g) * (elements per garment and timestep) after its base.
+    A packed source (uint8 bytes + exps) gives the WIDENING form: cols / lds in bytes = elements, ldd in 16-bit elements, exp the address of
+    the garment's exponent.  A 16-bit source (exps None) gives the COPY form of idmvton_kv_stream: cols, lds and ldd in BYTES, no exponent (0).
+    address(tensor) -> the address a kernel reads the tensor's first element under (default data_ptr(); ops.stream_address for a host-resident
+    source); it is asked once per source tensor."""
     I64 = torch.int64
     F = len(src_kv)
+    address = address or (lambda t: t.data_ptr())
+    copy = exps is None
+    esz = dst_kv[0][0].element_size()
     cols = torch.tensor([[kk.shape[1], vt.shape[2]] for kk, vt in src_kv], dtype=I64)                     # [F][2]: K rows are C wide, V^T rows ld
     rows = torch.tensor([[kk.shape[0] // (n * G), vt.shape[1]] for kk, vt in src_kv], dtype=I64)           # N_f K rows, C V^T rows
-    sbase = torch.tensor([[kk.data_ptr(), vt.data_ptr()] for kk, vt in src_kv], dtype=I64)
+    sbase = torch.tensor([[address(kk), address(vt)] for kk, vt in src_kv], dtype=I64)
     dbase = torch.tensor([[kk.data_ptr(), vt.data_ptr()] for kk, vt in dst_kv], dtype=I64)
-    esz = dst_kv[0][0].element_size()
     unit = rows * cols                                                                                     # elements per (timestep, garment)
     si = (torch.tensor(entries, dtype=I64).view(-1, 1) * G + torch.tensor(garments, dtype=I64).view(1, -1)).view(len(entries), len(garments), 1, 1)
     di = (torch.tensor(tslots, dtype=I64).view(-1, 1) * S + torch.tensor(gslots, dtype=I64).view(1, -1)).view(len(tslots), len(gslots), 1, 1)
-    ex = exps.data_ptr() + 4 * ((torch.tensor(garments, dtype=I64).view(1, -1, 1, 1) * F + torch.arange(F, dtype=I64).view(1, 1, F, 1)) * 2
-                                + torch.arange(2, dtype=I64).view(1, 1, 1, 2))
     from . import ops
+    if copy:                                                                                               # byte units throughout
+        return ops.kv_unpack_rows(sbase + si * unit * esz, dbase + di * unit * esz, 0, rows, cols * esz, cols * esz, cols * esz).reshape(-1, 5)
+    ex = address(exps) + 4 * ((torch.tensor(garments, dtype=I64).view(1, -1, 1, 1) * F + torch.arange(F, dtype=I64).view(1, 1, F, 1)) * 2
+                              + torch.arange(2, dtype=I64).view(1, 1, 1, 2))
     return ops.kv_unpack_rows(sbase + si * unit, dbase + di * unit * esz, ex, rows, cols, cols, cols).reshape(-1, 5)
 
 
@@ -587,21 +617,37 @@ class GarmentPool:
     (0.3-9.4 GB each at full size: unbounded), spill=<int> at most that many, dropping the one spilled longest ago; `drop(key)` frees one.
     mixed_sizes=True: the pool's cache is slotted -- `like` fixes the slot size, any garment that fits goes in, and a spilled garment has its own
     compact size on the host.  A slot's views are copied straight to and from the pinned tensors, with no temporary garment on the device.  Everything moves BEFORE the
-    call -- nothing is streamed during one -- and the pool's tensors never move, so an engine's graph states stay valid across swaps.
+    call -- a device-resident pool streams nothing during one -- and the pool's tensors never move, so an engine's graph states stay valid across swaps.
+    resident="host": the pool's cache itself lives in page-locked host memory (pageable where there is no GPU, so that the logic runs on a CPU)
+    and the engine streams every block of a call out of it (idmvton_kv_stream): capacity is bounded by host RAM, `get` and the LRU order are
+    unchanged, `put` blocks (GarmentCache.put).  Not with spill (there is no second tier to spill to) or mixed_sizes (slotted host caches are
+    not streamed).  The default "device" is the pool as it always was.
     A packed `like` (PackedGarmentCache) makes a packed pool: resident and spilled garments are e4m3 bytes + exponents, half the device and
     pinned host memory, and `encode` may return packed or 16-bit garments (the latter are packed on their way in); not with mixed_sizes.
         pool = GarmentPool(8, like=pipe.encode_garment(cloth=c0, ...))
         out = pipe(cloth=pool.cache, garment_index=pool.get(["sku7", "sku7", "sku3"], encode=my_encode), ...)"""
 
-    def __init__(self, capacity, like, spill=False, mixed_sizes=False):
+    def __init__(self, capacity, like, spill=False, mixed_sizes=False, resident="device"):
         if like.G != 1:
             raise ValueError(f"GarmentPool: `like` must hold one garment (G = {like.G})")
         if capacity < 1:
             raise ValueError(f"GarmentPool: capacity {capacity} < 1")
+        if resident not in ("device", "host"):
+            raise ValueError(f"GarmentPool: resident={resident!r} (\"device\" or \"host\")")
+        if resident == "host" and (spill or mixed_sizes):
+            raise ValueError(f"GarmentPool: resident=\"host\" cannot be combined with {'spill' if spill else 'mixed_sizes'} (the pool already lives in "
+                             "host memory; slotted host caches are not streamed)")
+        self.resident = resident
         self.capacity, self.spill = int(capacity), bool(spill)
         self.host_capacity = None if spill is True or not spill else int(spill)      # garments kept on the host; None: no bound
         n = len(like.timesteps)
-        if mixed_sizes:
+        if resident == "host":
+            pin = torch.cuda.is_available()
+            kv = [(torch.empty((a[0] * self.capacity,) + tuple(a[1:]), dtype=d, pin_memory=pin), torch.empty((b[0] * self.capacity,) + tuple(b[1:]), dtype=d, pin_memory=pin))
+                  for a, b, d in kv_shapes(like.kv)]
+            carry = dict(exps=torch.zeros((self.capacity, len(kv), 2), dtype=torch.int32, pin_memory=pin)) if like.packed else {}
+            self.cache = like._like(G=self.capacity, kv=kv, sizes=None, rows=None, **carry)
+        elif mixed_sizes:
             # a slotted cache (module docstring): `like` fixes the slot size, `get` accepts every garment that fits, host copies are compact.
             # Slots are 16-bit, whatever `like` holds
             shapes = [(a, b, like.dtype if d == torch.uint8 else d) for a, b, d in kv_shapes(like.kv)]

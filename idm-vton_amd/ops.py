@@ -379,6 +379,96 @@ def kv_unpack(descs, dtype, device=None):
     return descs
 
 
+KV_STREAM_CHUNK = 1024                                   # 16-byte items of one chunk of idmvton_kv_stream (csrc/kv_stream.hip)
+KV_STREAM_MAX_N = 1 << 20                                # descriptors per launch (IDMVTON_KVS_MAX_N)
+# persistent workgroups of a fill from page-locked host memory: the smallest count within 3 % of the best measured host-link rate
+# (tools/gpu_garment_stream.py --step fill; profiles/LOG.md: 56.5 GB/s from 16 workgroups on, 47.1 with 8, 26.2 with 4 -- and the count at
+# which a call loses least, TryonNet running slower for as long as a fill is in flight)
+KV_STREAM_WORKGROUPS = 16
+
+
+def stream_address(t):
+    """The address under which a kernel reads tensor t: data_ptr() of a device tensor, the device-visible address of a page-locked host tensor
+    (idmvton_host_device_ptr: once per tensor, when a table is built).  ValueError for a pageable host tensor -- the GPU would fault on its
+    address, so it never reaches a descriptor."""
+    if t.is_cuda:
+        return t.data_ptr()
+    if not t.is_pinned():
+        raise ValueError("kv_stream: a host tensor that a kernel reads must be page-locked (pin_memory=True); this one is pageable")
+    return ffi.host_device_ptr(t.data_ptr())
+
+
+def kv_stream_first(items):
+    """int64 [n] 16-byte items per run -> int32 [n + 1], the exclusive prefix sum of chunks per run (idmvton_kv_stream's `first`)."""
+    chunks = (items + KV_STREAM_CHUNK - 1) // KV_STREAM_CHUNK
+    return torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(chunks, 0)]).to(torch.int32)
+
+
+class KvStreamTable:
+    """The descriptor table of idmvton_kv_stream: `host` -- int64 CPU tensor [n][5] whose rows ARE idmvton_kv_stream_desc records, the layout
+    of KvUnpackTable's (in copy mode cols, lds and ldd are bytes and exp is 0) -- and the `slices` [(first, count)] of it that will be
+    launched (default: the whole table; `first` even, as a slice of the device copy has to start 16-byte aligned).  Every slice gets its own
+    prefix table; records and prefix tables are uploaded ONCE, here.  launch(dtype, which, workgroups) moves slice `which` in one launch."""
+
+    def __init__(self, host, device, mode=ffi.KVS_WIDEN_E4M3, slices=None):
+        self.host, self.mode = host.contiguous(), mode
+        self.n = self.host.shape[0]
+        self.slices = [(0, self.n)] if slices is None else [(int(f), int(c)) for f, c in slices]
+        for f, c in self.slices:
+            if f % 2 or f < 0 or c < 1 or c > KV_STREAM_MAX_N or f + c > self.n:
+                raise ValueError(f"kv_stream: descriptors [{f}, {f + c}) of {self.n} (an even first index, 1 to {KV_STREAM_MAX_N} descriptors)")
+        self.items = (self.host[:, 3] & 0xffffffff) * ((self.host[:, 3] >> 32) >> 4)
+        firsts = [kv_stream_first(self.items[f:f + c]) for f, c in self.slices]
+        self.first_at, at = [], 0
+        for t in firsts:
+            self.first_at.append(at)
+            at += t.numel()
+        self.first_host = torch.cat(firsts).contiguous()
+        self.dev, self.first_dev = self.host.to(device), self.first_host.to(device)
+
+    def launch(self, dtype, which=0, workgroups=None):
+        f0, c = self.slices[which]
+        a = ffi.KvStreamArgs()
+        a.dtype, a.mode, a.n, a.workgroups = _DT[dtype], self.mode, c, KV_STREAM_WORKGROUPS if workgroups is None else workgroups
+        a.desc, a.first = self.dev.data_ptr() + 40 * f0, self.first_dev.data_ptr() + 4 * self.first_at[which]
+        launch = lambda: ffi.call_kv_stream(a, self.host.data_ptr() + 40 * f0, self.first_host.data_ptr() + 4 * self.first_at[which], _stream())
+        if PROFILE is None:
+            return launch()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        launch()
+        e1.record()
+        PROFILE.append(("idmvton_kv_stream", e0, e1, 0.0, (48.0 if self.mode == ffi.KVS_WIDEN_E4M3 else 32.0) * float(self.items[f0:f0 + c].sum())))
+
+
+def kv_stream(descs, dtype, mode=ffi.KVS_WIDEN_E4M3, workgroups=None, device=None):
+    """idmvton_kv_stream on every run of `descs`, in one launch of `workgroups` persistent workgroups.  descs: a KvStreamTable (its slice 0), or a
+    list of (src, dst, exp) 2-D tensor views of equal shape, rows contiguous -- mode KVS_WIDEN_E4M3: src uint8 e4m3 bytes, dst of `dtype`, exp a
+    one-element int32 view, dst = dtype(e4m3(src) * 2^-exp) exactly; mode KVS_COPY: src and dst of one dtype, exp None, a copy.  src and exp
+    may each be a device tensor or a PAGE-LOCKED host tensor (stream_address: a pageable one is a ValueError), dst is a device tensor.
+    -> the table."""
+    if not isinstance(descs, KvStreamTable):
+        widen = mode == ffi.KVS_WIDEN_E4M3
+        rec = []
+        for src, dst, exp in descs:
+            ok = src.dim() == 2 and src.shape == dst.shape and src.stride(1) == 1 and dst.stride(1) == 1 and dst.is_cuda
+            if widen:
+                ok = ok and src.dtype == torch.uint8 and dst.dtype == dtype and exp is not None and exp.dtype == torch.int32 and exp.numel() == 1
+            else:
+                ok = ok and src.dtype == dst.dtype
+            if not ok:
+                raise ValueError("kv_stream: a run is (uint8 [rows][cols], %s [rows][cols], one int32) when widening, (x [rows][cols], x [rows][cols], None) "
+                                 "when copying; rows contiguous, the destination on the device" % dtype)
+            rows, cols = src.shape
+            sz = 1 if widen else src.element_size()          # copy mode: byte units
+            rec.append((stream_address(src), _ptr(dst), stream_address(exp) if widen else 0, rows | ((cols * sz) << 32),
+                        (src.stride(0) * sz) | ((dst.stride(0) * sz) << 32)))
+        device = descs[0][1].device if device is None else device
+        descs = KvStreamTable(torch.tensor(rec, dtype=torch.int64).reshape(-1, 5), device, mode)
+    descs.launch(dtype, 0, workgroups)
+    return descs
+
+
 def attention_f8(q8, out, segs, heads, *, qk_scale_exp, v_scale_exp, B, Nq, ldq=None, ldo=None):
     """fp8 self-attention (csrc/attention_f8.hip).  q8: uint8 [B*Nq][>= heads*64]; segs: list of dict(k8=, vt8=, nk=, ldk=, ldvt=, k_rows=, b0=[, nb=][, index=][, nk_table=]);
     nb / index / nk_table as in attention() (idmvton_attn_f8_shared / idmvton_attn_f8_indexed / idmvton_attn_f8_ragged)."""

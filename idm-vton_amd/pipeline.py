@@ -35,6 +35,10 @@ execution form is the pair of callables it hands over:
 A PACKED cache (GarmentCache.pack, encode_garment(storage="e4m3")) holds e4m3 bytes that TryonNet cannot read, so all four forms go through 16-bit
 sets: `_packed_fill` widens a block's cache entries into set p with ONE idmvton_kv_unpack launch, from a descriptor table built and uploaded once
 per call; the eager forms then use sets too (one, or two with overlap), and with garment_index the P-slot sets and slot table of the graph forms.
+A HOST-RESIDENT cache (page-locked CPU tensors: GarmentCache.to("cpu", pin_memory=True), GarmentPool(resident="host")), packed or 16-bit, goes
+the same way through sets in all four forms: `_stream_fill`, _packed_fill's twin, moves a block from host memory straight into set p with ONE
+idmvton_kv_stream launch (widening e4m3 bytes, or copying 16-bit values) -- in _fill_set's place in drive_blocks' order, so every block but
+the first crosses the host link behind the TryonNet steps of the block before it.  Nothing of the cache is in HBM before the call.
 With garment_index the two cache rows read through the table: eager on the cache's own views (nb = G, table = garment_index), graph on
 P-slot sets into which _fill_set gathers the U distinct garments of the call (table = person -> set slot, a persistent buffer of the state).
 
@@ -106,7 +110,9 @@ class TryonEngine:
         self.ramp = True                                     # first blocks of 1, 2, 4 timesteps
         # garment_batches: GarmentNet batches launched or replayed by this engine (a call on a GarmentCache adds none); garment_set_copies: blocks
         # of cached K / V^T copied into a persistent set by the graph forms (on a packed cache: widened into one, by every form)
-        self.stats = dict(garment_batches=0, garment_set_copies=0)
+        # garment_stream_launches: blocks moved from a host-resident cache into a set (one idmvton_kv_stream launch each)
+        self.stats = dict(garment_batches=0, garment_set_copies=0, garment_stream_launches=0)
+        self._streaming = []                                 # [cache, event of its last queued fill]: host memory a queued launch still reads
         self._weights_id = None
 
     # -------------------------------------------------------------------------------------------- shared by prepare / encode_garment
@@ -304,8 +310,12 @@ class TryonEngine:
         that does not cover the call (timestep, resolution, dtype mode, weights, B % G) raises ValueError before anything is launched.
         garment_index (with a GarmentCache only): B ints in [0, G), person i wears garment garment_index[i] -- any B >= 1, values may repeat,
         no B % G rule; the cache is a pool, and G may exceed B.  A cache with `sizes` (garments of several sizes in slots of one size) needs
-        garment_index: which size a person's garment has follows from the slot it names."""
+        garment_index: which size a person's garment has follows from the slot it names.
+        A HOST-RESIDENT cache (CPU tensors) is streamed into the sets block by block during the call (_stream_fill); every tensor -- and a
+        packed cache's `exps` -- must be page-locked (pin_memory), the cache must not have `sizes`, and the engine must not be attn_fp8: each
+        a ValueError naming the field, before anything is launched."""
         dev, dt = self.device, self.dtype
+        self._release_streamed()
         f32 = lambda t: t.to(dev, torch.float32).contiguous()
         gcache = cloth if isinstance(cloth, GarmentCache) else None
         if garment_index is not None and gcache is None:
@@ -320,6 +330,8 @@ class TryonEngine:
                                 f8_exp=self.unet.f8_exp, weights_id=self.weights_identity(), persons=image.shape[0], garment_index=garment_index)
             if garment_index is not None:
                 gidx, gindex = gidx
+            if gcache.host_resident:
+                self._check_host_cache(gcache)
         image, mask_image, pose_img = f32(image), f32(mask_image), f32(pose_img)
         cloth = f32(cloth) if gcache is None else None
         B = image.shape[0]
@@ -481,6 +493,64 @@ class TryonEngine:
         dt = lambda d: gc.dtype if gc.packed else d
         return slots, [((a[0] // gc.G * slots,) + a[1:], (b[0] // gc.G * slots,) + b[1:], dt(d)) for a, b, d in kv_shapes(gc.kv)]
 
+    def _check_host_cache(self, gc):
+        """The conditions under which a host-resident cache can be streamed; ValueError naming the field otherwise.  A pageable address must
+        never reach a descriptor (the GPU would fault on it), so the refusal is here, before any table is built."""
+        if self.unet.attn_fp8:
+            raise ValueError("host-resident GarmentCache attn_fp8 mismatch: an attn_fp8 engine does not stream a cache from host memory "
+                             "(move it with .to(device))")
+        if gc.sizes is not None:
+            raise ValueError("host-resident GarmentCache sizes mismatch: a cache with `sizes` (slotted / mixed_sizes) is not streamed from host "
+                             "memory (move it with .to(device))")
+        if not all(k.is_pinned() and vt.is_pinned() for k, vt in gc.kv):
+            raise ValueError("host-resident GarmentCache kv mismatch: the tensors are pageable host memory; the device reads page-locked memory "
+                             "only -- make the cache with .to(\"cpu\", pin_memory=True) or GarmentPool(resident=\"host\")")
+        if gc.packed and not gc.exps.is_pinned():
+            raise ValueError("host-resident GarmentCache exps mismatch: the exponents are pageable host memory; the device reads page-locked "
+                             "memory only -- make the cache with .to(\"cpu\", pin_memory=True) or GarmentPool(resident=\"host\")")
+
+    def _release_streamed(self):
+        """Drop the engine's references to host-resident caches whose last queued fill has completed (an event that was never recorded counts
+        as passed).  Called by every `prepare`, `decode` and `_stream_fill`, and after a graph state's warm-up: the engine keeps a streamed
+        cache alive from its first fill until the first of those calls after its last fill has finished -- not beyond the next call."""
+        self._streaming = [h for h in self._streaming if not h[1].query()]
+
+    def _stream_fill(self, st, sets, blocks=None):
+        """-> garment(bi, p) of a call on a HOST-RESIDENT cache, _packed_fill's twin: block bi's cache entries go from page-locked host memory
+        straight into the first timestep slots of sets[p] by ONE idmvton_kv_stream launch on the current stream -- widening e4m3 bytes (a
+        packed cache) or copying 16-bit values.  The gather is _fill_set's (entries by value; with garment_index the U distinct garments in
+        first-use order into slots 0 .. U - 1 of P-slot sets); table and prefix tables are built and uploaded ONCE, here, with one
+        idmvton_host_device_ptr per cache tensor, and a block is a slice.  `blocks`: build for these block numbers only (the warm-up).
+        The launches read host memory by raw address: the cache stays referenced by the engine until the last one has completed."""
+        gc, k = st["gcache"], st["k"]
+        n = len(gc.timesteps)
+        garments = list(range(gc.G)) if st["gindex"] is None else list(dict.fromkeys(st["gindex"]))
+        S = gc.G if st["gindex"] is None else st["B"]
+        built = [bi for bi in range(len(st["blocks"])) if blocks is None or bi in blocks]
+        steps = [(st["blocks"][bi][0] + j, j) for bi in built for j in range(st["blocks"][bi][1])]
+        first = {i: at for at, (i, _) in enumerate(steps)}   # step of the call -> its place in a set's part of the table
+        per = len(garments) * len(gc.kv) * 2                 # records per step: even, so every slice starts 16-byte aligned
+        addr = {}                                            # one idmvton_host_device_ptr per tensor, whatever the number of sets
+
+        def address(t):
+            if t.data_ptr() not in addr:
+                addr[t.data_ptr()] = ops.stream_address(t)
+            return addr[t.data_ptr()]
+        rec = torch.cat([fill_records(gc.kv, n, gc.G, fs["kv"], k, S, gc.exps if gc.packed else None, [st["gidx"][i] for i, _ in steps],
+                                      [j for _, j in steps], garments, list(range(len(garments))), address=address) for fs in sets])
+        which = {(p, bi): at for at, (p, bi) in enumerate((p, bi) for p in range(len(sets)) for bi in built)}
+        table = ops.KvStreamTable(rec, self.device, ops.ffi.KVS_WIDEN_E4M3 if gc.packed else ops.ffi.KVS_COPY,
+                                  [((p * len(steps) + first[st["blocks"][bi][0]]) * per, st["blocks"][bi][1] * per) for p, bi in which])
+        self._release_streamed()
+        hold = [gc, torch.cuda.Event()]
+        self._streaming.append(hold)
+
+        def garment(bi, p):
+            self.stats["garment_stream_launches"] += 1
+            table.launch(self.dtype, which[(p, bi)])
+            hold[1].record()                                 # the call's last fill so far: until it has passed, `hold` keeps the cache alive
+        return garment
+
     def _packed_fill(self, st, sets, blocks=None):
         """-> garment(bi, p) of a call on a PACKED cache: block bi's cache entries widened into the first timestep slots of sets[p] by ONE
         idmvton_kv_unpack launch on the current stream.  The gather is _fill_set's -- entries by value, consecutive or not; with
@@ -524,10 +594,11 @@ class TryonEngine:
             sets = [self._new_set(st) for _ in range(2 if overlap else 1)]
             garment = lambda bi, p: self._garment_side(st, st["temb_gk"][bi], sets[p], blocks[bi][1])
             kv = lambda i, j, p: sets[p]["step"][j]
-        elif st["gcache"].packed:                            # e4m3 bytes: TryonNet reads 16-bit sets, as the graph forms do (one, or two to overlap)
+        elif st["gcache"].packed or st["gcache"].host_resident:
+            # e4m3 bytes, or host memory: TryonNet reads 16-bit sets on the device, as the graph forms do (one, or two to overlap)
             slots, shapes = self._cache_set_shapes(st)
             sets = [self._alloc_set((), shapes, len(st["gcache"].timesteps), st["k"], slots) for _ in range(2 if overlap else 1)]
-            garment = self._packed_fill(st, sets)
+            garment = (self._stream_fill if st["gcache"].host_resident else self._packed_fill)(st, sets)
             st = dict(st, gix=self._slot_table(st))          # with garment_index: person -> set slot (the same tensors otherwise)
             kv = lambda i, j, p: sets[p]["step"][j]
         else:                                                # nothing to launch, so nothing to overlap: TryonNet reads the cache's own views
@@ -579,13 +650,16 @@ class TryonEngine:
                 gc = st["gcache"]
                 slots, shapes = self._cache_set_shapes(st)   # (with an index: one slot per person, whatever the pool holds)
                 G["sets"] = [self._alloc_set((), shapes, len(gc.timesteps), st["k"], slots) for _ in range(2)]
-                if gc.packed:                                # (a table of block 0 alone: complete before the synchronize below)
+                if gc.host_resident:                         # (a table of block 0 alone: complete before the synchronize below)
+                    self._stream_fill(st, G["sets"][:1], blocks=(0,))(0, 0)
+                elif gc.packed:
                     self._packed_fill(st, G["sets"][:1], blocks=(0,))(0, 0)
                 else:
                     self._fill_set(st, G["sets"][0], *st["blocks"][0])
             self._tryon_main(G, G["tt"], G["cf"], G["nz"], G["sets"][0]["step"][0])
         torch.cuda.current_stream().wait_stream(warm)
         torch.cuda.synchronize()
+        self._release_streamed()                             # (the warm-up fill of a host-resident cache has completed)
         st["latents"].copy_(saved)
         self._graphs[key] = G
         return G
@@ -624,6 +698,8 @@ class TryonEngine:
                 G["tgk"].copy_(st["temb_gk"][bi])
                 self.stats["garment_batches"] += 1
                 graphs[("garm", p, blocks[bi][1])].replay()
+        elif st["gcache"].host_resident:                     # in the same place: one launch that moves the block from host memory into set p
+            garment = self._stream_fill(st, G["sets"])
         elif st["gcache"].packed:                            # in the same place: one launch that widens the block's bytes into set p
             garment = self._packed_fill(st, G["sets"])
         else:                                                # in the GarmentNet graph's place in the stream / event order: a copy out of the cache
@@ -669,6 +745,7 @@ class TryonEngine:
 
     @torch.no_grad()
     def decode(self, latents):
+        self._release_streamed()
         img = self.vae.decode(latents / self.vae.cfg.scaling_factor)                       # :1876
         return (img / 2 + 0.5).clamp(0, 1)                                                 # postprocess
 

@@ -276,6 +276,37 @@ typedef struct {
 int idmvton_kv_unpack(const idmvton_kv_unpack_args* a, const idmvton_kv_unpack_desc* host_desc, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * idmvton_kv_stream : a block of a HOST-RESIDENT garment cache (page-locked host memory) -> 16-bit K / V^T, straight over the host link.
+ * ONE launch moves n independent strided 2-D runs, as idmvton_kv_unpack does, but with a PERSISTENT grid: `workgroups` workgroups (the
+ * host's choice, [1, 1024]) walk chunks blockIdx.x, += workgroups of one flat chunk list over all descriptors -- a chunk is 1024 16-byte
+ * source items --, and first[n + 1], the exclusive prefix sum of chunks per descriptor (first[0] = 0, first[n] = all chunks), maps a chunk to
+ * its descriptor.  Few long-lived workgroups keep the link's (rate x latency) bytes in flight without occupying the CUs a concurrent stream
+ * wants; a thread issues all loads of a chunk, and those of its next chunk, before it stores the current one.
+ * mode IDMVTON_KVS_WIDEN_E4M3: dst[r][c] = dtype(e4m3(src[r][c]) * 2^-*exp), bit for bit idmvton_kv_unpack's arithmetic (the exponent clamp
+ *   to [-7, 15] and the sign of byte 0x80 included); cols / lds in bytes = elements, ldd in 16-bit elements (a multiple of 8).
+ * mode IDMVTON_KVS_COPY: a byte copy; cols, lds AND ldd in bytes, multiples of 16; exp is ignored (may be NULL) and the dtype immaterial.
+ * idmvton_kv_stream_desc has idmvton_kv_unpack_desc's 40-byte layout (one table builder serves both).  Per descriptor, src -- and exp --
+ * is device memory or the DEVICE-VISIBLE address of page-locked host memory (idmvton_host_device_ptr); a pageable host address must never
+ * reach a table: the GPU would fault on it.  Bytes [cols, lds) of a source row are not read, [cols, ldd) of a destination row not written.
+ * host_desc[0..n) and host_first[0..n] are validated field by field before the launch (pointers, alignment, shapes as idmvton_kv_unpack;
+ * mode; 1 <= workgroups <= 1024; 1 <= n <= IDMVTON_KVS_MAX_N; host_first equal to the prefix sums recomputed from host_desc); the caller
+ * guarantees that a->desc / a->first are their uploaded copies.  No allocation, no synchronisation: capturable.  Plain vector stores.
+ * No reference counterpart.
+ * idmvton_host_device_ptr : hipHostGetDevicePointer -- the address under which the device reads page-locked, mapped host memory; IDMVTON_E_ARG
+ * (and *dev = NULL) for any other address.  Call it once per tensor when a table is built, never per launch.
+ * ------------------------------------------------------------------------------------------------------------- */
+enum { IDMVTON_KVS_WIDEN_E4M3 = 0, IDMVTON_KVS_COPY = 1 };
+#define IDMVTON_KVS_MAX_N (1 << 20)
+typedef idmvton_kv_unpack_desc idmvton_kv_stream_desc;
+typedef struct {
+    int32_t dtype; int32_t mode; int32_t n; int32_t workgroups;
+    const idmvton_kv_stream_desc* desc;   /* device copy of host_desc, 16-byte aligned */
+    const int32_t* first;                 /* device copy of host_first[n + 1] */
+} idmvton_kv_stream_args;
+int idmvton_kv_stream(const idmvton_kv_stream_args* a, const idmvton_kv_stream_desc* host_desc, const int32_t* host_first, void* stream);
+int idmvton_host_device_ptr(const void* host, void** dev);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * idmvton_attn_small : softmax(scale * q k^T [+ causal mask]) v for the one-off conditioning encoders -- the CLIP text towers
  * (transformers CLIPTextModel / CLIPTextModelWithProjection as called at src/tryon_pipeline.py:511-743: 77 tokens, causal) and
  * the CLIP-H vision tower (:460-482: 257 tokens, head_dim 80).  Any even head_dim <= 128, Lk <= 1024, fp32 arithmetic; one wave

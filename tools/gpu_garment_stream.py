@@ -1,0 +1,249 @@
+"""Host-resident garment cache measurements at the configs[1] shape (768x1024, 30 steps, B = 2, bf16), on a PACKED cache only (9.44 GB of
+page-locked host memory, pinned once; a 16-bit cache would pin 18.9 GB).  Engine set-up imported from bench.py.
+
+  (default)       the driver: runs the two steps below one after another, each as a fresh child process under a time limit of its own, and
+                  stops at the first one that fails or runs out of time (it opens no GPU itself); every step prints one JSON line, and the
+                  link rate the first step measured is handed to the second
+  --step fill     one steady 6-timestep block (G = 2: 1 887 436 800 source bytes) from SYNTHETIC cache contents in pinned host memory into a
+                  16-bit set, one idmvton_kv_stream launch, on an otherwise idle GPU, for workgroups in {4, 8, 16, 32, 64, 256}: microseconds
+                  and source GB/s.  The largest GB/s is the box's host-link rate; the default to ship for `workgroups`
+                  (ops.KV_STREAM_WORKGROUPS) is the smallest count within 3 % of it -- the box-to-box spread DESIGN.md states.  The set is
+                  compared bit for bit with the one the device-resident fill (idmvton_kv_unpack) writes.
+  --step call     cached graph + overlap call on the packed cache in pinned host memory and on the device-resident one (the parent's path,
+                  which this change must not move): three timed repeats each, interleaved, images/s; then one instrumented call per arm with
+                  events around every block's fill and every block's TryonNet steps.  The host arm is expected within (block 0's bytes /
+                  --link-gbps) per call plus the device arm's own spread; if it is not, the per-block times say whether a fill outran the
+                  TryonNet block it hides behind, or TryonNet itself ran slower next to the fills.  --workgroups N ...: further host arms
+                  with those `workgroups` values (the fill's rate against what it costs TryonNet).  --staged: a further arm, "staged",
+                  that brings each block's packed bytes from the pinned cache into a device staging cache with the copy engines
+                  (copy_ on the side stream) and widens them with the device-resident unpack launch: the same bytes over the same link,
+                  without a kernel that reads host memory.
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+DEV = torch.device("cuda", 0)
+H, W, STEPS, B = 1024, 768, 30, 2
+# (features, token rows, channels) of the two attention levels of the SDXL topology at a 128 x 96 latent (garment_cache.py, "Size")
+LEVELS = ((10, 3072, 640), (60, 768, 1280))
+WORKGROUPS = (4, 8, 16, 32, 64, 256)
+STEP_LIMITS = (("fill", 300), ("call", 540))
+SPEC_GBPS = 63.0                                         # the link's spec rate: what --step call assumes when no measured rate is given
+
+
+def timed_us(fn, n=5):
+    fn()
+    out = []
+    for _ in range(n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize(); e0.record()
+        fn()
+        e1.record(); e1.synchronize()
+        out.append(e0.elapsed_time(e1) * 1e3)
+    return out
+
+
+def fill_step(args):
+    from idm_vton_amd import ops
+    from idm_vton_amd.garment_cache import PackedGarmentCache
+    from idm_vton_amd.pipeline import TryonEngine
+    dt = torch.bfloat16
+    eng = TryonEngine(None, None, None, None, dt, DEV)       # the fills need no network: a set, a cache and one block
+    G, k = B, eng.garment_steps
+    gen = torch.Generator(device=DEV).manual_seed(0)
+
+    def rand_bytes(*shape):                                  # finite e4m3 bytes (0x7f / 0xff, the NaN bytes, become 0)
+        b = torch.randint(0, 256, shape, generator=gen, device=DEV, dtype=torch.uint8)
+        return torch.where((b & 0x7f) == 0x7f, torch.zeros_like(b), b)
+    kv = [(rand_bytes(k * G * N, C), rand_bytes(k * G, C, N)) for feats, N, C in LEVELS for _ in range(feats)]
+    exps = torch.randint(-7, 16, (G, len(kv), 2), generator=gen, device=DEV, dtype=torch.int32)
+    dev_cache = PackedGarmentCache(G=G, timesteps=list(range(k, 0, -1)), h=H // 8, w=W // 8, dtype=dt, attn_fp8=False, f8_exp=(0, 0, 0),
+                                   weights_id="synthetic", kv=kv, exps=exps)
+    t0 = time.perf_counter()
+    host = dev_cache.to("cpu", pin_memory=True)
+    pin_s = time.perf_counter() - t0
+    st = dict(gcache=host, gidx=list(range(k)), gindex=None, k=k, B=B, blocks=[(0, k)])       # ONE block: the k timesteps of the cache
+    slots, shapes = eng._cache_set_shapes(st)
+    fset, ref = eng._alloc_set((), shapes, k, k, slots), eng._alloc_set((), shapes, k, k, slots)
+    eng._packed_fill(dict(st, gcache=dev_cache), [ref])(0, 0)
+    t0 = time.perf_counter()
+    fill = eng._stream_fill(st, [fset])
+    torch.cuda.synchronize()
+    table_ms = (time.perf_counter() - t0) * 1e3
+    src_bytes = sum(a.numel() + b.numel() for a, b in host.kv)
+    rows = {}
+    for wg in WORKGROUPS:
+        ops.KV_STREAM_WORKGROUPS = wg
+        for a, b in fset["kv"]:
+            a.zero_(); b.zero_()
+        us = timed_us(lambda: fill(0, 0))
+        same = all(torch.equal(a, c) and torch.equal(b, d) for (a, b), (c, d) in zip(fset["kv"], ref["kv"]))
+        med = sorted(us)[len(us) // 2]
+        rows[wg] = dict(us=[round(x, 1) for x in us], GBps=round(src_bytes / med / 1e3, 2), bit_equal_to_device_fill=same)
+        print(f"workgroups {wg:4d}: median {med:10.1f} us, {rows[wg]['GBps']:7.2f} GB/s from host memory, bit-equal {same}", flush=True)
+    best = max(r["GBps"] for r in rows.values())
+    default = min(wg for wg, r in rows.items() if r["GBps"] >= 0.97 * best)
+    emit(args, dict(step="fill", shape=f"{W}x{H}, G={G}, one block of {k} timesteps, bf16 sets, packed synthetic cache in pinned host memory",
+                          source_bytes=src_bytes, pin_and_copy_s=round(pin_s, 2), table_build_upload_ms=round(table_ms, 2), per_workgroups=rows,
+                          link_GBps=best, spec_GBps=SPEC_GBPS, default_workgroups=default,
+                    all_bit_equal=all(r["bit_equal_to_device_fill"] for r in rows.values())))
+    return 0 if all(r["bit_equal_to_device_fill"] for r in rows.values()) else 1
+
+
+def call_step(args):
+    import bench
+    from idm_vton_amd import ops, pipeline
+    dt = torch.bfloat16
+    eng, _ = bench.build_engine(dt, DEV, 0, STEPS)
+    inp = bench.synth_inputs(B, H, W, STEPS, DEV, first_image_index=0)
+    kw = dict(num_inference_steps=STEPS, guidance_scale=2.0, scheduler="ddim", use_graph=True, overlap=True)
+    device = eng.encode_garment(cloth=inp["cloth"], text_embeds_cloth=inp["text_embeds_cloth"], noise_cloth=inp["noise"]["cloth"], height=H, width=W,
+                                num_inference_steps=STEPS, scheduler="ddim", storage="e4m3")
+    t0 = time.perf_counter()
+    host = device.to("cpu", pin_memory=True)
+    pin_s = time.perf_counter() - t0
+    # arms: the device-resident cache, the host-resident one with the shipped `workgroups` ("host"), and with every --workgroups value
+    arms = {"device": (device, None), "host": (host, ops.KV_STREAM_WORKGROUPS), **{f"host@{wg}": (host, wg) for wg in args.workgroups}}
+    if args.staged:
+        # the same bytes over the same link with the COPY ENGINES as the mover: a block's packed bytes go from the pinned cache into a device
+        # staging cache by one copy_(non_blocking=True) per tensor on the stream the fill runs on, then the device-resident unpack launch
+        # widens them -- a diagnostic arm (the staging cache here is a whole second cache in HBM), not a form the engine has
+        from idm_vton_amd.garment_cache import PackedGarmentCache
+        stage = PackedGarmentCache(exps=device.exps, **device._args(kv=[(torch.zeros_like(k), torch.zeros_like(v)) for k, v in device.kv]))
+        packed_fill = eng._packed_fill
+
+        def staged_fill(st, sets, blocks=None):
+            fill = packed_fill(st, sets, blocks)
+            if st["gcache"] is not stage:
+                return fill
+
+            def garment(bi, p):
+                s0, c = st["blocks"][bi]
+                for (dk, dv), (sk, sv) in zip(stage.run(st["gidx"][s0], c), host.run(st["gidx"][s0], c)):      # consecutive entries
+                    dk.copy_(sk, non_blocking=True)
+                    dv.copy_(sv, non_blocking=True)
+                fill(bi, p)
+            return garment
+        eng._packed_fill = staged_fill
+        arms["staged"] = (stage, None)
+
+    def call(a, **more):
+        cache, wg = arms[a]
+        if wg is not None:
+            ops.KV_STREAM_WORKGROUPS = wg
+        return eng(**kw, **more, **{**inp, "cloth": cache, "text_embeds_cloth": None})
+    lat = {a: call(a, return_latents=True).clone() for a in arms}                             # warm-up: graph capture; and the latents
+    torch.cuda.synchronize()
+    rows = {a: [] for a in arms}
+    for r in range(3):                                    # arms interleaved
+        for a in arms:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.calls):
+                call(a)
+            torch.cuda.synchronize()
+            rows[a].append(B * args.calls / (time.perf_counter() - t0))
+            print(f"repeat {r} {a:7s} {rows[a][-1]:.4f} images/s", flush=True)
+    # one instrumented call per arm: events around every block's fill (on the stream it runs on) and every block's TryonNet steps
+    blocks, drive = {}, pipeline.drive_blocks
+    for a in arms:
+        log = dict(fill=[], tryon=[])
+
+        def timed(kind, fn, log=log):
+            def run(bi, p):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                out = fn(bi, p)
+                e1.record()
+                log[kind].append((bi, e0, e1))
+                return out
+            return run
+        pipeline.drive_blocks = lambda bl, garment, tryon, *rest: drive(bl, timed("fill", garment), timed("tryon", tryon), *rest)
+        try:
+            call(a, return_latents=True)
+        finally:
+            pipeline.drive_blocks = drive
+        torch.cuda.synchronize()
+        blocks[a] = {kind: [round(e0.elapsed_time(e1), 3) for _, e0, e1 in sorted(v, key=lambda x: x[0])] for kind, v in log.items()}
+    mean = lambda v: sum(v) / len(v)
+    ms = {a: [1e3 * B / x for x in v] for a, v in rows.items()}          # per call
+    spread_ms = max(ms["device"]) - min(ms["device"])
+    _, sched = eng._block_schedule(STEPS)
+    per_step = (host.nbytes - host.exps.numel() * 4) // STEPS
+    block0_ms = sched[0][1] * per_step / (args.link_gbps * 1e6)
+    excess_ms = mean(ms["host"]) - mean(ms["device"])
+    within = excess_ms <= block0_ms + spread_ms
+    fh, th, td = blocks["host"]["fill"], blocks["host"]["tryon"], blocks["device"]["tryon"]
+    outran = [bi for bi in range(1, len(fh)) if fh[bi] > th[bi - 1]]      # block bi's fill runs behind TryonNet's block bi - 1
+    slowed_ms = sum(th) - sum(td)
+    verdict = ("within block 0's exposed transfer plus the device arm's spread" if within else
+               ("fills outran TryonNet in blocks %s" % outran if outran else "no fill outran its TryonNet block") +
+               f"; TryonNet's blocks took {slowed_ms:+.2f} ms in the host call against the device call")
+    emit(args, dict(step="call", shape=f"{W}x{H}, {STEPS} steps, B={B}, bf16, graph + overlap, packed cache", pin_and_copy_s=round(pin_s, 2),
+                          latents_equal=all(bool(torch.equal(lat[a], lat["device"])) for a in arms), workgroups={a: wg for a, (_, wg) in arms.items()},
+                          tryon_ms_beside_fills={a: round(sum(v["tryon"]), 2) for a, v in blocks.items()}, fill_ms={a: round(sum(v["fill"]), 2) for a, v in blocks.items()}, images_per_s={a: [round(x, 4) for x in v] for a, v in rows.items()},
+                          ms_per_call={a: round(mean(v), 2) for a, v in ms.items()}, device_spread_ms=round(spread_ms, 2),
+                          host_minus_device_ms=round(excess_ms, 2), link_GBps=args.link_gbps, block0_bytes=sched[0][1] * per_step,
+                          block0_exposed_ms=round(block0_ms, 2), within_expectation=within, verdict=verdict, block_timesteps=[c for _, c in sched],
+                          per_block_ms=blocks, serial_form_exposed_ms=round(sum(fh), 2),
+                    stream_launches=eng.stats["garment_stream_launches"], cache_nbytes=host.nbytes))
+    return 0 if all(torch.equal(lat[a], lat["device"]) for a in arms) else 1
+
+
+def drive(args):
+    import tempfile
+    link = None
+    with tempfile.TemporaryDirectory() as tmp:
+        for name, limit in STEP_LIMITS:
+            out = os.path.join(tmp, name + ".json")
+            cmd = [sys.executable, os.path.abspath(__file__), "--step", name, "--calls", str(args.calls), "--json-out", out]
+            if name == "call" and args.workgroups:
+                cmd += ["--workgroups"] + [str(wg) for wg in args.workgroups]
+            if name == "call" and args.staged:
+                cmd += ["--staged"]
+            if name == "call" and link:
+                cmd += ["--link-gbps", str(link)]
+            print(f"--- step {name} (limit {limit} s)", flush=True)
+            try:
+                rc = subprocess.run(cmd, timeout=limit).returncode
+            except subprocess.TimeoutExpired:
+                print(f"step {name} ran out of its {limit} s: stopping here", flush=True)
+                return 124
+            if rc != 0:
+                print(f"step {name} ended with status {rc}: stopping here", flush=True)
+                return rc
+            if name == "fill":
+                link = json.load(open(out))["link_GBps"]
+    return 0
+
+
+def emit(args, res):
+    print(json.dumps(res), flush=True)
+    if args.json_out:
+        with open(args.json_out, "w") as f:
+            json.dump(res, f)
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--step", choices=["fill", "call"], default=None)
+    ap.add_argument("--calls", type=int, default=2, help="timed calls per repeat")
+    ap.add_argument("--workgroups", type=int, nargs="*", default=[], help="--step call: further host arms with these `workgroups` values")
+    ap.add_argument("--staged", action="store_true", help="--step call: a further arm that moves the blocks with the copy engines (a diagnostic)")
+    ap.add_argument("--json-out", default=None, help="also write the step's JSON result to this file (the driver reads the link rate from it)")
+    ap.add_argument("--link-gbps", type=float, default=SPEC_GBPS, help="the host-link rate --step fill measured (default: the spec rate)")
+    a = ap.parse_args()
+    if a.step is None:
+        sys.exit(drive(a))
+    torch.cuda.set_device(0)
+    with torch.no_grad():
+        sys.exit(fill_step(a) if a.step == "fill" else call_step(a))
