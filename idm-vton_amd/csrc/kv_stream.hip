@@ -13,6 +13,18 @@
 // vmcnt(13)` after the 5 loads of one set, with 8 stores and the 5 loads of the other set behind the ones it waits for).
 // Two modes: WIDEN_E4M3 is kv_unpack's arithmetic, bit for bit (dst = T(e4m3(src) * 2^-clamp(*exp, -7, 15)), the sign of byte 0x80 OR-ed
 // back in); COPY moves bytes.  Plain vector loads and stores only.
+// idmvton_kv_fill is the same kernel body with FILL = true: a descriptor whose src is NULL is a ZERO RUN, written as a source of all-zero bytes
+// would be -- +0 (bits 0x0000) when widening, zero bytes when copying -- WITHOUT any load: kvs_read takes a workgroup-uniform branch on the
+// descriptor (it sits in scalar registers) and clears the chunk's registers instead of loading them; neither src nor exp of such a run is
+// dereferenced, and kvs_write is unchanged (e4m3 byte 0 times any 2^-e is +0).  That is how a compact garment goes into the front of a larger
+// set slot with the zero V^T tail behind it, in one launch.  Data chunks keep the shape above: the branch joins before the sched_barrier and
+// the loop is the same straight line of reads and writes with its one uniform exit.  What the join costs: one wait serves both arms, so the
+// compiler counts the FEWER operations issued behind the set a conversion needs -- the arm without loads.  Checked in the assembly, widening:
+// `s_waitcnt vmcnt(8)` for the exponent (the 8 stores of the write before; kv_stream_kernel has vmcnt(13) there), then `s_waitcnt vmcnt(3)`
+// before the first conversion, where kv_stream_kernel has vmcnt(8): after a data chunk's 5 loads that leaves the last 3 of the other set's
+// loads in flight, not all 5, and the write drains them as it goes (vmcnt(4), (5), (6)).  The rate does not show it (profiles/LOG.md: the
+// same data-only table, 16 workgroups, 56.7 GB/s against kv_stream_kernel's 55.4).  The three kv_stream_kernel instantiations take
+// FILL = false, where the branch does not exist: their code is what it was.
 #include "common.cuh"
 
 #define KVS_THREADS 256
@@ -44,7 +56,7 @@ struct kvs_chunk {                                       // what a thread holds 
     int e;
 };
 
-template <bool WIDEN>
+template <bool WIDEN, bool FILL>
 __device__ __forceinline__ void kvs_read(kvs_chunk& c, const idmvton_kv_stream_desc* __restrict__ desc, const int32_t* __restrict__ first, int n, int q) {
     const int di = kvs_find(first, n, q);
     c.d = desc[di];
@@ -52,14 +64,21 @@ __device__ __forceinline__ void kvs_read(kvs_chunk& c, const idmvton_kv_stream_d
     const unsigned cpr = (unsigned)c.d.cols >> 4;                      // 16-byte items per row
     const unsigned last = (unsigned)c.d.rows * cpr - 1;                // (the host refuses a run of 2^31 items or more)
     const GLOBAL_AS uint8_t* src = (const GLOBAL_AS uint8_t*)c.d.src;
+    if (FILL && c.d.src == nullptr) {                                  // a zero run (workgroup-uniform: the descriptor is): no load at all, and
+#pragma unroll                                                         // neither src nor exp is looked at -- the chunk a source of zero bytes
+        for (int it = 0; it < KVS_ITEMS; ++it) c.w[it] = u32x4{0u, 0u, 0u, 0u};   // would give.  Zero times 2^-e is +0 for every e: c.e takes a value
+        c.e = c.d.lds;                                                 // that is NOT a constant, or the compiler folds kvs_write's exponent
+                                                                       // arithmetic into both arms and waits for the loaded one right behind the loads
+    } else {
 #pragma unroll
-    for (int it = 0; it < KVS_ITEMS; ++it) {
-        unsigned idx = c.base + it * KVS_THREADS + threadIdx.x;
-        idx = idx < last ? idx : last;                                 // never predicated: an item beyond the run re-reads its last one
-        const unsigned r = idx / cpr, col = idx - r * cpr;
-        c.w[it] = *(const GLOBAL_AS u32x4*)(src + (size_t)r * c.d.lds + (size_t)col * 16);
+        for (int it = 0; it < KVS_ITEMS; ++it) {
+            unsigned idx = c.base + it * KVS_THREADS + threadIdx.x;
+            idx = idx < last ? idx : last;                             // never predicated: an item beyond the run re-reads its last one
+            const unsigned r = idx / cpr, col = idx - r * cpr;
+            c.w[it] = *(const GLOBAL_AS u32x4*)(src + (size_t)r * c.d.lds + (size_t)col * 16);
+        }
+        c.e = WIDEN ? *(const GLOBAL_AS int*)c.d.exp : 0;
     }
-    c.e = WIDEN ? *(const GLOBAL_AS int*)c.d.exp : 0;
     // nothing moves across this point: left alone, the scheduler starts converting the OTHER set between the address arithmetic above, and the
     // wait for that set's data then stands before these loads are issued
     __builtin_amdgcn_sched_barrier(0);
@@ -98,8 +117,8 @@ __device__ __forceinline__ void kvs_write(const kvs_chunk& c) {
     }
 }
 
-template <typename T, bool WIDEN>
-__global__ __launch_bounds__(KVS_THREADS) void kv_stream_kernel(const idmvton_kv_stream_desc* __restrict__ desc, const int32_t* __restrict__ first, int n) {
+template <typename T, bool WIDEN, bool FILL>
+__device__ __forceinline__ void kvs_body(const idmvton_kv_stream_desc* __restrict__ desc, const int32_t* __restrict__ first, int n) {
     const int chunks = first[n];
     const int q0 = blockIdx.x, step = (int)gridDim.x;
     if (q0 >= chunks) return;                                          // only when the host asked for more workgroups than there are chunks
@@ -109,21 +128,31 @@ __global__ __launch_bounds__(KVS_THREADS) void kv_stream_kernel(const idmvton_kv
     // set issued after the ones it needs, and there is no wait between a chunk's stores and the next chunk's loads: two chunks of loads per
     // thread are in flight.  No chunk is read twice.
     kvs_chunk a, b;
-    kvs_read<WIDEN>(a, desc, first, n, q0);
+    kvs_read<WIDEN, FILL>(a, desc, first, n, q0);
     int i = 1;                                                         // chunks read so far; `a` holds chunk i - 1
     for (; i + 1 < cnt; i += 2) {
-        kvs_read<WIDEN>(b, desc, first, n, q0 + i * step);             // the next chunk's loads are in flight while this one is converted and stored
+        kvs_read<WIDEN, FILL>(b, desc, first, n, q0 + i * step);       // the next chunk's loads are in flight while this one is converted and stored
         kvs_write<T, WIDEN>(a);
-        kvs_read<WIDEN>(a, desc, first, n, q0 + (i + 1) * step);
+        kvs_read<WIDEN, FILL>(a, desc, first, n, q0 + (i + 1) * step);
         kvs_write<T, WIDEN>(b);
     }
     if (i < cnt) {
-        kvs_read<WIDEN>(b, desc, first, n, q0 + i * step);
+        kvs_read<WIDEN, FILL>(b, desc, first, n, q0 + i * step);
         kvs_write<T, WIDEN>(a);
         kvs_write<T, WIDEN>(b);
     } else {
         kvs_write<T, WIDEN>(a);
     }
+}
+
+template <typename T, bool WIDEN>
+__global__ __launch_bounds__(KVS_THREADS) void kv_stream_kernel(const idmvton_kv_stream_desc* __restrict__ desc, const int32_t* __restrict__ first, int n) {
+    kvs_body<T, WIDEN, false>(desc, first, n);
+}
+
+template <typename T, bool WIDEN>                                      // idmvton_kv_fill: the same body, a NULL src is a zero run
+__global__ __launch_bounds__(KVS_THREADS) void kv_fill_kernel(const idmvton_kv_stream_desc* __restrict__ desc, const int32_t* __restrict__ first, int n) {
+    kvs_body<T, WIDEN, true>(desc, first, n);
 }
 
 extern "C" int idmvton_kv_stream(const idmvton_kv_stream_args* a, const idmvton_kv_stream_desc* host_desc, const int32_t* host_first, void* stream) {
@@ -159,6 +188,43 @@ extern "C" int idmvton_kv_stream(const idmvton_kv_stream_args* a, const idmvton_
     else if (a->dtype == IDMVTON_BF16) hipLaunchKernelGGL((kv_stream_kernel<bf16_t, true>), grid, block, 0, (hipStream_t)stream, a->desc, a->first, a->n);
     else hipLaunchKernelGGL((kv_stream_kernel<f16_t, true>), grid, block, 0, (hipStream_t)stream, a->desc, a->first, a->n);
     CHECK_LAUNCH("kv_stream");
+    return IDMVTON_OK;
+}
+
+extern "C" int idmvton_kv_fill(const idmvton_kv_stream_args* a, const idmvton_kv_stream_desc* host_desc, const int32_t* host_first, void* stream) {
+    CHECK_ARG(a && host_desc && host_first && a->desc && a->first, IDMVTON_E_ARG, "kv_fill: null args / descriptor table / prefix table");
+    CHECK_ARG(a->dtype == IDMVTON_F16 || a->dtype == IDMVTON_BF16, IDMVTON_E_DTYPE, "kv_fill: dtype %d (F16 or BF16)", a->dtype);
+    CHECK_ARG(a->mode == IDMVTON_KVS_WIDEN_E4M3 || a->mode == IDMVTON_KVS_COPY, IDMVTON_E_ARG, "kv_fill: mode %d (IDMVTON_KVS_WIDEN_E4M3 or IDMVTON_KVS_COPY)", a->mode);
+    CHECK_ARG(a->n >= 1 && a->n <= IDMVTON_KVS_MAX_N, IDMVTON_E_ARG, "kv_fill: n=%d outside [1, %d] descriptors", a->n, IDMVTON_KVS_MAX_N);
+    CHECK_ARG(a->workgroups >= 1 && a->workgroups <= 1024, IDMVTON_E_ARG, "kv_fill: workgroups=%d outside [1, 1024]", a->workgroups);
+    CHECK_ARG(((uintptr_t)a->desc & 15) == 0, IDMVTON_E_ALIGN, "kv_fill: the device descriptor table is not 16-byte aligned");
+    CHECK_ARG(((uintptr_t)a->first & 3) == 0, IDMVTON_E_ALIGN, "kv_fill: the device prefix table is not 4-byte aligned");
+    const bool widen = a->mode == IDMVTON_KVS_WIDEN_E4M3;
+    const int dmul = widen ? 8 : 16;                                   // ldd: elements when widening, bytes when copying
+    long chunks = 0;
+    for (int i = 0; i < a->n; ++i) {
+        const idmvton_kv_stream_desc* d = host_desc + i;
+        const bool zero = d->src == nullptr;                           // a zero run: exp and lds are not looked at
+        CHECK_ARG(d->dst && (zero || d->exp || !widen), IDMVTON_E_ARG, "kv_fill: descriptor %d has a null pointer (dst%s)", i, zero ? " of a zero run" : ", or exp of a data run");
+        CHECK_ARG(((uintptr_t)d->src & 15) == 0 && ((uintptr_t)d->dst & 15) == 0 && (zero || !widen || ((uintptr_t)d->exp & 3) == 0), IDMVTON_E_ALIGN,
+                  "kv_fill: descriptor %d: src / dst not 16-byte aligned (or exp not 4-byte aligned)", i);
+        CHECK_ARG(d->rows >= 1 && d->cols >= 16 && d->cols % 16 == 0, IDMVTON_E_SHAPE, "kv_fill: descriptor %d: rows=%d cols=%d (rows >= 1, cols a multiple of 16)",
+                  i, d->rows, d->cols);
+        CHECK_ARG(zero || (d->lds >= d->cols && d->lds % 16 == 0), IDMVTON_E_SHAPE, "kv_fill: descriptor %d: lds=%d (>= cols=%d, a multiple of 16)", i, d->lds, d->cols);
+        CHECK_ARG(d->ldd >= d->cols && d->ldd % dmul == 0, IDMVTON_E_SHAPE, "kv_fill: descriptor %d: ldd=%d (>= cols=%d, a multiple of %d)", i, d->ldd, d->cols, dmul);
+        const long items = (long)d->rows * (d->cols >> 4);
+        CHECK_ARG(items < (1L << 31), IDMVTON_E_SHAPE, "kv_fill: descriptor %d: rows=%d x cols=%d is 2^31 16-byte items or more", i, d->rows, d->cols);
+        CHECK_ARG(host_first[i] == chunks, IDMVTON_E_ARG, "kv_fill: host_first[%d]=%d, the runs before descriptor %d have %ld chunks of %d 16-byte items",
+                  i, host_first[i], i, chunks, KVS_CHUNK);
+        chunks += (items + KVS_CHUNK - 1) / KVS_CHUNK;
+        CHECK_ARG(chunks < (1L << 31), IDMVTON_E_SHAPE, "kv_fill: 2^31 chunks or more up to descriptor %d", i);
+    }
+    CHECK_ARG(host_first[a->n] == chunks, IDMVTON_E_ARG, "kv_fill: host_first[%d]=%d, the table has %ld chunks of %d 16-byte items", a->n, host_first[a->n], chunks, KVS_CHUNK);
+    const dim3 grid((unsigned)a->workgroups), block(KVS_THREADS);
+    if (!widen) hipLaunchKernelGGL((kv_fill_kernel<bf16_t, false>), grid, block, 0, (hipStream_t)stream, a->desc, a->first, a->n);
+    else if (a->dtype == IDMVTON_BF16) hipLaunchKernelGGL((kv_fill_kernel<bf16_t, true>), grid, block, 0, (hipStream_t)stream, a->desc, a->first, a->n);
+    else hipLaunchKernelGGL((kv_fill_kernel<f16_t, true>), grid, block, 0, (hipStream_t)stream, a->desc, a->first, a->n);
+    CHECK_LAUNCH("kv_fill");
     return IDMVTON_OK;
 }
 

@@ -132,7 +132,7 @@ SYMBOLS = ["idmvton_last_error", "idmvton_abi_version", "idmvton_sizeof", "idmvt
            "idmvton_rccl_comm_destroy", "idmvton_attn_f8", "idmvton_quant_f8", "idmvton_split", "idmvton_attn_fwd_shared",
            "idmvton_attn_f8_shared", "idmvton_attn_fwd_indexed", "idmvton_attn_f8_indexed",
            "idmvton_attn_fwd_ragged", "idmvton_attn_f8_ragged", "idmvton_kv_unpack", "idmvton_kv_stream",
-           "idmvton_host_device_ptr"]
+           "idmvton_host_device_ptr", "idmvton_kv_fill"]
 
 _lib = None
 
@@ -182,6 +182,8 @@ def lib():
     L.idmvton_kv_unpack.restype = C.c_int
     L.idmvton_kv_stream.argtypes = [vp, vp, vp, vp]                           # (args*, const desc* host_desc, const int32_t* host_first, stream)
     L.idmvton_kv_stream.restype = C.c_int
+    L.idmvton_kv_fill.argtypes = [vp, vp, vp, vp]                             # the same signature; a NULL src is a zero run
+    L.idmvton_kv_fill.restype = C.c_int
     L.idmvton_host_device_ptr.argtypes = [vp, C.POINTER(vp)]                  # (const void* host, void** dev)
     L.idmvton_host_device_ptr.restype = C.c_int
     L.idmvton_probe_mfma.argtypes = [C.c_int, vp, vp, vp, vp]
@@ -255,6 +257,15 @@ def call_kv_stream(args, host_desc, host_first, stream):
     rc = L.idmvton_kv_stream(C.byref(args), p(host_desc), p(host_first), C.c_void_p(stream))
     if rc != 0:
         raise RuntimeError(f"idmvton_kv_stream failed ({rc}): {L.idmvton_last_error().decode()}")
+
+
+def call_kv_fill(args, host_desc, host_first, stream):
+    """Invoke idmvton_kv_fill: call_kv_stream's arguments; a descriptor whose src is NULL is a zero run."""
+    L = lib()
+    p = lambda x: x if isinstance(x, int) else C.cast(x, vp)
+    rc = L.idmvton_kv_fill(C.byref(args), p(host_desc), p(host_first), C.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError(f"idmvton_kv_fill failed ({rc}): {L.idmvton_last_error().decode()}")
 
 
 def host_device_ptr(host):

@@ -38,6 +38,12 @@ Host-resident: a cache whose tensors are CPU tensors (`to("cpu", pin_memory=True
 The engine takes one that is PAGE-LOCKED as `cloth=`: every block of timesteps then goes from host memory straight into the 16-bit sets by
 one idmvton_kv_stream launch (pipeline.py, _stream_fill), so a catalogue is bounded by host RAM, not HBM.  Queued calls read such a cache
 by raw address, with no stream order to protect them: a `put` into it waits for the device first and copies blocking.
+
+Shelf: a GarmentShelf is a host catalogue of garments of MANY sizes, each kept COMPACT -- a G = 1 cache of its own (N'_f rows, ld'_f V^T
+positions) in page-locked memory, 16-bit or e4m3-packed -- so host RAM and the bytes a call moves over the host link follow the garments' own
+sizes, not the largest one's.  `get` hands out a ShelvedGarmentCache: the garments of a batch as `parts`, declared for one slot size; the
+engine puts each into the front of a slot of its 16-bit sets and writes the zero V^T tail behind it with one idmvton_kv_fill launch per block
+(shelf_records below, pipeline.py _shelf_fill), and reads them as it reads a slotted cache.
 """
 import torch
 
@@ -608,6 +614,232 @@ def fill_records(src_kv, n, G, dst_kv, k, S, exps, entries, tslots, garments, gs
     ex = address(exps) + 4 * ((torch.tensor(garments, dtype=I64).view(1, -1, 1, 1) * F + torch.arange(F, dtype=I64).view(1, 1, F, 1)) * 2
                               + torch.arange(2, dtype=I64).view(1, 1, 1, 2))
     return ops.kv_unpack_rows(sbase + si * unit, dbase + di * unit * esz, ex, rows, cols, cols, cols).reshape(-1, 5)
+
+
+def shelf_records(parts, packed, dst_kv, k, S, entries, tslots, gslots, address=None):
+    """The idmvton_kv_fill descriptor records (ops.KvFillTable: int64 [N][5]) that put the COMPACT garments `parts` (G = 1 caches of n
+    timesteps each, all packed or all 16-bit) into garment slots `gslots` of the 16-bit list dst_kv (k timesteps of S slots of the slot size),
+    for every pair (entry i, timestep slot j) of (entries, tslots).  Per (timestep, garment, feature):
+      K      one data run of the garment's own N'_f rows into the front of the slot (rows beyond are not written: no kernel reads them);
+      V^T    one data run of C_f rows x ld'_f positions, source row stride ld'_f, destination row stride the slot's ld_f;
+      tail   where ld'_f < ld_f, one ZERO RUN (src 0) of C_f rows x (ld_f - ld'_f) positions behind it -- the whole tail, as _put_slotted writes
+             it, so a set's V^T depends on the garment alone and not on what the slot held before.
+    Widening form (packed parts): cols / lds in bytes = elements, ldd in 16-bit elements, exp the address of the part's exponent; copy form:
+    cols, lds, ldd in bytes, exp 0.  A timestep's records are padded to an even count by repeating its smallest record (ops.kv_pad_even: a
+    slice of the table starts at an even index).  -> (records, per) with `per` the records of one timestep: timestep number t of
+    (entries, tslots) owns records [t * per, (t + 1) * per).  address(tensor): as fill_records, asked once per source tensor.  Pure address
+    arithmetic on CPU tensors."""
+    from . import ops
+    I64 = torch.int64
+    address = address or (lambda t: t.data_ptr())
+    esz = dst_kv[0][0].element_size()
+    su = 1 if packed else esz                              # source / column unit in bytes
+    tmpl, sinc, dinc = [], [], []                          # records of timestep (entry 0, slot 0); src / dst advance per entry / timestep slot
+    for part, u in zip(parts, gslots):
+        n = len(part.timesteps)
+        ex = address(part.exps) if packed else 0
+        for f, ((sk, sv), (dk, dv)) in enumerate(zip(part.kv, dst_kv)):
+            Nf, C, ldf = sk.shape[0] // n, sk.shape[1], sv.shape[2]
+            N, ld = dk.shape[0] // (k * S), dv.shape[2]
+            ek, ev = (ex + 4 * (f * 2), ex + 4 * (f * 2 + 1)) if packed else (0, 0)
+            dK, dV = dk.data_ptr() + u * N * C * esz, dv.data_ptr() + u * C * ld * esz
+            tmpl.append((address(sk), dK, ek, Nf | ((C * su) << 32), (C * su) | ((C * (1 if packed else esz)) << 32)))
+            sinc.append(Nf * C * su); dinc.append(S * N * C * esz)
+            tmpl.append((address(sv), dV, ev, C | ((ldf * su) << 32), (ldf * su) | ((ld * (1 if packed else esz)) << 32)))
+            sinc.append(C * ldf * su); dinc.append(S * C * ld * esz)
+            if ldf < ld:                                     # the zero run: nothing is loaded, lds is ignored
+                tmpl.append((0, dV + ldf * esz, 0, C | (((ld - ldf) * su) << 32), ((ld - ldf) * su) | ((ld * (1 if packed else esz)) << 32)))
+                sinc.append(0); dinc.append(S * C * ld * esz)
+    T = torch.tensor(tmpl, dtype=I64).reshape(-1, 5)
+    sinc, dinc = torch.tensor(sinc, dtype=I64), torch.tensor(dinc, dtype=I64)
+    if T.shape[0] % 2:
+        m = int(((T[:, 3] & 0xffffffff) * ((T[:, 3] >> 32) >> 4)).argmin())
+        T, sinc, dinc = ops.kv_pad_even(T), torch.cat([sinc, sinc[m:m + 1]]), torch.cat([dinc, dinc[m:m + 1]])
+    rec = T.unsqueeze(0).repeat(len(entries), 1, 1)
+    rec[:, :, 0] += torch.tensor(entries, dtype=I64).view(-1, 1) * sinc.view(1, -1)
+    rec[:, :, 1] += torch.tensor(tslots, dtype=I64).view(-1, 1) * dinc.view(1, -1)
+    return rec.reshape(-1, 5).contiguous(), T.shape[0]
+
+
+class ShelvedGarmentCache(GarmentCache):
+    """The garments of a batch as GarmentShelf.get hands them out: `parts`, G = 1 caches in host memory, each at its OWN compact size, declared
+    for slots of one size -- (gh, gw) and slot_shapes [((N_f, C_f), (C_f, ld_f))] --; sizes[g] is garment g's own (gh, gw).  There is no
+    single tensor list (kv is empty): the engine streams every part into the front of a set slot (module docstring), and what it computes is
+    what it computes on `slotted(device)`.  The cache keeps its parts alive: removing a key from the shelf while a call is queued is safe."""
+
+    def __init__(self, parts, *, gh, gw, slot_shapes, h=None, w=None):
+        parts = list(parts)
+        if not parts or any(p.G != 1 or p.sizes is not None for p in parts) or len({p.packed for p in parts}) != 1:
+            raise ValueError("ShelvedGarmentCache: needs at least one part, every part a G = 1 cache without `sizes`, all packed or all 16-bit")
+        p0 = parts[0]
+        super().__init__(G=len(parts), timesteps=p0.timesteps, h=p0.h if h is None else h, w=p0.w if w is None else w, gh=gh, gw=gw, dtype=p0.dtype,
+                         attn_fp8=p0.attn_fp8, f8_exp=p0.f8_exp, weights_id=p0.weights_id, kv=[], sizes=[(p.gh, p.gw) for p in parts])
+        self.parts = parts
+        self.packed = p0.packed
+        self.slot_shapes = [(tuple(a), tuple(b)) for a, b in slot_shapes]
+
+    @property
+    def nbytes(self):
+        return sum(p.nbytes for p in self.parts)
+
+    @property
+    def host_resident(self):
+        return True
+
+    def __repr__(self):
+        return (f"ShelvedGarmentCache(G={self.G}, steps={len(self.timesteps)}, latent={self.h}x{self.w}, slots of {self.gh}x{self.gw} holding "
+                f"{sorted(set(self.sizes))}, dtype={self.dtype}, {'e4m3-packed, ' if self.packed else ''}{self.nbytes / 2 ** 20:.1f} MiB compact in host memory)")
+
+    def _with(self, parts, **kw):
+        return ShelvedGarmentCache(parts, gh=self.gh, gw=self.gw, slot_shapes=self.slot_shapes, h=kw.get("h", self.h), w=kw.get("w", self.w))
+
+    def for_person_size(self, h, w):
+        return self._with(self.parts, h=h, w=w)              # the same parts, no copy
+
+    def select(self, ids):
+        """Garments ids[0], ids[1], ... as a new ShelvedGarmentCache on the SAME parts (they are never written in place); values may repeat."""
+        return self._with([self.parts[g] for g in self.garment_ids(ids, len(ids))])
+
+    def take(self, slot, device=None, pin_memory=False):
+        """A copy of part `slot`: a compact G = 1 cache (packed if the shelf is), on `device` (default: host memory)."""
+        if not 0 <= int(slot) < self.G:
+            raise ValueError(f"GarmentCache take: slot mismatch ({slot} outside [0, G = {self.G}))")
+        return self.parts[int(slot)].take(0, device, pin_memory)
+
+    def slotted(self, device=None):
+        """The 16-bit slotted GarmentCache that empty slots + put(g, take(g)) give (packed parts unpacked first), on `device` (default: host
+        memory): what an engine call on this cache is compared against.  K rows no garment fills are zero."""
+        device = torch.device("cpu" if device is None else device)
+        n, G = len(self.timesteps), self.G
+        kv = [(torch.zeros((n * G * a[0], a[1]), dtype=self.dtype, device=device), torch.zeros((n * G, b[0], b[1]), dtype=self.dtype, device=device))
+              for a, b in self.slot_shapes]
+        out = GarmentCache(G=G, timesteps=self.timesteps, h=self.h, w=self.w, gh=self.gh, gw=self.gw, dtype=self.dtype, attn_fp8=self.attn_fp8,
+                           f8_exp=self.f8_exp, weights_id=self.weights_id, kv=kv, sizes=[(self.gh, self.gw)] * G)
+        for g, part in enumerate(self.parts):
+            one = part.to(device)
+            out.put(g, (one.unpack() if one.packed else one).for_person_size(self.h, self.w))
+        return out
+
+    def _no(self, name):
+        raise ValueError(f"ShelvedGarmentCache {name}: a shelved cache has no single tensor list (its garments live in `parts`, each at its own "
+                         "size); use slotted(), take() or select()")
+
+    def put(self, slot, other): self._no("put")
+    def save(self, path): self._no("save")
+    def pack(self, exps=None): self._no("pack")
+    def unpack(self): self._no("unpack")
+    def repeat_garments(self, times): self._no("repeat_garments")
+    def run(self, i0, c=1): self._no("run")
+    def step(self, i): self._no("step")
+    def to(self, device, pin_memory=False): self._no("to")
+
+    @staticmethod
+    def cat(caches):
+        raise ValueError("ShelvedGarmentCache cat: a shelved cache has no single tensor list (its garments live in `parts`, each at its own "
+                         "size); use GarmentShelf.get for the garments of a batch")
+
+
+class GarmentShelf:
+    """A host catalogue of garments of many sizes: key -> a COMPACT G = 1 cache in page-locked host memory (pageable where there is no GPU, so
+    that the logic runs on a CPU), 16-bit (storage="native") or e4m3-packed ("e4m3": a 16-bit garment is packed on its way in, on the device
+    it lives on).  `like` -- a cache with `sizes`, as TryonEngine.empty_garment_cache makes it, or any G = 1 cache -- fixes what every garment
+    must agree with (timesteps, person size, dtype, attn_fp8, f8_exp, weights) and the SLOT size: every feature's K rows and V^T positions
+    must fit it.  Only like's fields and shapes are kept, not its tensors.  max_bytes bounds the shelf: `get` evicts the least recently used
+    garments that the batch does not name until it fits.
+        shelf = GarmentShelf(pipe.empty_garment_cache(1, 1024, 768, 30), storage="e4m3")
+        cache, index = shelf.get(["sku7", "sku3", "sku7"], encode=my_encode)
+        out = pipe(cloth=cache, garment_index=index, ...)"""
+    _IDENTITY = ("timesteps", "h", "w", "dtype", "attn_fp8", "f8_exp", "weights_id")
+
+    def __init__(self, like, storage="native", max_bytes=None):
+        if storage not in ("native", "e4m3"):
+            raise ValueError(f"GarmentShelf: storage={storage!r} (\"native\" or \"e4m3\")")
+        if isinstance(like, ShelvedGarmentCache):
+            self.slot_shapes = list(like.slot_shapes)
+        else:
+            n = len(like.timesteps)
+            self.slot_shapes = [((k.shape[0] // (n * like.G), k.shape[1]), (vt.shape[1], vt.shape[2])) for k, vt in like.kv]
+        self.like = {f: getattr(like, f) for f in self._IDENTITY}
+        self.gh, self.gw = like.gh, like.gw
+        self.storage, self.max_bytes = storage, None if max_bytes is None else int(max_bytes)
+        self._parts = {}                                     # key -> compact G = 1 cache, in use order: the first key is the least recently used
+        self.stats = dict(hits=0, encoded=0, restored=0, evicted=0)
+
+    def __contains__(self, key):
+        return key in self._parts
+
+    def __len__(self):
+        return len(self._parts)
+
+    @property
+    def nbytes(self):
+        return sum(p.nbytes for p in self._parts.values())
+
+    def keys(self):
+        """The keys, least recently used first."""
+        return list(self._parts)
+
+    def _compact(self, one):
+        """`one` checked against the shelf and copied compact into host memory; ValueError naming the field otherwise."""
+        if one.G != 1:
+            raise ValueError(f"GarmentShelf add: G mismatch (takes a cache of one garment, got G = {one.G})")
+        if one.attn_fp8:
+            raise ValueError("GarmentShelf add: attn_fp8 mismatch (an attn_fp8 garment holds e4m3 operands of the fp8 attention; a shelf is not "
+                             "streamed by an attn_fp8 engine)")
+        for f in self._IDENTITY:
+            if getattr(one, f) != self.like[f]:
+                raise ValueError(f"GarmentShelf add: {f} mismatch ({getattr(one, f)} against {self.like[f]})")
+        if one.packed and self.storage == "native":
+            raise ValueError("GarmentShelf add: packed mismatch (an e4m3-packed garment cannot go into a storage=\"native\" shelf: unpack() is not "
+                             "its 16-bit original)")
+        if one.sizes is not None:                            # a one-slot slotted cache: the garment at its own compact size
+            one = one.take(0)
+        n = len(one.timesteps)
+        if len(one.kv) != len(self.slot_shapes):
+            raise ValueError(f"GarmentShelf add: does not fit ({len(one.kv)} features against {len(self.slot_shapes)})")
+        for f, ((k, vt), ((N, C), (Cv, ld))) in enumerate(zip(one.kv, self.slot_shapes)):
+            if k.shape[1] != C or vt.shape[1] != Cv or k.shape[0] // n > N or vt.shape[2] > ld:
+                raise ValueError(f"GarmentShelf add: does not fit (feature {f}: a garment of latent {one.gh}x{one.gw} has K rows {k.shape[0] // n} x "
+                                 f"{k.shape[1]} and V^T {vt.shape[1]} x {vt.shape[2]}, a slot of {self.gh}x{self.gw} holds {N} x {C} and {Cv} x {ld})")
+        if self.storage == "e4m3" and not one.packed:
+            one = one.pack()                                 # on the device it lives on
+        return one.take(0, "cpu", pin_memory=torch.cuda.is_available())
+
+    def add(self, key, one):
+        """Put the one garment of `one` (G = 1, 16-bit or packed, of ANY size that fits the slot) on the shelf under `key`, compact, replacing
+        what the key held.  Complete on return."""
+        part = self._compact(one)
+        self._parts.pop(key, None)
+        self._parts[key] = part
+
+    def remove(self, key):
+        """Take a garment off the shelf (a ShelvedGarmentCache that names it keeps it alive)."""
+        self._parts.pop(key, None)
+
+    def get(self, keys, encode=None):
+        """-> (ShelvedGarmentCache of the distinct garments of `keys` in first-use order, garment_index of the batch).  encode(key) -> a G = 1
+        cache; it is called once per distinct key the shelf lacks (KeyError when there is none), and every garment is made before the shelf
+        changes: nothing is added or evicted if encode raises.  With max_bytes, the least recently used garments the batch does not name are
+        evicted until the shelf fits; ValueError when the batch alone exceeds the bound."""
+        keys = list(keys)
+        distinct = list(dict.fromkeys(keys))
+        missing = [key for key in distinct if key not in self._parts]
+        if missing and encode is None:
+            raise KeyError(f"GarmentShelf: {missing[0]!r} is not on the shelf and no `encode` was given")
+        new = {key: self._compact(encode(key)) for key in missing}
+        batch = {key: new[key] if key in new else self._parts[key] for key in distinct}
+        need = sum(p.nbytes for p in batch.values())
+        if self.max_bytes is not None and need > self.max_bytes:
+            raise ValueError(f"GarmentShelf: the batch alone holds {need} bytes, max_bytes is {self.max_bytes}")
+        for key in distinct:                                 # most recently used: to the end
+            self.stats["encoded" if key in new else "hits"] += 1
+            self._parts.pop(key, None)
+            self._parts[key] = batch[key]
+        while self.max_bytes is not None and self.nbytes > self.max_bytes:
+            del self._parts[next(k for k in self._parts if k not in batch)]
+            self.stats["evicted"] += 1
+        cache = ShelvedGarmentCache(list(batch.values()), gh=self.gh, gw=self.gw, slot_shapes=self.slot_shapes)
+        return cache, [distinct.index(key) for key in keys]
 
 
 class GarmentPool:

@@ -409,6 +409,7 @@ class KvStreamTable:
     of KvUnpackTable's (in copy mode cols, lds and ldd are bytes and exp is 0) -- and the `slices` [(first, count)] of it that will be
     launched (default: the whole table; `first` even, as a slice of the device copy has to start 16-byte aligned).  Every slice gets its own
     prefix table; records and prefix tables are uploaded ONCE, here.  launch(dtype, which, workgroups) moves slice `which` in one launch."""
+    ENTRY = "kv_stream"                                      # launched through ffi.call_<ENTRY> (KvFillTable: kv_fill)
 
     def __init__(self, host, device, mode=ffi.KVS_WIDEN_E4M3, slices=None):
         self.host, self.mode = host.contiguous(), mode
@@ -431,14 +432,42 @@ class KvStreamTable:
         a = ffi.KvStreamArgs()
         a.dtype, a.mode, a.n, a.workgroups = _DT[dtype], self.mode, c, KV_STREAM_WORKGROUPS if workgroups is None else workgroups
         a.desc, a.first = self.dev.data_ptr() + 40 * f0, self.first_dev.data_ptr() + 4 * self.first_at[which]
-        launch = lambda: ffi.call_kv_stream(a, self.host.data_ptr() + 40 * f0, self.first_host.data_ptr() + 4 * self.first_at[which], _stream())
+        call = getattr(ffi, "call_" + self.ENTRY)
+        launch = lambda: call(a, self.host.data_ptr() + 40 * f0, self.first_host.data_ptr() + 4 * self.first_at[which], _stream())
         if PROFILE is None:
             return launch()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         launch()
         e1.record()
-        PROFILE.append(("idmvton_kv_stream", e0, e1, 0.0, (48.0 if self.mode == ffi.KVS_WIDEN_E4M3 else 32.0) * float(self.items[f0:f0 + c].sum())))
+        PROFILE.append(("idmvton_" + self.ENTRY, e0, e1, 0.0, self.bytes_moved(f0, c)))
+
+    def bytes_moved(self, f0, c):
+        """Bytes loaded + stored by descriptors [f0, f0 + c): 16 in and 32 (widening) / 16 (copying) out per item."""
+        return (48.0 if self.mode == ffi.KVS_WIDEN_E4M3 else 32.0) * float(self.items[f0:f0 + c].sum())
+
+
+class KvFillTable(KvStreamTable):
+    """KvStreamTable launched through idmvton_kv_fill: a record whose src is 0 is a ZERO RUN (rows x cols of +0 / zero bytes written, nothing
+    loaded; exp and lds ignored).  Items and prefix tables are KvStreamTable's: a zero run counts like a data run."""
+    ENTRY = "kv_fill"
+
+    def link_bytes(self, f0=0, c=None):
+        """Bytes descriptors [f0, f0 + c) LOAD: 16 per item of a data run, none for a zero run."""
+        c = self.n - f0 if c is None else c
+        return 16.0 * float(self.items[f0:f0 + c][self.host[f0:f0 + c, 0] != 0].sum())
+
+    def bytes_moved(self, f0, c):                            # a zero run stores bytes and loads none
+        return self.link_bytes(f0, c) + (32.0 if self.mode == ffi.KVS_WIDEN_E4M3 else 16.0) * float(self.items[f0:f0 + c].sum())
+
+
+def kv_pad_even(rec):
+    """Descriptor records int64 [n][5] -> the same with the record of fewest items repeated at the end when n is odd: slices of a table start
+    at even record indices (16-byte aligned device addresses), and writing identical bytes twice is what clamped lanes already do."""
+    if rec.shape[0] % 2 == 0:
+        return rec
+    items = (rec[:, 3] & 0xffffffff) * ((rec[:, 3] >> 32) >> 4)
+    return torch.cat([rec, rec[int(items.argmin())].view(1, 5)])
 
 
 def kv_stream(descs, dtype, mode=ffi.KVS_WIDEN_E4M3, workgroups=None, device=None):
@@ -465,6 +494,37 @@ def kv_stream(descs, dtype, mode=ffi.KVS_WIDEN_E4M3, workgroups=None, device=Non
                         (src.stride(0) * sz) | ((dst.stride(0) * sz) << 32)))
         device = descs[0][1].device if device is None else device
         descs = KvStreamTable(torch.tensor(rec, dtype=torch.int64).reshape(-1, 5), device, mode)
+    descs.launch(dtype, 0, workgroups)
+    return descs
+
+
+def kv_fill(descs, dtype, mode=ffi.KVS_WIDEN_E4M3, workgroups=None, device=None):
+    """idmvton_kv_fill on every run of `descs`, in one launch: ops.kv_stream's arguments, and a run whose src is None is a ZERO RUN -- (None,
+    dst, None) writes +0 (widening) / zero bytes (copying) over dst's [rows][cols] and loads nothing.  descs: a KvFillTable (its slice 0) or
+    a list of (src | None, dst, exp | None) views.  -> the table."""
+    if not isinstance(descs, KvStreamTable):
+        widen = mode == ffi.KVS_WIDEN_E4M3
+        rec = []
+        for src, dst, exp in descs:
+            ok = dst.dim() == 2 and dst.stride(1) == 1 and dst.is_cuda and (not widen or dst.dtype == dtype)
+            if src is not None:
+                ok = ok and src.dim() == 2 and src.shape == dst.shape and src.stride(1) == 1
+                if widen:
+                    ok = ok and src.dtype == torch.uint8 and exp is not None and exp.dtype == torch.int32 and exp.numel() == 1
+                else:
+                    ok = ok and src.dtype == dst.dtype
+            if not ok:
+                raise ValueError("kv_fill: a run is (uint8 [rows][cols], %s [rows][cols], one int32) when widening, (x [rows][cols], x [rows][cols], None) "
+                                 "when copying, (None, dst [rows][cols], None) for a zero run; rows contiguous, the destination on the device" % dtype)
+            rows, cols = dst.shape
+            sz = 1 if widen else dst.element_size()          # copy mode: byte units
+            if src is None:
+                rec.append((0, _ptr(dst), 0, rows | ((cols * sz) << 32), (cols * sz) | ((dst.stride(0) * sz) << 32)))
+            else:
+                rec.append((stream_address(src), _ptr(dst), stream_address(exp) if widen else 0, rows | ((cols * sz) << 32),
+                            (src.stride(0) * sz) | ((dst.stride(0) * sz) << 32)))
+        device = descs[0][1].device if device is None else device
+        descs = KvFillTable(torch.tensor(rec, dtype=torch.int64).reshape(-1, 5), device, mode)
     descs.launch(dtype, 0, workgroups)
     return descs
 

@@ -39,6 +39,9 @@ A HOST-RESIDENT cache (page-locked CPU tensors: GarmentCache.to("cpu", pin_memor
 the same way through sets in all four forms: `_stream_fill`, _packed_fill's twin, moves a block from host memory straight into set p with ONE
 idmvton_kv_stream launch (widening e4m3 bytes, or copying 16-bit values) -- in _fill_set's place in drive_blocks' order, so every block but
 the first crosses the host link behind the TryonNet steps of the block before it.  Nothing of the cache is in HBM before the call.
+A SHELVED cache (ShelvedGarmentCache, GarmentShelf.get: compact garments of many sizes in page-locked memory) goes the same way again:
+`_shelf_fill` puts each garment into the front of a set slot and writes the zero V^T tail behind it with ONE idmvton_kv_fill launch per block;
+key-count table, slot table, set shapes and graph key are those of a device-resident slotted cache of the same slot size.
 With garment_index the two cache rows read through the table: eager on the cache's own views (nb = G, table = garment_index), graph on
 P-slot sets into which _fill_set gathers the U distinct garments of the call (table = person -> set slot, a persistent buffer of the state).
 
@@ -48,7 +51,8 @@ blocks.  The K / V^T layout of sets and cache (timestep-major) has one owner, ga
 import torch
 
 from . import ops
-from .garment_cache import GarmentCache, PackedGarmentCache, alloc_kv, fill_records, index_runs, kv_shapes, slot_run, timestep_run
+from .garment_cache import (GarmentCache, PackedGarmentCache, ShelvedGarmentCache, alloc_kv, fill_records, index_runs, kv_shapes, shelf_records,
+                            slot_run, timestep_run)
 from .scheduler import StepScheduler
 
 
@@ -110,7 +114,7 @@ class TryonEngine:
         self.ramp = True                                     # first blocks of 1, 2, 4 timesteps
         # garment_batches: GarmentNet batches launched or replayed by this engine (a call on a GarmentCache adds none); garment_set_copies: blocks
         # of cached K / V^T copied into a persistent set by the graph forms (on a packed cache: widened into one, by every form)
-        # garment_stream_launches: blocks moved from a host-resident cache into a set (one idmvton_kv_stream launch each)
+        # garment_stream_launches: blocks moved from a host-resident cache into a set (one idmvton_kv_stream / idmvton_kv_fill launch each)
         self.stats = dict(garment_batches=0, garment_set_copies=0, garment_stream_launches=0)
         self._streaming = []                                 # [cache, event of its last queued fill]: host memory a queued launch still reads
         self._weights_id = None
@@ -313,7 +317,8 @@ class TryonEngine:
         garment_index: which size a person's garment has follows from the slot it names.
         A HOST-RESIDENT cache (CPU tensors) is streamed into the sets block by block during the call (_stream_fill); every tensor -- and a
         packed cache's `exps` -- must be page-locked (pin_memory), the cache must not have `sizes`, and the engine must not be attn_fp8: each
-        a ValueError naming the field, before anything is launched."""
+        a ValueError naming the field, before anything is launched.  A ShelvedGarmentCache (GarmentShelf.get) is the host-resident cache WITH
+        sizes: garment_index is required, every part and every part's `exps` must be page-locked, the engine must not be attn_fp8."""
         dev, dt = self.device, self.dtype
         self._release_streamed()
         f32 = lambda t: t.to(dev, torch.float32).contiguous()
@@ -490,6 +495,9 @@ class TryonEngine:
         (a packed cache's bytes are widened on the way in)."""
         gc = st["gcache"]
         slots = gc.G if st["gindex"] is None else st["B"]
+        if isinstance(gc, ShelvedGarmentCache):              # no tensor list: the slot's shapes, what a slotted cache of that slot size has
+            n = len(gc.timesteps)
+            return slots, [((n * slots * a[0], a[1]), (n * slots, b[0], b[1]), gc.dtype) for a, b in gc.slot_shapes]
         dt = lambda d: gc.dtype if gc.packed else d
         return slots, [((a[0] // gc.G * slots,) + a[1:], (b[0] // gc.G * slots,) + b[1:], dt(d)) for a, b, d in kv_shapes(gc.kv)]
 
@@ -499,6 +507,10 @@ class TryonEngine:
         if self.unet.attn_fp8:
             raise ValueError("host-resident GarmentCache attn_fp8 mismatch: an attn_fp8 engine does not stream a cache from host memory "
                              "(move it with .to(device))")
+        if isinstance(gc, ShelvedGarmentCache):              # the host-resident cache WITH sizes: every part held to the same conditions
+            for part in gc.parts:
+                self._check_host_cache(part)
+            return
         if gc.sizes is not None:
             raise ValueError("host-resident GarmentCache sizes mismatch: a cache with `sizes` (slotted / mixed_sizes) is not streamed from host "
                              "memory (move it with .to(device))")
@@ -523,6 +535,8 @@ class TryonEngine:
         idmvton_host_device_ptr per cache tensor, and a block is a slice.  `blocks`: build for these block numbers only (the warm-up).
         The launches read host memory by raw address: the cache stays referenced by the engine until the last one has completed."""
         gc, k = st["gcache"], st["k"]
+        if isinstance(gc, ShelvedGarmentCache):
+            return self._shelf_fill(st, sets, blocks)
         n = len(gc.timesteps)
         garments = list(range(gc.G)) if st["gindex"] is None else list(dict.fromkeys(st["gindex"]))
         S = gc.G if st["gindex"] is None else st["B"]
@@ -549,6 +563,42 @@ class TryonEngine:
             self.stats["garment_stream_launches"] += 1
             table.launch(self.dtype, which[(p, bi)])
             hold[1].record()                                 # the call's last fill so far: until it has passed, `hold` keeps the cache alive
+        return garment
+
+    def _shelf_fill(self, st, sets, blocks=None):
+        """-> garment(bi, p) of a call on a SHELVED cache, _stream_fill's twin: the U distinct garments of the call, in first-use order, go from
+        their own compact tensors in page-locked host memory into the FRONT of slots 0 .. U - 1 of the first timestep slots of sets[p], and
+        the zero V^T tail behind each, by ONE idmvton_kv_fill launch per block on the current stream (shelf_records: K rows beyond a
+        garment's own are not written, no kernel reads them).  Table and prefix tables are built and uploaded ONCE, here, with one
+        idmvton_host_device_ptr per part tensor; a block is a slice.  The cache -- and through it its parts, whatever the shelf does
+        meanwhile -- stays referenced by the engine until the last launch has completed."""
+        gc, k = st["gcache"], st["k"]
+        garments = list(dict.fromkeys(st["gindex"]))         # (a cache with sizes is always indexed)
+        S = st["B"]
+        built = [bi for bi in range(len(st["blocks"])) if blocks is None or bi in blocks]
+        steps = [(st["blocks"][bi][0] + j, j) for bi in built for j in range(st["blocks"][bi][1])]
+        first = {i: at for at, (i, _) in enumerate(steps)}   # step of the call -> its place in a set's part of the table
+        addr = {}
+
+        def address(t):
+            if t.data_ptr() not in addr:
+                addr[t.data_ptr()] = ops.stream_address(t)
+            return addr[t.data_ptr()]
+        parts = [gc.parts[g] for g in garments]
+        recs = [shelf_records(parts, gc.packed, fs["kv"], k, S, [st["gidx"][i] for i, _ in steps], [j for _, j in steps],
+                              list(range(len(garments))), address=address) for fs in sets]
+        per = recs[0][1]                                     # records per step, padded even: every slice starts 16-byte aligned
+        which = {(p, bi): at for at, (p, bi) in enumerate((p, bi) for p in range(len(sets)) for bi in built)}
+        table = ops.KvFillTable(torch.cat([r for r, _ in recs]), self.device, ops.ffi.KVS_WIDEN_E4M3 if gc.packed else ops.ffi.KVS_COPY,
+                                [((p * len(steps) + first[st["blocks"][bi][0]]) * per, st["blocks"][bi][1] * per) for p, bi in which])
+        self._release_streamed()
+        hold = [gc, torch.cuda.Event()]
+        self._streaming.append(hold)
+
+        def garment(bi, p):
+            self.stats["garment_stream_launches"] += 1
+            table.launch(self.dtype, which[(p, bi)])
+            hold[1].record()
         return garment
 
     def _packed_fill(self, st, sets, blocks=None):

@@ -307,6 +307,20 @@ int idmvton_kv_stream(const idmvton_kv_stream_args* a, const idmvton_kv_stream_d
 int idmvton_host_device_ptr(const void* host, void** dev);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * idmvton_kv_fill : idmvton_kv_stream with ZERO RUNS -- a compact garment into the front of a larger set slot and the zero V^T tail behind
+ * it, in one launch (idm-vton_amd/garment_cache.py, GarmentShelf).  The same argument struct, the same 40-byte descriptors, modes, prefix
+ * table, persistent grid and guarantees (1 <= workgroups <= 1024, capturable, no allocation, plain vector stores, [cols, ldd) of a
+ * destination row not written).  The one difference: a descriptor whose src is NULL is a zero run.  It writes what a source of all-zero
+ * bytes would give -- rows x cols elements of +0 (bits 0x0000) when widening, rows x cols zero bytes when copying -- and issues NO load:
+ * neither src nor exp of a zero run is dereferenced (exp is ignored and may be NULL; lds is ignored).  cols and ldd of a zero run are in the
+ * units of a data run of that mode, and it counts rows * (cols >> 4) items in the chunk list like any other run.
+ * Validated before the launch: data runs exactly as idmvton_kv_stream validates them; zero runs need dst non-null and 16-byte aligned,
+ * rows >= 1, cols >= 16, cols % 16 == 0, ldd >= cols and a multiple of 8 (widening) / 16 (copying); host_first equal to the recomputed
+ * prefix sums.  A table of zero runs only is valid.  Additive: no new struct, the ABI version stays 9.  No reference counterpart.
+ * ------------------------------------------------------------------------------------------------------------- */
+int idmvton_kv_fill(const idmvton_kv_stream_args* a, const idmvton_kv_stream_desc* host_desc, const int32_t* host_first, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * idmvton_attn_small : softmax(scale * q k^T [+ causal mask]) v for the one-off conditioning encoders -- the CLIP text towers
  * (transformers CLIPTextModel / CLIPTextModelWithProjection as called at src/tryon_pipeline.py:511-743: 77 tokens, causal) and
  * the CLIP-H vision tower (:460-482: 257 tokens, head_dim 80).  Any even head_dim <= 128, Lk <= 1024, fp32 arithmetic; one wave

@@ -18,6 +18,15 @@ page-locked host memory, pinned once; a 16-bit cache would pin 18.9 GB).  Engine
                   that brings each block's packed bytes from the pinned cache into a device staging cache with the copy engines
                   (copy_ on the side stream) and widens them with the device-resident unpack launch: the same bytes over the same link,
                   without a kernel that reads host memory.
+  --step fillrate idmvton_kv_fill against idmvton_kv_stream (the reference: what plain host caches use) on the SAME data-only table -- one
+                  steady block of ONE packed 768x1024 garment from pinned memory, 16 workgroups --, in one process, alternating, nine timed
+                  launches each after one discarded: median source GB/s of both and the run-to-run spread (min .. max); the two sets are
+                  compared bit for bit.  Run on its own (the driver above does not include it).
+  --step shelf    the garment shelf in a call: B = 2 persons at 768x1024, 30 steps, graph + overlap, each in a 384x512 packed garment, from
+                  a GarmentShelf ("shelf"), from the device-resident slotted cache the same garments give ("device"), and with the garments
+                  encoded at 768x1024 in today's GarmentPool(resident="host") ("host_full"): images/s of the three, interleaved, three
+                  repeats; the bytes a call loads over the host link and the zero-tail bytes a block writes, both summed from the descriptor
+                  tables of the launches of one call.  Run on its own.
 """
 import argparse
 import json
@@ -199,6 +208,126 @@ def call_step(args):
     return 0 if all(torch.equal(lat[a], lat["device"]) for a in arms) else 1
 
 
+def fillrate_step(args):
+    from idm_vton_amd import ffi, ops
+    from idm_vton_amd.garment_cache import PackedGarmentCache, fill_records
+    from idm_vton_amd.pipeline import TryonEngine
+    dt = torch.bfloat16
+    eng = TryonEngine(None, None, None, None, dt, DEV)
+    G, k = 1, eng.garment_steps
+    gen = torch.Generator(device=DEV).manual_seed(0)
+
+    def rand_bytes(*shape):
+        b = torch.randint(0, 256, shape, generator=gen, device=DEV, dtype=torch.uint8)
+        return torch.where((b & 0x7f) == 0x7f, torch.zeros_like(b), b)
+    kv = [(rand_bytes(k * G * N, C), rand_bytes(k * G, C, N)) for feats, N, C in LEVELS for _ in range(feats)]
+    exps = torch.randint(-7, 16, (G, len(kv), 2), generator=gen, device=DEV, dtype=torch.int32)
+    host = PackedGarmentCache(G=G, timesteps=list(range(k, 0, -1)), h=H // 8, w=W // 8, dtype=dt, attn_fp8=False, f8_exp=(0, 0, 0),
+                              weights_id="synthetic", kv=kv, exps=exps).to("cpu", pin_memory=True)
+    st = dict(gcache=host, gidx=list(range(k)), gindex=None, k=k, B=B, blocks=[(0, k)])
+    slots, shapes = eng._cache_set_shapes(st)
+    sets = {name: eng._alloc_set((), shapes, k, k, slots) for name in ("kv_stream", "kv_fill")}
+    addr = {}
+
+    def address(t):
+        if t.data_ptr() not in addr:
+            addr[t.data_ptr()] = ops.stream_address(t)
+        return addr[t.data_ptr()]
+    # the same records, two destinations (so that neither launch finds the other's lines in a cache) and two entry points
+    tables = {}
+    for name, cls in (("kv_stream", ops.KvStreamTable), ("kv_fill", ops.KvFillTable)):
+        rec = fill_records(host.kv, k, G, sets[name]["kv"], k, slots, host.exps, list(range(k)), list(range(k)), [0], [0], address=address)
+        tables[name] = cls(rec, DEV, ffi.KVS_WIDEN_E4M3)
+    assert torch.equal(tables["kv_stream"].host[:, [0, 2, 3, 4]], tables["kv_fill"].host[:, [0, 2, 3, 4]]) and (tables["kv_fill"].host[:, 0] != 0).all()
+    src_bytes = sum(a.numel() + b.numel() for a, b in host.kv)
+    for t in tables.values():                                 # one discarded launch each
+        t.launch(dt, 0, args.fill_workgroups)
+    torch.cuda.synchronize()
+    us = {name: [] for name in tables}
+    for _ in range(9):                                        # alternating
+        for name, t in tables.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize(); e0.record()
+            t.launch(dt, 0, args.fill_workgroups)
+            e1.record(); e1.synchronize()
+            us[name].append(e0.elapsed_time(e1) * 1e3)
+    same = all(torch.equal(a, c) and torch.equal(b, d) for (a, b), (c, d) in zip(sets["kv_stream"]["kv"], sets["kv_fill"]["kv"]))
+    gbps = {name: sorted(src_bytes / x / 1e3 for x in v) for name, v in us.items()}
+    res = {name: dict(median_GBps=round(v[len(v) // 2], 2), min_GBps=round(v[0], 2), max_GBps=round(v[-1], 2), us=[round(x, 1) for x in us[name]])
+           for name, v in gbps.items()}
+    for name, r in res.items():
+        print(f"{name:10s} median {r['median_GBps']:6.2f} GB/s (min {r['min_GBps']:.2f} .. max {r['max_GBps']:.2f}) over 9 launches", flush=True)
+    emit(args, dict(step="fillrate", shape=f"{W}x{H}, one packed garment, one block of {k} timesteps, bf16 set, data-only table of {tables['kv_fill'].n} runs",
+                    source_bytes=src_bytes, workgroups=args.fill_workgroups, bit_equal=same, **res))
+    return 0 if same else 1
+
+
+def shelf_step(args):
+    import bench
+    import torch.nn.functional as F
+    from idm_vton_amd import ops
+    from idm_vton_amd.garment_cache import GarmentPool, GarmentShelf
+    dt = torch.bfloat16
+    eng, _ = bench.build_engine(dt, DEV, 0, STEPS)
+    inp = bench.synth_inputs(B, H, W, STEPS, DEV, first_image_index=0)
+    kw = dict(num_inference_steps=STEPS, guidance_scale=2.0, scheduler="ddim", use_graph=True, overlap=True)
+    gh, gw = H // 2, W // 2                                   # 512 x 384 garments (height x width) for 1024 x 768 persons
+    small = F.interpolate(inp["cloth"], size=(gh, gw), mode="bilinear", align_corners=False).clamp(-1, 1)
+    noise_small = torch.randn(B, 4, gh // 8, gw // 8, generator=torch.Generator().manual_seed(5)).to(DEV)
+    enc = lambda cloth, noise, i: eng.encode_garment(cloth=cloth[i:i + 1], text_embeds_cloth=inp["text_embeds_cloth"][i:i + 1], noise_cloth=noise[i:i + 1],
+                                                     height=H, width=W, num_inference_steps=STEPS, scheduler="ddim", storage="e4m3")
+    keys = [f"sku{i}" for i in range(B)]
+    shelf = GarmentShelf(eng.empty_garment_cache(1, H, W, STEPS, scheduler="ddim", height=H, width=W), storage="e4m3")
+    for i, key in enumerate(keys):
+        shelf.add(key, enc(small, noise_small, i))
+    shelved, index = shelf.get(keys)
+    full = {key: enc(inp["cloth"], inp["noise"]["cloth"], i) for i, key in enumerate(keys)}
+    pool = GarmentPool(B, like=full[keys[0]], resident="host")
+    pool_index = pool.get(keys, encode=full.get)
+    del full
+    arms = {"shelf": (shelved, index), "device": (shelved.slotted(DEV), index), "host_full": (pool.cache, pool_index)}
+
+    def call(a, **more):
+        cache, idx = arms[a]
+        return eng(**kw, **more, **{**inp, "cloth": cache, "garment_index": idx, "text_embeds_cloth": None})
+    lat = {a: call(a, return_latents=True).clone() for a in arms}                             # warm-up: graph capture; and the latents
+    torch.cuda.synchronize()
+    # link and zero-tail bytes of ONE call, summed from the descriptor tables of its launches
+    traffic, launch = {}, ops.KvStreamTable.launch
+    for a in ("shelf", "host_full"):
+        log = []
+
+        def counted(self, dtype, which=0, workgroups=None, log=log):
+            f0, c = self.slices[which]
+            data = self.host[f0:f0 + c, 0] != 0
+            log.append((16 * int(self.items[f0:f0 + c][data].sum()), 32 * int(self.items[f0:f0 + c][~data].sum())))
+            return launch(self, dtype, which, workgroups)
+        ops.KvStreamTable.launch = counted
+        try:
+            call(a)
+        finally:
+            ops.KvStreamTable.launch = launch
+        torch.cuda.synchronize()
+        traffic[a] = dict(launches=len(log), link_bytes_per_call=sum(x for x, _ in log), zero_tail_bytes_per_block=[z for _, z in log])
+    rows = {a: [] for a in arms}
+    for r in range(3):                                        # arms interleaved
+        for a in arms:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.calls):
+                call(a)
+            torch.cuda.synchronize()
+            rows[a].append(B * args.calls / (time.perf_counter() - t0))
+            print(f"repeat {r} {a:9s} {rows[a][-1]:.4f} images/s", flush=True)
+    equal = bool(torch.equal(lat["shelf"], lat["device"]))
+    _, sched = eng._block_schedule(STEPS)
+    emit(args, dict(step="shelf", shape=f"{W}x{H} persons, {gw}x{gh} packed garments, {STEPS} steps, B={B}, bf16, graph + overlap",
+                    shelf_latents_equal_device_slotted=equal, images_per_s={a: [round(x, 4) for x in v] for a, v in rows.items()},
+                    traffic=traffic, link_ratio_shelf_to_host_full=round(traffic["shelf"]["link_bytes_per_call"] / traffic["host_full"]["link_bytes_per_call"], 4),
+                    block_timesteps=[c for _, c in sched], shelf_nbytes=shelf.nbytes, host_full_nbytes=pool.cache.nbytes))
+    return 0 if equal else 1
+
+
 def drive(args):
     import tempfile
     link = None
@@ -235,15 +364,16 @@ def emit(args, res):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--step", choices=["fill", "call"], default=None)
+    ap.add_argument("--step", choices=["fill", "call", "fillrate", "shelf"], default=None)
     ap.add_argument("--calls", type=int, default=2, help="timed calls per repeat")
     ap.add_argument("--workgroups", type=int, nargs="*", default=[], help="--step call: further host arms with these `workgroups` values")
     ap.add_argument("--staged", action="store_true", help="--step call: a further arm that moves the blocks with the copy engines (a diagnostic)")
     ap.add_argument("--json-out", default=None, help="also write the step's JSON result to this file (the driver reads the link rate from it)")
+    ap.add_argument("--fill-workgroups", type=int, default=16, help="--step fillrate: persistent workgroups of both launches")
     ap.add_argument("--link-gbps", type=float, default=SPEC_GBPS, help="the host-link rate --step fill measured (default: the spec rate)")
     a = ap.parse_args()
     if a.step is None:
         sys.exit(drive(a))
     torch.cuda.set_device(0)
     with torch.no_grad():
-        sys.exit(fill_step(a) if a.step == "fill" else call_step(a))
+        sys.exit({"fill": fill_step, "call": call_step, "fillrate": fillrate_step, "shelf": shelf_step}[a.step](a))
