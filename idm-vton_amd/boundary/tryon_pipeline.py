@@ -95,6 +95,7 @@ class StableDiffusionXLInpaintPipeline:
         self._clip = {}                                     # name -> (params_version, HipCLIPText | HipCLIPVision)
         self._guidance_scale = 7.5
         self.use_graph, self.overlap = True, True          # engine execution mode (hipGraph replay, two-stream loop)
+        self.host_transport = "kernel"                      # how a host-resident GarmentCache crosses the host link ("kernel" | "copy": TryonEngine.denoise)
 
     # ------------------------------------------------------------------------------------------ construction
     @classmethod
@@ -519,7 +520,8 @@ class StableDiffusionXLInpaintPipeline:
                 if callback is not None and i % (callback_steps or 1) == 0:
                     callback(i, tt, lat.to(_dt))                                                 # :1859-1863 (scheduler order 1)
                 return self._interrupt                                                            # :1766-1767: the remaining steps are skipped
-        lat = eng(image_dtype=prompt_embeds.dtype, return_latents=True, use_graph=self.use_graph, overlap=self.overlap, on_step=on_step, **call)
+        lat = eng(image_dtype=prompt_embeds.dtype, return_latents=True, use_graph=self.use_graph, overlap=self.overlap, on_step=on_step,
+                  host_transport=self.host_transport, **call)
         if output_type == "latent":
             return (lat.clone(),)
         out = eng.decode(lat)                                                                    # :1876 + postprocess

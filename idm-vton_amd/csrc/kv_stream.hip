@@ -155,6 +155,17 @@ __global__ __launch_bounds__(KVS_THREADS) void kv_fill_kernel(const idmvton_kv_s
     kvs_body<T, WIDEN, true>(desc, first, n);
 }
 
+// idmvton_kv_place: the same runs, zero runs included, when the sources are in HBM (the staging arena of pipeline.py's _staged_fill).  A short
+// HBM-bound pass wants what the persistent body above avoids: the whole machine for as short a time as possible.  So the grid is the flat chunk
+// list itself -- first[n] workgroups, workgroup q owns chunk q --: one descriptor search, one kvs_read (a zero run: registers cleared), one
+// kvs_write; no loop, no second register set, no idle workgroup.  Lane clamp, arithmetic and zero-run rule are kvs_read's and kvs_write's.
+template <typename T, bool WIDEN>
+__global__ __launch_bounds__(KVS_THREADS) void kv_place_kernel(const idmvton_kv_stream_desc* __restrict__ desc, const int32_t* __restrict__ first, int n) {
+    kvs_chunk c;
+    kvs_read<WIDEN, true>(c, desc, first, n, (int)blockIdx.x);         // (the host launches exactly first[n] workgroups)
+    kvs_write<T, WIDEN>(c);
+}
+
 extern "C" int idmvton_kv_stream(const idmvton_kv_stream_args* a, const idmvton_kv_stream_desc* host_desc, const int32_t* host_first, void* stream) {
     CHECK_ARG(a && host_desc && host_first && a->desc && a->first, IDMVTON_E_ARG, "kv_stream: null args / descriptor table / prefix table");
     CHECK_ARG(a->dtype == IDMVTON_F16 || a->dtype == IDMVTON_BF16, IDMVTON_E_DTYPE, "kv_stream: dtype %d (F16 or BF16)", a->dtype);
@@ -225,6 +236,43 @@ extern "C" int idmvton_kv_fill(const idmvton_kv_stream_args* a, const idmvton_kv
     else if (a->dtype == IDMVTON_BF16) hipLaunchKernelGGL((kv_fill_kernel<bf16_t, true>), grid, block, 0, (hipStream_t)stream, a->desc, a->first, a->n);
     else hipLaunchKernelGGL((kv_fill_kernel<f16_t, true>), grid, block, 0, (hipStream_t)stream, a->desc, a->first, a->n);
     CHECK_LAUNCH("kv_fill");
+    return IDMVTON_OK;
+}
+
+extern "C" int idmvton_kv_place(const idmvton_kv_stream_args* a, const idmvton_kv_stream_desc* host_desc, const int32_t* host_first, void* stream) {
+    CHECK_ARG(a && host_desc && host_first && a->desc && a->first, IDMVTON_E_ARG, "kv_place: null args / descriptor table / prefix table");
+    CHECK_ARG(a->dtype == IDMVTON_F16 || a->dtype == IDMVTON_BF16, IDMVTON_E_DTYPE, "kv_place: dtype %d (F16 or BF16)", a->dtype);
+    CHECK_ARG(a->mode == IDMVTON_KVS_WIDEN_E4M3 || a->mode == IDMVTON_KVS_COPY, IDMVTON_E_ARG, "kv_place: mode %d (IDMVTON_KVS_WIDEN_E4M3 or IDMVTON_KVS_COPY)", a->mode);
+    CHECK_ARG(a->n >= 1 && a->n <= IDMVTON_KVS_MAX_N, IDMVTON_E_ARG, "kv_place: n=%d outside [1, %d] descriptors", a->n, IDMVTON_KVS_MAX_N);
+    CHECK_ARG(a->workgroups == 0, IDMVTON_E_ARG, "kv_place: workgroups=%d must be 0 (the grid is the table's chunk count, one workgroup per chunk)", a->workgroups);
+    CHECK_ARG(((uintptr_t)a->desc & 15) == 0, IDMVTON_E_ALIGN, "kv_place: the device descriptor table is not 16-byte aligned");
+    CHECK_ARG(((uintptr_t)a->first & 3) == 0, IDMVTON_E_ALIGN, "kv_place: the device prefix table is not 4-byte aligned");
+    const bool widen = a->mode == IDMVTON_KVS_WIDEN_E4M3;
+    const int dmul = widen ? 8 : 16;                                   // ldd: elements when widening, bytes when copying
+    long chunks = 0;
+    for (int i = 0; i < a->n; ++i) {
+        const idmvton_kv_stream_desc* d = host_desc + i;
+        const bool zero = d->src == nullptr;                           // a zero run: exp and lds are not looked at
+        CHECK_ARG(d->dst && (zero || d->exp || !widen), IDMVTON_E_ARG, "kv_place: descriptor %d has a null pointer (dst%s)", i, zero ? " of a zero run" : ", or exp of a data run");
+        CHECK_ARG(((uintptr_t)d->src & 15) == 0 && ((uintptr_t)d->dst & 15) == 0 && (zero || !widen || ((uintptr_t)d->exp & 3) == 0), IDMVTON_E_ALIGN,
+                  "kv_place: descriptor %d: src / dst not 16-byte aligned (or exp not 4-byte aligned)", i);
+        CHECK_ARG(d->rows >= 1 && d->cols >= 16 && d->cols % 16 == 0, IDMVTON_E_SHAPE, "kv_place: descriptor %d: rows=%d cols=%d (rows >= 1, cols a multiple of 16)",
+                  i, d->rows, d->cols);
+        CHECK_ARG(zero || (d->lds >= d->cols && d->lds % 16 == 0), IDMVTON_E_SHAPE, "kv_place: descriptor %d: lds=%d (>= cols=%d, a multiple of 16)", i, d->lds, d->cols);
+        CHECK_ARG(d->ldd >= d->cols && d->ldd % dmul == 0, IDMVTON_E_SHAPE, "kv_place: descriptor %d: ldd=%d (>= cols=%d, a multiple of %d)", i, d->ldd, d->cols, dmul);
+        const long items = (long)d->rows * (d->cols >> 4);
+        CHECK_ARG(items < (1L << 31), IDMVTON_E_SHAPE, "kv_place: descriptor %d: rows=%d x cols=%d is 2^31 16-byte items or more", i, d->rows, d->cols);
+        CHECK_ARG(host_first[i] == chunks, IDMVTON_E_ARG, "kv_place: host_first[%d]=%d, the runs before descriptor %d have %ld chunks of %d 16-byte items",
+                  i, host_first[i], i, chunks, KVS_CHUNK);
+        chunks += (items + KVS_CHUNK - 1) / KVS_CHUNK;
+        CHECK_ARG(chunks < (1L << 31), IDMVTON_E_SHAPE, "kv_place: 2^31 chunks or more up to descriptor %d", i);
+    }
+    CHECK_ARG(host_first[a->n] == chunks, IDMVTON_E_ARG, "kv_place: host_first[%d]=%d, the table has %ld chunks of %d 16-byte items", a->n, host_first[a->n], chunks, KVS_CHUNK);
+    const dim3 grid((unsigned)chunks), block(KVS_THREADS);             // one workgroup per chunk: at least one (n >= 1, every run has a chunk)
+    if (!widen) hipLaunchKernelGGL((kv_place_kernel<bf16_t, false>), grid, block, 0, (hipStream_t)stream, a->desc, a->first, a->n);
+    else if (a->dtype == IDMVTON_BF16) hipLaunchKernelGGL((kv_place_kernel<bf16_t, true>), grid, block, 0, (hipStream_t)stream, a->desc, a->first, a->n);
+    else hipLaunchKernelGGL((kv_place_kernel<f16_t, true>), grid, block, 0, (hipStream_t)stream, a->desc, a->first, a->n);
+    CHECK_LAUNCH("kv_place");
     return IDMVTON_OK;
 }
 

@@ -132,7 +132,7 @@ SYMBOLS = ["idmvton_last_error", "idmvton_abi_version", "idmvton_sizeof", "idmvt
            "idmvton_rccl_comm_destroy", "idmvton_attn_f8", "idmvton_quant_f8", "idmvton_split", "idmvton_attn_fwd_shared",
            "idmvton_attn_f8_shared", "idmvton_attn_fwd_indexed", "idmvton_attn_f8_indexed",
            "idmvton_attn_fwd_ragged", "idmvton_attn_f8_ragged", "idmvton_kv_unpack", "idmvton_kv_stream",
-           "idmvton_host_device_ptr", "idmvton_kv_fill"]
+           "idmvton_host_device_ptr", "idmvton_kv_fill", "idmvton_kv_place"]
 
 _lib = None
 
@@ -184,6 +184,8 @@ def lib():
     L.idmvton_kv_stream.restype = C.c_int
     L.idmvton_kv_fill.argtypes = [vp, vp, vp, vp]                             # the same signature; a NULL src is a zero run
     L.idmvton_kv_fill.restype = C.c_int
+    L.idmvton_kv_place.argtypes = [vp, vp, vp, vp]                            # the same signature; workgroups must be 0: one workgroup per chunk
+    L.idmvton_kv_place.restype = C.c_int
     L.idmvton_host_device_ptr.argtypes = [vp, C.POINTER(vp)]                  # (const void* host, void** dev)
     L.idmvton_host_device_ptr.restype = C.c_int
     L.idmvton_probe_mfma.argtypes = [C.c_int, vp, vp, vp, vp]
@@ -266,6 +268,15 @@ def call_kv_fill(args, host_desc, host_first, stream):
     rc = L.idmvton_kv_fill(C.byref(args), p(host_desc), p(host_first), C.c_void_p(stream))
     if rc != 0:
         raise RuntimeError(f"idmvton_kv_fill failed ({rc}): {L.idmvton_last_error().decode()}")
+
+
+def call_kv_place(args, host_desc, host_first, stream):
+    """Invoke idmvton_kv_place: call_kv_fill's arguments; args.workgroups must be 0 (the grid is the table's chunk count)."""
+    L = lib()
+    p = lambda x: x if isinstance(x, int) else C.cast(x, vp)
+    rc = L.idmvton_kv_place(C.byref(args), p(host_desc), p(host_first), C.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError(f"idmvton_kv_place failed ({rc}): {L.idmvton_last_error().decode()}")
 
 
 def host_device_ptr(host):

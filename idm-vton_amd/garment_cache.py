@@ -37,7 +37,9 @@ and opt-in, for the garment segment alone; `dtype` stays the engine's 16-bit dty
 Host-resident: a cache whose tensors are CPU tensors (`to("cpu", pin_memory=True)`, GarmentPool(resident="host")) has `host_resident` true.
 The engine takes one that is PAGE-LOCKED as `cloth=`: every block of timesteps then goes from host memory straight into the 16-bit sets by
 one idmvton_kv_stream launch (pipeline.py, _stream_fill), so a catalogue is bounded by host RAM, not HBM.  Queued calls read such a cache
-by raw address, with no stream order to protect them: a `put` into it waits for the device first and copies blocking.
+by raw address, with no stream order to protect them: a `put` into it waits for the device first and copies blocking.  With
+host_transport="copy" the blocks cross the link by the copy engines into a staging arena instead and one idmvton_kv_place launch places them
+(staged_plan below: the arena, the copy list and the place tables, for plain and shelved caches alike).
 
 Shelf: a GarmentShelf is a host catalogue of garments of MANY sizes, each kept COMPACT -- a G = 1 cache of its own (N'_f rows, ld'_f V^T
 positions) in page-locked memory, 16-bit or e4m3-packed -- so host RAM and the bytes a call moves over the host link follow the garments' own
@@ -659,6 +661,83 @@ def shelf_records(parts, packed, dst_kv, k, S, entries, tslots, gslots, address=
     rec[:, :, 0] += torch.tensor(entries, dtype=I64).view(-1, 1) * sinc.view(1, -1)
     rec[:, :, 1] += torch.tensor(tslots, dtype=I64).view(-1, 1) * dinc.view(1, -1)
     return rec.reshape(-1, 5).contiguous(), T.shape[0]
+
+
+class _StagedPart:
+    """What shelf_records reads of a part, for the part's k-timestep image in a staging arena."""
+
+    def __init__(self, kv, k, exps):
+        self.kv, self.timesteps, self.exps = kv, range(k), exps
+
+
+def staged_plan(gc, gindex, k, S, dst_kvs, device, arena=None, exps=None):
+    """The copy-engine transport of a host-resident cache (pipeline.py, _staged_fill), as data: no kernel and no GPU call in here, so it runs on
+    CPU tensors.  A block of c <= k timesteps of the call's U distinct garments (first-use order; all G without gindex) is first COPIED into a
+    staging arena -- a k-timestep, U-garment list in the source's own storage (uint8 of a packed cache, else its 16-bit dtype); for a
+    ShelvedGarmentCache each part's compact k-timestep, one-garment list, back to back -- and then PLACED by one idmvton_kv_place launch into
+    slots 0 .. U - 1 of the first c timestep slots of a 16-bit list of k timesteps of S slots.
+    The arena is one flat uint8 tensor on `device`: k * (the used garments' source bytes per timestep), every tensor carved at a multiple of
+    16 bytes.  Pass the `arena` / `exps` of an earlier plan to use them again (an arena that is too small is replaced).  dst_kvs: the
+    destination lists, one per set.  ->
+      arena, nbytes   the flat tensor and the bytes of it this plan uses
+      exps            int32 [U][F][2] on `device` (None for a 16-bit source), exps_copies [(dst, src)] that fill it from the cache's exponents
+      copies(idx)     [(dst, src)] tensor views that bring cache entries idx (a block, by value) into arena timestep slots 0 .. len(idx) - 1:
+                      _fill_set's gather -- one pair per tensor when the entries are consecutive and there is no index (shelved: per part
+                      tensor), else one per timestep and run of consecutive garments
+      rec, per        the place records of every set (fill_records / shelf_records pointed at the arena) and the records per timestep: set p's
+                      block of c timesteps is records [p * k * per, p * k * per + c * per) -- a prefix, as the arena's addresses never change."""
+    shelved = isinstance(gc, ShelvedGarmentCache)
+    n = len(gc.timesteps)
+    garments = list(range(gc.G)) if gindex is None else list(dict.fromkeys(gindex))
+    U = len(garments)
+    sources = [(gc.parts[g].kv, 1, 1) for g in garments] if shelved else [(gc.kv, gc.G, U)]   # (list, garments it holds, garments the arena takes)
+    shapes = [[(((a[0] // (n * G)) * k * u,) + a[1:], ((b[0] // (n * G)) * k * u,) + b[1:], d) for a, b, d in kv_shapes(kv)] for kv, G, u in sources]
+    size = lambda sh, d: torch.Size(sh).numel() * torch.empty((), dtype=d).element_size()
+    nbytes = sum(size(a, d) + size(b, d) for lst in shapes for a, b, d in lst)
+    if arena is None or arena.numel() < nbytes:
+        arena = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    lists, at = [], 0
+    for lst in shapes:
+        kv = []
+        for a, b, d in lst:
+            pair = []
+            for sh in (a, b):
+                pair.append(arena[at:at + size(sh, d)].view(d).view(sh))
+                at += size(sh, d)
+            kv.append(tuple(pair))
+        lists.append(kv)
+    pairs = lambda dst, src: [(d, s) for dp, sp in zip(dst, src) for d, s in zip(dp, sp)]
+    exps_copies = []
+    if gc.packed:
+        F = len(lists[0])
+        if exps is None:
+            exps = torch.empty((U, F, 2), dtype=torch.int32, device=device)
+        if shelved:
+            exps_copies = [(exps[u:u + 1], gc.parts[g].exps) for u, g in enumerate(garments)]
+        else:
+            exps_copies = [(exps[d0:d0 + cc], gc.exps[g0:g0 + cc]) for d0, g0, cc in index_runs(garments)]
+    else:
+        exps = None
+    if shelved:
+        parts = [_StagedPart(kv, k, exps[u:u + 1] if gc.packed else None) for u, kv in enumerate(lists)]
+        recs = [shelf_records(parts, gc.packed, dst, k, S, list(range(k)), list(range(k)), list(range(U))) for dst in dst_kvs]
+        rec, per = torch.cat([r for r, _ in recs]), recs[0][1]
+    else:
+        rec = torch.cat([fill_records(lists[0], k, U, dst, k, S, exps, list(range(k)), list(range(k)), list(range(U)), list(range(U))) for dst in dst_kvs])
+        per = U * len(lists[0]) * 2
+
+    def copies(idx):
+        idx = list(idx)
+        c = len(idx)
+        steps = [(0, idx[0], c)] if idx == list(range(idx[0], idx[0] + c)) else [(j, i, 1) for j, i in enumerate(idx)]
+        if shelved:
+            return [p for kv, g in zip(lists, garments) for j0, i0, cc in steps
+                    for p in pairs(timestep_run(kv, k, 1, j0, cc), timestep_run(gc.parts[g].kv, n, 1, i0, cc))]
+        if gindex is None:
+            return [p for j0, i0, cc in steps for p in pairs(timestep_run(lists[0], k, U, j0, cc), timestep_run(gc.kv, n, gc.G, i0, cc))]
+        return [p for j, i in enumerate(idx) for d0, g0, cc in index_runs(garments)
+                for p in pairs(slot_run(lists[0], k, U, j, d0, cc), slot_run(gc.kv, n, gc.G, i, g0, cc))]
+    return dict(arena=arena, nbytes=nbytes, exps=exps, exps_copies=exps_copies, copies=copies, rec=rec.contiguous(), per=per, lists=lists)
 
 
 class ShelvedGarmentCache(GarmentCache):

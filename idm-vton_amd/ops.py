@@ -461,6 +461,15 @@ class KvFillTable(KvStreamTable):
         return self.link_bytes(f0, c) + (32.0 if self.mode == ffi.KVS_WIDEN_E4M3 else 16.0) * float(self.items[f0:f0 + c].sum())
 
 
+class KvPlaceTable(KvFillTable):
+    """KvFillTable launched through idmvton_kv_place: the same records, zero runs, items and prefix tables, for sources that are already in
+    HBM (a staging arena).  The grid is the slice's chunk count -- one workgroup per chunk --, so `workgroups` is always 0."""
+    ENTRY = "kv_place"
+
+    def launch(self, dtype, which=0, workgroups=None):
+        return super().launch(dtype, which, 0)
+
+
 def kv_pad_even(rec):
     """Descriptor records int64 [n][5] -> the same with the record of fewest items repeated at the end when n is odd: slices of a table start
     at even record indices (16-byte aligned device addresses), and writing identical bytes twice is what clamped lanes already do."""
@@ -498,34 +507,49 @@ def kv_stream(descs, dtype, mode=ffi.KVS_WIDEN_E4M3, workgroups=None, device=Non
     return descs
 
 
+def _kv_fill_table(cls, descs, dtype, mode, device):
+    """(src | None, dst, exp | None) views -> a table of class `cls` (KvFillTable / KvPlaceTable): a run whose src is None is a zero run."""
+    widen = mode == ffi.KVS_WIDEN_E4M3
+    rec = []
+    for src, dst, exp in descs:
+        ok = dst.dim() == 2 and dst.stride(1) == 1 and dst.is_cuda and (not widen or dst.dtype == dtype)
+        if src is not None:
+            ok = ok and src.dim() == 2 and src.shape == dst.shape and src.stride(1) == 1
+            if widen:
+                ok = ok and src.dtype == torch.uint8 and exp is not None and exp.dtype == torch.int32 and exp.numel() == 1
+            else:
+                ok = ok and src.dtype == dst.dtype
+        if not ok:
+            raise ValueError("%s: a run is (uint8 [rows][cols], %s [rows][cols], one int32) when widening, (x [rows][cols], x [rows][cols], None) "
+                             "when copying, (None, dst [rows][cols], None) for a zero run; rows contiguous, the destination on the device" % (cls.ENTRY, dtype))
+        rows, cols = dst.shape
+        sz = 1 if widen else dst.element_size()          # copy mode: byte units
+        if src is None:
+            rec.append((0, _ptr(dst), 0, rows | ((cols * sz) << 32), (cols * sz) | ((dst.stride(0) * sz) << 32)))
+        else:
+            rec.append((stream_address(src), _ptr(dst), stream_address(exp) if widen else 0, rows | ((cols * sz) << 32),
+                        (src.stride(0) * sz) | ((dst.stride(0) * sz) << 32)))
+    device = descs[0][1].device if device is None else device
+    return cls(torch.tensor(rec, dtype=torch.int64).reshape(-1, 5), device, mode)
+
+
 def kv_fill(descs, dtype, mode=ffi.KVS_WIDEN_E4M3, workgroups=None, device=None):
     """idmvton_kv_fill on every run of `descs`, in one launch: ops.kv_stream's arguments, and a run whose src is None is a ZERO RUN -- (None,
     dst, None) writes +0 (widening) / zero bytes (copying) over dst's [rows][cols] and loads nothing.  descs: a KvFillTable (its slice 0) or
     a list of (src | None, dst, exp | None) views.  -> the table."""
     if not isinstance(descs, KvStreamTable):
-        widen = mode == ffi.KVS_WIDEN_E4M3
-        rec = []
-        for src, dst, exp in descs:
-            ok = dst.dim() == 2 and dst.stride(1) == 1 and dst.is_cuda and (not widen or dst.dtype == dtype)
-            if src is not None:
-                ok = ok and src.dim() == 2 and src.shape == dst.shape and src.stride(1) == 1
-                if widen:
-                    ok = ok and src.dtype == torch.uint8 and exp is not None and exp.dtype == torch.int32 and exp.numel() == 1
-                else:
-                    ok = ok and src.dtype == dst.dtype
-            if not ok:
-                raise ValueError("kv_fill: a run is (uint8 [rows][cols], %s [rows][cols], one int32) when widening, (x [rows][cols], x [rows][cols], None) "
-                                 "when copying, (None, dst [rows][cols], None) for a zero run; rows contiguous, the destination on the device" % dtype)
-            rows, cols = dst.shape
-            sz = 1 if widen else dst.element_size()          # copy mode: byte units
-            if src is None:
-                rec.append((0, _ptr(dst), 0, rows | ((cols * sz) << 32), (cols * sz) | ((dst.stride(0) * sz) << 32)))
-            else:
-                rec.append((stream_address(src), _ptr(dst), stream_address(exp) if widen else 0, rows | ((cols * sz) << 32),
-                            (src.stride(0) * sz) | ((dst.stride(0) * sz) << 32)))
-        device = descs[0][1].device if device is None else device
-        descs = KvFillTable(torch.tensor(rec, dtype=torch.int64).reshape(-1, 5), device, mode)
+        descs = _kv_fill_table(KvFillTable, descs, dtype, mode, device)
     descs.launch(dtype, 0, workgroups)
+    return descs
+
+
+def kv_place(descs, dtype, mode=ffi.KVS_WIDEN_E4M3, device=None):
+    """idmvton_kv_place on every run of `descs`, in one launch of one workgroup per chunk: ops.kv_fill's arguments without `workgroups`, zero
+    runs included.  descs: a KvPlaceTable (its slice 0) or a list of (src | None, dst, exp | None) views; src and exp may each be a device
+    tensor -- what the entry point is built for -- or a page-locked host tensor.  -> the table."""
+    if not isinstance(descs, KvStreamTable):
+        descs = _kv_fill_table(KvPlaceTable, descs, dtype, mode, device)
+    descs.launch(dtype, 0)
     return descs
 
 

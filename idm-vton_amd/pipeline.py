@@ -42,6 +42,9 @@ the first crosses the host link behind the TryonNet steps of the block before it
 A SHELVED cache (ShelvedGarmentCache, GarmentShelf.get: compact garments of many sizes in page-locked memory) goes the same way again:
 `_shelf_fill` puts each garment into the front of a set slot and writes the zero V^T tail behind it with ONE idmvton_kv_fill launch per block;
 key-count table, slot table, set shapes and graph key are those of a device-resident slotted cache of the same slot size.
+Both host-resident forms have a second TRANSPORT, host_transport="copy" (opt-in per call; "kernel" is the above): `_staged_fill` brings a block's
+source bytes into a block-sized staging arena in HBM with copy_(non_blocking=True) -- the copy engines -- and ONE idmvton_kv_place launch puts
+them into set p, so no kernel reads host memory beside TryonNet.  Same sets, same bits, same graph states.
 With garment_index the two cache rows read through the table: eager on the cache's own views (nb = G, table = garment_index), graph on
 P-slot sets into which _fill_set gathers the U distinct garments of the call (table = person -> set slot, a persistent buffer of the state).
 
@@ -52,7 +55,7 @@ import torch
 
 from . import ops
 from .garment_cache import (GarmentCache, PackedGarmentCache, ShelvedGarmentCache, alloc_kv, fill_records, index_runs, kv_shapes, shelf_records,
-                            slot_run, timestep_run)
+                            slot_run, staged_plan, timestep_run)
 from .scheduler import StepScheduler
 
 
@@ -115,8 +118,11 @@ class TryonEngine:
         # garment_batches: GarmentNet batches launched or replayed by this engine (a call on a GarmentCache adds none); garment_set_copies: blocks
         # of cached K / V^T copied into a persistent set by the graph forms (on a packed cache: widened into one, by every form)
         # garment_stream_launches: blocks moved from a host-resident cache into a set (one idmvton_kv_stream / idmvton_kv_fill launch each)
-        self.stats = dict(garment_batches=0, garment_set_copies=0, garment_stream_launches=0)
+        # garment_stage_copies / garment_stage_launches: host_transport="copy" -- tensor copies from a host-resident cache into the staging
+        # arena (the copy engines), and blocks placed from the arena into a set (one idmvton_kv_place launch each)
+        self.stats = dict(garment_batches=0, garment_set_copies=0, garment_stream_launches=0, garment_stage_copies=0, garment_stage_launches=0)
         self._streaming = []                                 # [cache, event of its last queued fill]: host memory a queued launch still reads
+        self._arenas = {}                                    # _staged_fill's staging arenas: one per call shape, reused across calls
         self._weights_id = None
 
     # -------------------------------------------------------------------------------------------- shared by prepare / encode_garment
@@ -601,6 +607,56 @@ class TryonEngine:
             hold[1].record()
         return garment
 
+    def _staged_fill(self, st, sets, blocks=None):
+        """-> garment(bi, p) of a call on a host-resident cache -- plain or shelved, packed or 16-bit -- with host_transport="copy", the twin of
+        _stream_fill / _shelf_fill: block bi's source bytes go from page-locked host memory into a block-sized STAGING ARENA in HBM by
+        copy_(non_blocking=True) -- the copy engines, no kernel reads the host link -- and ONE idmvton_kv_place launch then puts them into the
+        first timestep slots of sets[p]: widening or copying, the V^T row stride changed, the zero V^T tails written (garment_cache.staged_plan
+        holds the gather and the tables; they are fill_records / shelf_records pointed at the arena).  Copies and launch go to the current
+        stream, so block b + 1's copies follow block b's place launch and ONE arena serves both sets.  The arena belongs to the engine, one
+        per call shape (the sets' key, the source's storage, the number U of distinct garments), k x the used garments' source bytes per
+        timestep -- never the size of the cache; a shelved call with larger garments replaces it.  A packed source's exponents go to a small
+        device tensor once per call, here, ahead of the first launch in stream order.  The arena's addresses never change, so the table
+        covers k timesteps per set and a block of c is a prefix slice (`blocks` is not needed).  The cache stays referenced until the event
+        behind the last block has passed, as in _stream_fill."""
+        gc, k = st["gcache"], st["k"]
+        S = gc.G if st["gindex"] is None else st["B"]
+        U = gc.G if st["gindex"] is None else len(set(st["gindex"]))
+        key = self._set_key(st) + (torch.uint8 if gc.packed else gc.dtype, U)
+        plan = staged_plan(gc, st["gindex"], k, S, [fs["kv"] for fs in sets], self.device, *self._arenas.get(key, (None, None)))
+        self._arenas[key] = (plan["arena"], plan["exps"])
+        per = plan["per"]
+        which = {(p, c): at for at, (p, c) in enumerate((p, c) for p in range(len(sets)) for c in sorted({c for _, c in st["blocks"]}))}
+        table = ops.KvPlaceTable(plan["rec"], self.device, ops.ffi.KVS_WIDEN_E4M3 if gc.packed else ops.ffi.KVS_COPY,
+                                 [(p * k * per, c * per) for p, c in which])
+        copies = [plan["copies"](st["gidx"][s0:s0 + c]) for s0, c in st["blocks"]]
+        self._release_streamed()
+        hold = [gc, torch.cuda.Event()]
+        self._streaming.append(hold)
+        for dst, src in plan["exps_copies"]:
+            dst.copy_(src, non_blocking=True)
+
+        def garment(bi, p):
+            for dst, src in copies[bi]:
+                dst.copy_(src, non_blocking=True)
+            self.stats["garment_stage_copies"] += len(copies[bi])
+            self.stats["garment_stage_launches"] += 1
+            table.launch(self.dtype, which[(p, st["blocks"][bi][1])])
+            hold[1].record()                                 # behind the call's last copy so far: until it has passed, `hold` keeps the cache alive
+        return garment
+
+    HOST_TRANSPORTS = ("kernel", "copy")
+
+    @classmethod
+    def _check_host_transport(cls, host_transport):
+        if host_transport not in cls.HOST_TRANSPORTS:
+            raise ValueError(f"host_transport={host_transport!r}: \"kernel\" (a kernel reads the page-locked cache: idmvton_kv_stream / idmvton_kv_fill) "
+                             "or \"copy\" (the copy engines fill a staging arena, idmvton_kv_place places it)")
+
+    def _host_fill(self, st, sets, blocks=None):
+        """-> garment(bi, p) of a call on a host-resident cache, by the transport the call asked for (denoise: st["host_transport"])."""
+        return (self._staged_fill if st.get("host_transport") == "copy" else self._stream_fill)(st, sets, blocks)
+
     def _packed_fill(self, st, sets, blocks=None):
         """-> garment(bi, p) of a call on a PACKED cache: block bi's cache entries widened into the first timestep slots of sets[p] by ONE
         idmvton_kv_unpack launch on the current stream.  The gather is _fill_set's -- entries by value, consecutive or not; with
@@ -648,7 +704,7 @@ class TryonEngine:
             # e4m3 bytes, or host memory: TryonNet reads 16-bit sets on the device, as the graph forms do (one, or two to overlap)
             slots, shapes = self._cache_set_shapes(st)
             sets = [self._alloc_set((), shapes, len(st["gcache"].timesteps), st["k"], slots) for _ in range(2 if overlap else 1)]
-            garment = (self._stream_fill if st["gcache"].host_resident else self._packed_fill)(st, sets)
+            garment = (self._host_fill if st["gcache"].host_resident else self._packed_fill)(st, sets)
             st = dict(st, gix=self._slot_table(st))          # with garment_index: person -> set slot (the same tensors otherwise)
             kv = lambda i, j, p: sets[p]["step"][j]
         else:                                                # nothing to launch, so nothing to overlap: TryonNet reads the cache's own views
@@ -701,7 +757,7 @@ class TryonEngine:
                 slots, shapes = self._cache_set_shapes(st)   # (with an index: one slot per person, whatever the pool holds)
                 G["sets"] = [self._alloc_set((), shapes, len(gc.timesteps), st["k"], slots) for _ in range(2)]
                 if gc.host_resident:                         # (a table of block 0 alone: complete before the synchronize below)
-                    self._stream_fill(st, G["sets"][:1], blocks=(0,))(0, 0)
+                    self._host_fill(st, G["sets"][:1], blocks=(0,))(0, 0)
                 elif gc.packed:
                     self._packed_fill(st, G["sets"][:1], blocks=(0,))(0, 0)
                 else:
@@ -749,7 +805,7 @@ class TryonEngine:
                 self.stats["garment_batches"] += 1
                 graphs[("garm", p, blocks[bi][1])].replay()
         elif st["gcache"].host_resident:                     # in the same place: one launch that moves the block from host memory into set p
-            garment = self._stream_fill(st, G["sets"])
+            garment = self._host_fill(st, G["sets"])
         elif st["gcache"].packed:                            # in the same place: one launch that widens the block's bytes into set p
             garment = self._packed_fill(st, G["sets"])
         else:                                                # in the GarmentNet graph's place in the stream / event order: a copy out of the cache
@@ -765,14 +821,20 @@ class TryonEngine:
         return garment, step, G["latents"], (G["side"], G["ready"], G["free"]) if overlap else None
 
     @torch.no_grad()
-    def denoise(self, st, use_graph=False, trace=None, overlap=False, on_step=None):
+    def denoise(self, st, use_graph=False, trace=None, overlap=False, on_step=None, host_transport="kernel"):
         """The loop.  Four execution forms with bit-identical results: {serial, two-stream overlap} x {eager, hipGraph replay}, each on a live
         GarmentNet or on a GarmentCache.  on_step(i, t, latents) runs after step i on the live latents (it may rewrite them in place); a true
         return value ends the loop (the reference's per-step callbacks and `interrupt`, tryon_pipeline.py:1766-1767,1840-1863: host code
         between two steps, which only the un-captured serial form can run, so it selects that form).  trace["step_latents"] receives a copy
-        of the latents after every step.  Graph forms return their persistent latents buffer, eager forms st["latents"]."""
+        of the latents after every step.  Graph forms return their persistent latents buffer, eager forms st["latents"].
+        host_transport: how a HOST-RESIDENT cache crosses the host link -- "kernel" (_stream_fill / _shelf_fill: a kernel reads page-locked
+        memory) or "copy" (_staged_fill: the copy engines into a staging arena, one idmvton_kv_place launch per block); the same bits in the
+        sets, the same graph states.  Any other value is a ValueError before anything is launched; on a device-resident cache or a live call
+        the keyword has no effect.  A service sets it once."""
+        self._check_host_transport(host_transport)
         if on_step is not None:
             use_graph = overlap = False
+        st = dict(st, host_transport=host_transport)         # (read by _host_fill alone: the same tensors, no key of a state or a set)
         live = st["gcache"] is None                          # the one place a call chooses where its garment K / V^T come from
         garment, step, latents, sync = (self._graph_form if use_graph else self._eager_form)(st, live, overlap)
         blocks = st["blocks"]
@@ -800,16 +862,17 @@ class TryonEngine:
         return (img / 2 + 0.5).clamp(0, 1)                                                 # postprocess
 
     @torch.no_grad()
-    def __call__(self, *, return_latents=False, use_graph=False, overlap=False, timing=None, on_step=None, **kw):
+    def __call__(self, *, return_latents=False, use_graph=False, overlap=False, timing=None, on_step=None, host_transport="kernel", **kw):
         """timing: a list that receives one (start, prepared, denoised, decoded) tuple of HIP events recorded on the current stream
-        (bench.py: the loop's share of a timed call without a second, instrumented run)."""
+        (bench.py: the loop's share of a timed call without a second, instrumented run).  host_transport: see denoise."""
+        self._check_host_transport(host_transport)           # before prepare launches anything
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if timing is not None else None
         if ev:
             ev[0].record()
         st = self.prepare(**kw)
         if ev:
             ev[1].record()
-        lat = self.denoise(st, use_graph=use_graph, overlap=overlap, on_step=on_step)
+        lat = self.denoise(st, use_graph=use_graph, overlap=overlap, on_step=on_step, host_transport=host_transport)
         if ev:
             ev[2].record()
         out = lat if return_latents else self.decode(lat)

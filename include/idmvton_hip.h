@@ -321,6 +321,19 @@ int idmvton_host_device_ptr(const void* host, void** dev);
 int idmvton_kv_fill(const idmvton_kv_stream_args* a, const idmvton_kv_stream_desc* host_desc, const int32_t* host_first, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * idmvton_kv_place : idmvton_kv_fill's runs -- data runs and zero runs -- for sources that are already in HBM: the second half of the
+ * copy-engine transport of a host-resident garment cache (idm-vton_amd/pipeline.py, _staged_fill: the copy engines bring a block's bytes
+ * into a staging arena, this launch widens or copies them into the 16-bit set, changes the V^T row stride and writes the zero V^T tails).
+ * The same argument struct, 40-byte descriptors, modes, prefix table, zero-run rule and arithmetic; src / exp may still be device memory or
+ * the device-visible address of page-locked host memory.  The one difference is the grid: ONE workgroup per chunk of the flat chunk list,
+ * first[n] workgroups of 256 threads, each finding its descriptor once -- no persistent loop.  a->workgroups must therefore be 0
+ * (IDMVTON_E_ARG otherwise); a table of 2^31 chunks or more is refused.  Every other field is validated as idmvton_kv_fill validates it.
+ * Capturable, no allocation, plain vector stores, [cols, ldd) of a destination row not written.  Additive: no new struct, the ABI version
+ * stays 9.  No reference counterpart.
+ * ------------------------------------------------------------------------------------------------------------- */
+int idmvton_kv_place(const idmvton_kv_stream_args* a, const idmvton_kv_stream_desc* host_desc, const int32_t* host_first, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * idmvton_attn_small : softmax(scale * q k^T [+ causal mask]) v for the one-off conditioning encoders -- the CLIP text towers
  * (transformers CLIPTextModel / CLIPTextModelWithProjection as called at src/tryon_pipeline.py:511-743: 77 tokens, causal) and
  * the CLIP-H vision tower (:460-482: 257 tokens, head_dim 80).  Any even head_dim <= 128, Lk <= 1024, fp32 arithmetic; one wave

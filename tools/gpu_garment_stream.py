@@ -14,18 +14,20 @@ page-locked host memory, pinned once; a 16-bit cache would pin 18.9 GB).  Engine
                   events around every block's fill and every block's TryonNet steps.  The host arm is expected within (block 0's bytes /
                   --link-gbps) per call plus the device arm's own spread; if it is not, the per-block times say whether a fill outran the
                   TryonNet block it hides behind, or TryonNet itself ran slower next to the fills.  --workgroups N ...: further host arms
-                  with those `workgroups` values (the fill's rate against what it costs TryonNet).  --staged: a further arm, "staged",
-                  that brings each block's packed bytes from the pinned cache into a device staging cache with the copy engines
-                  (copy_ on the side stream) and widens them with the device-resident unpack launch: the same bytes over the same link,
-                  without a kernel that reads host memory.
+                  with those `workgroups` values (the fill's rate against what it costs TryonNet).  The arm "copy" is the same host cache
+                  with host_transport="copy": each block's packed bytes go into the engine's staging arena with the copy engines and one
+                  idmvton_kv_place launch places them -- the same bytes over the same link, without a kernel that reads host memory.  It is
+                  held to one condition: its ms per call below the host arm's by more than the device arm's own spread.
   --step fillrate idmvton_kv_fill against idmvton_kv_stream (the reference: what plain host caches use) on the SAME data-only table -- one
                   steady block of ONE packed 768x1024 garment from pinned memory, 16 workgroups --, in one process, alternating, nine timed
                   launches each after one discarded: median source GB/s of both and the run-to-run spread (min .. max); the two sets are
-                  compared bit for bit.  Run on its own (the driver above does not include it).
+                  compared bit for bit.  Then, the same way, idmvton_kv_place against idmvton_kv_unpack (the reference: what device-resident
+                  packed caches use) on that table with the SAME bytes in device memory: medians, spread, bit equality, and whether the
+                  new launch's median lies within +3 % of the old one's or below it.  Run on its own (the driver above does not include it).
   --step shelf    the garment shelf in a call: B = 2 persons at 768x1024, 30 steps, graph + overlap, each in a 384x512 packed garment, from
                   a GarmentShelf ("shelf"), from the device-resident slotted cache the same garments give ("device"), and with the garments
-                  encoded at 768x1024 in today's GarmentPool(resident="host") ("host_full"): images/s of the three, interleaved, three
-                  repeats; the bytes a call loads over the host link and the zero-tail bytes a block writes, both summed from the descriptor
+                  encoded at 768x1024 in today's GarmentPool(resident="host") ("host_full"), and from the shelf again with
+                  host_transport="copy" ("shelf_copy"): images/s of the four, interleaved, three repeats; the bytes a call loads over the host link and the zero-tail bytes a block writes, both summed from the descriptor
                   tables of the launches of one call.  Run on its own.
 """
 import argparse
@@ -120,36 +122,16 @@ def call_step(args):
     t0 = time.perf_counter()
     host = device.to("cpu", pin_memory=True)
     pin_s = time.perf_counter() - t0
-    # arms: the device-resident cache, the host-resident one with the shipped `workgroups` ("host"), and with every --workgroups value
-    arms = {"device": (device, None), "host": (host, ops.KV_STREAM_WORKGROUPS), **{f"host@{wg}": (host, wg) for wg in args.workgroups}}
-    if args.staged:
-        # the same bytes over the same link with the COPY ENGINES as the mover: a block's packed bytes go from the pinned cache into a device
-        # staging cache by one copy_(non_blocking=True) per tensor on the stream the fill runs on, then the device-resident unpack launch
-        # widens them -- a diagnostic arm (the staging cache here is a whole second cache in HBM), not a form the engine has
-        from idm_vton_amd.garment_cache import PackedGarmentCache
-        stage = PackedGarmentCache(exps=device.exps, **device._args(kv=[(torch.zeros_like(k), torch.zeros_like(v)) for k, v in device.kv]))
-        packed_fill = eng._packed_fill
-
-        def staged_fill(st, sets, blocks=None):
-            fill = packed_fill(st, sets, blocks)
-            if st["gcache"] is not stage:
-                return fill
-
-            def garment(bi, p):
-                s0, c = st["blocks"][bi]
-                for (dk, dv), (sk, sv) in zip(stage.run(st["gidx"][s0], c), host.run(st["gidx"][s0], c)):      # consecutive entries
-                    dk.copy_(sk, non_blocking=True)
-                    dv.copy_(sv, non_blocking=True)
-                fill(bi, p)
-            return garment
-        eng._packed_fill = staged_fill
-        arms["staged"] = (stage, None)
+    # arms: the device-resident cache, the host-resident one with the shipped `workgroups` ("host"), with every --workgroups value, and with
+    # the copy-engine transport ("copy")
+    arms = {"device": (device, None, "kernel"), "host": (host, ops.KV_STREAM_WORKGROUPS, "kernel"),
+            **{f"host@{wg}": (host, wg, "kernel") for wg in args.workgroups}, "copy": (host, None, "copy")}
 
     def call(a, **more):
-        cache, wg = arms[a]
+        cache, wg, transport = arms[a]
         if wg is not None:
             ops.KV_STREAM_WORKGROUPS = wg
-        return eng(**kw, **more, **{**inp, "cloth": cache, "text_embeds_cloth": None})
+        return eng(**kw, **more, host_transport=transport, **{**inp, "cloth": cache, "text_embeds_cloth": None})
     lat = {a: call(a, return_latents=True).clone() for a in arms}                             # warm-up: graph capture; and the latents
     torch.cuda.synchronize()
     rows = {a: [] for a in arms}
@@ -190,6 +172,7 @@ def call_step(args):
     per_step = (host.nbytes - host.exps.numel() * 4) // STEPS
     block0_ms = sched[0][1] * per_step / (args.link_gbps * 1e6)
     excess_ms = mean(ms["host"]) - mean(ms["device"])
+    gain_ms = mean(ms["host"]) - mean(ms["copy"])            # the one condition on the copy arm: below the host arm by more than the device arm's spread
     within = excess_ms <= block0_ms + spread_ms
     fh, th, td = blocks["host"]["fill"], blocks["host"]["tryon"], blocks["device"]["tryon"]
     outran = [bi for bi in range(1, len(fh)) if fh[bi] > th[bi - 1]]      # block bi's fill runs behind TryonNet's block bi - 1
@@ -198,12 +181,16 @@ def call_step(args):
                ("fills outran TryonNet in blocks %s" % outran if outran else "no fill outran its TryonNet block") +
                f"; TryonNet's blocks took {slowed_ms:+.2f} ms in the host call against the device call")
     emit(args, dict(step="call", shape=f"{W}x{H}, {STEPS} steps, B={B}, bf16, graph + overlap, packed cache", pin_and_copy_s=round(pin_s, 2),
-                          latents_equal=all(bool(torch.equal(lat[a], lat["device"])) for a in arms), workgroups={a: wg for a, (_, wg) in arms.items()},
+                          latents_equal=all(bool(torch.equal(lat[a], lat["device"])) for a in arms), workgroups={a: wg for a, (_, wg, _) in arms.items()},
                           tryon_ms_beside_fills={a: round(sum(v["tryon"]), 2) for a, v in blocks.items()}, fill_ms={a: round(sum(v["fill"]), 2) for a, v in blocks.items()}, images_per_s={a: [round(x, 4) for x in v] for a, v in rows.items()},
                           ms_per_call={a: round(mean(v), 2) for a, v in ms.items()}, device_spread_ms=round(spread_ms, 2),
                           host_minus_device_ms=round(excess_ms, 2), link_GBps=args.link_gbps, block0_bytes=sched[0][1] * per_step,
                           block0_exposed_ms=round(block0_ms, 2), within_expectation=within, verdict=verdict, block_timesteps=[c for _, c in sched],
                           per_block_ms=blocks, serial_form_exposed_ms=round(sum(fh), 2),
+                          copy_minus_device_ms=round(mean(ms["copy"]) - mean(ms["device"]), 2), host_minus_copy_ms=round(gain_ms, 2),
+                          copy_below_host_by_more_than_device_spread=gain_ms > spread_ms,
+                          stage_launches=eng.stats["garment_stage_launches"], stage_copies=eng.stats["garment_stage_copies"],
+                          arena_bytes=[a.numel() for a, _ in eng._arenas.values()],
                     stream_launches=eng.stats["garment_stream_launches"], cache_nbytes=host.nbytes))
     return 0 if all(torch.equal(lat[a], lat["device"]) for a in arms) else 1
 
@@ -222,11 +209,12 @@ def fillrate_step(args):
         return torch.where((b & 0x7f) == 0x7f, torch.zeros_like(b), b)
     kv = [(rand_bytes(k * G * N, C), rand_bytes(k * G, C, N)) for feats, N, C in LEVELS for _ in range(feats)]
     exps = torch.randint(-7, 16, (G, len(kv), 2), generator=gen, device=DEV, dtype=torch.int32)
-    host = PackedGarmentCache(G=G, timesteps=list(range(k, 0, -1)), h=H // 8, w=W // 8, dtype=dt, attn_fp8=False, f8_exp=(0, 0, 0),
-                              weights_id="synthetic", kv=kv, exps=exps).to("cpu", pin_memory=True)
+    dev = PackedGarmentCache(G=G, timesteps=list(range(k, 0, -1)), h=H // 8, w=W // 8, dtype=dt, attn_fp8=False, f8_exp=(0, 0, 0),
+                             weights_id="synthetic", kv=kv, exps=exps)
+    host = dev.to("cpu", pin_memory=True)
     st = dict(gcache=host, gidx=list(range(k)), gindex=None, k=k, B=B, blocks=[(0, k)])
     slots, shapes = eng._cache_set_shapes(st)
-    sets = {name: eng._alloc_set((), shapes, k, k, slots) for name in ("kv_stream", "kv_fill")}
+    sets = {name: eng._alloc_set((), shapes, k, k, slots) for name in ("kv_stream", "kv_fill", "kv_unpack", "kv_place")}
     addr = {}
 
     def address(t):
@@ -239,26 +227,36 @@ def fillrate_step(args):
         rec = fill_records(host.kv, k, G, sets[name]["kv"], k, slots, host.exps, list(range(k)), list(range(k)), [0], [0], address=address)
         tables[name] = cls(rec, DEV, ffi.KVS_WIDEN_E4M3)
     assert torch.equal(tables["kv_stream"].host[:, [0, 2, 3, 4]], tables["kv_fill"].host[:, [0, 2, 3, 4]]) and (tables["kv_fill"].host[:, 0] != 0).all()
+    # the same table again with the same bytes in DEVICE memory: the parent's idmvton_kv_unpack against idmvton_kv_place
+    rec = {name: fill_records(dev.kv, k, G, sets[name]["kv"], k, slots, dev.exps, list(range(k)), list(range(k)), [0], [0]) for name in ("kv_unpack", "kv_place")}
+    unpack, place = ops.KvUnpackTable(rec["kv_unpack"], DEV), ops.KvPlaceTable(rec["kv_place"], DEV, ffi.KVS_WIDEN_E4M3)
+    assert torch.equal(unpack.host[:, [0, 2, 3, 4]], place.host[:, [0, 2, 3, 4]]) and torch.equal(place.host[:, [3, 4]], tables["kv_fill"].host[:, [3, 4]])
+    launches = {"kv_stream": lambda: tables["kv_stream"].launch(dt, 0, args.fill_workgroups), "kv_fill": lambda: tables["kv_fill"].launch(dt, 0, args.fill_workgroups),
+                "kv_unpack": lambda: unpack.launch(dt), "kv_place": lambda: place.launch(dt)}
     src_bytes = sum(a.numel() + b.numel() for a, b in host.kv)
-    for t in tables.values():                                 # one discarded launch each
-        t.launch(dt, 0, args.fill_workgroups)
-    torch.cuda.synchronize()
-    us = {name: [] for name in tables}
-    for _ in range(9):                                        # alternating
-        for name, t in tables.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize(); e0.record()
-            t.launch(dt, 0, args.fill_workgroups)
-            e1.record(); e1.synchronize()
-            us[name].append(e0.elapsed_time(e1) * 1e3)
-    same = all(torch.equal(a, c) and torch.equal(b, d) for (a, b), (c, d) in zip(sets["kv_stream"]["kv"], sets["kv_fill"]["kv"]))
+    us = {name: [] for name in launches}
+    for pair in (("kv_stream", "kv_fill"), ("kv_unpack", "kv_place")):
+        for name in pair:                                     # one discarded launch each
+            launches[name]()
+        torch.cuda.synchronize()
+        for _ in range(9):                                    # alternating
+            for name in pair:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize(); e0.record()
+                launches[name]()
+                e1.record(); e1.synchronize()
+                us[name].append(e0.elapsed_time(e1) * 1e3)
+    same = all(torch.equal(a, c) and torch.equal(b, d) for other in ("kv_fill", "kv_unpack", "kv_place")
+               for (a, b), (c, d) in zip(sets["kv_stream"]["kv"], sets[other]["kv"]))
     gbps = {name: sorted(src_bytes / x / 1e3 for x in v) for name, v in us.items()}
-    res = {name: dict(median_GBps=round(v[len(v) // 2], 2), min_GBps=round(v[0], 2), max_GBps=round(v[-1], 2), us=[round(x, 1) for x in us[name]])
-           for name, v in gbps.items()}
+    res = {name: dict(median_GBps=round(v[len(v) // 2], 2), min_GBps=round(v[0], 2), max_GBps=round(v[-1], 2), us=[round(x, 1) for x in us[name]],
+                      median_us=round(sorted(us[name])[len(us[name]) // 2], 1)) for name, v in gbps.items()}
+    ratio = res["kv_place"]["median_us"] / res["kv_unpack"]["median_us"]
     for name, r in res.items():
-        print(f"{name:10s} median {r['median_GBps']:6.2f} GB/s (min {r['min_GBps']:.2f} .. max {r['max_GBps']:.2f}) over 9 launches", flush=True)
+        print(f"{name:10s} median {r['median_us']:9.1f} us, {r['median_GBps']:8.2f} source GB/s (min {r['min_GBps']:.2f} .. max {r['max_GBps']:.2f}) over 9 launches", flush=True)
     emit(args, dict(step="fillrate", shape=f"{W}x{H}, one packed garment, one block of {k} timesteps, bf16 set, data-only table of {tables['kv_fill'].n} runs",
-                    source_bytes=src_bytes, workgroups=args.fill_workgroups, bit_equal=same, **res))
+                    source_bytes=src_bytes, workgroups=args.fill_workgroups, bit_equal=same, place_over_unpack_median=round(ratio, 4),
+                    place_within_3_percent_of_unpack_or_better=ratio <= 1.03, **res))
     return 0 if same else 1
 
 
@@ -285,11 +283,12 @@ def shelf_step(args):
     pool = GarmentPool(B, like=full[keys[0]], resident="host")
     pool_index = pool.get(keys, encode=full.get)
     del full
-    arms = {"shelf": (shelved, index), "device": (shelved.slotted(DEV), index), "host_full": (pool.cache, pool_index)}
+    arms = {"shelf": (shelved, index, "kernel"), "device": (shelved.slotted(DEV), index, "kernel"), "host_full": (pool.cache, pool_index, "kernel"),
+            "shelf_copy": (shelved, index, "copy")}
 
     def call(a, **more):
-        cache, idx = arms[a]
-        return eng(**kw, **more, **{**inp, "cloth": cache, "garment_index": idx, "text_embeds_cloth": None})
+        cache, idx, transport = arms[a]
+        return eng(**kw, **more, host_transport=transport, **{**inp, "cloth": cache, "garment_index": idx, "text_embeds_cloth": None})
     lat = {a: call(a, return_latents=True).clone() for a in arms}                             # warm-up: graph capture; and the latents
     torch.cuda.synchronize()
     # link and zero-tail bytes of ONE call, summed from the descriptor tables of its launches
@@ -318,11 +317,12 @@ def shelf_step(args):
                 call(a)
             torch.cuda.synchronize()
             rows[a].append(B * args.calls / (time.perf_counter() - t0))
-            print(f"repeat {r} {a:9s} {rows[a][-1]:.4f} images/s", flush=True)
-    equal = bool(torch.equal(lat["shelf"], lat["device"]))
+            print(f"repeat {r} {a:10s} {rows[a][-1]:.4f} images/s", flush=True)
+    equal = bool(torch.equal(lat["shelf"], lat["device"])) and bool(torch.equal(lat["shelf_copy"], lat["device"]))
     _, sched = eng._block_schedule(STEPS)
     emit(args, dict(step="shelf", shape=f"{W}x{H} persons, {gw}x{gh} packed garments, {STEPS} steps, B={B}, bf16, graph + overlap",
-                    shelf_latents_equal_device_slotted=equal, images_per_s={a: [round(x, 4) for x in v] for a, v in rows.items()},
+                    shelf_latents_equal_device_slotted=equal, ms_per_call={a: round(sum(1e3 * B / x for x in v) / len(v), 2) for a, v in rows.items()},
+                    arena_bytes=[a.numel() for a, _ in eng._arenas.values()], images_per_s={a: [round(x, 4) for x in v] for a, v in rows.items()},
                     traffic=traffic, link_ratio_shelf_to_host_full=round(traffic["shelf"]["link_bytes_per_call"] / traffic["host_full"]["link_bytes_per_call"], 4),
                     block_timesteps=[c for _, c in sched], shelf_nbytes=shelf.nbytes, host_full_nbytes=pool.cache.nbytes))
     return 0 if equal else 1
@@ -337,8 +337,6 @@ def drive(args):
             cmd = [sys.executable, os.path.abspath(__file__), "--step", name, "--calls", str(args.calls), "--json-out", out]
             if name == "call" and args.workgroups:
                 cmd += ["--workgroups"] + [str(wg) for wg in args.workgroups]
-            if name == "call" and args.staged:
-                cmd += ["--staged"]
             if name == "call" and link:
                 cmd += ["--link-gbps", str(link)]
             print(f"--- step {name} (limit {limit} s)", flush=True)
@@ -367,7 +365,6 @@ if __name__ == "__main__":
     ap.add_argument("--step", choices=["fill", "call", "fillrate", "shelf"], default=None)
     ap.add_argument("--calls", type=int, default=2, help="timed calls per repeat")
     ap.add_argument("--workgroups", type=int, nargs="*", default=[], help="--step call: further host arms with these `workgroups` values")
-    ap.add_argument("--staged", action="store_true", help="--step call: a further arm that moves the blocks with the copy engines (a diagnostic)")
     ap.add_argument("--json-out", default=None, help="also write the step's JSON result to this file (the driver reads the link rate from it)")
     ap.add_argument("--fill-workgroups", type=int, default=16, help="--step fillrate: persistent workgroups of both launches")
     ap.add_argument("--link-gbps", type=float, default=SPEC_GBPS, help="the host-link rate --step fill measured (default: the spec rate)")
