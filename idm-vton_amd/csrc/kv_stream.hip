@@ -166,114 +166,67 @@ __global__ __launch_bounds__(KVS_THREADS) void kv_place_kernel(const idmvton_kv_
     kvs_write<T, WIDEN>(c);
 }
 
-extern "C" int idmvton_kv_stream(const idmvton_kv_stream_args* a, const idmvton_kv_stream_desc* host_desc, const int32_t* host_first, void* stream) {
-    CHECK_ARG(a && host_desc && host_first && a->desc && a->first, IDMVTON_E_ARG, "kv_stream: null args / descriptor table / prefix table");
-    CHECK_ARG(a->dtype == IDMVTON_F16 || a->dtype == IDMVTON_BF16, IDMVTON_E_DTYPE, "kv_stream: dtype %d (F16 or BF16)", a->dtype);
-    CHECK_ARG(a->mode == IDMVTON_KVS_WIDEN_E4M3 || a->mode == IDMVTON_KVS_COPY, IDMVTON_E_ARG, "kv_stream: mode %d (IDMVTON_KVS_WIDEN_E4M3 or IDMVTON_KVS_COPY)", a->mode);
-    CHECK_ARG(a->n >= 1 && a->n <= IDMVTON_KVS_MAX_N, IDMVTON_E_ARG, "kv_stream: n=%d outside [1, %d] descriptors", a->n, IDMVTON_KVS_MAX_N);
-    CHECK_ARG(a->workgroups >= 1 && a->workgroups <= 1024, IDMVTON_E_ARG, "kv_stream: workgroups=%d outside [1, 1024]", a->workgroups);
-    CHECK_ARG(((uintptr_t)a->desc & 15) == 0, IDMVTON_E_ALIGN, "kv_stream: the device descriptor table is not 16-byte aligned");
-    CHECK_ARG(((uintptr_t)a->first & 3) == 0, IDMVTON_E_ALIGN, "kv_stream: the device prefix table is not 4-byte aligned");
+// What the three entry points check, written once.  `name` is the entry's own in the messages; `zero_ok`: a descriptor whose src is NULL is a zero
+// run, not a refusal; `persistent`: workgroups is the grid and lies in [1, 1024], else it must be 0 (the grid is the chunk count).  Returns the
+// table's chunk count (>= 1: n >= 1 and every run has a chunk), or the error code (< 0).
+static long kvs_check(const idmvton_kv_stream_args* a, const idmvton_kv_stream_desc* host_desc, const int32_t* host_first, const char* name, bool zero_ok, bool persistent) {
+    CHECK_ARG(a && host_desc && host_first && a->desc && a->first, IDMVTON_E_ARG, "%s: null args / descriptor table / prefix table", name);
+    CHECK_ARG(a->dtype == IDMVTON_F16 || a->dtype == IDMVTON_BF16, IDMVTON_E_DTYPE, "%s: dtype %d (F16 or BF16)", name, a->dtype);
+    CHECK_ARG(a->mode == IDMVTON_KVS_WIDEN_E4M3 || a->mode == IDMVTON_KVS_COPY, IDMVTON_E_ARG, "%s: mode %d (IDMVTON_KVS_WIDEN_E4M3 or IDMVTON_KVS_COPY)", name, a->mode);
+    CHECK_ARG(a->n >= 1 && a->n <= IDMVTON_KVS_MAX_N, IDMVTON_E_ARG, "%s: n=%d outside [1, %d] descriptors", name, a->n, IDMVTON_KVS_MAX_N);
+    CHECK_ARG(!persistent || (a->workgroups >= 1 && a->workgroups <= 1024), IDMVTON_E_ARG, "%s: workgroups=%d outside [1, 1024]", name, a->workgroups);
+    CHECK_ARG(persistent || a->workgroups == 0, IDMVTON_E_ARG, "%s: workgroups=%d must be 0 (the grid is the table's chunk count, one workgroup per chunk)", name, a->workgroups);
+    CHECK_ARG(((uintptr_t)a->desc & 15) == 0, IDMVTON_E_ALIGN, "%s: the device descriptor table is not 16-byte aligned", name);
+    CHECK_ARG(((uintptr_t)a->first & 3) == 0, IDMVTON_E_ALIGN, "%s: the device prefix table is not 4-byte aligned", name);
     const bool widen = a->mode == IDMVTON_KVS_WIDEN_E4M3;
     const int dmul = widen ? 8 : 16;                                   // ldd: elements when widening, bytes when copying
     long chunks = 0;
     for (int i = 0; i < a->n; ++i) {
         const idmvton_kv_stream_desc* d = host_desc + i;
-        CHECK_ARG(d->src && d->dst && (d->exp || !widen), IDMVTON_E_ARG, "kv_stream: descriptor %d has a null pointer", i);
-        CHECK_ARG(((uintptr_t)d->src & 15) == 0 && ((uintptr_t)d->dst & 15) == 0 && (!widen || ((uintptr_t)d->exp & 3) == 0), IDMVTON_E_ALIGN,
-                  "kv_stream: descriptor %d: src / dst not 16-byte aligned (or exp not 4-byte aligned)", i);
-        CHECK_ARG(d->rows >= 1 && d->cols >= 16 && d->cols % 16 == 0, IDMVTON_E_SHAPE, "kv_stream: descriptor %d: rows=%d cols=%d (rows >= 1, cols a multiple of 16)",
-                  i, d->rows, d->cols);
-        CHECK_ARG(d->lds >= d->cols && d->lds % 16 == 0, IDMVTON_E_SHAPE, "kv_stream: descriptor %d: lds=%d (>= cols=%d, a multiple of 16)", i, d->lds, d->cols);
-        CHECK_ARG(d->ldd >= d->cols && d->ldd % dmul == 0, IDMVTON_E_SHAPE, "kv_stream: descriptor %d: ldd=%d (>= cols=%d, a multiple of %d)", i, d->ldd, d->cols, dmul);
+        const bool zero = zero_ok && d->src == nullptr;                // a zero run: exp and lds are not looked at
+        CHECK_ARG((d->src || zero) && d->dst && (zero || d->exp || !widen), IDMVTON_E_ARG, "%s: descriptor %d has a null pointer%s", name, i,
+                  !zero_ok ? "" : zero ? " (dst of a zero run)" : " (dst, or exp of a data run)");
+        CHECK_ARG(((uintptr_t)d->src & 15) == 0 && ((uintptr_t)d->dst & 15) == 0 && (zero || !widen || ((uintptr_t)d->exp & 3) == 0), IDMVTON_E_ALIGN,
+                  "%s: descriptor %d: src / dst not 16-byte aligned (or exp not 4-byte aligned)", name, i);
+        CHECK_ARG(d->rows >= 1 && d->cols >= 16 && d->cols % 16 == 0, IDMVTON_E_SHAPE, "%s: descriptor %d: rows=%d cols=%d (rows >= 1, cols a multiple of 16)",
+                  name, i, d->rows, d->cols);
+        CHECK_ARG(zero || (d->lds >= d->cols && d->lds % 16 == 0), IDMVTON_E_SHAPE, "%s: descriptor %d: lds=%d (>= cols=%d, a multiple of 16)", name, i, d->lds, d->cols);
+        CHECK_ARG(d->ldd >= d->cols && d->ldd % dmul == 0, IDMVTON_E_SHAPE, "%s: descriptor %d: ldd=%d (>= cols=%d, a multiple of %d)", name, i, d->ldd, d->cols, dmul);
         const long items = (long)d->rows * (d->cols >> 4);
-        CHECK_ARG(items < (1L << 31), IDMVTON_E_SHAPE, "kv_stream: descriptor %d: rows=%d x cols=%d is 2^31 16-byte items or more", i, d->rows, d->cols);
-        CHECK_ARG(host_first[i] == chunks, IDMVTON_E_ARG, "kv_stream: host_first[%d]=%d, the runs before descriptor %d have %ld chunks of %d 16-byte items",
-                  i, host_first[i], i, chunks, KVS_CHUNK);
+        CHECK_ARG(items < (1L << 31), IDMVTON_E_SHAPE, "%s: descriptor %d: rows=%d x cols=%d is 2^31 16-byte items or more", name, i, d->rows, d->cols);
+        CHECK_ARG(host_first[i] == chunks, IDMVTON_E_ARG, "%s: host_first[%d]=%d, the runs before descriptor %d have %ld chunks of %d 16-byte items",
+                  name, i, host_first[i], i, chunks, KVS_CHUNK);
         chunks += (items + KVS_CHUNK - 1) / KVS_CHUNK;
-        CHECK_ARG(chunks < (1L << 31), IDMVTON_E_SHAPE, "kv_stream: 2^31 chunks or more up to descriptor %d", i);
+        CHECK_ARG(chunks < (1L << 31), IDMVTON_E_SHAPE, "%s: 2^31 chunks or more up to descriptor %d", name, i);
     }
-    CHECK_ARG(host_first[a->n] == chunks, IDMVTON_E_ARG, "kv_stream: host_first[%d]=%d, the table has %ld chunks of %d 16-byte items", a->n, host_first[a->n], chunks, KVS_CHUNK);
-    const dim3 grid((unsigned)a->workgroups), block(KVS_THREADS);
-    if (!widen) hipLaunchKernelGGL((kv_stream_kernel<bf16_t, false>), grid, block, 0, (hipStream_t)stream, a->desc, a->first, a->n);
-    else if (a->dtype == IDMVTON_BF16) hipLaunchKernelGGL((kv_stream_kernel<bf16_t, true>), grid, block, 0, (hipStream_t)stream, a->desc, a->first, a->n);
-    else hipLaunchKernelGGL((kv_stream_kernel<f16_t, true>), grid, block, 0, (hipStream_t)stream, a->desc, a->first, a->n);
-    CHECK_LAUNCH("kv_stream");
+    CHECK_ARG(host_first[a->n] == chunks, IDMVTON_E_ARG, "%s: host_first[%d]=%d, the table has %ld chunks of %d 16-byte items", name, a->n, host_first[a->n], chunks, KVS_CHUNK);
+    return chunks;
+}
+
+// Launches the instantiation a call asks for, out of the three of one kernel template (COPY = <bf16_t, false>: copying never looks at T).
+typedef void (*kvs_kernel_t)(const idmvton_kv_stream_desc*, const int32_t*, int);
+template <kvs_kernel_t COPY, kvs_kernel_t BF16, kvs_kernel_t F16>
+static int kvs_launch(const idmvton_kv_stream_args* a, long grid, void* stream, const char* name) {
+    const kvs_kernel_t k = a->mode == IDMVTON_KVS_COPY ? COPY : a->dtype == IDMVTON_BF16 ? BF16 : F16;
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(KVS_THREADS), 0, (hipStream_t)stream, a->desc, a->first, a->n);
+    CHECK_LAUNCH(name);
     return IDMVTON_OK;
+}
+#define KVS_OF(K) K<bf16_t, false>, K<bf16_t, true>, K<f16_t, true>
+
+extern "C" int idmvton_kv_stream(const idmvton_kv_stream_args* a, const idmvton_kv_stream_desc* host_desc, const int32_t* host_first, void* stream) {
+    const long chunks = kvs_check(a, host_desc, host_first, "kv_stream", false, true);
+    return chunks < 0 ? (int)chunks : kvs_launch<KVS_OF(kv_stream_kernel)>(a, a->workgroups, stream, "kv_stream");
 }
 
 extern "C" int idmvton_kv_fill(const idmvton_kv_stream_args* a, const idmvton_kv_stream_desc* host_desc, const int32_t* host_first, void* stream) {
-    CHECK_ARG(a && host_desc && host_first && a->desc && a->first, IDMVTON_E_ARG, "kv_fill: null args / descriptor table / prefix table");
-    CHECK_ARG(a->dtype == IDMVTON_F16 || a->dtype == IDMVTON_BF16, IDMVTON_E_DTYPE, "kv_fill: dtype %d (F16 or BF16)", a->dtype);
-    CHECK_ARG(a->mode == IDMVTON_KVS_WIDEN_E4M3 || a->mode == IDMVTON_KVS_COPY, IDMVTON_E_ARG, "kv_fill: mode %d (IDMVTON_KVS_WIDEN_E4M3 or IDMVTON_KVS_COPY)", a->mode);
-    CHECK_ARG(a->n >= 1 && a->n <= IDMVTON_KVS_MAX_N, IDMVTON_E_ARG, "kv_fill: n=%d outside [1, %d] descriptors", a->n, IDMVTON_KVS_MAX_N);
-    CHECK_ARG(a->workgroups >= 1 && a->workgroups <= 1024, IDMVTON_E_ARG, "kv_fill: workgroups=%d outside [1, 1024]", a->workgroups);
-    CHECK_ARG(((uintptr_t)a->desc & 15) == 0, IDMVTON_E_ALIGN, "kv_fill: the device descriptor table is not 16-byte aligned");
-    CHECK_ARG(((uintptr_t)a->first & 3) == 0, IDMVTON_E_ALIGN, "kv_fill: the device prefix table is not 4-byte aligned");
-    const bool widen = a->mode == IDMVTON_KVS_WIDEN_E4M3;
-    const int dmul = widen ? 8 : 16;                                   // ldd: elements when widening, bytes when copying
-    long chunks = 0;
-    for (int i = 0; i < a->n; ++i) {
-        const idmvton_kv_stream_desc* d = host_desc + i;
-        const bool zero = d->src == nullptr;                           // a zero run: exp and lds are not looked at
-        CHECK_ARG(d->dst && (zero || d->exp || !widen), IDMVTON_E_ARG, "kv_fill: descriptor %d has a null pointer (dst%s)", i, zero ? " of a zero run" : ", or exp of a data run");
-        CHECK_ARG(((uintptr_t)d->src & 15) == 0 && ((uintptr_t)d->dst & 15) == 0 && (zero || !widen || ((uintptr_t)d->exp & 3) == 0), IDMVTON_E_ALIGN,
-                  "kv_fill: descriptor %d: src / dst not 16-byte aligned (or exp not 4-byte aligned)", i);
-        CHECK_ARG(d->rows >= 1 && d->cols >= 16 && d->cols % 16 == 0, IDMVTON_E_SHAPE, "kv_fill: descriptor %d: rows=%d cols=%d (rows >= 1, cols a multiple of 16)",
-                  i, d->rows, d->cols);
-        CHECK_ARG(zero || (d->lds >= d->cols && d->lds % 16 == 0), IDMVTON_E_SHAPE, "kv_fill: descriptor %d: lds=%d (>= cols=%d, a multiple of 16)", i, d->lds, d->cols);
-        CHECK_ARG(d->ldd >= d->cols && d->ldd % dmul == 0, IDMVTON_E_SHAPE, "kv_fill: descriptor %d: ldd=%d (>= cols=%d, a multiple of %d)", i, d->ldd, d->cols, dmul);
-        const long items = (long)d->rows * (d->cols >> 4);
-        CHECK_ARG(items < (1L << 31), IDMVTON_E_SHAPE, "kv_fill: descriptor %d: rows=%d x cols=%d is 2^31 16-byte items or more", i, d->rows, d->cols);
-        CHECK_ARG(host_first[i] == chunks, IDMVTON_E_ARG, "kv_fill: host_first[%d]=%d, the runs before descriptor %d have %ld chunks of %d 16-byte items",
-                  i, host_first[i], i, chunks, KVS_CHUNK);
-        chunks += (items + KVS_CHUNK - 1) / KVS_CHUNK;
-        CHECK_ARG(chunks < (1L << 31), IDMVTON_E_SHAPE, "kv_fill: 2^31 chunks or more up to descriptor %d", i);
-    }
-    CHECK_ARG(host_first[a->n] == chunks, IDMVTON_E_ARG, "kv_fill: host_first[%d]=%d, the table has %ld chunks of %d 16-byte items", a->n, host_first[a->n], chunks, KVS_CHUNK);
-    const dim3 grid((unsigned)a->workgroups), block(KVS_THREADS);
-    if (!widen) hipLaunchKernelGGL((kv_fill_kernel<bf16_t, false>), grid, block, 0, (hipStream_t)stream, a->desc, a->first, a->n);
-    else if (a->dtype == IDMVTON_BF16) hipLaunchKernelGGL((kv_fill_kernel<bf16_t, true>), grid, block, 0, (hipStream_t)stream, a->desc, a->first, a->n);
-    else hipLaunchKernelGGL((kv_fill_kernel<f16_t, true>), grid, block, 0, (hipStream_t)stream, a->desc, a->first, a->n);
-    CHECK_LAUNCH("kv_fill");
-    return IDMVTON_OK;
+    const long chunks = kvs_check(a, host_desc, host_first, "kv_fill", true, true);
+    return chunks < 0 ? (int)chunks : kvs_launch<KVS_OF(kv_fill_kernel)>(a, a->workgroups, stream, "kv_fill");
 }
 
 extern "C" int idmvton_kv_place(const idmvton_kv_stream_args* a, const idmvton_kv_stream_desc* host_desc, const int32_t* host_first, void* stream) {
-    CHECK_ARG(a && host_desc && host_first && a->desc && a->first, IDMVTON_E_ARG, "kv_place: null args / descriptor table / prefix table");
-    CHECK_ARG(a->dtype == IDMVTON_F16 || a->dtype == IDMVTON_BF16, IDMVTON_E_DTYPE, "kv_place: dtype %d (F16 or BF16)", a->dtype);
-    CHECK_ARG(a->mode == IDMVTON_KVS_WIDEN_E4M3 || a->mode == IDMVTON_KVS_COPY, IDMVTON_E_ARG, "kv_place: mode %d (IDMVTON_KVS_WIDEN_E4M3 or IDMVTON_KVS_COPY)", a->mode);
-    CHECK_ARG(a->n >= 1 && a->n <= IDMVTON_KVS_MAX_N, IDMVTON_E_ARG, "kv_place: n=%d outside [1, %d] descriptors", a->n, IDMVTON_KVS_MAX_N);
-    CHECK_ARG(a->workgroups == 0, IDMVTON_E_ARG, "kv_place: workgroups=%d must be 0 (the grid is the table's chunk count, one workgroup per chunk)", a->workgroups);
-    CHECK_ARG(((uintptr_t)a->desc & 15) == 0, IDMVTON_E_ALIGN, "kv_place: the device descriptor table is not 16-byte aligned");
-    CHECK_ARG(((uintptr_t)a->first & 3) == 0, IDMVTON_E_ALIGN, "kv_place: the device prefix table is not 4-byte aligned");
-    const bool widen = a->mode == IDMVTON_KVS_WIDEN_E4M3;
-    const int dmul = widen ? 8 : 16;                                   // ldd: elements when widening, bytes when copying
-    long chunks = 0;
-    for (int i = 0; i < a->n; ++i) {
-        const idmvton_kv_stream_desc* d = host_desc + i;
-        const bool zero = d->src == nullptr;                           // a zero run: exp and lds are not looked at
-        CHECK_ARG(d->dst && (zero || d->exp || !widen), IDMVTON_E_ARG, "kv_place: descriptor %d has a null pointer (dst%s)", i, zero ? " of a zero run" : ", or exp of a data run");
-        CHECK_ARG(((uintptr_t)d->src & 15) == 0 && ((uintptr_t)d->dst & 15) == 0 && (zero || !widen || ((uintptr_t)d->exp & 3) == 0), IDMVTON_E_ALIGN,
-                  "kv_place: descriptor %d: src / dst not 16-byte aligned (or exp not 4-byte aligned)", i);
-        CHECK_ARG(d->rows >= 1 && d->cols >= 16 && d->cols % 16 == 0, IDMVTON_E_SHAPE, "kv_place: descriptor %d: rows=%d cols=%d (rows >= 1, cols a multiple of 16)",
-                  i, d->rows, d->cols);
-        CHECK_ARG(zero || (d->lds >= d->cols && d->lds % 16 == 0), IDMVTON_E_SHAPE, "kv_place: descriptor %d: lds=%d (>= cols=%d, a multiple of 16)", i, d->lds, d->cols);
-        CHECK_ARG(d->ldd >= d->cols && d->ldd % dmul == 0, IDMVTON_E_SHAPE, "kv_place: descriptor %d: ldd=%d (>= cols=%d, a multiple of %d)", i, d->ldd, d->cols, dmul);
-        const long items = (long)d->rows * (d->cols >> 4);
-        CHECK_ARG(items < (1L << 31), IDMVTON_E_SHAPE, "kv_place: descriptor %d: rows=%d x cols=%d is 2^31 16-byte items or more", i, d->rows, d->cols);
-        CHECK_ARG(host_first[i] == chunks, IDMVTON_E_ARG, "kv_place: host_first[%d]=%d, the runs before descriptor %d have %ld chunks of %d 16-byte items",
-                  i, host_first[i], i, chunks, KVS_CHUNK);
-        chunks += (items + KVS_CHUNK - 1) / KVS_CHUNK;
-        CHECK_ARG(chunks < (1L << 31), IDMVTON_E_SHAPE, "kv_place: 2^31 chunks or more up to descriptor %d", i);
-    }
-    CHECK_ARG(host_first[a->n] == chunks, IDMVTON_E_ARG, "kv_place: host_first[%d]=%d, the table has %ld chunks of %d 16-byte items", a->n, host_first[a->n], chunks, KVS_CHUNK);
-    const dim3 grid((unsigned)chunks), block(KVS_THREADS);             // one workgroup per chunk: at least one (n >= 1, every run has a chunk)
-    if (!widen) hipLaunchKernelGGL((kv_place_kernel<bf16_t, false>), grid, block, 0, (hipStream_t)stream, a->desc, a->first, a->n);
-    else if (a->dtype == IDMVTON_BF16) hipLaunchKernelGGL((kv_place_kernel<bf16_t, true>), grid, block, 0, (hipStream_t)stream, a->desc, a->first, a->n);
-    else hipLaunchKernelGGL((kv_place_kernel<f16_t, true>), grid, block, 0, (hipStream_t)stream, a->desc, a->first, a->n);
-    CHECK_LAUNCH("kv_place");
-    return IDMVTON_OK;
+    const long chunks = kvs_check(a, host_desc, host_first, "kv_place", true, false);
+    return chunks < 0 ? (int)chunks : kvs_launch<KVS_OF(kv_place_kernel)>(a, chunks, stream, "kv_place");   // one workgroup per chunk
 }
 
 extern "C" int idmvton_host_device_ptr(const void* host, void** dev) {

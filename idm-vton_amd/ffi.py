@@ -4,6 +4,7 @@ The mirror is verified at load time against `idmvton_sizeof()` exported by the l
 and the header fails loudly instead of corrupting kernel arguments.
 """
 import ctypes as C
+import functools
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -180,12 +181,9 @@ def lib():
         getattr(L, s).restype = C.c_int
     L.idmvton_kv_unpack.argtypes = [vp, vp, vp]                               # (args*, const desc* host_desc, stream)
     L.idmvton_kv_unpack.restype = C.c_int
-    L.idmvton_kv_stream.argtypes = [vp, vp, vp, vp]                           # (args*, const desc* host_desc, const int32_t* host_first, stream)
-    L.idmvton_kv_stream.restype = C.c_int
-    L.idmvton_kv_fill.argtypes = [vp, vp, vp, vp]                             # the same signature; a NULL src is a zero run
-    L.idmvton_kv_fill.restype = C.c_int
-    L.idmvton_kv_place.argtypes = [vp, vp, vp, vp]                            # the same signature; workgroups must be 0: one workgroup per chunk
-    L.idmvton_kv_place.restype = C.c_int
+    for s in ("idmvton_kv_stream", "idmvton_kv_fill", "idmvton_kv_place"):    # (args*, const desc* host_desc, const int32_t* host_first, stream)
+        getattr(L, s).argtypes = [vp, vp, vp, vp]
+        getattr(L, s).restype = C.c_int
     L.idmvton_host_device_ptr.argtypes = [vp, C.POINTER(vp)]                  # (const void* host, void** dev)
     L.idmvton_host_device_ptr.restype = C.c_int
     L.idmvton_probe_mfma.argtypes = [C.c_int, vp, vp, vp, vp]
@@ -251,32 +249,21 @@ def call_kv_unpack(args, host_desc, stream):
         raise RuntimeError(f"idmvton_kv_unpack failed ({rc}): {L.idmvton_last_error().decode()}")
 
 
-def call_kv_stream(args, host_desc, host_first, stream):
-    """Invoke idmvton_kv_stream(const args*, const desc* host_desc, const int32_t* host_first, void* stream); host_desc / host_first: ctypes
-    arrays or the addresses of such (what the library validates -- args.desc / args.first are their device copies)."""
+def _call_kv_table(fn_name, args, host_desc, host_first, stream):
+    """Invoke `int f(const args*, const desc* host_desc, const int32_t* host_first, void* stream)`: idmvton_kv_stream, idmvton_kv_fill (a
+    descriptor whose src is NULL is a zero run) or idmvton_kv_place (the same, and args.workgroups must be 0: the grid is the table's chunk
+    count).  host_desc / host_first: ctypes arrays or the addresses of such (what the library validates -- args.desc / args.first are their
+    device copies)."""
     L = lib()
     p = lambda x: x if isinstance(x, int) else C.cast(x, vp)
-    rc = L.idmvton_kv_stream(C.byref(args), p(host_desc), p(host_first), C.c_void_p(stream))
+    rc = getattr(L, fn_name)(C.byref(args), p(host_desc), p(host_first), C.c_void_p(stream))
     if rc != 0:
-        raise RuntimeError(f"idmvton_kv_stream failed ({rc}): {L.idmvton_last_error().decode()}")
+        raise RuntimeError(f"{fn_name} failed ({rc}): {L.idmvton_last_error().decode()}")
 
 
-def call_kv_fill(args, host_desc, host_first, stream):
-    """Invoke idmvton_kv_fill: call_kv_stream's arguments; a descriptor whose src is NULL is a zero run."""
-    L = lib()
-    p = lambda x: x if isinstance(x, int) else C.cast(x, vp)
-    rc = L.idmvton_kv_fill(C.byref(args), p(host_desc), p(host_first), C.c_void_p(stream))
-    if rc != 0:
-        raise RuntimeError(f"idmvton_kv_fill failed ({rc}): {L.idmvton_last_error().decode()}")
-
-
-def call_kv_place(args, host_desc, host_first, stream):
-    """Invoke idmvton_kv_place: call_kv_fill's arguments; args.workgroups must be 0 (the grid is the table's chunk count)."""
-    L = lib()
-    p = lambda x: x if isinstance(x, int) else C.cast(x, vp)
-    rc = L.idmvton_kv_place(C.byref(args), p(host_desc), p(host_first), C.c_void_p(stream))
-    if rc != 0:
-        raise RuntimeError(f"idmvton_kv_place failed ({rc}): {L.idmvton_last_error().decode()}")
+call_kv_stream = functools.partial(_call_kv_table, "idmvton_kv_stream")
+call_kv_fill = functools.partial(_call_kv_table, "idmvton_kv_fill")
+call_kv_place = functools.partial(_call_kv_table, "idmvton_kv_place")
 
 
 def host_device_ptr(host):

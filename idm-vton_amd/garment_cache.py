@@ -36,7 +36,7 @@ and opt-in, for the garment segment alone; `dtype` stays the engine's 16-bit dty
 
 Host-resident: a cache whose tensors are CPU tensors (`to("cpu", pin_memory=True)`, GarmentPool(resident="host")) has `host_resident` true.
 The engine takes one that is PAGE-LOCKED as `cloth=`: every block of timesteps then goes from host memory straight into the 16-bit sets by
-one idmvton_kv_stream launch (pipeline.py, _stream_fill), so a catalogue is bounded by host RAM, not HBM.  Queued calls read such a cache
+one idmvton_kv_stream launch (pipeline.py, _cached_fill), so a catalogue is bounded by host RAM, not HBM.  Queued calls read such a cache
 by raw address, with no stream order to protect them: a `put` into it waits for the device first and copies blocking.  With
 host_transport="copy" the blocks cross the link by the copy engines into a staging arena instead and one idmvton_kv_place launch places them
 (staged_plan below: the arena, the copy list and the place tables, for plain and shelved caches alike).
@@ -45,7 +45,7 @@ Shelf: a GarmentShelf is a host catalogue of garments of MANY sizes, each kept C
 positions) in page-locked memory, 16-bit or e4m3-packed -- so host RAM and the bytes a call moves over the host link follow the garments' own
 sizes, not the largest one's.  `get` hands out a ShelvedGarmentCache: the garments of a batch as `parts`, declared for one slot size; the
 engine puts each into the front of a slot of its 16-bit sets and writes the zero V^T tail behind it with one idmvton_kv_fill launch per block
-(shelf_records below, pipeline.py _shelf_fill), and reads them as it reads a slotted cache.
+(kv_records below, pipeline.py _cached_fill), and reads them as it reads a slotted cache.
 """
 import torch
 
@@ -588,94 +588,86 @@ class PackedGarmentCache(GarmentCache):
         return GarmentCache(**self._args(kv=kv))
 
 
-def fill_records(src_kv, n, G, dst_kv, k, S, exps, entries, tslots, garments, gslots, address=None):
-    """The idmvton_kv_unpack / idmvton_kv_stream descriptor records (ops.KvUnpackTable, ops.KvStreamTable: int64 [N][5]) that move, for every
-    pair (entry i, timestep slot j) of (entries, tslots) and every pair (garment g, garment slot u) of (garments, gslots), feature f's K and
-    V^T of (i, g) of the list src_kv (n timesteps of G) into (j, u) of the 16-bit list dst_kv (k timesteps of S): one record per (timestep,
-    garment, feature, K | V^T), in that order.  Pure address arithmetic on the one layout rule (timestep_run / slot_run): element (i, g) of a
-    tensor starts (i * G + g) * (elements per garment and timestep) after its base.
-    A packed source (uint8 bytes + exps) gives the WIDENING form: cols / lds in bytes = elements, ldd in 16-bit elements, exp the address of
-    the garment's exponent.  A 16-bit source (exps None) gives the COPY form of idmvton_kv_stream: cols, lds and ldd in BYTES, no exponent (0).
-    address(tensor) -> the address a kernel reads the tensor's first element under (default data_ptr(); ops.stream_address for a host-resident
-    source); it is asked once per source tensor."""
+def kv_records(sources, dst_kvs, k, S, entries, tslots, address=None):
+    """THE descriptor records (int64 [N][5]: ops.KvUnpackTable and the idmvton_kv_stream / _fill / _place tables) that move garments into each
+    of the 16-bit lists dst_kvs (the sets: k timesteps of S garment slots, of equal shapes), for every pair (entry i, timestep slot j) of
+    (entries, tslots): first all records of dst_kvs[0], then those of dst_kvs[1], ...  A SOURCE is
+    (kv, n, G, garments, gslots, exps): garment g of the timestep-major list kv (n timesteps of G) goes into garment slot u, for every pair
+    (g, u) of (garments, gslots) -- some garments of a cache, one shelf part (G = 1, garment 0) or their image in a staging arena.  Pure
+    address arithmetic on the one layout rule (timestep_run / slot_run): (i, g) of a tensor starts (i * G + g) * (elements per garment and
+    timestep) after its base, so per feature a garment is a base address, G such units to advance per entry, and its own N'_f K rows and
+    ld'_f V^T positions, which may be fewer than the slot's N_f / ld_f.  Per (timestep, source, garment, feature), in that order:
+      K      one data run of the N'_f rows into the front of the slot (rows beyond are not written: no kernel reads them);
+      V^T    one data run of C_f rows x ld'_f positions, source row stride ld'_f, destination row stride ld_f;
+      tail   exactly where ld'_f < ld_f, one ZERO RUN (src 0) of C_f rows x (ld_f - ld'_f) positions behind it -- the whole tail, as _put_slotted
+             writes it, so a set's V^T depends on the garment alone and not on what the slot held before.
+    exps (int32 [G][F][2]) gives the WIDENING form: the source is e4m3 bytes, cols / lds in bytes = elements, ldd in 16-bit elements, exp the
+    address of the garment's exponent.  exps None gives the COPY form: a 16-bit source, cols, lds and ldd in BYTES, exp 0.  An odd number of
+    records per timestep is made even by repeating the smallest (a slice of a table starts at an even index; identical bytes written twice
+    are what clamped lanes already do).  address(tensor) -> the address a kernel reads the tensor's first element under (default
+    data_ptr(); ops.stream_address for a host-resident source); it is asked once per source tensor.
+    -> (records, per): timestep number t of (entries, tslots) owns records [t * per, (t + 1) * per) of a set's part."""
     I64 = torch.int64
-    F = len(src_kv)
-    address = address or (lambda t: t.data_ptr())
-    copy = exps is None
-    esz = dst_kv[0][0].element_size()
-    cols = torch.tensor([[kk.shape[1], vt.shape[2]] for kk, vt in src_kv], dtype=I64)                     # [F][2]: K rows are C wide, V^T rows ld
-    rows = torch.tensor([[kk.shape[0] // (n * G), vt.shape[1]] for kk, vt in src_kv], dtype=I64)           # N_f K rows, C V^T rows
-    sbase = torch.tensor([[address(kk), address(vt)] for kk, vt in src_kv], dtype=I64)
-    dbase = torch.tensor([[kk.data_ptr(), vt.data_ptr()] for kk, vt in dst_kv], dtype=I64)
-    unit = rows * cols                                                                                     # elements per (timestep, garment)
-    si = (torch.tensor(entries, dtype=I64).view(-1, 1) * G + torch.tensor(garments, dtype=I64).view(1, -1)).view(len(entries), len(garments), 1, 1)
-    di = (torch.tensor(tslots, dtype=I64).view(-1, 1) * S + torch.tensor(gslots, dtype=I64).view(1, -1)).view(len(tslots), len(gslots), 1, 1)
+    address = address or (lambda x: x.data_ptr())
+    t = lambda v: v if isinstance(v, torch.Tensor) else torch.tensor(v, dtype=I64)
+    # a list's [F][3][2]: per feature (K, V^T) leading rows / row length / address; a timestep's rows are the leading rows over `per`
+    facts = lambda kv, per, ptr: torch.tensor([[a.shape[0] // per, b.shape[1], a.shape[1], b.shape[2], ptr(a), ptr(b)] for a, b in kv], dtype=I64).view(-1, 3, 2)
+
+    def runs(src, dst, exp, rows, cols, ldd, sinc, dinc):    # [...][7]: a record (lds = cols), then what its src / dst advance per entry / timestep slot
+        return torch.stack(torch.broadcast_tensors(*[t(v) for v in (src, dst, exp, rows | (cols << 32), cols | (ldd << 32), sinc, dinc)]), dim=-1)
+    F, P, esz = len(dst_kvs[0]), len(dst_kvs), dst_kvs[0][0][0].element_size()
+    drows, dcols, dbase = torch.stack([facts(d, k * S, lambda x: x.data_ptr()) for d in dst_kvs]).unbind(2)   # [P][F][2]: (N_f, C_f), (C_f, ld_f)
+    drows, dcols, dbase = drows[0], dcols[0], dbase.unsqueeze(1)
+    dunit = drows * dcols * esz                                                                              # bytes of one slot
+    tmpl = []                                                # per source, the records of timestep (entry 0, slot 0) of every set
+    for kv, n, G, garments, gslots, exps in sources:
+        su = esz if exps is None else 1                      # source / column unit in bytes
+        rows, cols, base = facts(kv, n * G, address).unbind(1)                                               # (N'_f, C_f), (C_f, ld'_f)
+        g, u = t(garments).view(-1, 1, 1), t(gslots).view(-1, 1, 1)
+        unit = rows * cols * su                                                                              # bytes per (timestep, garment)
+        dst = dbase + u * dunit
+        exp = 0 if exps is None else address(exps) + 4 * (g * (2 * F) + torch.arange(2 * F).view(F, 2))
+        rec = runs(base + g * unit, dst, exp, rows, cols * su, dcols * su, G * unit, S * dunit)              # [P][U][F][2][7]
+        if bool((dcols > cols).any()):                       # (K, V^T, the V^T zero run) of every feature, the last where there is a tail
+            tail = runs(0, dst + cols * esz, 0, rows, (dcols - cols) * su, dcols * su, 0, S * dunit)[:, :, :, 1:]
+            keep = torch.cat([torch.ones(F, 2, dtype=torch.bool), dcols[:, 1:] > cols[:, 1:]], dim=1)
+            rec = torch.cat([rec, tail], dim=3)[keep.expand(P, len(garments), F, 3)]
+        tmpl.append(rec.reshape(P, -1, 7))
     from . import ops
-    if copy:                                                                                               # byte units throughout
-        return ops.kv_unpack_rows(sbase + si * unit * esz, dbase + di * unit * esz, 0, rows, cols * esz, cols * esz, cols * esz).reshape(-1, 5)
-    ex = address(exps) + 4 * ((torch.tensor(garments, dtype=I64).view(1, -1, 1, 1) * F + torch.arange(F, dtype=I64).view(1, 1, F, 1)) * 2
-                              + torch.arange(2, dtype=I64).view(1, 1, 1, 2))
-    return ops.kv_unpack_rows(sbase + si * unit, dbase + di * unit * esz, ex, rows, cols, cols, cols).reshape(-1, 5)
+    T = torch.stack([ops.kv_pad_even(x) for x in torch.cat(tmpl, dim=1)])   # [P][per][7], per even
+    rec = T[:, None, :, :5].repeat(1, len(entries), 1, 1)
+    rec[..., :2] += torch.tensor([entries, tslots], dtype=I64).t().unsqueeze(1) * T[:, None, :, 5:]
+    return rec.reshape(-1, 5), T.shape[1]
+
+
+def cache_sources(gc, garments):
+    """The sources (kv_records) that put garments `garments` of cache gc into garment slots 0, 1, ...: the cache's one list, or, shelved,
+    one compact part each."""
+    slots = list(range(len(garments)))
+    if isinstance(gc, ShelvedGarmentCache):
+        return [(gc.parts[g].kv, len(gc.timesteps), 1, [0], [u], gc.parts[g].exps if gc.packed else None) for u, g in zip(slots, garments)]
+    return [(gc.kv, len(gc.timesteps), gc.G, garments, slots, gc.exps if gc.packed else None)]
+
+
+def fill_records(src_kv, n, G, dst_kv, k, S, exps, entries, tslots, garments, gslots, address=None):
+    """kv_records of ONE source of the slots' own size -- garments `garments` of the list src_kv (n timesteps of G; packed with exps, 16-bit
+    with None) into garment slots `gslots` --: one record per (timestep, garment, feature, K | V^T), in that order."""
+    return kv_records([(src_kv, n, G, garments, gslots, exps)], [dst_kv], k, S, entries, tslots, address)[0]
 
 
 def shelf_records(parts, packed, dst_kv, k, S, entries, tslots, gslots, address=None):
-    """The idmvton_kv_fill descriptor records (ops.KvFillTable: int64 [N][5]) that put the COMPACT garments `parts` (G = 1 caches of n
-    timesteps each, all packed or all 16-bit) into garment slots `gslots` of the 16-bit list dst_kv (k timesteps of S slots of the slot size),
-    for every pair (entry i, timestep slot j) of (entries, tslots).  Per (timestep, garment, feature):
-      K      one data run of the garment's own N'_f rows into the front of the slot (rows beyond are not written: no kernel reads them);
-      V^T    one data run of C_f rows x ld'_f positions, source row stride ld'_f, destination row stride the slot's ld_f;
-      tail   where ld'_f < ld_f, one ZERO RUN (src 0) of C_f rows x (ld_f - ld'_f) positions behind it -- the whole tail, as _put_slotted writes
-             it, so a set's V^T depends on the garment alone and not on what the slot held before.
-    Widening form (packed parts): cols / lds in bytes = elements, ldd in 16-bit elements, exp the address of the part's exponent; copy form:
-    cols, lds, ldd in bytes, exp 0.  A timestep's records are padded to an even count by repeating its smallest record (ops.kv_pad_even: a
-    slice of the table starts at an even index).  -> (records, per) with `per` the records of one timestep: timestep number t of
-    (entries, tslots) owns records [t * per, (t + 1) * per).  address(tensor): as fill_records, asked once per source tensor.  Pure address
-    arithmetic on CPU tensors."""
-    from . import ops
-    I64 = torch.int64
-    address = address or (lambda t: t.data_ptr())
-    esz = dst_kv[0][0].element_size()
-    su = 1 if packed else esz                              # source / column unit in bytes
-    tmpl, sinc, dinc = [], [], []                          # records of timestep (entry 0, slot 0); src / dst advance per entry / timestep slot
-    for part, u in zip(parts, gslots):
-        n = len(part.timesteps)
-        ex = address(part.exps) if packed else 0
-        for f, ((sk, sv), (dk, dv)) in enumerate(zip(part.kv, dst_kv)):
-            Nf, C, ldf = sk.shape[0] // n, sk.shape[1], sv.shape[2]
-            N, ld = dk.shape[0] // (k * S), dv.shape[2]
-            ek, ev = (ex + 4 * (f * 2), ex + 4 * (f * 2 + 1)) if packed else (0, 0)
-            dK, dV = dk.data_ptr() + u * N * C * esz, dv.data_ptr() + u * C * ld * esz
-            tmpl.append((address(sk), dK, ek, Nf | ((C * su) << 32), (C * su) | ((C * (1 if packed else esz)) << 32)))
-            sinc.append(Nf * C * su); dinc.append(S * N * C * esz)
-            tmpl.append((address(sv), dV, ev, C | ((ldf * su) << 32), (ldf * su) | ((ld * (1 if packed else esz)) << 32)))
-            sinc.append(C * ldf * su); dinc.append(S * C * ld * esz)
-            if ldf < ld:                                     # the zero run: nothing is loaded, lds is ignored
-                tmpl.append((0, dV + ldf * esz, 0, C | (((ld - ldf) * su) << 32), ((ld - ldf) * su) | ((ld * (1 if packed else esz)) << 32)))
-                sinc.append(0); dinc.append(S * C * ld * esz)
-    T = torch.tensor(tmpl, dtype=I64).reshape(-1, 5)
-    sinc, dinc = torch.tensor(sinc, dtype=I64), torch.tensor(dinc, dtype=I64)
-    if T.shape[0] % 2:
-        m = int(((T[:, 3] & 0xffffffff) * ((T[:, 3] >> 32) >> 4)).argmin())
-        T, sinc, dinc = ops.kv_pad_even(T), torch.cat([sinc, sinc[m:m + 1]]), torch.cat([dinc, dinc[m:m + 1]])
-    rec = T.unsqueeze(0).repeat(len(entries), 1, 1)
-    rec[:, :, 0] += torch.tensor(entries, dtype=I64).view(-1, 1) * sinc.view(1, -1)
-    rec[:, :, 1] += torch.tensor(tslots, dtype=I64).view(-1, 1) * dinc.view(1, -1)
-    return rec.reshape(-1, 5).contiguous(), T.shape[0]
-
-
-class _StagedPart:
-    """What shelf_records reads of a part, for the part's k-timestep image in a staging arena."""
-
-    def __init__(self, kv, k, exps):
-        self.kv, self.timesteps, self.exps = kv, range(k), exps
+    """kv_records of the COMPACT garments `parts` (G = 1 caches, all packed or all 16-bit), one source each, into the front of garment slots
+    `gslots`, zero V^T tails included.  -> (records, per)."""
+    return kv_records([(p.kv, len(p.timesteps), 1, [0], [u], p.exps if packed else None) for p, u in zip(parts, gslots)],
+                      [dst_kv], k, S, entries, tslots, address)
 
 
 def staged_plan(gc, gindex, k, S, dst_kvs, device, arena=None, exps=None):
-    """The copy-engine transport of a host-resident cache (pipeline.py, _staged_fill), as data: no kernel and no GPU call in here, so it runs on
+    """The copy-engine transport of a host-resident cache (pipeline.py, _cached_fill), as data: no kernel and no GPU call in here, so it runs on
     CPU tensors.  A block of c <= k timesteps of the call's U distinct garments (first-use order; all G without gindex) is first COPIED into a
-    staging arena -- a k-timestep, U-garment list in the source's own storage (uint8 of a packed cache, else its 16-bit dtype); for a
-    ShelvedGarmentCache each part's compact k-timestep, one-garment list, back to back -- and then PLACED by one idmvton_kv_place launch into
-    slots 0 .. U - 1 of the first c timestep slots of a 16-bit list of k timesteps of S slots.
+    staging arena -- per source (cache_sources) a k-timestep list of its used garments in its own storage (uint8 of a packed cache, else its
+    16-bit dtype), back to back -- and then PLACED by one idmvton_kv_place launch into slots 0 .. U - 1 of the first c timestep slots of a
+    16-bit list of k timesteps of S slots.
     The arena is one flat uint8 tensor on `device`: k * (the used garments' source bytes per timestep), every tensor carved at a multiple of
     16 bytes.  Pass the `arena` / `exps` of an earlier plan to use them again (an arena that is too small is replaced).  dst_kvs: the
     destination lists, one per set.  ->
@@ -684,14 +676,15 @@ def staged_plan(gc, gindex, k, S, dst_kvs, device, arena=None, exps=None):
       copies(idx)     [(dst, src)] tensor views that bring cache entries idx (a block, by value) into arena timestep slots 0 .. len(idx) - 1:
                       _fill_set's gather -- one pair per tensor when the entries are consecutive and there is no index (shelved: per part
                       tensor), else one per timestep and run of consecutive garments
-      rec, per        the place records of every set (fill_records / shelf_records pointed at the arena) and the records per timestep: set p's
+      rec, per        the place records of every set (kv_records with the arena's lists as sources) and the records per timestep: set p's
                       block of c timesteps is records [p * k * per, p * k * per + c * per) -- a prefix, as the arena's addresses never change."""
-    shelved = isinstance(gc, ShelvedGarmentCache)
     n = len(gc.timesteps)
     garments = list(range(gc.G)) if gindex is None else list(dict.fromkeys(gindex))
     U = len(garments)
-    sources = [(gc.parts[g].kv, 1, 1) for g in garments] if shelved else [(gc.kv, gc.G, U)]   # (list, garments it holds, garments the arena takes)
-    shapes = [[(((a[0] // (n * G)) * k * u,) + a[1:], ((b[0] // (n * G)) * k * u,) + b[1:], d) for a, b, d in kv_shapes(kv)] for kv, G, u in sources]
+    srcs = cache_sources(gc, garments)
+    whole = gindex is None or isinstance(gc, ShelvedGarmentCache)   # every source list moves whole: all its garments, in its own order
+    shapes = [[(((a[0] // (n * G)) * k * len(gs),) + a[1:], ((b[0] // (n * G)) * k * len(gs),) + b[1:], d) for a, b, d in kv_shapes(kv)]
+              for kv, _, G, gs, _, _ in srcs]
     size = lambda sh, d: torch.Size(sh).numel() * torch.empty((), dtype=d).element_size()
     nbytes = sum(size(a, d) + size(b, d) for lst in shapes for a, b, d in lst)
     if arena is None or arena.numel() < nbytes:
@@ -707,37 +700,24 @@ def staged_plan(gc, gindex, k, S, dst_kvs, device, arena=None, exps=None):
             kv.append(tuple(pair))
         lists.append(kv)
     pairs = lambda dst, src: [(d, s) for dp, sp in zip(dst, src) for d, s in zip(dp, sp)]
-    exps_copies = []
     if gc.packed:
-        F = len(lists[0])
-        if exps is None:
-            exps = torch.empty((U, F, 2), dtype=torch.int32, device=device)
-        if shelved:
-            exps_copies = [(exps[u:u + 1], gc.parts[g].exps) for u, g in enumerate(garments)]
-        else:
-            exps_copies = [(exps[d0:d0 + cc], gc.exps[g0:g0 + cc]) for d0, g0, cc in index_runs(garments)]
+        exps = torch.empty((U, len(lists[0]), 2), dtype=torch.int32, device=device) if exps is None else exps
+        exps_copies = [(exps[us[0] + d0:us[0] + d0 + cc], ex[g0:g0 + cc]) for _, _, _, gs, us, ex in srcs for d0, g0, cc in index_runs(gs)]
     else:
-        exps = None
-    if shelved:
-        parts = [_StagedPart(kv, k, exps[u:u + 1] if gc.packed else None) for u, kv in enumerate(lists)]
-        recs = [shelf_records(parts, gc.packed, dst, k, S, list(range(k)), list(range(k)), list(range(U))) for dst in dst_kvs]
-        rec, per = torch.cat([r for r, _ in recs]), recs[0][1]
-    else:
-        rec = torch.cat([fill_records(lists[0], k, U, dst, k, S, exps, list(range(k)), list(range(k)), list(range(U)), list(range(U))) for dst in dst_kvs])
-        per = U * len(lists[0]) * 2
+        exps, exps_copies = None, []
+    staged = [(lst, k, len(gs), list(range(len(gs))), us, exps[us[0]:us[0] + len(us)] if gc.packed else None) for lst, (_, _, _, gs, us, _) in zip(lists, srcs)]
+    rec, per = kv_records(staged, dst_kvs, k, S, list(range(k)), list(range(k)))
 
     def copies(idx):
         idx = list(idx)
         c = len(idx)
         steps = [(0, idx[0], c)] if idx == list(range(idx[0], idx[0] + c)) else [(j, i, 1) for j, i in enumerate(idx)]
-        if shelved:
-            return [p for kv, g in zip(lists, garments) for j0, i0, cc in steps
-                    for p in pairs(timestep_run(kv, k, 1, j0, cc), timestep_run(gc.parts[g].kv, n, 1, i0, cc))]
-        if gindex is None:
-            return [p for j0, i0, cc in steps for p in pairs(timestep_run(lists[0], k, U, j0, cc), timestep_run(gc.kv, n, gc.G, i0, cc))]
+        if whole:
+            return [p for lst, (kv, _, G, _, _, _) in zip(lists, srcs) for j0, i0, cc in steps
+                    for p in pairs(timestep_run(lst, k, G, j0, cc), timestep_run(kv, n, G, i0, cc))]
         return [p for j, i in enumerate(idx) for d0, g0, cc in index_runs(garments)
                 for p in pairs(slot_run(lists[0], k, U, j, d0, cc), slot_run(gc.kv, n, gc.G, i, g0, cc))]
-    return dict(arena=arena, nbytes=nbytes, exps=exps, exps_copies=exps_copies, copies=copies, rec=rec.contiguous(), per=per, lists=lists)
+    return dict(arena=arena, nbytes=nbytes, exps=exps, exps_copies=exps_copies, copies=copies, rec=rec, per=per, lists=lists)
 
 
 class ShelvedGarmentCache(GarmentCache):

@@ -320,6 +320,11 @@ KV_UNPACK_CHUNK = 1024                                   # 16-byte items one wor
 KV_UNPACK_MAX_N = 65534                                  # descriptors per launch (grid.y; even: a slice of a table stays 16-byte aligned)
 
 
+def kv_items(rec):
+    """Descriptor records int64 [n][5] -> int64 [n], the 16-byte items of each run: rows x cols / 16."""
+    return (rec[:, 3] & 0xffffffff) * ((rec[:, 3] >> 32) >> 4)
+
+
 class KvUnpackTable:
     """The descriptor table of idmvton_kv_unpack: `host` -- int64 CPU tensor [n][5] whose rows ARE idmvton_kv_unpack_desc records (src, dst,
     exp, rows | cols << 32, lds | ldd << 32: little-endian, 40 bytes) --, `dev` its device copy (one upload), and `items` the 16-byte items
@@ -329,8 +334,7 @@ class KvUnpackTable:
     def __init__(self, host, device):
         self.host = host.contiguous()
         self.n = self.host.shape[0]
-        lo = lambda c: self.host[:, c] & 0xffffffff
-        self.items = lo(3) * ((self.host[:, 3] >> 32) >> 4)
+        self.items = kv_items(self.host)
         self.dev = self.host.to(device)
 
     def launch(self, dtype, first=0, count=None):
@@ -351,13 +355,6 @@ class KvUnpackTable:
             launch()
             e1.record()
             PROFILE.append(("idmvton_kv_unpack", e0, e1, 0.0, 48.0 * float(self.items[f0:f0 + c].sum())))
-
-
-def kv_unpack_rows(src, dst, exp, rows, cols, lds, ldd):
-    """int64 [..., 5] descriptor records from broadcastable int64 tensors / ints (addresses and sizes): see KvUnpackTable."""
-    t = lambda v: v if isinstance(v, torch.Tensor) else torch.tensor(v, dtype=torch.int64)
-    src, dst, exp, rows, cols, lds, ldd = torch.broadcast_tensors(*[t(v) for v in (src, dst, exp, rows, cols, lds, ldd)])
-    return torch.stack([src, dst, exp, rows | (cols << 32), lds | (ldd << 32)], dim=-1)
 
 
 def kv_unpack(descs, dtype, device=None):
@@ -418,7 +415,7 @@ class KvStreamTable:
         for f, c in self.slices:
             if f % 2 or f < 0 or c < 1 or c > KV_STREAM_MAX_N or f + c > self.n:
                 raise ValueError(f"kv_stream: descriptors [{f}, {f + c}) of {self.n} (an even first index, 1 to {KV_STREAM_MAX_N} descriptors)")
-        self.items = (self.host[:, 3] & 0xffffffff) * ((self.host[:, 3] >> 32) >> 4)
+        self.items = kv_items(self.host)
         firsts = [kv_stream_first(self.items[f:f + c]) for f, c in self.slices]
         self.first_at, at = [], 0
         for t in firsts:
@@ -475,53 +472,29 @@ def kv_pad_even(rec):
     at even record indices (16-byte aligned device addresses), and writing identical bytes twice is what clamped lanes already do."""
     if rec.shape[0] % 2 == 0:
         return rec
-    items = (rec[:, 3] & 0xffffffff) * ((rec[:, 3] >> 32) >> 4)
-    return torch.cat([rec, rec[int(items.argmin())].view(1, 5)])
+    m = int(kv_items(rec).argmin())
+    return torch.cat([rec, rec[m:m + 1]])
 
 
-def kv_stream(descs, dtype, mode=ffi.KVS_WIDEN_E4M3, workgroups=None, device=None):
-    """idmvton_kv_stream on every run of `descs`, in one launch of `workgroups` persistent workgroups.  descs: a KvStreamTable (its slice 0), or a
-    list of (src, dst, exp) 2-D tensor views of equal shape, rows contiguous -- mode KVS_WIDEN_E4M3: src uint8 e4m3 bytes, dst of `dtype`, exp a
-    one-element int32 view, dst = dtype(e4m3(src) * 2^-exp) exactly; mode KVS_COPY: src and dst of one dtype, exp None, a copy.  src and exp
-    may each be a device tensor or a PAGE-LOCKED host tensor (stream_address: a pageable one is a ValueError), dst is a device tensor.
-    -> the table."""
-    if not isinstance(descs, KvStreamTable):
-        widen = mode == ffi.KVS_WIDEN_E4M3
-        rec = []
-        for src, dst, exp in descs:
-            ok = src.dim() == 2 and src.shape == dst.shape and src.stride(1) == 1 and dst.stride(1) == 1 and dst.is_cuda
-            if widen:
-                ok = ok and src.dtype == torch.uint8 and dst.dtype == dtype and exp is not None and exp.dtype == torch.int32 and exp.numel() == 1
-            else:
-                ok = ok and src.dtype == dst.dtype
-            if not ok:
-                raise ValueError("kv_stream: a run is (uint8 [rows][cols], %s [rows][cols], one int32) when widening, (x [rows][cols], x [rows][cols], None) "
-                                 "when copying; rows contiguous, the destination on the device" % dtype)
-            rows, cols = src.shape
-            sz = 1 if widen else src.element_size()          # copy mode: byte units
-            rec.append((stream_address(src), _ptr(dst), stream_address(exp) if widen else 0, rows | ((cols * sz) << 32),
-                        (src.stride(0) * sz) | ((dst.stride(0) * sz) << 32)))
-        device = descs[0][1].device if device is None else device
-        descs = KvStreamTable(torch.tensor(rec, dtype=torch.int64).reshape(-1, 5), device, mode)
-    descs.launch(dtype, 0, workgroups)
-    return descs
-
-
-def _kv_fill_table(cls, descs, dtype, mode, device):
-    """(src | None, dst, exp | None) views -> a table of class `cls` (KvFillTable / KvPlaceTable): a run whose src is None is a zero run."""
-    widen = mode == ffi.KVS_WIDEN_E4M3
+def _kv_table(cls, descs, dtype, mode, device):
+    """A table of class `cls`, or a list of (src, dst, exp) 2-D tensor views from which one is built -> the table.  Where cls launches through
+    an entry point with zero runs (every one but KvStreamTable's), a run whose src is None is one."""
+    if isinstance(descs, KvStreamTable):
+        return descs
+    widen, zero_ok = mode == ffi.KVS_WIDEN_E4M3, cls is not KvStreamTable
     rec = []
     for src, dst, exp in descs:
-        ok = dst.dim() == 2 and dst.stride(1) == 1 and dst.is_cuda and (not widen or dst.dtype == dtype)
-        if src is not None:
-            ok = ok and src.dim() == 2 and src.shape == dst.shape and src.stride(1) == 1
+        ok = dst.dim() == 2 and dst.stride(1) == 1 and dst.is_cuda and (not widen or dst.dtype == dtype) and (zero_ok or src is not None)
+        if ok and src is not None:
+            ok = src.dim() == 2 and src.shape == dst.shape and src.stride(1) == 1
             if widen:
                 ok = ok and src.dtype == torch.uint8 and exp is not None and exp.dtype == torch.int32 and exp.numel() == 1
             else:
                 ok = ok and src.dtype == dst.dtype
         if not ok:
             raise ValueError("%s: a run is (uint8 [rows][cols], %s [rows][cols], one int32) when widening, (x [rows][cols], x [rows][cols], None) "
-                             "when copying, (None, dst [rows][cols], None) for a zero run; rows contiguous, the destination on the device" % (cls.ENTRY, dtype))
+                             "when copying%s; rows contiguous, the destination on the device"
+                             % (cls.ENTRY, dtype, ", (None, dst [rows][cols], None) for a zero run" if zero_ok else ""))
         rows, cols = dst.shape
         sz = 1 if widen else dst.element_size()          # copy mode: byte units
         if src is None:
@@ -533,12 +506,22 @@ def _kv_fill_table(cls, descs, dtype, mode, device):
     return cls(torch.tensor(rec, dtype=torch.int64).reshape(-1, 5), device, mode)
 
 
+def kv_stream(descs, dtype, mode=ffi.KVS_WIDEN_E4M3, workgroups=None, device=None):
+    """idmvton_kv_stream on every run of `descs`, in one launch of `workgroups` persistent workgroups.  descs: a KvStreamTable (its slice 0), or a
+    list of (src, dst, exp) 2-D tensor views of equal shape, rows contiguous -- mode KVS_WIDEN_E4M3: src uint8 e4m3 bytes, dst of `dtype`, exp a
+    one-element int32 view, dst = dtype(e4m3(src) * 2^-exp) exactly; mode KVS_COPY: src and dst of one dtype, exp None, a copy.  src and exp
+    may each be a device tensor or a PAGE-LOCKED host tensor (stream_address: a pageable one is a ValueError), dst is a device tensor.
+    -> the table."""
+    descs = _kv_table(KvStreamTable, descs, dtype, mode, device)
+    descs.launch(dtype, 0, workgroups)
+    return descs
+
+
 def kv_fill(descs, dtype, mode=ffi.KVS_WIDEN_E4M3, workgroups=None, device=None):
     """idmvton_kv_fill on every run of `descs`, in one launch: ops.kv_stream's arguments, and a run whose src is None is a ZERO RUN -- (None,
     dst, None) writes +0 (widening) / zero bytes (copying) over dst's [rows][cols] and loads nothing.  descs: a KvFillTable (its slice 0) or
     a list of (src | None, dst, exp | None) views.  -> the table."""
-    if not isinstance(descs, KvStreamTable):
-        descs = _kv_fill_table(KvFillTable, descs, dtype, mode, device)
+    descs = _kv_table(KvFillTable, descs, dtype, mode, device)
     descs.launch(dtype, 0, workgroups)
     return descs
 
@@ -547,8 +530,7 @@ def kv_place(descs, dtype, mode=ffi.KVS_WIDEN_E4M3, device=None):
     """idmvton_kv_place on every run of `descs`, in one launch of one workgroup per chunk: ops.kv_fill's arguments without `workgroups`, zero
     runs included.  descs: a KvPlaceTable (its slice 0) or a list of (src | None, dst, exp | None) views; src and exp may each be a device
     tensor -- what the entry point is built for -- or a page-locked host tensor.  -> the table."""
-    if not isinstance(descs, KvStreamTable):
-        descs = _kv_fill_table(KvPlaceTable, descs, dtype, mode, device)
+    descs = _kv_table(KvPlaceTable, descs, dtype, mode, device)
     descs.launch(dtype, 0)
     return descs
 

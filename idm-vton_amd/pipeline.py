@@ -31,20 +31,18 @@ execution form is the pair of callables it hands over:
     eager, live    _garment_side into set p                          _tryon_main on set p's views of slot j
     eager, cache   nothing to launch                                 _tryon_main on the cache's own views of entry gidx[i]
     graph, live    copy temb_gk[bi], replay ('garm', p, c)           copy tt / cf / nz, replay ('tryon', p, j)
-    graph, cache   _fill_set: the block's cache entries -> set p     as graph, live
-A PACKED cache (GarmentCache.pack, encode_garment(storage="e4m3")) holds e4m3 bytes that TryonNet cannot read, so all four forms go through 16-bit
-sets: `_packed_fill` widens a block's cache entries into set p with ONE idmvton_kv_unpack launch, from a descriptor table built and uploaded once
-per call; the eager forms then use sets too (one, or two with overlap), and with garment_index the P-slot sets and slot table of the graph forms.
-A HOST-RESIDENT cache (page-locked CPU tensors: GarmentCache.to("cpu", pin_memory=True), GarmentPool(resident="host")), packed or 16-bit, goes
-the same way through sets in all four forms: `_stream_fill`, _packed_fill's twin, moves a block from host memory straight into set p with ONE
-idmvton_kv_stream launch (widening e4m3 bytes, or copying 16-bit values) -- in _fill_set's place in drive_blocks' order, so every block but
-the first crosses the host link behind the TryonNet steps of the block before it.  Nothing of the cache is in HBM before the call.
-A SHELVED cache (ShelvedGarmentCache, GarmentShelf.get: compact garments of many sizes in page-locked memory) goes the same way again:
-`_shelf_fill` puts each garment into the front of a set slot and writes the zero V^T tail behind it with ONE idmvton_kv_fill launch per block;
-key-count table, slot table, set shapes and graph key are those of a device-resident slotted cache of the same slot size.
-Both host-resident forms have a second TRANSPORT, host_transport="copy" (opt-in per call; "kernel" is the above): `_staged_fill` brings a block's
-source bytes into a block-sized staging arena in HBM with copy_(non_blocking=True) -- the copy engines -- and ONE idmvton_kv_place launch puts
-them into set p, so no kernel reads host memory beside TryonNet.  Same sets, same bits, same graph states.
+    graph, cache   _cached_fill: the block's cache entries -> set p  as graph, live
+Only a 16-bit cache on the device can be read in place.  A PACKED cache (GarmentCache.pack, encode_garment(storage="e4m3")) holds e4m3 bytes,
+a HOST-RESIDENT one (page-locked CPU tensors: GarmentCache.to("cpu", pin_memory=True), GarmentPool(resident="host")) is not in HBM, and a
+SHELVED one (ShelvedGarmentCache, GarmentShelf.get) holds compact garments of many sizes in page-locked memory: those go through 16-bit sets
+in all four forms -- the eager forms then use sets too (one, or two with overlap), and with garment_index the P-slot sets and slot table of
+the graph forms.  `_cached_fill` returns garment(bi, p) for every kind of cache, in _fill_set's place in drive_blocks' order (so every block
+but the first crosses the host link behind the TryonNet steps of the block before it): ONE launch per block from a descriptor table built
+and uploaded once per call -- idmvton_kv_unpack (packed, on the device), idmvton_kv_stream (host-resident), idmvton_kv_fill (shelved: the
+zero V^T tail behind each garment too); key-count table, slot table, set shapes and graph key of a shelved cache are those of a
+device-resident slotted cache of the same slot size.  The host-resident kinds have a second TRANSPORT, host_transport="copy" (opt-in per
+call; "kernel" is the above): the copy engines bring a block's source bytes into a block-sized staging arena in HBM and ONE idmvton_kv_place
+launch puts them into set p, so no kernel reads host memory beside TryonNet.  Same sets, same bits, same graph states.
 With garment_index the two cache rows read through the table: eager on the cache's own views (nb = G, table = garment_index), graph on
 P-slot sets into which _fill_set gathers the U distinct garments of the call (table = person -> set slot, a persistent buffer of the state).
 
@@ -54,7 +52,7 @@ blocks.  The K / V^T layout of sets and cache (timestep-major) has one owner, ga
 import torch
 
 from . import ops
-from .garment_cache import (GarmentCache, PackedGarmentCache, ShelvedGarmentCache, alloc_kv, fill_records, index_runs, kv_shapes, shelf_records,
+from .garment_cache import (GarmentCache, PackedGarmentCache, ShelvedGarmentCache, alloc_kv, cache_sources, index_runs, kv_records, kv_shapes,
                             slot_run, staged_plan, timestep_run)
 from .scheduler import StepScheduler
 
@@ -122,7 +120,7 @@ class TryonEngine:
         # arena (the copy engines), and blocks placed from the arena into a set (one idmvton_kv_place launch each)
         self.stats = dict(garment_batches=0, garment_set_copies=0, garment_stream_launches=0, garment_stage_copies=0, garment_stage_launches=0)
         self._streaming = []                                 # [cache, event of its last queued fill]: host memory a queued launch still reads
-        self._arenas = {}                                    # _staged_fill's staging arenas: one per call shape, reused across calls
+        self._arenas = {}                                    # _cached_fill's staging arenas: one per call shape, reused across calls
         self._weights_id = None
 
     # -------------------------------------------------------------------------------------------- shared by prepare / encode_garment
@@ -321,7 +319,7 @@ class TryonEngine:
         garment_index (with a GarmentCache only): B ints in [0, G), person i wears garment garment_index[i] -- any B >= 1, values may repeat,
         no B % G rule; the cache is a pool, and G may exceed B.  A cache with `sizes` (garments of several sizes in slots of one size) needs
         garment_index: which size a person's garment has follows from the slot it names.
-        A HOST-RESIDENT cache (CPU tensors) is streamed into the sets block by block during the call (_stream_fill); every tensor -- and a
+        A HOST-RESIDENT cache (CPU tensors) is streamed into the sets block by block during the call (_cached_fill); every tensor -- and a
         packed cache's `exps` -- must be page-locked (pin_memory), the cache must not have `sizes`, and the engine must not be attn_fp8: each
         a ValueError naming the field, before anything is launched.  A ShelvedGarmentCache (GarmentShelf.get) is the host-resident cache WITH
         sizes: garment_index is required, every part and every part's `exps` must be page-locked, the engine must not be attn_fp8."""
@@ -529,121 +527,9 @@ class TryonEngine:
 
     def _release_streamed(self):
         """Drop the engine's references to host-resident caches whose last queued fill has completed (an event that was never recorded counts
-        as passed).  Called by every `prepare`, `decode` and `_stream_fill`, and after a graph state's warm-up: the engine keeps a streamed
+        as passed).  Called by every `prepare`, `decode` and `_cached_fill`, and after a graph state's warm-up: the engine keeps a streamed
         cache alive from its first fill until the first of those calls after its last fill has finished -- not beyond the next call."""
         self._streaming = [h for h in self._streaming if not h[1].query()]
-
-    def _stream_fill(self, st, sets, blocks=None):
-        """-> garment(bi, p) of a call on a HOST-RESIDENT cache, _packed_fill's twin: block bi's cache entries go from page-locked host memory
-        straight into the first timestep slots of sets[p] by ONE idmvton_kv_stream launch on the current stream -- widening e4m3 bytes (a
-        packed cache) or copying 16-bit values.  The gather is _fill_set's (entries by value; with garment_index the U distinct garments in
-        first-use order into slots 0 .. U - 1 of P-slot sets); table and prefix tables are built and uploaded ONCE, here, with one
-        idmvton_host_device_ptr per cache tensor, and a block is a slice.  `blocks`: build for these block numbers only (the warm-up).
-        The launches read host memory by raw address: the cache stays referenced by the engine until the last one has completed."""
-        gc, k = st["gcache"], st["k"]
-        if isinstance(gc, ShelvedGarmentCache):
-            return self._shelf_fill(st, sets, blocks)
-        n = len(gc.timesteps)
-        garments = list(range(gc.G)) if st["gindex"] is None else list(dict.fromkeys(st["gindex"]))
-        S = gc.G if st["gindex"] is None else st["B"]
-        built = [bi for bi in range(len(st["blocks"])) if blocks is None or bi in blocks]
-        steps = [(st["blocks"][bi][0] + j, j) for bi in built for j in range(st["blocks"][bi][1])]
-        first = {i: at for at, (i, _) in enumerate(steps)}   # step of the call -> its place in a set's part of the table
-        per = len(garments) * len(gc.kv) * 2                 # records per step: even, so every slice starts 16-byte aligned
-        addr = {}                                            # one idmvton_host_device_ptr per tensor, whatever the number of sets
-
-        def address(t):
-            if t.data_ptr() not in addr:
-                addr[t.data_ptr()] = ops.stream_address(t)
-            return addr[t.data_ptr()]
-        rec = torch.cat([fill_records(gc.kv, n, gc.G, fs["kv"], k, S, gc.exps if gc.packed else None, [st["gidx"][i] for i, _ in steps],
-                                      [j for _, j in steps], garments, list(range(len(garments))), address=address) for fs in sets])
-        which = {(p, bi): at for at, (p, bi) in enumerate((p, bi) for p in range(len(sets)) for bi in built)}
-        table = ops.KvStreamTable(rec, self.device, ops.ffi.KVS_WIDEN_E4M3 if gc.packed else ops.ffi.KVS_COPY,
-                                  [((p * len(steps) + first[st["blocks"][bi][0]]) * per, st["blocks"][bi][1] * per) for p, bi in which])
-        self._release_streamed()
-        hold = [gc, torch.cuda.Event()]
-        self._streaming.append(hold)
-
-        def garment(bi, p):
-            self.stats["garment_stream_launches"] += 1
-            table.launch(self.dtype, which[(p, bi)])
-            hold[1].record()                                 # the call's last fill so far: until it has passed, `hold` keeps the cache alive
-        return garment
-
-    def _shelf_fill(self, st, sets, blocks=None):
-        """-> garment(bi, p) of a call on a SHELVED cache, _stream_fill's twin: the U distinct garments of the call, in first-use order, go from
-        their own compact tensors in page-locked host memory into the FRONT of slots 0 .. U - 1 of the first timestep slots of sets[p], and
-        the zero V^T tail behind each, by ONE idmvton_kv_fill launch per block on the current stream (shelf_records: K rows beyond a
-        garment's own are not written, no kernel reads them).  Table and prefix tables are built and uploaded ONCE, here, with one
-        idmvton_host_device_ptr per part tensor; a block is a slice.  The cache -- and through it its parts, whatever the shelf does
-        meanwhile -- stays referenced by the engine until the last launch has completed."""
-        gc, k = st["gcache"], st["k"]
-        garments = list(dict.fromkeys(st["gindex"]))         # (a cache with sizes is always indexed)
-        S = st["B"]
-        built = [bi for bi in range(len(st["blocks"])) if blocks is None or bi in blocks]
-        steps = [(st["blocks"][bi][0] + j, j) for bi in built for j in range(st["blocks"][bi][1])]
-        first = {i: at for at, (i, _) in enumerate(steps)}   # step of the call -> its place in a set's part of the table
-        addr = {}
-
-        def address(t):
-            if t.data_ptr() not in addr:
-                addr[t.data_ptr()] = ops.stream_address(t)
-            return addr[t.data_ptr()]
-        parts = [gc.parts[g] for g in garments]
-        recs = [shelf_records(parts, gc.packed, fs["kv"], k, S, [st["gidx"][i] for i, _ in steps], [j for _, j in steps],
-                              list(range(len(garments))), address=address) for fs in sets]
-        per = recs[0][1]                                     # records per step, padded even: every slice starts 16-byte aligned
-        which = {(p, bi): at for at, (p, bi) in enumerate((p, bi) for p in range(len(sets)) for bi in built)}
-        table = ops.KvFillTable(torch.cat([r for r, _ in recs]), self.device, ops.ffi.KVS_WIDEN_E4M3 if gc.packed else ops.ffi.KVS_COPY,
-                                [((p * len(steps) + first[st["blocks"][bi][0]]) * per, st["blocks"][bi][1] * per) for p, bi in which])
-        self._release_streamed()
-        hold = [gc, torch.cuda.Event()]
-        self._streaming.append(hold)
-
-        def garment(bi, p):
-            self.stats["garment_stream_launches"] += 1
-            table.launch(self.dtype, which[(p, bi)])
-            hold[1].record()
-        return garment
-
-    def _staged_fill(self, st, sets, blocks=None):
-        """-> garment(bi, p) of a call on a host-resident cache -- plain or shelved, packed or 16-bit -- with host_transport="copy", the twin of
-        _stream_fill / _shelf_fill: block bi's source bytes go from page-locked host memory into a block-sized STAGING ARENA in HBM by
-        copy_(non_blocking=True) -- the copy engines, no kernel reads the host link -- and ONE idmvton_kv_place launch then puts them into the
-        first timestep slots of sets[p]: widening or copying, the V^T row stride changed, the zero V^T tails written (garment_cache.staged_plan
-        holds the gather and the tables; they are fill_records / shelf_records pointed at the arena).  Copies and launch go to the current
-        stream, so block b + 1's copies follow block b's place launch and ONE arena serves both sets.  The arena belongs to the engine, one
-        per call shape (the sets' key, the source's storage, the number U of distinct garments), k x the used garments' source bytes per
-        timestep -- never the size of the cache; a shelved call with larger garments replaces it.  A packed source's exponents go to a small
-        device tensor once per call, here, ahead of the first launch in stream order.  The arena's addresses never change, so the table
-        covers k timesteps per set and a block of c is a prefix slice (`blocks` is not needed).  The cache stays referenced until the event
-        behind the last block has passed, as in _stream_fill."""
-        gc, k = st["gcache"], st["k"]
-        S = gc.G if st["gindex"] is None else st["B"]
-        U = gc.G if st["gindex"] is None else len(set(st["gindex"]))
-        key = self._set_key(st) + (torch.uint8 if gc.packed else gc.dtype, U)
-        plan = staged_plan(gc, st["gindex"], k, S, [fs["kv"] for fs in sets], self.device, *self._arenas.get(key, (None, None)))
-        self._arenas[key] = (plan["arena"], plan["exps"])
-        per = plan["per"]
-        which = {(p, c): at for at, (p, c) in enumerate((p, c) for p in range(len(sets)) for c in sorted({c for _, c in st["blocks"]}))}
-        table = ops.KvPlaceTable(plan["rec"], self.device, ops.ffi.KVS_WIDEN_E4M3 if gc.packed else ops.ffi.KVS_COPY,
-                                 [(p * k * per, c * per) for p, c in which])
-        copies = [plan["copies"](st["gidx"][s0:s0 + c]) for s0, c in st["blocks"]]
-        self._release_streamed()
-        hold = [gc, torch.cuda.Event()]
-        self._streaming.append(hold)
-        for dst, src in plan["exps_copies"]:
-            dst.copy_(src, non_blocking=True)
-
-        def garment(bi, p):
-            for dst, src in copies[bi]:
-                dst.copy_(src, non_blocking=True)
-            self.stats["garment_stage_copies"] += len(copies[bi])
-            self.stats["garment_stage_launches"] += 1
-            table.launch(self.dtype, which[(p, st["blocks"][bi][1])])
-            hold[1].record()                                 # behind the call's last copy so far: until it has passed, `hold` keeps the cache alive
-        return garment
 
     HOST_TRANSPORTS = ("kernel", "copy")
 
@@ -653,31 +539,70 @@ class TryonEngine:
             raise ValueError(f"host_transport={host_transport!r}: \"kernel\" (a kernel reads the page-locked cache: idmvton_kv_stream / idmvton_kv_fill) "
                              "or \"copy\" (the copy engines fill a staging arena, idmvton_kv_place places it)")
 
-    def _host_fill(self, st, sets, blocks=None):
-        """-> garment(bi, p) of a call on a host-resident cache, by the transport the call asked for (denoise: st["host_transport"])."""
-        return (self._staged_fill if st.get("host_transport") == "copy" else self._stream_fill)(st, sets, blocks)
-
-    def _packed_fill(self, st, sets, blocks=None):
-        """-> garment(bi, p) of a call on a PACKED cache: block bi's cache entries widened into the first timestep slots of sets[p] by ONE
-        idmvton_kv_unpack launch on the current stream.  The gather is _fill_set's -- entries by value, consecutive or not; with
-        garment_index the U distinct garments in first-use order into slots 0 .. U - 1 of P-slot sets -- written as descriptors, one per
-        (timestep, garment, feature, K | V^T): cache, set and exponent addresses are all stable, so the table of every (set, step) is built on
-        the host and uploaded ONCE, here, and a block is a slice of it.  `blocks`: build for these block numbers only (the warm-up)."""
-        gc, k = st["gcache"], st["k"]
-        n = len(gc.timesteps)
+    def _cached_fill(self, st, sets, blocks=None):
+        """-> garment(bi, p) of a call on a GarmentCache: block bi's cache entries -> the first timestep slots of sets[p], on the current
+        stream.  The gather is always _fill_set's -- entries by value, consecutive or not; with garment_index the U distinct garments in
+        first-use order into slots 0 .. U - 1 of P-slot sets --; what the cache is decides how it is carried out:
+          16-bit, on the device      _fill_set itself: copies.
+          packed, on the device      ONE idmvton_kv_unpack launch widens the block's bytes.
+          host-resident              ONE idmvton_kv_stream launch (shelved: idmvton_kv_fill, which also writes the zero V^T tail behind each
+                                     compact garment) reads page-locked host memory, widening e4m3 bytes or copying 16-bit values.
+          host-resident, st["host_transport"] == "copy"
+                                     the block's source bytes go into a block-sized STAGING ARENA in HBM by copy_(non_blocking=True) -- the
+                                     copy engines, no kernel reads the host link -- and ONE idmvton_kv_place launch places them
+                                     (garment_cache.staged_plan).  Block b + 1's copies follow block b's launch in stream order, so one arena
+                                     serves both sets; it belongs to the engine, one per call shape (the sets' key, the source's storage, U),
+                                     k x the used garments' source bytes per timestep, and a shelved call with larger garments replaces it.
+                                     A packed source's exponents go to a small device tensor once per call, here.
+        The launched forms are descriptors (garment_cache.kv_records), one table for every (set, step): cache, set, arena and exponent
+        addresses are all stable, so table and prefix tables are built and uploaded ONCE, here, with one idmvton_host_device_ptr per host
+        tensor, and a block is a slice.  `blocks`: build for these block numbers only (the warm-up; the arena's table covers k timesteps per
+        set whatever the blocks, a block of c being a prefix).  Launches and copies read a host-resident cache by raw address: it stays
+        referenced by the engine until the event behind the last one has passed (_release_streamed)."""
+        gc, k, B = st["gcache"], st["k"], st["blocks"]
+        if not (gc.packed or gc.host_resident):
+            return lambda bi, p: self._fill_set(st, sets[p], *B[bi])
         garments = list(range(gc.G)) if st["gindex"] is None else list(dict.fromkeys(st["gindex"]))
         S = gc.G if st["gindex"] is None else st["B"]
-        steps = [(s0 + j, j) for bi, (s0, c) in enumerate(st["blocks"]) if blocks is None or bi in blocks for j in range(c)]
-        first = {i: at for at, (i, _) in enumerate(steps)}   # step of the call -> its place in a set's part of the table
-        per = len(garments) * len(gc.kv) * 2                 # records per step: even, so every slice starts 16-byte aligned
-        rec = torch.cat([fill_records(gc.kv, n, gc.G, fs["kv"], k, S, gc.exps, [st["gidx"][i] for i, _ in steps], [j for _, j in steps], garments,
-                                      list(range(len(garments)))) for fs in sets])
-        table = ops.KvUnpackTable(rec, self.device)
+        staged = gc.host_resident and st.get("host_transport") == "copy"
+        built = [bi for bi in range(len(B)) if staged or blocks is None or bi in blocks]
+        if staged:
+            key = self._set_key(st) + (torch.uint8 if gc.packed else gc.dtype, len(garments))
+            plan = staged_plan(gc, st["gindex"], k, S, [fs["kv"] for fs in sets], self.device, *self._arenas.get(key, (None, None)))
+            self._arenas[key] = (plan["arena"], plan["exps"])
+            rec, per, rows, row = plan["rec"], plan["per"], k, dict.fromkeys(built, 0)
+            copies = [plan["copies"](st["gidx"][s0:s0 + c]) for s0, c in B]
+        else:
+            steps = [(B[bi][0] + j, j) for bi in built for j in range(B[bi][1])]
+            first = {i: at for at, (i, _) in enumerate(steps)}
+            rows, row = len(steps), {bi: first[B[bi][0]] for bi in built}   # block -> the place of its first step in a set's part of the table
+            rec, per = kv_records(cache_sources(gc, garments), [fs["kv"] for fs in sets], k, S, [st["gidx"][i] for i, _ in steps], [j for _, j in steps],
+                                  ops.stream_address if gc.host_resident else None)   # (records per step, even: every slice starts 16-byte aligned)
+        at = {(p, bi): ((p * rows + row[bi]) * per, B[bi][1] * per) for p in range(len(sets)) for bi in built}
+        if not gc.host_resident:
+            table = ops.KvUnpackTable(rec, self.device)
+
+            def garment(bi, p):
+                self.stats["garment_set_copies"] += 1
+                table.launch(self.dtype, *at[(p, bi)])
+            return garment
+        slices = sorted(set(at.values()))
+        cls = ops.KvPlaceTable if staged else ops.KvFillTable if isinstance(gc, ShelvedGarmentCache) else ops.KvStreamTable
+        table = cls(rec, self.device, ops.ffi.KVS_WIDEN_E4M3 if gc.packed else ops.ffi.KVS_COPY, slices)
+        self._release_streamed()
+        hold = [gc, torch.cuda.Event()]
+        self._streaming.append(hold)
+        for dst, src in plan["exps_copies"] if staged else ():
+            dst.copy_(src, non_blocking=True)
 
         def garment(bi, p):
-            s0, c = st["blocks"][bi]
-            self.stats["garment_set_copies"] += 1
-            table.launch(self.dtype, (p * len(steps) + first[s0]) * per, c * per)
+            if staged:
+                for dst, src in copies[bi]:
+                    dst.copy_(src, non_blocking=True)
+                self.stats["garment_stage_copies"] += len(copies[bi])
+            self.stats["garment_stage_launches" if staged else "garment_stream_launches"] += 1
+            table.launch(self.dtype, slices.index(at[(p, bi)]))
+            hold[1].record()                                 # the call's last fill so far: until it has passed, `hold` keeps the cache alive
         return garment
 
     def _slot_table(self, st):
@@ -704,7 +629,7 @@ class TryonEngine:
             # e4m3 bytes, or host memory: TryonNet reads 16-bit sets on the device, as the graph forms do (one, or two to overlap)
             slots, shapes = self._cache_set_shapes(st)
             sets = [self._alloc_set((), shapes, len(st["gcache"].timesteps), st["k"], slots) for _ in range(2 if overlap else 1)]
-            garment = (self._host_fill if st["gcache"].host_resident else self._packed_fill)(st, sets)
+            garment = self._cached_fill(st, sets)
             st = dict(st, gix=self._slot_table(st))          # with garment_index: person -> set slot (the same tensors otherwise)
             kv = lambda i, j, p: sets[p]["step"][j]
         else:                                                # nothing to launch, so nothing to overlap: TryonNet reads the cache's own views
@@ -756,12 +681,7 @@ class TryonEngine:
                 gc = st["gcache"]
                 slots, shapes = self._cache_set_shapes(st)   # (with an index: one slot per person, whatever the pool holds)
                 G["sets"] = [self._alloc_set((), shapes, len(gc.timesteps), st["k"], slots) for _ in range(2)]
-                if gc.host_resident:                         # (a table of block 0 alone: complete before the synchronize below)
-                    self._host_fill(st, G["sets"][:1], blocks=(0,))(0, 0)
-                elif gc.packed:
-                    self._packed_fill(st, G["sets"][:1], blocks=(0,))(0, 0)
-                else:
-                    self._fill_set(st, G["sets"][0], *st["blocks"][0])
+                self._cached_fill(st, G["sets"][:1], blocks=(0,))(0, 0)   # (a table of block 0 alone: complete before the synchronize below)
             self._tryon_main(G, G["tt"], G["cf"], G["nz"], G["sets"][0]["step"][0])
         torch.cuda.current_stream().wait_stream(warm)
         torch.cuda.synchronize()
@@ -804,12 +724,8 @@ class TryonEngine:
                 G["tgk"].copy_(st["temb_gk"][bi])
                 self.stats["garment_batches"] += 1
                 graphs[("garm", p, blocks[bi][1])].replay()
-        elif st["gcache"].host_resident:                     # in the same place: one launch that moves the block from host memory into set p
-            garment = self._host_fill(st, G["sets"])
-        elif st["gcache"].packed:                            # in the same place: one launch that widens the block's bytes into set p
-            garment = self._packed_fill(st, G["sets"])
-        else:                                                # in the GarmentNet graph's place in the stream / event order: a copy out of the cache
-            garment = lambda bi, p: self._fill_set(st, G["sets"][p], *blocks[bi])
+        else:                                                # in the GarmentNet graph's place in the stream / event order: the block out of the cache
+            garment = self._cached_fill(st, G["sets"])
         tt, cf, nz = G["tt"], G["cf"], G["nz"]
 
         def step(i, j, p):
@@ -827,14 +743,14 @@ class TryonEngine:
         return value ends the loop (the reference's per-step callbacks and `interrupt`, tryon_pipeline.py:1766-1767,1840-1863: host code
         between two steps, which only the un-captured serial form can run, so it selects that form).  trace["step_latents"] receives a copy
         of the latents after every step.  Graph forms return their persistent latents buffer, eager forms st["latents"].
-        host_transport: how a HOST-RESIDENT cache crosses the host link -- "kernel" (_stream_fill / _shelf_fill: a kernel reads page-locked
-        memory) or "copy" (_staged_fill: the copy engines into a staging arena, one idmvton_kv_place launch per block); the same bits in the
+        host_transport: how a HOST-RESIDENT cache crosses the host link -- "kernel" (a kernel reads page-locked
+        memory) or "copy" (the copy engines into a staging arena, one idmvton_kv_place launch per block); the same bits in the
         sets, the same graph states.  Any other value is a ValueError before anything is launched; on a device-resident cache or a live call
         the keyword has no effect.  A service sets it once."""
         self._check_host_transport(host_transport)
         if on_step is not None:
             use_graph = overlap = False
-        st = dict(st, host_transport=host_transport)         # (read by _host_fill alone: the same tensors, no key of a state or a set)
+        st = dict(st, host_transport=host_transport)         # (read by _cached_fill alone: the same tensors, no key of a state or a set)
         live = st["gcache"] is None                          # the one place a call chooses where its garment K / V^T come from
         garment, step, latents, sync = (self._graph_form if use_graph else self._eager_form)(st, live, overlap)
         blocks = st["blocks"]

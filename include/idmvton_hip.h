@@ -322,7 +322,7 @@ int idmvton_kv_fill(const idmvton_kv_stream_args* a, const idmvton_kv_stream_des
 
 /* ---------------------------------------------------------------------------------------------------------------
  * idmvton_kv_place : idmvton_kv_fill's runs -- data runs and zero runs -- for sources that are already in HBM: the second half of the
- * copy-engine transport of a host-resident garment cache (idm-vton_amd/pipeline.py, _staged_fill: the copy engines bring a block's bytes
+ * copy-engine transport of a host-resident garment cache (idm-vton_amd/pipeline.py, _cached_fill: the copy engines bring a block's bytes
  * into a staging arena, this launch widens or copies them into the 16-bit set, changes the V^T row stride and writes the zero V^T tails).
  * The same argument struct, 40-byte descriptors, modes, prefix table, zero-run rule and arithmetic; src / exp may still be device memory or
  * the device-visible address of page-locked host memory.  The one difference is the grid: ONE workgroup per chunk of the flat chunk list,

@@ -62,7 +62,7 @@ def fill_step(args):
     want = [(a.clone(), b.clone()) for a, b in fset["kv"][:2]]
     stp = dict(st, gcache=packed)
     t0 = time.perf_counter()
-    fill = eng._packed_fill(stp, [fset])
+    fill = eng._cached_fill(stp, [fset])
     torch.cuda.synchronize()
     table_ms = (time.perf_counter() - t0) * 1e3
     tp = timed_us(lambda: fill(bi, 0))

@@ -85,9 +85,9 @@ def fill_step(args):
     st = dict(gcache=host, gidx=list(range(k)), gindex=None, k=k, B=B, blocks=[(0, k)])       # ONE block: the k timesteps of the cache
     slots, shapes = eng._cache_set_shapes(st)
     fset, ref = eng._alloc_set((), shapes, k, k, slots), eng._alloc_set((), shapes, k, k, slots)
-    eng._packed_fill(dict(st, gcache=dev_cache), [ref])(0, 0)
+    eng._cached_fill(dict(st, gcache=dev_cache), [ref])(0, 0)
     t0 = time.perf_counter()
-    fill = eng._stream_fill(st, [fset])
+    fill = eng._cached_fill(st, [fset])
     torch.cuda.synchronize()
     table_ms = (time.perf_counter() - t0) * 1e3
     src_bytes = sum(a.numel() + b.numel() for a, b in host.kv)
