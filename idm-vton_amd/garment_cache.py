@@ -41,6 +41,13 @@ by raw address, with no stream order to protect them: a `put` into it waits for 
 host_transport="copy" the blocks cross the link by the copy engines into a staging arena instead and one idmvton_kv_place launch places them
 (staged_plan below: the arena, the copy list and the place tables, for plain and shelved caches alike).
 
+Features: a FEATURE cache (`features` true; encode_garment(storage="features")) holds what K and V^T are both made of -- per feature ONE
+tensor F [n * G * N_f][C_f], GarmentNet's exported feature, pad rows included, in the engine's 16-bit dtype -- as one-tensor entries (F,) of
+`kv`, under the same row rule: timestep_run cuts every tensor of an entry by its own rows per timestep.  Exactly half the bytes of the K / V^T
+cache, with no loss; packed, `exps` is [G][F][1].  Every primitive here iterates the tensors of an entry and so serves both kinds; mixing
+kinds is a ValueError naming `features`, and a feature cache has no `sizes` and is not shelved.  The engine projects each block of a call
+(pipeline.py, _cached_fill); TryonEngine.project_garment gives the K / V^T cache.
+
 Shelf: a GarmentShelf is a host catalogue of garments of MANY sizes, each kept COMPACT -- a G = 1 cache of its own (N'_f rows, ld'_f V^T
 positions) in page-locked memory, 16-bit or e4m3-packed -- so host RAM and the bytes a call moves over the host link follow the garments' own
 sizes, not the largest one's.  `get` hands out a ShelvedGarmentCache: the garments of a batch as `parts`, declared for one slot size; the
@@ -54,11 +61,7 @@ def timestep_run(kv, n, G, i0, c=1):
     """THE layout rule, in one place: views of entries i0 .. i0 + c - 1 of a timestep-major (K, V^T) list that holds n timesteps of G
     elements -- K rows [i0 * r, (i0 + c) * r) with r = rows // n, V^T elements [i0 * G, (i0 + c) * G).  The cache itself, the engine's
     persistent sets and the rows encode_garment projects into are all cut with it."""
-    out = []
-    for k, vt in kv:
-        r = k.shape[0] // n                              # K rows per timestep: G * N_f
-        out.append((k[i0 * r:(i0 + c) * r], vt[i0 * G:(i0 + c) * G]))
-    return out
+    return [tuple(t[i0 * (t.shape[0] // n):(i0 + c) * (t.shape[0] // n)] for t in e) for e in kv]   # per timestep: G * N_f K rows, G V^T elements
 
 
 def slot_run(kv, n, G, i, g0, c=1):
@@ -79,13 +82,13 @@ def index_runs(ids):
 
 
 def alloc_kv(shapes, n, m, device):
-    """An uninitialised timestep-major (K, V^T) list for m timesteps, from the [(K shape, V^T shape, dtype)] of one that holds n."""
-    return [(torch.empty((a[0] // n * m,) + tuple(a[1:]), dtype=d, device=device), torch.empty((b[0] // n * m,) + tuple(b[1:]), dtype=d, device=device))
-            for a, b, d in shapes]
+    """An uninitialised timestep-major (K, V^T) list for m timesteps, from the [(K shape, V^T shape, dtype)] of one that holds n (a feature
+    cache's list: [(F shape, dtype)])."""
+    return [tuple(torch.empty((a[0] // n * m,) + tuple(a[1:]), dtype=e[-1], device=device) for a in e[:-1]) for e in shapes]
 
 
 def kv_shapes(kv):
-    return [(tuple(k.shape), tuple(vt.shape), k.dtype) for k, vt in kv]
+    return [tuple(tuple(t.shape) for t in e) + (e[0].dtype,) for e in kv]
 
 
 def _f8_positions(ld):
@@ -147,8 +150,9 @@ def _garment_major(t, n, G):
 class GarmentCache:
     packed = False                                       # PackedGarmentCache: True
 
-    def __init__(self, *, G, timesteps, h, w, dtype, attn_fp8, f8_exp, weights_id, kv, gh=None, gw=None, sizes=None, rows=None):
+    def __init__(self, *, G, timesteps, h, w, dtype, attn_fp8, f8_exp, weights_id, kv, gh=None, gw=None, sizes=None, rows=None, features=False):
         self.G = int(G)
+        self.features = bool(features)                   # a FEATURE cache (module docstring): kv holds one-tensor entries (F,)
         self.timesteps = [int(t) for t in timesteps]
         self.h, self.w = int(h), int(w)
         self.gh, self.gw = int(h if gh is None else gh), int(w if gw is None else gw)    # the garment's own latent size (default: the person's)
@@ -167,13 +171,23 @@ class GarmentCache:
         self.rows = [None] * self.G if rows is None else [None if r is None else [(int(a), int(b)) for a, b in r] for r in rows]
         if self.sizes is not None and len(self.sizes) != self.G or len(self.rows) != self.G:
             raise ValueError(f"GarmentCache: sizes / rows need one entry per garment (G={self.G}, sizes={self.sizes})")
+        if self.features:
+            if self.sizes is not None or self.attn_fp8:
+                raise ValueError("GarmentCache: features mismatch (a feature cache has no `sizes` -- slotted caches and shelves hold K / V^T -- and "
+                                 "is not made or read by an attn_fp8 engine)")
+            self.kv = [tuple(e) for e in self.kv]
+            for f, e in enumerate(self.kv):
+                if len(e) != 1 or e[0].dim() != 2 or e[0].shape[0] % (n * self.G):
+                    raise ValueError(f"GarmentCache: feature {f} of a feature cache is one tensor F [n * G * N_f][C_f] for {n} timesteps x {self.G} "
+                                     f"garments, got {[tuple(t.shape) for t in e]}")
+            return
         for f, (k, vt) in enumerate(self.kv):
             if k.shape[0] % (n * self.G) or vt.shape[0] != n * self.G or k.dtype != vt.dtype:
                 raise ValueError(f"GarmentCache: feature {f} has K {tuple(k.shape)} / V^T {tuple(vt.shape)} for {n} timesteps x {self.G} garments")
 
     @property
     def nbytes(self):
-        return sum(k.numel() * k.element_size() + vt.numel() * vt.element_size() for k, vt in self.kv)
+        return sum(t.numel() * t.element_size() for e in self.kv for t in e)
 
     @property
     def host_resident(self):
@@ -195,11 +209,12 @@ class GarmentCache:
         if self.sizes is not None:
             garment = f", slots of {self.gh}x{self.gw} holding {sorted(set(self.sizes))}"
         return (f"GarmentCache(G={self.G}, steps={len(self.timesteps)}, latent={self.h}x{self.w}{garment}, dtype={self.dtype}, "
-                f"attn_fp8={self.attn_fp8}, {self.nbytes / 2 ** 20:.1f} MiB)")
+                f"attn_fp8={self.attn_fp8}, {'features, ' if self.features else ''}{self.nbytes / 2 ** 20:.1f} MiB)")
 
     def _args(self, **kw):
         args = dict(G=self.G, timesteps=self.timesteps, h=self.h, w=self.w, gh=self.gh, gw=self.gw, dtype=self.dtype, attn_fp8=self.attn_fp8,
-                    f8_exp=self.f8_exp, weights_id=self.weights_id, kv=self.kv, sizes=self.sizes, rows=self.rows if self.sizes is not None else None)
+                    f8_exp=self.f8_exp, weights_id=self.weights_id, kv=self.kv, sizes=self.sizes, rows=self.rows if self.sizes is not None else None,
+                    features=self.features)
         args.update(kw)
         return args
 
@@ -280,12 +295,8 @@ class GarmentCache:
         """The same cache with every garment materialised `times` times (garment order g0..gG-1, g0..gG-1, ...): what a shared segment replaces.
         For tests and A/B measurements."""
         n, G = len(self.timesteps), self.G
-        kv = []
-        for k, vt in self.kv:
-            r = k.shape[0] // n
-            kk = k.reshape(n, 1, r, k.shape[1]).expand(n, times, r, k.shape[1]).reshape(n * times * r, k.shape[1]).contiguous()
-            vv = vt.reshape(n, 1, G, *vt.shape[1:]).expand(n, times, G, *vt.shape[1:]).reshape(n * times * G, *vt.shape[1:]).contiguous()
-            kv.append((kk, vv))
+        rep = lambda t: t.reshape(n, 1, -1).expand(n, times, t.numel() // n).reshape((t.shape[0] * times,) + t.shape[1:]).contiguous()
+        kv = [tuple(rep(t) for t in e) for e in self.kv]
         return self._like(G=G * times, kv=kv, sizes=None if self.sizes is None else self.sizes * times, rows=self.rows * times,
                           **self._carry([(self, g) for _ in range(times) for g in range(G)]))
 
@@ -295,14 +306,18 @@ class GarmentCache:
 
     def _agrees(self, other, what, devices=True):
         """ValueError naming the first field in which `other` differs from this cache (G aside; devices=False: and where its tensors live)."""
+        if self.features != other.features:
+            raise ValueError(f"GarmentCache {what}: features mismatch ({self.features} against {other.features}: a feature cache holds GarmentNet's "
+                             "features, a K / V^T cache their projections -- engine.project_garment(features) gives the K / V^T cache)")
         if self.packed != other.packed:
             raise ValueError(f"GarmentCache {what}: packed mismatch ({self.packed} against {other.packed}: pack() or unpack() one of them)")
         for f in self._FIELDS:
             if getattr(self, f) != getattr(other, f):
                 raise ValueError(f"GarmentCache {what}: {f} mismatch ({getattr(self, f)} against {getattr(other, f)})")
         n = len(self.timesteps)
-        mine = [(k.shape[0] // (n * self.G),) + tuple(k.shape[1:]) + tuple(vt.shape[1:]) + (k.dtype, k.device.type if devices else None) for k, vt in self.kv]
-        theirs = [(k.shape[0] // (n * other.G),) + tuple(k.shape[1:]) + tuple(vt.shape[1:]) + (k.dtype, k.device.type if devices else None) for k, vt in other.kv]
+        facts = lambda c: [(e[0].shape[0] // (n * c.G),) + tuple(x for t in e for x in t.shape[1:]) + (e[0].dtype, e[0].device.type if devices else None)
+                           for e in c.kv]
+        mine, theirs = facts(self), facts(other)
         if mine != theirs:
             raise ValueError(f"GarmentCache {what}: kv mismatch (feature shapes, dtypes or devices differ)")
 
@@ -320,9 +335,9 @@ class GarmentCache:
             j = e
         for i in range(n):
             for j0, src, g0, c in runs:
-                for (dk, dv), (sk, sv) in zip(slot_run(kv, n, U, i, j0, c), slot_run(src.kv, n, src.G, i, g0, c)):
-                    dk.copy_(sk)
-                    dv.copy_(sv)
+                for d, s in zip(slot_run(kv, n, U, i, j0, c), slot_run(src.kv, n, src.G, i, g0, c)):
+                    for dt, st in zip(d, s):
+                        dt.copy_(st)
         slotted = any(c.sizes is not None for c, _ in sources)       # equal slot size (_agrees): whole slots moved, the sizes go along
         return self._like(G=U, kv=kv, sizes=[c.sizes[g] if c.sizes is not None else (c.gh, c.gw) for c, g in sources] if slotted else None,
                           rows=[c.rows[g] for c, g in sources] if slotted else None, **self._carry(sources))
@@ -353,14 +368,17 @@ class GarmentCache:
         if other.G != 1:
             raise ValueError(f"GarmentCache put: G mismatch (takes a cache of one garment, got G = {other.G})")
         if self.sizes is not None:
+            if other.features:
+                raise ValueError("GarmentCache put: features mismatch (a cache with `sizes` (slotted / mixed_sizes) holds K / V^T: slots of features "
+                                 "are not built -- engine.project_garment(features) gives the K / V^T garment)")
             return self._put_slotted(int(slot), other)
         self._agrees(other, "put", devices=False)
         n = len(self.timesteps)
         nb = self._put_mode()
         for i in range(n):
-            for (dk, dv), (sk, sv) in zip(slot_run(self.kv, n, self.G, i, int(slot)), timestep_run(other.kv, n, 1, i)):
-                dk.copy_(sk, non_blocking=nb(sk))
-                dv.copy_(sv, non_blocking=nb(sv))
+            for d, s in zip(slot_run(self.kv, n, self.G, i, int(slot)), timestep_run(other.kv, n, 1, i)):
+                for dt, st in zip(d, s):
+                    dt.copy_(st, non_blocking=nb(st))
         return self
 
     def _put_slotted(self, slot, other):
@@ -410,6 +428,12 @@ class GarmentCache:
         n = len(self.timesteps)
         device = self.kv[0][0].device if device is None else torch.device(device)
         pin = bool(pin_memory) and device.type == "cpu"
+        if self.features:                                # one tensor per feature, never slotted: the slot's rows as they are
+            kv = [(torch.empty((f.shape[0] // self.G, f.shape[1]), dtype=f.dtype, device=device, pin_memory=pin),) for f, in self.kv]
+            for i in range(n):
+                for (d,), (s,) in zip(timestep_run(kv, n, 1, i), slot_run(self.kv, n, self.G, i, int(slot))):
+                    d.copy_(s)
+            return self._like(G=1, kv=kv, **self._carry([(self, int(slot))], device, pin))
         # a slotted cache gives the garment back at its own compact size: the rows / positions `put` filled
         fill = self.rows[int(slot)] or [(k.shape[0] // (n * self.G), vt.shape[2]) for k, vt in self.kv]
         kv = [(torch.empty((n * Nf,) + tuple(k.shape[1:]), dtype=k.dtype, device=device, pin_memory=pin),
@@ -428,7 +452,7 @@ class GarmentCache:
         compared or saved at once; only pinned host -> device is queued asynchronously (stream-ordered before any later launch).  The same
         device without pinning returns self."""
         device = torch.device(device)
-        if not pin_memory and all(k.device == device for k, _ in self.kv):
+        if not pin_memory and all(e[0].device == device for e in self.kv):
             return self
 
         def move(t):
@@ -437,19 +461,21 @@ class GarmentCache:
                 out.copy_(t)
                 return out
             return t.to(device, non_blocking=device.type != "cpu" and t.device.type == "cpu" and t.is_pinned())
-        return self._like(kv=[(move(k), move(vt)) for k, vt in self.kv])
+        return self._like(kv=[tuple(move(t) for t in e) for e in self.kv])
 
     FORMAT_VERSION = 1
 
     def save(self, path):
         """-> a safetensors file: tensors k.<f> / vt.<f> (e4m3 caches are uint8 bytes) and a metadata record (format version, G, timesteps, both
         sizes, dtype, attn_fp8, f8_exp, weights_id).  A cache with `sizes` writes format version 2, which adds sizes and rows; one without
-        writes version 1 exactly as before.  A packed cache writes version 3: `packed: true` and the tensor `exps`."""
+        writes version 1 exactly as before.  A packed cache writes version 3: `packed: true` and the tensor `exps`.  A FEATURE cache writes
+        version 4: `kind: "features"`, tensors f.<f> in place of k / vt, and -- packed -- `packed: true` and `exps` as in version 3."""
         import json
         from safetensors.torch import save_file
         tensors = {}
-        for f, (k, vt) in enumerate(self.kv):
-            tensors[f"k.{f:03d}"], tensors[f"vt.{f:03d}"] = k.detach().cpu().contiguous(), vt.detach().cpu().contiguous()
+        for f, e in enumerate(self.kv):
+            for name, t in zip(("f",) if self.features else ("k", "vt"), e):
+                tensors[f"{name}.{f:03d}"] = t.detach().cpu().contiguous()
         meta = dict(format="idmvton_garment_cache", version=self.FORMAT_VERSION, G=self.G, timesteps=self.timesteps, h=self.h, w=self.w, gh=self.gh,
                     gw=self.gw, dtype=str(self.dtype), attn_fp8=self.attn_fp8, f8_exp=list(self.f8_exp), weights_id=self.weights_id, features=len(self.kv))
         if self.packed:                                  # version 3: e4m3 bytes + the exponents
@@ -457,6 +483,8 @@ class GarmentCache:
             tensors["exps"] = self.exps.detach().cpu().contiguous()
         if self.sizes is not None:
             meta.update(version=2, sizes=[list(sz) for sz in self.sizes], rows=[None if r is None else [list(x) for x in r] for r in self.rows])
+        if self.features:
+            meta.update(version=4, kind="features")
         save_file(tensors, path, metadata={k: json.dumps(v) for k, v in meta.items()})
 
     @staticmethod
@@ -467,20 +495,21 @@ class GarmentCache:
         from safetensors import safe_open
         with safe_open(path, framework="pt", device=str(device)) as f:
             meta = {k: json.loads(v) for k, v in (f.metadata() or {}).items()}
-            if meta.get("format") != "idmvton_garment_cache" or meta.get("version") not in (GarmentCache.FORMAT_VERSION, 2, 3):
+            if meta.get("format") != "idmvton_garment_cache" or meta.get("version") not in (GarmentCache.FORMAT_VERSION, 2, 3, 4):
                 raise ValueError(f"GarmentCache load: {path} is not a garment cache of format version {GarmentCache.FORMAT_VERSION} "
                                  f"(format={meta.get('format')!r}, version={meta.get('version')!r})")
-            kv = [(f.get_tensor(f"k.{i:03d}"), f.get_tensor(f"vt.{i:03d}")) for i in range(meta["features"])]
+            feats = meta.get("kind") == "features"
+            kv = [tuple(f.get_tensor(f"{name}.{i:03d}") for name in (("f",) if feats else ("k", "vt"))) for i in range(meta["features"])]
             exps = f.get_tensor("exps") if meta.get("packed") else None
         dtype = {str(d): d for d in (torch.float16, torch.bfloat16, torch.float32)}[meta["dtype"]]
         args = dict(G=meta["G"], timesteps=meta["timesteps"], h=meta["h"], w=meta["w"], gh=meta["gh"], gw=meta["gw"], dtype=dtype,
-                    attn_fp8=meta["attn_fp8"], f8_exp=meta["f8_exp"], weights_id=meta["weights_id"], kv=kv, sizes=meta.get("sizes"), rows=meta.get("rows"))
+                    attn_fp8=meta["attn_fp8"], f8_exp=meta["f8_exp"], weights_id=meta["weights_id"], kv=kv, sizes=meta.get("sizes"), rows=meta.get("rows"), features=feats)
         return PackedGarmentCache(exps=exps, **args) if exps is not None else GarmentCache(**args)
 
     # ---- packed storage ---------------------------------------------------------------------------------------------------
     def pack_exps(self):
-        """int32 [G][F][2] (0 = K, 1 = V^T): pack_exponent of the largest |x| of every garment's tensors over ALL timesteps, on the device the
-        cache lives on, without a host sync."""
+        """int32 [G][F][2] (0 = K, 1 = V^T; a feature cache: [G][F][1]): pack_exponent of the largest |x| of every garment's tensors over ALL
+        timesteps, on the device the cache lives on, without a host sync."""
         n, G = len(self.timesteps), self.G
         amax = [torch.stack([_garment_major(t, n, G).abs().amax(dim=(0, 2)).float() for t in kvf], dim=-1) for kvf in self.kv]   # F x [G][2]
         return pack_exponent(torch.stack(amax, dim=1))
@@ -519,12 +548,13 @@ class PackedGarmentCache(GarmentCache):
 
     def __init__(self, *, exps=None, **kw):
         super().__init__(**kw)
-        if self.sizes is not None or self.attn_fp8 or any(k.dtype != torch.uint8 for k, _ in self.kv):
+        if self.sizes is not None or self.attn_fp8 or any(e[0].dtype != torch.uint8 for e in self.kv):
             raise ValueError("PackedGarmentCache: holds e4m3 bytes (torch.uint8) of a cache without `sizes` and without attn_fp8")
         dev = self.kv[0][0].device
-        self.exps = torch.zeros(self.G, len(self.kv), 2, dtype=torch.int32, device=dev) if exps is None else exps
-        if tuple(self.exps.shape) != (self.G, len(self.kv), 2) or self.exps.dtype != torch.int32 or self.exps.device.type != dev.type:
-            raise ValueError(f"PackedGarmentCache: exps must be int32 [G = {self.G}][F = {len(self.kv)}][2] on {dev.type}, got "
+        T = len(self.kv[0])                              # tensors per feature: (K, V^T), or the one F of a feature cache
+        self.exps = torch.zeros(self.G, len(self.kv), T, dtype=torch.int32, device=dev) if exps is None else exps
+        if tuple(self.exps.shape) != (self.G, len(self.kv), T) or self.exps.dtype != torch.int32 or self.exps.device.type != dev.type:
+            raise ValueError(f"PackedGarmentCache: exps must be int32 [G = {self.G}][F = {len(self.kv)}][{T}] on {dev.type}, got "
                              f"{self.exps.dtype} {tuple(self.exps.shape)} on {self.exps.device.type}")
 
     @property
@@ -543,7 +573,7 @@ class PackedGarmentCache(GarmentCache):
 
     def _carry(self, sources, device=None, pin_memory=False):
         dev = self.exps.device if device is None else torch.device(device)
-        out = torch.empty((len(sources), len(self.kv), 2), dtype=torch.int32, device=dev, pin_memory=bool(pin_memory) and dev.type == "cpu")
+        out = torch.empty((len(sources),) + tuple(self.exps.shape[1:]), dtype=torch.int32, device=dev, pin_memory=bool(pin_memory) and dev.type == "cpu")
         for j, (c, g) in enumerate(sources):
             out[j].copy_(c.exps[g])
         return dict(exps=out)
@@ -576,14 +606,14 @@ class PackedGarmentCache(GarmentCache):
         """-> the 16-bit GarmentCache (a copy) of x' = e4m3(byte) * 2^-e: exactly what the engine's sets hold during a call on this cache (on
         the GPU the same idmvton_kv_unpack kernel writes it)."""
         n, G = len(self.timesteps), self.G
-        kv = alloc_kv([(a, b, self.dtype) for a, b, _ in kv_shapes(self.kv)], n, n, self.kv[0][0].device)
+        kv = alloc_kv([e[:-1] + (self.dtype,) for e in kv_shapes(self.kv)], n, n, self.kv[0][0].device)
         if self.kv[0][0].is_cuda:
             from . import ops
             ops.KvUnpackTable(fill_records(self.kv, n, G, kv, n, G, self.exps, list(range(n)), list(range(n)), list(range(G)), list(range(G))),
                               self.kv[0][0].device).launch(self.dtype)
         else:
             for f, (src, dst) in enumerate(zip(self.kv, kv)):
-                for j in range(2):
+                for j in range(len(src)):
                     _garment_major(dst[j], n, G).copy_(unpack_values(_garment_major(src[j], n, G), self.exps[:, f, j].view(1, G, 1), self.dtype))
         return GarmentCache(**self._args(kv=kv))
 
@@ -611,11 +641,13 @@ def kv_records(sources, dst_kvs, k, S, entries, tslots, address=None):
     address = address or (lambda x: x.data_ptr())
     t = lambda v: v if isinstance(v, torch.Tensor) else torch.tensor(v, dtype=I64)
     # a list's [F][3][2]: per feature (K, V^T) leading rows / row length / address; a timestep's rows are the leading rows over `per`
-    facts = lambda kv, per, ptr: torch.tensor([[a.shape[0] // per, b.shape[1], a.shape[1], b.shape[2], ptr(a), ptr(b)] for a, b in kv], dtype=I64).view(-1, 3, 2)
+    # (a feature cache's lists hold F alone -- a K-shaped tensor: [F][3][1], and every record below is a K record)
+    fact = lambda per, ptr, a, *b: [a.shape[0] // per] + [x.shape[1] for x in b] + [a.shape[1]] + [x.shape[2] for x in b] + [ptr(x) for x in (a,) + b]
+    facts = lambda kv, per, ptr: torch.tensor([fact(per, ptr, *e) for e in kv], dtype=I64).view(len(kv), 3, -1)
 
     def runs(src, dst, exp, rows, cols, ldd, sinc, dinc):    # [...][7]: a record (lds = cols), then what its src / dst advance per entry / timestep slot
         return torch.stack(torch.broadcast_tensors(*[t(v) for v in (src, dst, exp, rows | (cols << 32), cols | (ldd << 32), sinc, dinc)]), dim=-1)
-    F, P, esz = len(dst_kvs[0]), len(dst_kvs), dst_kvs[0][0][0].element_size()
+    F, T, P, esz = len(dst_kvs[0]), len(dst_kvs[0][0]), len(dst_kvs), dst_kvs[0][0][0].element_size()
     drows, dcols, dbase = torch.stack([facts(d, k * S, lambda x: x.data_ptr()) for d in dst_kvs]).unbind(2)   # [P][F][2]: (N_f, C_f), (C_f, ld_f)
     drows, dcols, dbase = drows[0], dcols[0], dbase.unsqueeze(1)
     dunit = drows * dcols * esz                                                                              # bytes of one slot
@@ -626,7 +658,7 @@ def kv_records(sources, dst_kvs, k, S, entries, tslots, address=None):
         g, u = t(garments).view(-1, 1, 1), t(gslots).view(-1, 1, 1)
         unit = rows * cols * su                                                                              # bytes per (timestep, garment)
         dst = dbase + u * dunit
-        exp = 0 if exps is None else address(exps) + 4 * (g * (2 * F) + torch.arange(2 * F).view(F, 2))
+        exp = 0 if exps is None else address(exps) + 4 * (g * (T * F) + torch.arange(T * F).view(F, T))
         rec = runs(base + g * unit, dst, exp, rows, cols * su, dcols * su, G * unit, S * dunit)              # [P][U][F][2][7]
         if bool((dcols > cols).any()):                       # (K, V^T, the V^T zero run) of every feature, the last where there is a tail
             tail = runs(0, dst + cols * esz, 0, rows, (dcols - cols) * su, dcols * su, 0, S * dunit)[:, :, :, 1:]
@@ -683,25 +715,24 @@ def staged_plan(gc, gindex, k, S, dst_kvs, device, arena=None, exps=None):
     U = len(garments)
     srcs = cache_sources(gc, garments)
     whole = gindex is None or isinstance(gc, ShelvedGarmentCache)   # every source list moves whole: all its garments, in its own order
-    shapes = [[(((a[0] // (n * G)) * k * len(gs),) + a[1:], ((b[0] // (n * G)) * k * len(gs),) + b[1:], d) for a, b, d in kv_shapes(kv)]
-              for kv, _, G, gs, _, _ in srcs]
+    shapes = [[tuple(((a[0] // (n * G)) * k * len(gs),) + a[1:] for a in e[:-1]) + e[-1:] for e in kv_shapes(kv)] for kv, _, G, gs, _, _ in srcs]
     size = lambda sh, d: torch.Size(sh).numel() * torch.empty((), dtype=d).element_size()
-    nbytes = sum(size(a, d) + size(b, d) for lst in shapes for a, b, d in lst)
+    nbytes = sum(size(a, e[-1]) for lst in shapes for e in lst for a in e[:-1])
     if arena is None or arena.numel() < nbytes:
         arena = torch.empty(nbytes, dtype=torch.uint8, device=device)
     lists, at = [], 0
     for lst in shapes:
         kv = []
-        for a, b, d in lst:
+        for *shs, d in lst:
             pair = []
-            for sh in (a, b):
+            for sh in shs:
                 pair.append(arena[at:at + size(sh, d)].view(d).view(sh))
                 at += size(sh, d)
             kv.append(tuple(pair))
         lists.append(kv)
     pairs = lambda dst, src: [(d, s) for dp, sp in zip(dst, src) for d, s in zip(dp, sp)]
     if gc.packed:
-        exps = torch.empty((U, len(lists[0]), 2), dtype=torch.int32, device=device) if exps is None else exps
+        exps = torch.empty((U, len(lists[0]), len(lists[0][0])), dtype=torch.int32, device=device) if exps is None else exps
         exps_copies = [(exps[us[0] + d0:us[0] + d0 + cc], ex[g0:g0 + cc]) for _, _, _, gs, us, ex in srcs for d0, g0, cc in index_runs(gs)]
     else:
         exps, exps_copies = None, []
@@ -728,6 +759,8 @@ class ShelvedGarmentCache(GarmentCache):
 
     def __init__(self, parts, *, gh, gw, slot_shapes, h=None, w=None):
         parts = list(parts)
+        if any(p.features for p in parts):
+            raise ValueError("ShelvedGarmentCache: features mismatch (a shelf holds compact K / V^T garments; feature caches are not shelved)")
         if not parts or any(p.G != 1 or p.sizes is not None for p in parts) or len({p.packed for p in parts}) != 1:
             raise ValueError("ShelvedGarmentCache: needs at least one part, every part a G = 1 cache without `sizes`, all packed or all 16-bit")
         p0 = parts[0]
@@ -840,6 +873,9 @@ class GarmentShelf:
 
     def _compact(self, one):
         """`one` checked against the shelf and copied compact into host memory; ValueError naming the field otherwise."""
+        if one.features:
+            raise ValueError("GarmentShelf add: features mismatch (a shelf holds compact K / V^T garments, whose zero V^T tails the fill writes; "
+                             "feature caches are not shelved -- engine.project_garment(features) gives the K / V^T garment)")
         if one.G != 1:
             raise ValueError(f"GarmentShelf add: G mismatch (takes a cache of one garment, got G = {one.G})")
         if one.attn_fp8:
@@ -928,15 +964,16 @@ class GarmentPool:
         if resident == "host" and (spill or mixed_sizes):
             raise ValueError(f"GarmentPool: resident=\"host\" cannot be combined with {'spill' if spill else 'mixed_sizes'} (the pool already lives in "
                              "host memory; slotted host caches are not streamed)")
+        if like.features and mixed_sizes:
+            raise ValueError("GarmentPool: features mismatch (mixed_sizes makes a slotted cache, which holds K / V^T; a feature cache cannot be its `like`)")
         self.resident = resident
         self.capacity, self.spill = int(capacity), bool(spill)
         self.host_capacity = None if spill is True or not spill else int(spill)      # garments kept on the host; None: no bound
         n = len(like.timesteps)
         if resident == "host":
             pin = torch.cuda.is_available()
-            kv = [(torch.empty((a[0] * self.capacity,) + tuple(a[1:]), dtype=d, pin_memory=pin), torch.empty((b[0] * self.capacity,) + tuple(b[1:]), dtype=d, pin_memory=pin))
-                  for a, b, d in kv_shapes(like.kv)]
-            carry = dict(exps=torch.zeros((self.capacity, len(kv), 2), dtype=torch.int32, pin_memory=pin)) if like.packed else {}
+            kv = [tuple(torch.empty((a[0] * self.capacity,) + tuple(a[1:]), dtype=e[-1], pin_memory=pin) for a in e[:-1]) for e in kv_shapes(like.kv)]
+            carry = dict(exps=torch.zeros((self.capacity,) + tuple(like.exps.shape[1:]), dtype=torch.int32, pin_memory=pin)) if like.packed else {}
             self.cache = like._like(G=self.capacity, kv=kv, sizes=None, rows=None, **carry)
         elif mixed_sizes:
             # a slotted cache (module docstring): `like` fixes the slot size, `get` accepts every garment that fits, host copies are compact.
@@ -947,7 +984,7 @@ class GarmentPool:
         else:
             self.cache = like._like(G=self.capacity, kv=alloc_kv(kv_shapes(like.kv), 1, self.capacity, like.kv[0][0].device), sizes=None, rows=None)
         # alloc_kv scales the leading dimension of a list that holds n timesteps: [n * 1 ...] -> [n * capacity ...] is "capacity times as many"
-        assert all(vt.shape[0] == n * self.capacity for _, vt in self.cache.kv)
+        assert all(t.shape[0] == l.shape[0] * self.capacity for e, le in zip(self.cache.kv, like.kv) for t, l in zip(e, le))
         self._slot = {}                                      # key -> slot, in use order: the first key is the least recently used
         self._free = list(range(self.capacity))
         self.host = {}                                       # key -> spilled G = 1 cache in pinned host memory

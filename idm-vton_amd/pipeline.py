@@ -43,6 +43,8 @@ zero V^T tail behind each garment too); key-count table, slot table, set shapes 
 device-resident slotted cache of the same slot size.  The host-resident kinds have a second TRANSPORT, host_transport="copy" (opt-in per
 call; "kernel" is the above): the copy engines bring a block's source bytes into a block-sized staging arena in HBM and ONE idmvton_kv_place
 launch puts them into set p, so no kernel reads host memory beside TryonNet.  Same sets, same bits, same graph states.
+A FEATURE cache (GarmentCache.features: GarmentNet's features in place of their K / V^T, half the bytes) goes through sets in every form too:
+_cached_fill moves the block's features into a staging list of the set by the same means and projects them with one project_garment_kv.
 With garment_index the two cache rows read through the table: eager on the cache's own views (nb = G, table = garment_index), graph on
 P-slot sets into which _fill_set gathers the U distinct garments of the call (table = person -> set slot, a persistent buffer of the state).
 
@@ -104,6 +106,13 @@ def _is_attn1_kv(key):
     return ".attn1.to_k." in key or ".attn1.to_v." in key
 
 
+class _Counters(dict):
+    """TryonEngine.stats: a counter that has not counted yet reads 0 without being listed."""
+
+    def __missing__(self, key):
+        return 0
+
+
 class TryonEngine:
     def __init__(self, unet, unet_encoder, vae, resampler=None, dtype=torch.bfloat16, device="cuda"):
         self.unet, self.unet_encoder, self.vae, self.resampler = unet, unet_encoder, vae, resampler
@@ -118,7 +127,10 @@ class TryonEngine:
         # garment_stream_launches: blocks moved from a host-resident cache into a set (one idmvton_kv_stream / idmvton_kv_fill launch each)
         # garment_stage_copies / garment_stage_launches: host_transport="copy" -- tensor copies from a host-resident cache into the staging
         # arena (the copy engines), and blocks placed from the arena into a set (one idmvton_kv_place launch each)
-        self.stats = dict(garment_batches=0, garment_set_copies=0, garment_stream_launches=0, garment_stage_copies=0, garment_stage_launches=0)
+        # garment_projections: blocks of a call on a FEATURE cache projected into a set (one project_garment_kv each, behind the block's
+        # fill); it reads 0 and is listed from the first such block on (_Counters), so an engine that never saw a feature cache lists what
+        # it always did
+        self.stats = _Counters(garment_batches=0, garment_set_copies=0, garment_stream_launches=0, garment_stage_copies=0, garment_stage_launches=0)
         self._streaming = []                                 # [cache, event of its last queued fill]: host memory a queued launch still reads
         self._arenas = {}                                    # _cached_fill's staging arenas: one per call shape, reused across calls
         self._weights_id = None
@@ -216,7 +228,17 @@ class TryonEngine:
         persons and this num_inference_steps / strength, so every launch is the launch that call makes and the cached K / V^T are its bits.
         For the same reason a cloth of the person's size goes through the VAE encoder in the third slot of a 3G-image pass, where an uncached
         call encodes it (prepare: [masked image | pose | cloth]): per image the arithmetic does not depend on the batch, but which GEMM tile
-        runs may.  A cloth of another size has a pass of its own there, and here."""
+        runs may.  A cloth of another size has a pass of its own there, and here.
+        storage="features": -> a FEATURE cache (GarmentCache.features): the same preamble and block schedule, but each block's GarmentNet
+        features F are kept -- GarmentNet writes them into the cache's own rows -- in place of their K / V^T: exactly half the bytes, no loss.
+        A call on it projects every block behind its fill (_cached_fill), and project_garment gives the native cache.
+        storage="features-e4m3": encode_garment(storage="features").pack(), bit for bit -- a quarter of the native bytes.  One 16-bit
+        feature cache is resident during the encode: half of what "native" needs (the exponents need the largest |x| over all timesteps).
+        An attn_fp8 engine refuses both (its sets mix e4m3 and 16-bit tensors): ValueError naming attn_fp8, before anything is launched."""
+        if storage not in ("native", "e4m3", "features", "features-e4m3"):
+            raise ValueError(f"encode_garment: storage={storage!r} (\"native\", \"e4m3\", \"features\" or \"features-e4m3\")")
+        if storage.startswith("features"):
+            self._refuse_features_fp8("encode_garment(storage=\"%s\")" % storage)
         dev = self.device
         f32 = lambda t: t.to(dev, torch.float32).contiguous()
         cloth, nz = f32(cloth), f32(noise_cloth)
@@ -236,16 +258,60 @@ class TryonEngine:
         gs = dict(B=G, gh=gh, gw=gw, **self._garment_inputs(cloth_lat, text_embeds_cloth, timesteps, G))
         n, k = len(timesteps), gs["k"]
         fs, ks = self._discover_set_shapes(gs)
-        feats = [torch.empty(sh, dtype=self.dtype, device=dev) for sh in fs]
+        feats = [torch.empty(sh, dtype=self.dtype, device=dev) for sh in fs] if not storage.startswith("features") else None
         if storage == "e4m3":
             return self._encode_packed(gs, feats, ks, timesteps, h, w)
-        if storage != "native":
-            raise ValueError(f"encode_garment: storage={storage!r} (\"native\" or \"e4m3\")")
+        meta = dict(G=G, timesteps=timesteps, h=h, w=w, gh=gh, gw=gw, dtype=self.dtype, attn_fp8=self.unet.attn_fp8, f8_exp=self.unet.f8_exp,
+                    weights_id=self.weights_identity())
+        if storage != "native":                              # each block's features land in the cache's own rows; nothing is projected
+            F = alloc_kv([((sh[0] * sh[1], sh[2]), self.dtype) for sh in fs], k, n, dev)
+            for bi, (s0, c) in enumerate(gs["blocks"]):
+                self._garment_feats(gs, gs["temb_gk"][bi], self._feature_views(timestep_run(F, n, G, s0, c), c * G), c)
+            fc = GarmentCache(kv=F, features=True, **meta)
+            return fc.pack() if storage == "features-e4m3" else fc
         kv = alloc_kv(ks, k, n, dev)
         for bi, (s0, c) in enumerate(gs["blocks"]):          # each block's projections land in the cache's own rows
             self._garment_side(gs, gs["temb_gk"][bi], dict(feats=feats, kv=timestep_run(kv, n, G, s0, c)), c)
-        return GarmentCache(G=G, timesteps=timesteps, h=h, w=w, gh=gh, gw=gw, dtype=self.dtype, attn_fp8=self.unet.attn_fp8, f8_exp=self.unet.f8_exp,
-                            weights_id=self.weights_identity(), kv=kv)
+        return GarmentCache(kv=kv, **meta)
+
+    def _refuse_features_fp8(self, what):
+        if self.unet.attn_fp8:
+            raise ValueError(f"{what}: attn_fp8 mismatch (an attn_fp8 engine neither makes nor takes a feature cache: its sets mix e4m3 and 16-bit "
+                             "tensors; encode K / V^T with storage=\"native\")")
+
+    @staticmethod
+    def _feature_views(entries, Bg):
+        """Timestep-major feature entries [(F [Bg * N_f][C_f],)] -> GarmentNet's feature list [F as [Bg][N_f][C_f]]: what feats_buf and
+        project_garment_kv take."""
+        return [f.view(Bg, f.shape[0] // Bg, f.shape[1]) for f, in entries]
+
+    @torch.no_grad()
+    def project_garment(self, features):
+        """A feature cache -> the native GarmentCache (a new one, on this engine's device): attn1.to_k / to_v applied to its features in the
+        encode's block schedule at the cache's G, so every projection launch is the one encode_garment(storage="native") makes and the K / V^T
+        are its bits.  A packed feature cache is unpacked first (exactly) and gives the K / V^T of its widened values.  The migration path
+        from features to K / V^T, and what a call on a feature cache is compared against."""
+        if not isinstance(features, GarmentCache) or not features.features:
+            raise ValueError("project_garment: features mismatch (takes a feature cache: encode_garment(storage=\"features\"))")
+        self._refuse_features_fp8("project_garment")
+        if features.dtype != self.dtype or features.weights_id != self.weights_identity():
+            raise ValueError(f"project_garment: {'dtype' if features.dtype != self.dtype else 'weights'} mismatch (the cache was built in "
+                             f"{features.dtype} with weights {features.weights_id}; the engine runs {self.dtype} with {self.weights_identity()})")
+        fc = features.to(self.device)
+        fc = fc.unpack() if fc.packed else fc
+        n, G = len(fc.timesteps), fc.G
+        k, blocks = self._block_schedule(n)
+        kv = alloc_kv(self._feature_kv_shapes(fc, G), n, n, self.device)
+        for s0, c in blocks:
+            self.unet.project_garment_kv(self._feature_views(fc.run(s0, c), c * G), out=timestep_run(kv, n, G, s0, c))
+        return GarmentCache(**fc._args(kv=kv, features=False))
+
+    @staticmethod
+    def _feature_kv_shapes(fc, slots):
+        """(K, V^T) shapes of a list that holds the n timesteps of `slots` garments of feature cache fc, derived from F's: K is F's shape,
+        V^T (C_f, N_f) per garment and timestep."""
+        n = len(fc.timesteps)
+        return [((f.shape[0] // fc.G * slots, f.shape[1]), (n * slots, f.shape[1], f.shape[0] // (n * fc.G)), fc.dtype) for f, in fc.kv]
 
     def _encode_packed(self, gs, feats, ks, timesteps, h, w):
         """encode_garment(storage="e4m3") after the shared preamble: see its docstring."""
@@ -327,6 +393,8 @@ class TryonEngine:
         self._release_streamed()
         f32 = lambda t: t.to(dev, torch.float32).contiguous()
         gcache = cloth if isinstance(cloth, GarmentCache) else None
+        if gcache is not None and gcache.features:
+            self._refuse_features_fp8("prepare(cloth=<feature cache>)")
         if garment_index is not None and gcache is None:
             raise ValueError("garment_index names garments of a GarmentCache: pass one as `cloth=` (a live call encodes one garment per person)")
         gindex = None
@@ -428,12 +496,15 @@ class TryonEngine:
     # The GarmentNet batch of block b+1 -- and the attn1 K / V^T projections of its features with TryonNet's weights -- can run on a
     # second HIP stream while TryonNet runs the steps of block b (drive_blocks).  Two feature sets alternate; there is no other coupling.
     # `st` below is a call's state (prepare) or a persistent graph state (_graph_state): both carry the keys these two read.
-    def _garment_side(self, st, temb_gk, fset, c=None):
+    def _garment_feats(self, st, temb_gk, feats_buf, c=None):
+        """One GarmentNet batch over c timesteps -> its 70 features, written into feats_buf."""
         B, h, w = st["B"], st["gh"], st["gw"]                # GarmentNet runs at the garment's own latent size
         c = st["k"] if c is None else c                      # timesteps in this batch (the set's buffers hold up to st["k"])
         self.stats["garment_batches"] += 1
-        _, feats = self.unet_encoder.forward(st["cloth_k"][:c * B], temb_gk[:c * B], st["ctx_gk"], c * B, h, w, feats_buf=fset["feats"])   # :1787
-        self.unet.project_garment_kv(feats, out=fset["kv"])
+        return self.unet_encoder.forward(st["cloth_k"][:c * B], temb_gk[:c * B], st["ctx_gk"], c * B, h, w, feats_buf=feats_buf)[1]   # :1787
+
+    def _garment_side(self, st, temb_gk, fset, c=None):
+        self.unet.project_garment_kv(self._garment_feats(st, temb_gk, fset["feats"], c), out=fset["kv"])
 
     def _tryon_main(self, st, temb_t, coef, noise, kv_j):
         B, h, w = st["B"], st["h"], st["w"]
@@ -482,23 +553,26 @@ class TryonEngine:
             runs = index_runs(list(dict.fromkeys(st["gindex"])))
             for j, i in enumerate(idx):
                 for d0, g0, cc in runs:
-                    for (dk, dv), (sk, sv) in zip(slot_run(fset["kv"], st["k"], P, j, d0, cc), slot_run(gc.kv, n, gc.G, i, g0, cc)):
-                        dk.copy_(sk)
-                        dv.copy_(sv)
+                    for d, s in zip(slot_run(fset["kv"], st["k"], P, j, d0, cc), slot_run(gc.kv, n, gc.G, i, g0, cc)):
+                        for dt, src in zip(d, s):
+                            dt.copy_(src)
             return
         runs = [(0, idx[0], c)] if idx == list(range(idx[0], idx[0] + c)) else [(j, i, 1) for j, i in enumerate(idx)]
         for j0, i0, cc in runs:
-            for (dk, dv), (sk, sv) in zip(timestep_run(fset["kv"], st["k"], gc.G, j0, cc), gc.run(i0, cc)):
-                dk.copy_(sk)
-                dv.copy_(sv)
+            for d, s in zip(timestep_run(fset["kv"], st["k"], gc.G, j0, cc), gc.run(i0, cc)):
+                for dt, src in zip(d, s):
+                    dt.copy_(src)
 
     @staticmethod
     def _cache_set_shapes(st):
         """-> (slots, shapes) of a persistent set for a call on a GarmentCache: one slot per garment of the cache -- or, with garment_index,
         one per PERSON, whatever the pool holds --, (K, V^T) shapes of a list holding the cache's n timesteps, in the engine's 16-bit dtype
-        (a packed cache's bytes are widened on the way in)."""
+        (a packed cache's bytes are widened on the way in).  A feature cache gives the shapes a K / V^T cache of the same garments gives,
+        derived from F's: the sets hold what the block's projection writes."""
         gc = st["gcache"]
         slots = gc.G if st["gindex"] is None else st["B"]
+        if gc.features:
+            return slots, TryonEngine._feature_kv_shapes(gc, slots)
         if isinstance(gc, ShelvedGarmentCache):              # no tensor list: the slot's shapes, what a slotted cache of that slot size has
             n = len(gc.timesteps)
             return slots, [((n * slots * a[0], a[1]), (n * slots, b[0], b[1]), gc.dtype) for a, b in gc.slot_shapes]
@@ -518,7 +592,7 @@ class TryonEngine:
         if gc.sizes is not None:
             raise ValueError("host-resident GarmentCache sizes mismatch: a cache with `sizes` (slotted / mixed_sizes) is not streamed from host "
                              "memory (move it with .to(device))")
-        if not all(k.is_pinned() and vt.is_pinned() for k, vt in gc.kv):
+        if not all(t.is_pinned() for e in gc.kv for t in e):
             raise ValueError("host-resident GarmentCache kv mismatch: the tensors are pageable host memory; the device reads page-locked memory "
                              "only -- make the cache with .to(\"cpu\", pin_memory=True) or GarmentPool(resident=\"host\")")
         if gc.packed and not gc.exps.is_pinned():
@@ -558,17 +632,41 @@ class TryonEngine:
         addresses are all stable, so table and prefix tables are built and uploaded ONCE, here, with one idmvton_host_device_ptr per host
         tensor, and a block is a slice.  `blocks`: build for these block numbers only (the warm-up; the arena's table covers k timesteps per
         set whatever the blocks, a block of c being a prefix).  Launches and copies read a host-resident cache by raw address: it stays
-        referenced by the engine until the event behind the last one has passed (_release_streamed)."""
+        referenced by the engine until the event behind the last one has passed (_release_streamed).
+        A FEATURE cache (gc.features) holds GarmentNet's features F, not their K / V^T: every form above then moves the block's F entries into
+        the first c * S slots of a feature STAGING list of set p -- a live set's `feats` shapes, allocated on first use and kept by the set --
+        in place of the set's K / V^T, and ONE project_garment_kv(staging, out=sets[p]["kv"]) follows it on the same stream: the launches
+        an uncached call makes behind its GarmentNet batch.  Same tables, same records (F is K-shaped: kv_records), same transports, same sets
+        and graph states.  A device-resident 16-bit block of consecutive entries without an index is projected from the cache's own views,
+        with no copy.  Slots no person reads are projected from whatever the staging list holds."""
         gc, k, B = st["gcache"], st["k"], st["blocks"]
-        if not (gc.packed or gc.host_resident):
-            return lambda bi, p: self._fill_set(st, sets[p], *B[bi])
-        garments = list(range(gc.G)) if st["gindex"] is None else list(dict.fromkeys(st["gindex"]))
         S = gc.G if st["gindex"] is None else st["B"]
+        dsts, project = [fs["kv"] for fs in sets], lambda bi, p, feats=None: None
+        if gc.features:
+            n = len(gc.timesteps)
+            for fs in sets:
+                if not fs["feats"]:
+                    fs["feats"] = [torch.empty(k * S, f.shape[0] // (n * gc.G), f.shape[1], dtype=self.dtype, device=self.device) for f, in gc.kv]
+            dsts = [[(f.view(-1, f.shape[-1]),) for f in fs["feats"]] for fs in sets]
+
+            def project(bi, p, feats=None):
+                self.stats["garment_projections"] += 1
+                self.unet.project_garment_kv([f[:B[bi][1] * S] for f in sets[p]["feats"]] if feats is None else feats, out=sets[p]["kv"])
+        if not (gc.packed or gc.host_resident):
+            def garment(bi, p):
+                s0, c = B[bi]
+                idx = st["gidx"][s0:s0 + c]
+                if gc.features and st["gindex"] is None and idx == list(range(idx[0], idx[0] + c)):
+                    return project(bi, p, self._feature_views(gc.run(idx[0], c), c * S))
+                self._fill_set(st, dict(kv=dsts[p]), s0, c)
+                project(bi, p)
+            return garment
+        garments = list(range(gc.G)) if st["gindex"] is None else list(dict.fromkeys(st["gindex"]))
         staged = gc.host_resident and st.get("host_transport") == "copy"
         built = [bi for bi in range(len(B)) if staged or blocks is None or bi in blocks]
         if staged:
-            key = self._set_key(st) + (torch.uint8 if gc.packed else gc.dtype, len(garments))
-            plan = staged_plan(gc, st["gindex"], k, S, [fs["kv"] for fs in sets], self.device, *self._arenas.get(key, (None, None)))
+            key = self._set_key(st) + (torch.uint8 if gc.packed else gc.dtype, len(garments), gc.features)
+            plan = staged_plan(gc, st["gindex"], k, S, dsts, self.device, *self._arenas.get(key, (None, None)))
             self._arenas[key] = (plan["arena"], plan["exps"])
             rec, per, rows, row = plan["rec"], plan["per"], k, dict.fromkeys(built, 0)
             copies = [plan["copies"](st["gidx"][s0:s0 + c]) for s0, c in B]
@@ -576,7 +674,7 @@ class TryonEngine:
             steps = [(B[bi][0] + j, j) for bi in built for j in range(B[bi][1])]
             first = {i: at for at, (i, _) in enumerate(steps)}
             rows, row = len(steps), {bi: first[B[bi][0]] for bi in built}   # block -> the place of its first step in a set's part of the table
-            rec, per = kv_records(cache_sources(gc, garments), [fs["kv"] for fs in sets], k, S, [st["gidx"][i] for i, _ in steps], [j for _, j in steps],
+            rec, per = kv_records(cache_sources(gc, garments), dsts, k, S, [st["gidx"][i] for i, _ in steps], [j for _, j in steps],
                                   ops.stream_address if gc.host_resident else None)   # (records per step, even: every slice starts 16-byte aligned)
         at = {(p, bi): ((p * rows + row[bi]) * per, B[bi][1] * per) for p in range(len(sets)) for bi in built}
         if not gc.host_resident:
@@ -585,6 +683,7 @@ class TryonEngine:
             def garment(bi, p):
                 self.stats["garment_set_copies"] += 1
                 table.launch(self.dtype, *at[(p, bi)])
+                project(bi, p)
             return garment
         slices = sorted(set(at.values()))
         cls = ops.KvPlaceTable if staged else ops.KvFillTable if isinstance(gc, ShelvedGarmentCache) else ops.KvStreamTable
@@ -603,6 +702,7 @@ class TryonEngine:
             self.stats["garment_stage_launches" if staged else "garment_stream_launches"] += 1
             table.launch(self.dtype, slices.index(at[(p, bi)]))
             hold[1].record()                                 # the call's last fill so far: until it has passed, `hold` keeps the cache alive
+            project(bi, p)
         return garment
 
     def _slot_table(self, st):
@@ -625,8 +725,9 @@ class TryonEngine:
             sets = [self._new_set(st) for _ in range(2 if overlap else 1)]
             garment = lambda bi, p: self._garment_side(st, st["temb_gk"][bi], sets[p], blocks[bi][1])
             kv = lambda i, j, p: sets[p]["step"][j]
-        elif st["gcache"].packed or st["gcache"].host_resident:
-            # e4m3 bytes, or host memory: TryonNet reads 16-bit sets on the device, as the graph forms do (one, or two to overlap)
+        elif st["gcache"].packed or st["gcache"].host_resident or st["gcache"].features:
+            # e4m3 bytes, host memory, or features still to be projected: TryonNet reads 16-bit sets on the device, as the graph forms do
+            # (one, or two to overlap)
             slots, shapes = self._cache_set_shapes(st)
             sets = [self._alloc_set((), shapes, len(st["gcache"].timesteps), st["k"], slots) for _ in range(2 if overlap else 1)]
             garment = self._cached_fill(st, sets)
@@ -682,6 +783,8 @@ class TryonEngine:
                 slots, shapes = self._cache_set_shapes(st)   # (with an index: one slot per person, whatever the pool holds)
                 G["sets"] = [self._alloc_set((), shapes, len(gc.timesteps), st["k"], slots) for _ in range(2)]
                 self._cached_fill(st, G["sets"][:1], blocks=(0,))(0, 0)   # (a table of block 0 alone: complete before the synchronize below)
+                if gc.features:                              # garment_projections counts the blocks of calls: not the warm-up's
+                    self.stats["garment_projections"] -= 1
             self._tryon_main(G, G["tt"], G["cf"], G["nz"], G["sets"][0]["step"][0])
         torch.cuda.current_stream().wait_stream(warm)
         torch.cuda.synchronize()
