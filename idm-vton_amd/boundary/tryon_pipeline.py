@@ -363,7 +363,9 @@ class StableDiffusionXLInpaintPipeline:
         is declared for (GarmentCache.for_person_size declares it for another).  Image quality at other garment sizes is not evaluated.
         The reference has no counterpart (it runs GarmentNet in every step of every call, tryon_pipeline.py:1781-1787).
         storage="features" / "features-e4m3": a feature cache (GarmentNet's features in place of their K / V^T: half / a quarter of the
-        native bytes; the call projects each block of timesteps), taken as `cloth=` like any other; not on an attn_fp8 engine.
+        native bytes; the call projects each block of timesteps), taken as `cloth=` like any other; not on an attn_fp8 engine.  Feature
+        caches of many sizes go on a GarmentShelf(storage="features" / "features-e4m3"), whose `get` gives the `cloth=` / `garment_index=`
+        pair of a batch (self.host_transport applies).
         storage="e4m3": a packed cache (garment_cache.PackedGarmentCache) -- e4m3 bytes, half the resident memory, lossy for the garment keys
         and values alone; passed as `cloth=` (and pooled, indexed, saved) like any other.
 

@@ -45,14 +45,17 @@ Features: a FEATURE cache (`features` true; encode_garment(storage="features")) 
 tensor F [n * G * N_f][C_f], GarmentNet's exported feature, pad rows included, in the engine's 16-bit dtype -- as one-tensor entries (F,) of
 `kv`, under the same row rule: timestep_run cuts every tensor of an entry by its own rows per timestep.  Exactly half the bytes of the K / V^T
 cache, with no loss; packed, `exps` is [G][F][1].  Every primitive here iterates the tensors of an entry and so serves both kinds; mixing
-kinds is a ValueError naming `features`, and a feature cache has no `sizes` and is not shelved.  The engine projects each block of a call
-(pipeline.py, _cached_fill); TryonEngine.project_garment gives the K / V^T cache.
+kinds is a ValueError naming `features`, and a feature cache's tensor list has no `sizes` (feature caches of several sizes live on a
+shelf, below).  The engine projects each block of a call (pipeline.py, _cached_fill); TryonEngine.project_garment gives the K / V^T cache.
 
 Shelf: a GarmentShelf is a host catalogue of garments of MANY sizes, each kept COMPACT -- a G = 1 cache of its own (N'_f rows, ld'_f V^T
 positions) in page-locked memory, 16-bit or e4m3-packed -- so host RAM and the bytes a call moves over the host link follow the garments' own
 sizes, not the largest one's.  `get` hands out a ShelvedGarmentCache: the garments of a batch as `parts`, declared for one slot size; the
 engine puts each into the front of a slot of its 16-bit sets and writes the zero V^T tail behind it with one idmvton_kv_fill launch per block
-(kv_records below, pipeline.py _cached_fill), and reads them as it reads a slotted cache.
+(kv_records below, pipeline.py _cached_fill), and reads them as it reads a slotted cache.  A shelf of storage "features" / "features-e4m3"
+holds compact FEATURE caches instead (half / a quarter of the bytes): the same launch puts each F into the front of a slot of a feature
+staging list and writes the zero ROWS behind it, and the block's one projection makes the slot's K / V^T of them -- zero rows give the zero
+V^T tail.  Sets, tables and graph states are those of the K / V^T shelf call at the same slot size.
 """
 import torch
 
@@ -172,9 +175,9 @@ class GarmentCache:
         if self.sizes is not None and len(self.sizes) != self.G or len(self.rows) != self.G:
             raise ValueError(f"GarmentCache: sizes / rows need one entry per garment (G={self.G}, sizes={self.sizes})")
         if self.features:
-            if self.sizes is not None or self.attn_fp8:
-                raise ValueError("GarmentCache: features mismatch (a feature cache has no `sizes` -- slotted caches and shelves hold K / V^T -- and "
-                                 "is not made or read by an attn_fp8 engine)")
+            if (self.sizes is not None and self.kv) or self.attn_fp8:    # (sizes without a tensor list: a ShelvedGarmentCache of feature parts)
+                raise ValueError("GarmentCache: features mismatch (a feature cache's tensor list has no `sizes` -- slotted caches hold K / V^T; "
+                                 "features of several sizes live compact on a GarmentShelf -- and is not made or read by an attn_fp8 engine)")
             self.kv = [tuple(e) for e in self.kv]
             for f, e in enumerate(self.kv):
                 if len(e) != 1 or e[0].dim() != 2 or e[0].shape[0] % (n * self.G):
@@ -631,8 +634,13 @@ def kv_records(sources, dst_kvs, k, S, entries, tslots, address=None):
       V^T    one data run of C_f rows x ld'_f positions, source row stride ld'_f, destination row stride ld_f;
       tail   exactly where ld'_f < ld_f, one ZERO RUN (src 0) of C_f rows x (ld_f - ld'_f) positions behind it -- the whole tail, as _put_slotted
              writes it, so a set's V^T depends on the garment alone and not on what the slot held before.
-    exps (int32 [G][F][2]) gives the WIDENING form: the source is e4m3 bytes, cols / lds in bytes = elements, ldd in 16-bit elements, exp the
-    address of the garment's exponent.  exps None gives the COPY form: a 16-bit source, cols, lds and ldd in BYTES, exp 0.  An odd number of
+    FEATURE lists (one-tensor entries (F,), source and destination alike: a staging list that project_garment_kv reads) have, per (timestep,
+    source, garment, feature):
+      F      one data run of the N'_f rows into the front of the slot;
+      rows   exactly where N'_f < N_f, one ZERO RUN (src 0, exp 0) of (N_f - N'_f) rows x C_f directly behind it -- the whole row tail: the
+             projection reads every row of a slot, and zero rows project to the zero K rows and the zero V^T tail (to_k / to_v have no bias).
+    exps (int32 [G][F][2]; feature lists: [G][F][1]) gives the WIDENING form: the source is e4m3 bytes, cols / lds in bytes = elements,
+    ldd in 16-bit elements, exp the address of the garment's exponent.  exps None gives the COPY form: a 16-bit source, cols, lds and ldd in BYTES, exp 0.  An odd number of
     records per timestep is made even by repeating the smallest (a slice of a table starts at an even index; identical bytes written twice
     are what clamped lanes already do).  address(tensor) -> the address a kernel reads the tensor's first element under (default
     data_ptr(); ops.stream_address for a host-resident source); it is asked once per source tensor.
@@ -664,6 +672,10 @@ def kv_records(sources, dst_kvs, k, S, entries, tslots, address=None):
             tail = runs(0, dst + cols * esz, 0, rows, (dcols - cols) * su, dcols * su, 0, S * dunit)[:, :, :, 1:]
             keep = torch.cat([torch.ones(F, 2, dtype=torch.bool), dcols[:, 1:] > cols[:, 1:]], dim=1)
             rec = torch.cat([rec, tail], dim=3)[keep.expand(P, len(garments), F, 3)]
+        if T == 1 and bool((drows > rows).any()):            # (F, the zero ROW run) of every feature, the last where the garment has fewer rows
+            tail = runs(0, dst + rows * cols * esz, 0, drows - rows, dcols * su, dcols * su, 0, S * dunit)
+            keep = torch.cat([torch.ones(F, 1, dtype=torch.bool), drows > rows], dim=1)
+            rec = torch.cat([rec, tail], dim=3)[keep.expand(P, len(garments), F, 2)]
         tmpl.append(rec.reshape(P, -1, 7))
     from . import ops
     T = torch.stack([ops.kv_pad_even(x) for x in torch.cat(tmpl, dim=1)])   # [P][per][7], per even
@@ -689,7 +701,7 @@ def fill_records(src_kv, n, G, dst_kv, k, S, exps, entries, tslots, garments, gs
 
 def shelf_records(parts, packed, dst_kv, k, S, entries, tslots, gslots, address=None):
     """kv_records of the COMPACT garments `parts` (G = 1 caches, all packed or all 16-bit), one source each, into the front of garment slots
-    `gslots`, zero V^T tails included.  -> (records, per)."""
+    `gslots`, zero V^T tails included -- feature parts into a feature list dst_kv: zero ROW runs included.  -> (records, per)."""
     return kv_records([(p.kv, len(p.timesteps), 1, [0], [u], p.exps if packed else None) for p, u in zip(parts, gslots)],
                       [dst_kv], k, S, entries, tslots, address)
 
@@ -755,17 +767,22 @@ class ShelvedGarmentCache(GarmentCache):
     """The garments of a batch as GarmentShelf.get hands them out: `parts`, G = 1 caches in host memory, each at its OWN compact size, declared
     for slots of one size -- (gh, gw) and slot_shapes [((N_f, C_f), (C_f, ld_f))] --; sizes[g] is garment g's own (gh, gw).  There is no
     single tensor list (kv is empty): the engine streams every part into the front of a set slot (module docstring), and what it computes is
-    what it computes on `slotted(device)`.  The cache keeps its parts alive: removing a key from the shelf while a call is queued is safe."""
+    what it computes on `slotted(device)`.  The cache keeps its parts alive: removing a key from the shelf while a call is queued is safe.
+    The parts may all be FEATURE caches (a GarmentShelf of storage "features" / "features-e4m3"): `features` is then true, slot_shapes are
+    still the slot's ((N_f, C_f), (C_f, ld_f)) -- F has K's shape --, the engine streams each part's F into the front of a slot of a staging
+    list with the zero rows behind it and projects the block; there is no slotted feature cache, so `slotted` is refused by name and
+    TryonEngine.project_garment gives the K / V^T shelved cache to compare against."""
 
     def __init__(self, parts, *, gh, gw, slot_shapes, h=None, w=None):
         parts = list(parts)
-        if any(p.features for p in parts):
-            raise ValueError("ShelvedGarmentCache: features mismatch (a shelf holds compact K / V^T garments; feature caches are not shelved)")
+        if len({p.features for p in parts}) > 1:
+            raise ValueError("ShelvedGarmentCache: features mismatch (the parts are all feature caches or all K / V^T caches, never mixed)")
         if not parts or any(p.G != 1 or p.sizes is not None for p in parts) or len({p.packed for p in parts}) != 1:
             raise ValueError("ShelvedGarmentCache: needs at least one part, every part a G = 1 cache without `sizes`, all packed or all 16-bit")
         p0 = parts[0]
         super().__init__(G=len(parts), timesteps=p0.timesteps, h=p0.h if h is None else h, w=p0.w if w is None else w, gh=gh, gw=gw, dtype=p0.dtype,
-                         attn_fp8=p0.attn_fp8, f8_exp=p0.f8_exp, weights_id=p0.weights_id, kv=[], sizes=[(p.gh, p.gw) for p in parts])
+                         attn_fp8=p0.attn_fp8, f8_exp=p0.f8_exp, weights_id=p0.weights_id, kv=[], sizes=[(p.gh, p.gw) for p in parts],
+                         features=p0.features)
         self.parts = parts
         self.packed = p0.packed
         self.slot_shapes = [(tuple(a), tuple(b)) for a, b in slot_shapes]
@@ -780,7 +797,8 @@ class ShelvedGarmentCache(GarmentCache):
 
     def __repr__(self):
         return (f"ShelvedGarmentCache(G={self.G}, steps={len(self.timesteps)}, latent={self.h}x{self.w}, slots of {self.gh}x{self.gw} holding "
-                f"{sorted(set(self.sizes))}, dtype={self.dtype}, {'e4m3-packed, ' if self.packed else ''}{self.nbytes / 2 ** 20:.1f} MiB compact in host memory)")
+                f"{sorted(set(self.sizes))}, dtype={self.dtype}, {'features, ' if self.features else ''}{'e4m3-packed, ' if self.packed else ''}"
+                f"{self.nbytes / 2 ** 20:.1f} MiB compact in host memory)")
 
     def _with(self, parts, **kw):
         return ShelvedGarmentCache(parts, gh=self.gh, gw=self.gw, slot_shapes=self.slot_shapes, h=kw.get("h", self.h), w=kw.get("w", self.w))
@@ -800,7 +818,11 @@ class ShelvedGarmentCache(GarmentCache):
 
     def slotted(self, device=None):
         """The 16-bit slotted GarmentCache that empty slots + put(g, take(g)) give (packed parts unpacked first), on `device` (default: host
-        memory): what an engine call on this cache is compared against.  K rows no garment fills are zero."""
+        memory): what an engine call on this cache is compared against.  K rows no garment fills are zero.  Refused on feature parts: a
+        cache with `sizes` and a tensor list holds K / V^T."""
+        if self.features:
+            raise ValueError("ShelvedGarmentCache slotted: features mismatch (there is no slotted feature cache: a cache with `sizes` and a tensor "
+                             "list holds K / V^T -- engine.project_garment(<this cache>).slotted() is the slotted cache of these garments)")
         device = torch.device("cpu" if device is None else device)
         n, G = len(self.timesteps), self.G
         kv = [(torch.zeros((n * G * a[0], a[1]), dtype=self.dtype, device=device), torch.zeros((n * G, b[0], b[1]), dtype=self.dtype, device=device))
@@ -838,16 +860,25 @@ class GarmentShelf:
     must agree with (timesteps, person size, dtype, attn_fp8, f8_exp, weights) and the SLOT size: every feature's K rows and V^T positions
     must fit it.  Only like's fields and shapes are kept, not its tensors.  max_bytes bounds the shelf: `get` evicts the least recently used
     garments that the batch does not name until it fits.
+    storage="features" / "features-e4m3": a shelf of compact FEATURE caches (encode_garment(storage="features")), 16-bit / e4m3-packed --
+    half / a quarter of the bytes of the K / V^T garment, in host RAM and over the host link.  `like` may then also be a G = 1 feature cache;
+    either way the slot's F shape per feature is the slot's K shape (N_f, C_f), and a garment fits when its C_f is equal and its rows per
+    timestep are at most N_f.  Kinds do not mix: a K / V^T garment into a feature shelf, and a feature garment into a K / V^T shelf, are
+    ValueErrors naming `features`.
         shelf = GarmentShelf(pipe.empty_garment_cache(1, 1024, 768, 30), storage="e4m3")
         cache, index = shelf.get(["sku7", "sku3", "sku7"], encode=my_encode)
         out = pipe(cloth=cache, garment_index=index, ...)"""
     _IDENTITY = ("timesteps", "h", "w", "dtype", "attn_fp8", "f8_exp", "weights_id")
 
     def __init__(self, like, storage="native", max_bytes=None):
-        if storage not in ("native", "e4m3"):
-            raise ValueError(f"GarmentShelf: storage={storage!r} (\"native\" or \"e4m3\")")
+        if storage not in ("native", "e4m3", "features", "features-e4m3"):
+            raise ValueError(f"GarmentShelf: storage={storage!r} (\"native\", \"e4m3\", \"features\" or \"features-e4m3\")")
+        self.features = storage.startswith("features")       # the shelf's kind: compact feature caches, or compact K / V^T caches
         if isinstance(like, ShelvedGarmentCache):
             self.slot_shapes = list(like.slot_shapes)
+        elif like.features:                                  # F [n * G * N_f][C_f]: K's shape, and V^T is (C_f, N_f) (project_garment)
+            n = len(like.timesteps)
+            self.slot_shapes = [((f.shape[0] // (n * like.G), f.shape[1]), (f.shape[1], f.shape[0] // (n * like.G))) for f, in like.kv]
         else:
             n = len(like.timesteps)
             self.slot_shapes = [((k.shape[0] // (n * like.G), k.shape[1]), (vt.shape[1], vt.shape[2])) for k, vt in like.kv]
@@ -873,9 +904,13 @@ class GarmentShelf:
 
     def _compact(self, one):
         """`one` checked against the shelf and copied compact into host memory; ValueError naming the field otherwise."""
-        if one.features:
-            raise ValueError("GarmentShelf add: features mismatch (a shelf holds compact K / V^T garments, whose zero V^T tails the fill writes; "
-                             "feature caches are not shelved -- engine.project_garment(features) gives the K / V^T garment)")
+        if one.features and not self.features:
+            raise ValueError(f"GarmentShelf add: features mismatch (a storage=\"{self.storage}\" shelf holds compact K / V^T garments; a feature "
+                             "cache goes on a shelf of storage \"features\" / \"features-e4m3\" -- or engine.project_garment(features) gives "
+                             "the K / V^T garment)")
+        if self.features and not one.features:
+            raise ValueError(f"GarmentShelf add: features mismatch (a storage=\"{self.storage}\" shelf holds compact feature caches; encode the "
+                             "garment with storage=\"features\", or put its K / V^T on a \"native\" / \"e4m3\" shelf)")
         if one.G != 1:
             raise ValueError(f"GarmentShelf add: G mismatch (takes a cache of one garment, got G = {one.G})")
         if one.attn_fp8:
@@ -884,19 +919,25 @@ class GarmentShelf:
         for f in self._IDENTITY:
             if getattr(one, f) != self.like[f]:
                 raise ValueError(f"GarmentShelf add: {f} mismatch ({getattr(one, f)} against {self.like[f]})")
-        if one.packed and self.storage == "native":
-            raise ValueError("GarmentShelf add: packed mismatch (an e4m3-packed garment cannot go into a storage=\"native\" shelf: unpack() is not "
-                             "its 16-bit original)")
+        if one.packed and not self.storage.endswith("e4m3"):
+            raise ValueError(f"GarmentShelf add: packed mismatch (an e4m3-packed garment cannot go into a storage=\"{self.storage}\" shelf: unpack() "
+                             "is not its 16-bit original)")
         if one.sizes is not None:                            # a one-slot slotted cache: the garment at its own compact size
             one = one.take(0)
         n = len(one.timesteps)
         if len(one.kv) != len(self.slot_shapes):
             raise ValueError(f"GarmentShelf add: does not fit ({len(one.kv)} features against {len(self.slot_shapes)})")
-        for f, ((k, vt), ((N, C), (Cv, ld))) in enumerate(zip(one.kv, self.slot_shapes)):
+        for f, (e, ((N, C), (Cv, ld))) in enumerate(zip(one.kv, self.slot_shapes)):
+            if self.features:
+                if e[0].shape[1] != C or e[0].shape[0] // n > N:
+                    raise ValueError(f"GarmentShelf add: does not fit (feature {f}: a garment of latent {one.gh}x{one.gw} has F rows "
+                                     f"{e[0].shape[0] // n} x {e[0].shape[1]}, a slot of {self.gh}x{self.gw} holds {N} x {C})")
+                continue
+            k, vt = e
             if k.shape[1] != C or vt.shape[1] != Cv or k.shape[0] // n > N or vt.shape[2] > ld:
                 raise ValueError(f"GarmentShelf add: does not fit (feature {f}: a garment of latent {one.gh}x{one.gw} has K rows {k.shape[0] // n} x "
                                  f"{k.shape[1]} and V^T {vt.shape[1]} x {vt.shape[2]}, a slot of {self.gh}x{self.gw} holds {N} x {C} and {Cv} x {ld})")
-        if self.storage == "e4m3" and not one.packed:
+        if self.storage.endswith("e4m3") and not one.packed:
             one = one.pack()                                 # on the device it lives on
         return one.take(0, "cpu", pin_memory=torch.cuda.is_available())
 

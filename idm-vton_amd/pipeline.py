@@ -45,6 +45,7 @@ call; "kernel" is the above): the copy engines bring a block's source bytes into
 launch puts them into set p, so no kernel reads host memory beside TryonNet.  Same sets, same bits, same graph states.
 A FEATURE cache (GarmentCache.features: GarmentNet's features in place of their K / V^T, half the bytes) goes through sets in every form too:
 _cached_fill moves the block's features into a staging list of the set by the same means and projects them with one project_garment_kv.
+A shelved cache may hold feature parts (GarmentShelf(storage="features")): the fill then also writes the zero rows behind each compact F.
 With garment_index the two cache rows read through the table: eager on the cache's own views (nb = G, table = garment_index), graph on
 P-slot sets into which _fill_set gathers the U distinct garments of the call (table = person -> set slot, a persistent buffer of the state).
 
@@ -290,10 +291,16 @@ class TryonEngine:
         """A feature cache -> the native GarmentCache (a new one, on this engine's device): attn1.to_k / to_v applied to its features in the
         encode's block schedule at the cache's G, so every projection launch is the one encode_garment(storage="native") makes and the K / V^T
         are its bits.  A packed feature cache is unpacked first (exactly) and gives the K / V^T of its widened values.  The migration path
-        from features to K / V^T, and what a call on a feature cache is compared against."""
+        from features to K / V^T, and what a call on a feature cache is compared against.
+        A ShelvedGarmentCache of feature parts (GarmentShelf(storage="features" / "features-e4m3").get) gives the K / V^T ShelvedGarmentCache
+        of the same garments for the same slots: every part is projected at its OWN size as above and compacted into page-locked memory
+        (16-bit parts, whatever the source's storage)."""
         if not isinstance(features, GarmentCache) or not features.features:
             raise ValueError("project_garment: features mismatch (takes a feature cache: encode_garment(storage=\"features\"))")
         self._refuse_features_fp8("project_garment")
+        if isinstance(features, ShelvedGarmentCache):
+            parts = [self.project_garment(part).take(0, "cpu", pin_memory=torch.cuda.is_available()) for part in features.parts]
+            return ShelvedGarmentCache(parts, gh=features.gh, gw=features.gw, slot_shapes=features.slot_shapes, h=features.h, w=features.w)
         if features.dtype != self.dtype or features.weights_id != self.weights_identity():
             raise ValueError(f"project_garment: {'dtype' if features.dtype != self.dtype else 'weights'} mismatch (the cache was built in "
                              f"{features.dtype} with weights {features.weights_id}; the engine runs {self.dtype} with {self.weights_identity()})")
@@ -388,7 +395,8 @@ class TryonEngine:
         A HOST-RESIDENT cache (CPU tensors) is streamed into the sets block by block during the call (_cached_fill); every tensor -- and a
         packed cache's `exps` -- must be page-locked (pin_memory), the cache must not have `sizes`, and the engine must not be attn_fp8: each
         a ValueError naming the field, before anything is launched.  A ShelvedGarmentCache (GarmentShelf.get) is the host-resident cache WITH
-        sizes: garment_index is required, every part and every part's `exps` must be page-locked, the engine must not be attn_fp8."""
+        sizes: garment_index is required, every part and every part's `exps` must be page-locked, the engine must not be attn_fp8; its
+        parts are compact K / V^T caches or compact feature caches (GarmentShelf(storage="features" / "features-e4m3"))."""
         dev, dt = self.device, self.dtype
         self._release_streamed()
         f32 = lambda t: t.to(dev, torch.float32).contiguous()
@@ -571,11 +579,11 @@ class TryonEngine:
         derived from F's: the sets hold what the block's projection writes."""
         gc = st["gcache"]
         slots = gc.G if st["gindex"] is None else st["B"]
+        if isinstance(gc, ShelvedGarmentCache):              # no tensor list: the slot's shapes, what a slotted cache of that slot size has
+            n = len(gc.timesteps)                            # (K / V^T and feature parts alike: the sets hold what the projection writes)
+            return slots, [((n * slots * a[0], a[1]), (n * slots, b[0], b[1]), gc.dtype) for a, b in gc.slot_shapes]
         if gc.features:
             return slots, TryonEngine._feature_kv_shapes(gc, slots)
-        if isinstance(gc, ShelvedGarmentCache):              # no tensor list: the slot's shapes, what a slotted cache of that slot size has
-            n = len(gc.timesteps)
-            return slots, [((n * slots * a[0], a[1]), (n * slots, b[0], b[1]), gc.dtype) for a, b in gc.slot_shapes]
         dt = lambda d: gc.dtype if gc.packed else d
         return slots, [((a[0] // gc.G * slots,) + a[1:], (b[0] // gc.G * slots,) + b[1:], dt(d)) for a, b, d in kv_shapes(gc.kv)]
 
@@ -638,15 +646,21 @@ class TryonEngine:
         in place of the set's K / V^T, and ONE project_garment_kv(staging, out=sets[p]["kv"]) follows it on the same stream: the launches
         an uncached call makes behind its GarmentNet batch.  Same tables, same records (F is K-shaped: kv_records), same transports, same sets
         and graph states.  A device-resident 16-bit block of consecutive entries without an index is projected from the cache's own views,
-        with no copy.  Slots no person reads are projected from whatever the staging list holds."""
+        with no copy.  Slots no person reads are projected from whatever the staging list holds.
+        A SHELVED feature cache (ShelvedGarmentCache of feature parts) is both at once: idmvton_kv_fill / idmvton_kv_place puts each compact
+        F into the front of its staging slot and writes the zero ROWS behind it (kv_records), and the projection -- at slot size whatever
+        the garments' sizes -- makes zero K rows and the zero V^T tail of them: to_k / to_v have no bias.  The sets, tables and graph states
+        are those of the K / V^T shelf call at the same slot size."""
         gc, k, B = st["gcache"], st["k"], st["blocks"]
         S = gc.G if st["gindex"] is None else st["B"]
         dsts, project = [fs["kv"] for fs in sets], lambda bi, p, feats=None: None
         if gc.features:
             n = len(gc.timesteps)
+            # (N_f, C_f) of a staging slot: a shelved cache has no tensor list -- the slot's K shape, whatever its compact parts hold
+            fshapes = [a for a, _ in gc.slot_shapes] if isinstance(gc, ShelvedGarmentCache) else [(f.shape[0] // (n * gc.G), f.shape[1]) for f, in gc.kv]
             for fs in sets:
                 if not fs["feats"]:
-                    fs["feats"] = [torch.empty(k * S, f.shape[0] // (n * gc.G), f.shape[1], dtype=self.dtype, device=self.device) for f, in gc.kv]
+                    fs["feats"] = [torch.empty(k * S, N, Cc, dtype=self.dtype, device=self.device) for N, Cc in fshapes]
             dsts = [[(f.view(-1, f.shape[-1]),) for f in fs["feats"]] for fs in sets]
 
             def project(bi, p, feats=None):
