@@ -117,6 +117,67 @@ static void sp_grid(AttnParams& p, int qrows, dim3& grid) {   // (also sets pp_f
 
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
+// ---- what the kernels below do the same way: Q staging, segment facts, the absent-segment count, the output store.  Their shape
+// (which arguments go by value, which through a reference that is filled) is the one that leaves hipcc's code for the kernels as it was:
+// tools/asm_diff.py, profiles/LOG.md ----
+
+// Q tile of one wave: 32 rows (row0 on, clamped to the last row) x 128 B -> LDS at dq (4 DMA instructions, K's swizzle); read back after the first wait
+// (descriptor and scalars by value: read through the params struct in here, hipcc renumbers the registers of every kernel)
+__device__ __forceinline__ void stage_q_tile(const __amdgpu_buffer_rsrc_t rs_q, int Nq, int ldq, char* dq, int b, int h, int row0, int lane) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int R = i * 8 + (lane >> 3);
+        const int c = (lane & 7) ^ ((R >> 1) & 7);
+        int row = row0 + R;
+        row = row < Nq ? row : Nq - 1;
+        dma16(rs_q, dq + i * 1024, (uint32_t)((((size_t)b * Nq + row) * ldq + h * 64 + c * 8) * 2));
+    }
+}
+
+// The key segments as batch element b sees them (block-uniform, scalar): present or absent (CFG-unconditional half), this batch's key counts
+// (the capacity, or the ragged table's entry), 64-key tiles to walk, and the batch element of each segment it reads (shared / indexed segments).
+struct SegFacts {
+    bool pres0, pres1;
+    int nk0, nk1, nt0, nt1, nt, bsg0, bsg1;
+};
+__device__ __forceinline__ void seg_facts(const AttnParams& p, int b, SegFacts& f) {
+    f.pres0 = p.nseg > 0 && b >= p.seg_b0[0];
+    f.pres1 = p.nseg > 1 && b >= p.seg_b0[1];
+    f.nk0 = seg_keys(b, p.nk[0], p.seg_nkt[0]); f.nk1 = seg_keys(b, p.nk[1], p.seg_nkt[1]);
+    f.nt0 = f.pres0 ? (f.nk0 + 63) >> 6 : 0;
+    f.nt1 = f.pres1 ? (f.nk1 + 63) >> 6 : 0;
+    f.nt = f.nt0 + f.nt1;
+    f.bsg0 = seg_batch_ix(b, p.seg_b0[0], p.seg_nb[0], p.seg_ix[0]); f.bsg1 = seg_batch_ix(b, p.seg_b0[1], p.seg_nb[1], p.seg_ix[1]);
+}
+// Keys of the absent (all-zero) segments: they enter the softmax in closed form, nz keys with logit 0 and value 0 (m = 0, l = nz)
+__device__ __forceinline__ int absent_keys(const AttnParams& p, const SegFacts& f) {
+    int nz = 0;
+    if (p.nseg > 0 && !f.pres0) nz += f.nk0;
+    if (p.nseg > 1 && !f.pres1) nz += f.nk1;
+    return nz;
+}
+
+// Finalise and store: lane holds O[q_row][h*64 + db*32 + 8g + 4u + j] = oacc[db][8g + 4k + j] * inv; both lanes of a pair (l, l+32) hold the same
+// query row
+template <typename T>
+__device__ __forceinline__ void finalise_store(const AttnParams& p, int b, int h, int q_row, int u, const f32x16 (&oacc)[2], float inv) {
+    typedef typename VT<T>::v4 v4;
+    if (q_row < p.Nq) {
+        T* op = (T*)p.out + ((size_t)b * p.Nq + q_row) * p.ldo + h * 64 + 8 * u;
+#pragma unroll
+        for (int db = 0; db < 2; ++db)
+#pragma unroll
+            for (int gp = 0; gp < 2; ++gp) {
+                v4 o[2];
+#pragma unroll
+                for (int k = 0; k < 2; ++k)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) o[k][j] = (T)(oacc[db][8 * gp + 4 * k + j] * inv);
+                store_cols8(op + db * 32 + 16 * gp, o[0], o[1]);
+            }
+    }
+}
+
 template <typename T, int MODE, int NWAVES, int ST>
 __global__ __launch_bounds__(NWAVES * 64) void attn_kernel(const AttnParams p) {
     typedef typename VT<T>::v8 v8;
@@ -145,35 +206,19 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_kernel(const AttnParams p) {
 #pragma unroll
         for (int s = 0; s < 4; ++s) qf[s] = *(const v8*)(qp + 16 * s);
     } else {
-        // Q tile of this wave: 32 rows x 128 B -> LDS (4 DMA instructions, same swizzle as K); read back after the first wait
-        const __amdgpu_buffer_rsrc_t rs_q = make_rsrc(p.q, p.qbytes);
-        char* dq = smem + ST * STAGE + wave * 4096;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int R = i * 8 + (lane >> 3);
-            const int c = (lane & 7) ^ ((R >> 1) & 7);
-            int row = qb * QB + wave * 32 + R;
-            row = row < p.Nq ? row : p.Nq - 1;
-            dma16(rs_q, dq + i * 1024, (uint32_t)((((size_t)b * p.Nq + row) * p.ldq + h * 64 + c * 8) * 2));
-        }
+        stage_q_tile(make_rsrc(p.q, p.qbytes), p.Nq, p.ldq, smem + ST * STAGE + wave * 4096, b, h, qb * QB + wave * 32, lane);
     }
 
-    // ---- which segments exist for this batch element (block-uniform) ----
-    const bool pres0 = p.nseg > 0 && b >= p.seg_b0[0];
-    const bool pres1 = p.nseg > 1 && b >= p.seg_b0[1];
-    const int nk0 = seg_keys(b, p.nk[0], p.seg_nkt[0]), nk1 = seg_keys(b, p.nk[1], p.seg_nkt[1]);   // this batch's key counts: per workgroup, scalar
-    const int nt0 = pres0 ? (nk0 + 63) >> 6 : 0;
-    const int nt1 = pres1 ? (nk1 + 63) >> 6 : 0;
-    const int nt = nt0 + nt1;
-    const int bsg0 = seg_batch_ix(b, p.seg_b0[0], p.seg_nb[0], p.seg_ix[0]), bsg1 = seg_batch_ix(b, p.seg_b0[1], p.seg_nb[1], p.seg_ix[1]);   // per workgroup, scalar
+    SegFacts sf;
+    seg_facts(p, b, sf);
 
     // ---- loader ----
     const int lrow = lane >> 3, lslot = lane & 7;
     auto issue = [&](int t, char* tile) {
-        const int sg = t < nt0 ? 0 : 1;
-        const int kt = sg ? t - nt0 : t;
-        const int nk = sg ? nk1 : nk0;
-        const int bsg = sg ? bsg1 : bsg0;
+        const int sg = t < sf.nt0 ? 0 : 1;
+        const int kt = sg ? t - sf.nt0 : t;
+        const int nk = sg ? sf.nk1 : sf.nk0;
+        const int bsg = sg ? sf.bsg1 : sf.bsg0;
         char* dst = tile + wave * (IPW * 1024);
 #pragma unroll
         for (int i = 0; i < IPW; ++i) {
@@ -214,17 +259,15 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_kernel(const AttnParams p) {
     float m_run = NEG_BIG, l_run = 0.f;
     if (MODE == IDMVTON_ATTN_SELF) {
         // closed form for absent (all-zero) segments: nk keys with logit 0, value 0
-        int nz = 0;
-        if (p.nseg > 0 && !pres0) nz += nk0;
-        if (p.nseg > 1 && !pres1) nz += nk1;
+        const int nz = absent_keys(p, sf);
         if (nz > 0) { m_run = 0.f; l_run = u == 0 ? (float)nz : 0.f; }
     }
 
-    const int ns = (nt + KT - 1) / KT;                    // stages
+    const int ns = (sf.nt + KT - 1) / KT;                    // stages
     auto issue_stage = [&](int s, int bufi) {
 #pragma unroll
         for (int sub = 0; sub < KT; ++sub)
-            if (s * KT + sub < nt) issue(s * KT + sub, smem + bufi * STAGE + sub * 16384);
+            if (s * KT + sub < sf.nt) issue(s * KT + sub, smem + bufi * STAGE + sub * 16384);
     };
     if constexpr (ST == 2) { if (ns > 0) issue_stage(0, 0); }
     else {
@@ -255,11 +298,11 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_kernel(const AttnParams p) {
 #pragma unroll
       for (int sub = 0; sub < KT; ++sub) {
         const int t = st_i * KT + sub;
-        if (t >= nt) break;
+        if (t >= sf.nt) break;
         const char* buf = sbuf + sub * 16384;
-        const int sg = t < nt0 ? 0 : 1;
-        const int kt = sg ? t - nt0 : t;
-        const int valid = (sg ? nk1 : nk0) - kt * 64;    // keys of this tile that exist (>= 64: all)
+        const int sg = t < sf.nt0 ? 0 : 1;
+        const int kt = sg ? t - sf.nt0 : t;
+        const int valid = (sg ? sf.nk1 : sf.nk0) - kt * 64;    // keys of this tile that exist (>= 64: all)
 
         // ---- S^T = K . Q^T ----
         f32x16 sacc[2];
@@ -320,7 +363,7 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_kernel(const AttnParams p) {
                 oacc[db] = VT<T>::mfma(vf, pf[ks], oacc[db]);
             }
         if (MODE == IDMVTON_ATTN_CROSS) {
-            if (t == nt0 - 1) {                          // end of the text group: finalise it and restart the softmax
+            if (t == sf.nt0 - 1) {                          // end of the text group: finalise it and restart the softmax
                 const float lt = xhalf_sum(l_run);
                 const float inv = 1.0f / lt;
 #pragma unroll
@@ -337,7 +380,7 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_kernel(const AttnParams p) {
     const float lt = xhalf_sum(l_run);
     const float inv = lt > 0.f ? 1.0f / lt : 0.f;
     const float sc = MODE == IDMVTON_ATTN_CROSS ? p.ip_scale * inv : inv;
-    if (q_row < p.Nq) {                                  // both lanes of a pair (l, l+32) hold the same query row
+    if (q_row < p.Nq) {                                  // (finalise_store with the CROSS mode's first softmax and scale folded in)
         T* op = (T*)p.out + ((size_t)b * p.Nq + q_row) * p.ldo + h * 64 + 8 * u;
 #pragma unroll
         for (int db = 0; db < 2; ++db)
@@ -402,29 +445,15 @@ __global__ __launch_bounds__(512, DEEP ? 2 : 4) void attn_pp_kernel(const AttnPa
     if (!attn_work(p, blockIdx.x, b, h, qb)) return;     // block-uniform
     const int q_row = qb * QB + wave * 32 + l31;
 
-    {   // Q tile of this wave: 32 rows x 128 B -> LDS (4 DMA instructions, K's swizzle)
-        const __amdgpu_buffer_rsrc_t rs_q = make_rsrc(p.q, p.qbytes);
-        char* dq = smem + ST * 16384 + wave * 4096;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int R = i * 8 + (lane >> 3);
-            const int c = (lane & 7) ^ ((R >> 1) & 7);
-            int row = qb * QB + wave * 32 + R;
-            row = row < p.Nq ? row : p.Nq - 1;
-            dma16(rs_q, dq + i * 1024, (uint32_t)((((size_t)b * p.Nq + row) * p.ldq + h * 64 + c * 8) * 2));
-        }
-    }
-    const bool pres0 = p.nseg > 0 && b >= p.seg_b0[0];
-    const bool pres1 = p.nseg > 1 && b >= p.seg_b0[1];
-    const int nk0 = seg_keys(b, p.nk[0], p.seg_nkt[0]), nk1 = seg_keys(b, p.nk[1], p.seg_nkt[1]);   // this batch's key counts: per workgroup, scalar
-    const int nt0 = pres0 ? (nk0 + 63) >> 6 : 0;
-    const int nt1 = pres1 ? (nk1 + 63) >> 6 : 0;
-    const int nt = nt0 + nt1;
+    stage_q_tile(make_rsrc(p.q, p.qbytes), p.Nq, p.ldq, smem + ST * 16384 + wave * 4096, b, h, qb * QB + wave * 32, lane);
+    SegFacts sf;
+    seg_facts(p, b, sf);
 
     // ---- loader: stage s = K(s) (DMA instructions j = 0..7: waves 0-3) | V^T(s-1) (j = 8..15: waves 4-7).  A wave loads
     // either K rows or V^T rows for the whole kernel, so everything that depends on that choice is folded into per-lane
     // constants here and the in-loop issue is branch-free: offset = rowbase[seg][i] + kt * tstep[seg]; a chunk is fetched iff
     // its smallest key index lim[i] + 64 kt exists (< nk[seg]); everything else (tiles -1 and nt, key tails) reads zeros.
+    // (attn_pf_kernel holds a copy of this loader, see there: a change here is a change there.)
     const int lrow = lane >> 3, lslot = lane & 7;
     const bool is_k = wave < 4;                          // (nk0 / nk1 are locals, in SGPRs: indexing p.nk[] by a loop value makes hipcc re-load it
                                                          // from the kernarg segment -- s_load + lgkmcnt(0) -- in every phase)
@@ -451,10 +480,10 @@ __global__ __launch_bounds__(512, DEEP ? 2 : 4) void attn_pp_kernel(const AttnPa
     auto issue_stage = [&](int s, int bufi) {
         char* dst = smem + bufi * 16384 + wave * (IPW * 1024);
         const int t = s - t_shift;
-        const bool in_range = t >= 0 && t < nt;
-        const bool sg1 = t >= nt0;
-        const int kt = sg1 ? t - nt0 : t;
-        const int room = in_range ? (sg1 ? nk1 : nk0) - kt * 64 : 0;               // keys of this tile that exist
+        const bool in_range = t >= 0 && t < sf.nt;
+        const bool sg1 = t >= sf.nt0;
+        const int kt = sg1 ? t - sf.nt0 : t;
+        const int room = in_range ? (sg1 ? sf.nk1 : sf.nk0) - kt * 64 : 0;               // keys of this tile that exist
         const uint32_t toff = (uint32_t)kt * (sg1 ? tstep[1] : tstep[0]);
 #pragma unroll
         for (int i = 0; i < IPW; ++i) {
@@ -499,9 +528,7 @@ __global__ __launch_bounds__(512, DEEP ? 2 : 4) void attn_pp_kernel(const AttnPa
     float m_run = 0.f, l_run = 0.f;
     float thr_cur = -3.0e38f, floor_cur = -3.0e38f;      // first tile: the branch below is always taken and delta = the row max
     {
-        int nz = 0;
-        if (p.nseg > 0 && !pres0) nz += nk0;
-        if (p.nseg > 1 && !pres1) nz += nk1;
+        const int nz = absent_keys(p, sf);
         if (nz > 0) {
             l_run = u == 0 ? (float)nz : 0.f; thr_cur = thr; floor_cur = 0.f;
             if constexpr (LSUM) {
@@ -513,8 +540,8 @@ __global__ __launch_bounds__(512, DEEP ? 2 : 4) void attn_pp_kernel(const AttnPa
 
 #pragma unroll
     for (int s = 0; s < ST - 1; ++s)
-        if (s <= nt) issue_stage(s, s);
-    if (nt >= ST - 2) wait_vmcnt<(ST - 1) * IPW>(); else wait_vmcnt<0>();       // Q (oldest DMAs, own rows) has landed
+        if (s <= sf.nt) issue_stage(s, s);
+    if (sf.nt >= ST - 2) wait_vmcnt<(ST - 1) * IPW>(); else wait_vmcnt<0>();       // Q (oldest DMAs, own rows) has landed
     // Q fragments (B operand of S^T), kept in registers.  cs: softmax scale folded with log2(e), 1 when q arrives pre-multiplied
     // (the NEGM build is only launched with a pre-multiplied q: scaling q here would round it a second time).
     const char* const dq = smem + ST * 16384 + wave * 4096 + l31 * 128;
@@ -570,8 +597,8 @@ __global__ __launch_bounds__(512, DEEP ? 2 : 4) void attn_pp_kernel(const AttnPa
             l_run += 1.f;
             return;
         }
-        const bool sg1 = j >= nt0;
-        const int valid = sg1 ? nk1 - (j - nt0) * 64 : nk0 - j * 64;     // keys of this tile that exist (>= 64: all)
+        const bool sg1 = j >= sf.nt0;
+        const int valid = sg1 ? sf.nk1 - (j - sf.nt0) * 64 : sf.nk0 - j * 64;     // keys of this tile that exist (>= 64: all)
         if (valid < 64) {
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
@@ -623,11 +650,11 @@ __global__ __launch_bounds__(512, DEEP ? 2 : 4) void attn_pp_kernel(const AttnPa
     // register assignment across the blocks.
     int cbuf = 0, ibuf = ST - 1;
     auto sync_stage = [&](int s) -> const char* {
-        if (s + ST - 2 <= nt) wait_vmcnt<(ST - 2) * IPW>(); else wait_vmcnt<0>();
+        if (s + ST - 2 <= sf.nt) wait_vmcnt<(ST - 2) * IPW>(); else wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("" ::: "memory");
-        if (s + ST - 1 <= nt) issue_stage(s + ST - 1, ibuf);
+        if (s + ST - 1 <= sf.nt) issue_stage(s + ST - 1, ibuf);
         const char* buf = smem + cbuf * 16384;
         cbuf = cbuf + 1 == ST ? 0 : cbuf + 1;
         ibuf = ibuf + 1 == ST ? 0 : ibuf + 1;
@@ -640,15 +667,15 @@ __global__ __launch_bounds__(512, DEEP ? 2 : 4) void attn_pp_kernel(const AttnPa
         asm volatile("" ::: "memory");
     };
     if (grp == 0) {
-        for (int s = 0; s <= nt; ++s) {
+        for (int s = 0; s <= sf.nt; ++s) {
             const char* buf = sync_stage(s);             // phase 2s
             mfma_block(buf);
             mid_barrier();                               // phase 2s+1
-            if (s < nt) valu_block(s);
+            if (s < sf.nt) valu_block(s);
             __builtin_amdgcn_sched_barrier(0);
         }
     } else {
-        for (int s = 0; s <= nt; ++s) {
+        for (int s = 0; s <= sf.nt; ++s) {
             const char* buf = sync_stage(s);             // phase 2s
             if (s >= 1) valu_block(s - 1);
             mid_barrier();                               // phase 2s+1
@@ -660,7 +687,7 @@ __global__ __launch_bounds__(512, DEEP ? 2 : 4) void attn_pp_kernel(const AttnPa
     // ---- finalise and store: lane holds O[q][h*64 + db*32 + 8g + 4u + j] ----
     const float lt = LSUM ? lacc[0] : xhalf_sum(l_run);     // (LSUM: every row of the accumulator holds this lane's query-row sum over all keys)
     const float inv = lt > 0.f ? 1.0f / lt : 0.f;
-    if (q_row < p.Nq) {
+    if (q_row < p.Nq) {                                  // (finalise_store, written out: through the helper the DEEP = false build's stores come out in another order)
         T* op = (T*)p.out + ((size_t)b * p.Nq + q_row) * p.ldo + h * 64 + 8 * u;
 #pragma unroll
         for (int db = 0; db < 2; ++db)
@@ -702,7 +729,6 @@ extern "C" int idmvton_attn_dbg_read(void* dst, size_t bytes) { return (int)hipM
 template <typename T, bool LSUM, int ABL = 0>
 __global__ __launch_bounds__(512, 2) void attn_pf_kernel(const AttnParams p) {
     typedef typename VT<T>::v8 v8;
-    typedef typename VT<T>::v4 v4;
     constexpr int NW = 8, QB = 256, IPW = 2, ST = 3;
     __shared__ __attribute__((aligned(1024))) char smem[ST * 16384 + NW * 4096];   // [stage][K | V^T] + per-wave Q tile
 
@@ -722,26 +748,12 @@ __global__ __launch_bounds__(512, 2) void attn_pf_kernel(const AttnParams p) {
     if (!attn_work(p, blockIdx.x, b, h, qb)) return;     // block-uniform
     const int q_row = qb * QB + wave * 32 + l31;
 
-    {   // Q tile of this wave: 32 rows x 128 B -> LDS (4 DMA instructions, K's swizzle)
-        const __amdgpu_buffer_rsrc_t rs_q = make_rsrc(p.q, p.qbytes);
-        char* dq = smem + ST * 16384 + wave * 4096;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int R = i * 8 + (lane >> 3);
-            const int c = (lane & 7) ^ ((R >> 1) & 7);
-            int row = qb * QB + wave * 32 + R;
-            row = row < p.Nq ? row : p.Nq - 1;
-            dma16(rs_q, dq + i * 1024, (uint32_t)((((size_t)b * p.Nq + row) * p.ldq + h * 64 + c * 8) * 2));
-        }
-    }
-    const bool pres0 = p.nseg > 0 && b >= p.seg_b0[0];
-    const bool pres1 = p.nseg > 1 && b >= p.seg_b0[1];
-    const int nk0 = seg_keys(b, p.nk[0], p.seg_nkt[0]), nk1 = seg_keys(b, p.nk[1], p.seg_nkt[1]);   // this batch's key counts: per workgroup, scalar
-    const int nt0 = pres0 ? (nk0 + 63) >> 6 : 0;
-    const int nt1 = pres1 ? (nk1 + 63) >> 6 : 0;
-    const int nt = nt0 + nt1;
+    stage_q_tile(make_rsrc(p.q, p.qbytes), p.Nq, p.ldq, smem + ST * 16384 + wave * 4096, b, h, qb * QB + wave * 32, lane);
+    SegFacts sf;
+    seg_facts(p, b, sf);
 
-    // ---- loader (as attn_pp_kernel): waves 0-3 fetch K(s), waves 4-7 V^T(s-1); per-lane constants, branch-free issue ----
+    // ---- loader (as attn_pp_kernel): waves 0-3 fetch K(s), waves 4-7 V^T(s-1); per-lane constants, branch-free issue.  (A copy: with the
+    // constants in a function or struct shared by the two kernels hipcc merges the kernarg loads otherwise and both kernels' SGPR counts move.) ----
     const int lrow = lane >> 3, lslot = lane & 7;
     const bool is_k = wave < 4;
     const int t_shift = is_k ? 0 : 1;
@@ -766,10 +778,10 @@ __global__ __launch_bounds__(512, 2) void attn_pf_kernel(const AttnParams p) {
     auto issue_stage = [&](int s, int bufi) {
         char* dst = smem + bufi * 16384 + wave * (IPW * 1024);
         const int t = s - t_shift;
-        const bool in_range = t >= 0 && t < nt;
-        const bool sg1 = t >= nt0;
-        const int kt = sg1 ? t - nt0 : t;
-        const int room = in_range ? (sg1 ? nk1 : nk0) - kt * 64 : 0;
+        const bool in_range = t >= 0 && t < sf.nt;
+        const bool sg1 = t >= sf.nt0;
+        const int kt = sg1 ? t - sf.nt0 : t;
+        const int room = in_range ? (sg1 ? sf.nk1 : sf.nk0) - kt * 64 : 0;
         const uint32_t toff = (uint32_t)kt * (sg1 ? tstep[1] : tstep[0]);
 #pragma unroll
         for (int i = 0; i < IPW; ++i) {
@@ -801,9 +813,7 @@ __global__ __launch_bounds__(512, 2) void attn_pf_kernel(const AttnParams p) {
     float m_run = 0.f, l_run = 0.f;
     float thr_cur = -3.0e38f, floor_cur = -3.0e38f;      // first tile: the max is forced to the tile's own row max (see attn_pp_kernel)
     {
-        int nz = 0;
-        if (p.nseg > 0 && !pres0) nz += nk0;
-        if (p.nseg > 1 && !pres1) nz += nk1;
+        const int nz = absent_keys(p, sf);
         if (nz > 0) {
             l_run = u == 0 ? (float)nz : 0.f; thr_cur = thr; floor_cur = 0.f;
             if constexpr (LSUM) {
@@ -814,7 +824,7 @@ __global__ __launch_bounds__(512, 2) void attn_pf_kernel(const AttnParams p) {
     }
 
     // ---- prologue: stages 0..2 in flight, Q and stage 0 landed ----
-    const int npro = nt + 1 < ST ? nt + 1 : ST;          // stages 0..nt exist
+    const int npro = sf.nt + 1 < ST ? sf.nt + 1 : ST;          // stages 0..nt exist
 #pragma unroll
     for (int s = 0; s < ST; ++s)
         if (s < npro) issue_stage(s, s);
@@ -851,8 +861,8 @@ __global__ __launch_bounds__(512, 2) void attn_pf_kernel(const AttnParams p) {
     };
     // VALU block j: online softmax of S'(j) -> P(j) (PV B operand); re-seeds sacc with -m_run for QK^T(j+1)
     auto valu_block = [&](int j) {
-        const bool sg1 = j >= nt0;
-        const int valid = sg1 ? nk1 - (j - nt0) * 64 : nk0 - j * 64;
+        const bool sg1 = j >= sf.nt0;
+        const int valid = sg1 ? sf.nk1 - (j - sf.nt0) * 64 : sf.nk0 - j * 64;
         if (valid < 64) {
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
@@ -911,7 +921,7 @@ __global__ __launch_bounds__(512, 2) void attn_pf_kernel(const AttnParams p) {
     // barrier M_s: own share of stage s+1 landed (stage s+2, if it exists, stays in flight), LDS reads of this phase done
     auto mid_barrier = [&](int s) {
         __builtin_amdgcn_sched_barrier(0);
-        if (s + 2 <= nt) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(IPW) : "memory");
+        if (s + 2 <= sf.nt) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(IPW) : "memory");
         else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
@@ -925,7 +935,7 @@ __global__ __launch_bounds__(512, 2) void attn_pf_kernel(const AttnParams p) {
 #endif
     if (grp == 0) {
         read_frags(smem);                                // F(0)
-        for (int s = 0; s <= nt; ++s) {
+        for (int s = 0; s <= sf.nt; ++s) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             DBG_STAMP(2);
             phase_barrier();                             // A_s
@@ -935,14 +945,14 @@ __global__ __launch_bounds__(512, 2) void attn_pf_kernel(const AttnParams p) {
             DBG_STAMP(0);
             mid_barrier(s);                              // B_s
             DBG_STAMP(1);
-            if ((ABL != 2 && ABL < 5) && s + 1 <= nt) read_frags(smem + b1i * 16384);
+            if ((ABL != 2 && ABL < 5) && s + 1 <= sf.nt) read_frags(smem + b1i * 16384);
             __builtin_amdgcn_sched_barrier(0);
-            if ((ABL != 1 && ABL < 5) && s + 3 <= nt) issue_stage(s + 3, b0i);
-            if (s < nt) valu_block(s);
+            if ((ABL != 1 && ABL < 5) && s + 3 <= sf.nt) issue_stage(s + 3, b0i);
+            if (s < sf.nt) valu_block(s);
             rotate();
         }
     } else {
-        for (int s = 0; s <= nt; ++s) {
+        for (int s = 0; s <= sf.nt; ++s) {
             DBG_STAMP(2);
             phase_barrier();                             // A_s
             DBG_STAMP(3);
@@ -955,7 +965,7 @@ __global__ __launch_bounds__(512, 2) void attn_pf_kernel(const AttnParams p) {
             DBG_STAMP(1);
             mfma_block();
             __builtin_amdgcn_sched_barrier(0);
-            if ((ABL != 1 && ABL < 5) && s + 3 <= nt) issue_stage(s + 3, b0i);
+            if ((ABL != 1 && ABL < 5) && s + 3 <= sf.nt) issue_stage(s + 3, b0i);
             rotate();
         }
     }
@@ -968,20 +978,7 @@ __global__ __launch_bounds__(512, 2) void attn_pf_kernel(const AttnParams p) {
 
     const float lt = LSUM ? lacc[0] : xhalf_sum(l_run);
     const float inv = lt > 0.f ? 1.0f / lt : 0.f;
-    if (q_row < p.Nq) {
-        T* op = (T*)p.out + ((size_t)b * p.Nq + q_row) * p.ldo + h * 64 + 8 * u;
-#pragma unroll
-        for (int db = 0; db < 2; ++db)
-#pragma unroll
-            for (int gp = 0; gp < 2; ++gp) {
-                v4 o[2];
-#pragma unroll
-                for (int k = 0; k < 2; ++k)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) o[k][j] = (T)(oacc[db][8 * gp + 4 * k + j] * inv);
-                store_cols8(op + db * 32 + 16 * gp, o[0], o[1]);
-            }
-    }
+    finalise_store<T>(p, b, h, q_row, u, oacc, inv);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1010,7 +1007,6 @@ __global__ __launch_bounds__(512, 2) void attn_pf_kernel(const AttnParams p) {
 template <typename T, int NW, int ABL = 0>
 __global__ __launch_bounds__(NW * 64, 2) void attn_sp_kernel(const AttnParams p) {
     typedef typename VT<T>::v8 v8;
-    typedef typename VT<T>::v4 v4;
     constexpr int QB = 32 * NW, IPW = 16 / NW, ST = 3;    // NW = 8: one workgroup per CU; NW = 4: two (independent) workgroups per CU
     __shared__ __attribute__((aligned(1024))) char smem[ST * 16384 + NW * 4096];   // [stage][K | V^T] + per-wave Q tile
 
@@ -1023,24 +1019,9 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_sp_kernel(const AttnParams p)
     if (!sp_work(p, blockIdx.x, b, h, qb)) return;       // block-uniform
     const int q_row = qb * QB + wave * 32 + l31;
 
-    {   // Q tile of this wave: 32 rows x 128 B -> LDS (4 DMA instructions, K's swizzle)
-        const __amdgpu_buffer_rsrc_t rs_q = make_rsrc(p.q, p.qbytes);
-        char* dq = smem + ST * 16384 + wave * 4096;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int R = i * 8 + (lane >> 3);
-            const int c = (lane & 7) ^ ((R >> 1) & 7);
-            int row = qb * QB + wave * 32 + R;
-            row = row < p.Nq ? row : p.Nq - 1;
-            dma16(rs_q, dq + i * 1024, (uint32_t)((((size_t)b * p.Nq + row) * p.ldq + h * 64 + c * 8) * 2));
-        }
-    }
-    const bool pres0 = p.nseg > 0 && b >= p.seg_b0[0];
-    const bool pres1 = p.nseg > 1 && b >= p.seg_b0[1];
-    const int nk0 = seg_keys(b, p.nk[0], p.seg_nkt[0]), nk1 = seg_keys(b, p.nk[1], p.seg_nkt[1]);   // this batch's key counts: per workgroup, scalar
-    const int nt0 = pres0 ? (nk0 + 63) >> 6 : 0;
-    const int nt1 = pres1 ? (nk1 + 63) >> 6 : 0;
-    const int nt = nt0 + nt1;
+    stage_q_tile(make_rsrc(p.q, p.qbytes), p.Nq, p.ldq, smem + ST * 16384 + wave * 4096, b, h, qb * QB + wave * 32, lane);
+    SegFacts sf;
+    seg_facts(p, b, sf);
 
     // ---- loader: waves 0-3 fetch K(i), waves 4-7 V^T(i-2).  The stages are issued strictly in order, so the segment walk is running scalar
     // state: ld_t = tile of the next stage for this wave (negative: V^T's two-stage lag; >= nt: past the end -> zero fill), ld_off = byte
@@ -1050,9 +1031,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_sp_kernel(const AttnParams p)
     // per-lane byte offsets of this wave's IPW DMA rows inside segment sg (tile 0).  Only the CURRENT segment's set lives in registers; it is
     // recomputed at the segment switch.  lane_lim(i): the smallest key index piece i fetches (only a segment's partial last tile needs it).
     uint32_t rb[IPW];
-    const int bsg0 = seg_batch_ix(b, p.seg_b0[0], p.seg_nb[0], p.seg_ix[0]), bsg1 = seg_batch_ix(b, p.seg_b0[1], p.seg_nb[1], p.seg_ix[1]);   // per workgroup, scalar
     auto seg_base = [&](int sg) {
-        const size_t bsg = (size_t)(sg ? bsg1 : bsg0);
+        const size_t bsg = (size_t)(sg ? sf.bsg1 : sf.bsg0);
 #pragma unroll
         for (int i = 0; i < IPW; ++i) {
             const int R = ((wave * IPW + i) & 7) * 8 + lrow;
@@ -1069,17 +1049,17 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_sp_kernel(const AttnParams p)
     const uint32_t tstep0 = is_k ? (uint32_t)(64 * p.ldk[0] * 2) : 128u, tstep1 = is_k ? (uint32_t)(64 * p.ldk[1] * 2) : 128u;
     const __amdgpu_buffer_rsrc_t rs0 = is_k ? make_rsrc(p.k[0], p.kbytes[0]) : make_rsrc(p.vt[0], p.vtbytes[0]);
     const __amdgpu_buffer_rsrc_t rs1 = is_k ? make_rsrc(p.k[1], p.kbytes[1]) : make_rsrc(p.vt[1], p.vtbytes[1]);
-    int ld_t = is_k ? 0 : -2, ld_room = nt0 > 0 ? nk0 : nk1;
-    bool ld_seg1 = nt0 == 0;
+    int ld_t = is_k ? 0 : -2, ld_room = sf.nt0 > 0 ? sf.nk0 : sf.nk1;
+    bool ld_seg1 = sf.nt0 == 0;
     uint32_t ld_off = 0;
     seg_base(ld_seg1 ? 1 : 0);
     auto issue_next = [&](int bufi) {
         char* dst = smem + bufi * 16384 + wave * (IPW * 1024);
-        if (ld_t < 0 || ld_t >= nt) {                    // outside the walk: zero fill (all lanes out of range)
+        if (ld_t < 0 || ld_t >= sf.nt) {                    // outside the walk: zero fill (all lanes out of range)
 #pragma unroll
             for (int i = 0; i < IPW; ++i) dma16(rs0, dst + i * 1024, OOB_SENTINEL);
         } else {
-            if (!ld_seg1 && ld_t == nt0) { ld_seg1 = true; ld_off = 0; ld_room = nk1; seg_base(1); }
+            if (!ld_seg1 && ld_t == sf.nt0) { ld_seg1 = true; ld_off = 0; ld_room = sf.nk1; seg_base(1); }
             if (ld_room >= 64) {                          // full tile: no per-lane masking
 #pragma unroll
                 for (int i = 0; i < IPW; ++i) { if (ld_seg1) dma16(rs1, dst + i * 1024, rb[i] + ld_off); else dma16(rs0, dst + i * 1024, rb[i] + ld_off); }
@@ -1115,14 +1095,12 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_sp_kernel(const AttnParams p)
     float m_run = 0.f, l_run = 0.f;
     float lim_cur = -1.f, floor_cur = -3.0e38f;
     {
-        int nz = 0;
-        if (p.nseg > 0 && !pres0) nz += nk0;
-        if (p.nseg > 1 && !pres1) nz += nk1;
+        const int nz = absent_keys(p, sf);
         if (nz > 0) { l_run = u == 0 ? (float)nz : 0.f; lim_cur = limit; floor_cur = 0.f; }
     }
 
     // ---- prologue: stages 0, 1 in flight; Q and stage 0 landed ----
-    const int last = nt + 1;                              // stages 0 .. nt + 1 exist
+    const int last = sf.nt + 1;                              // stages 0 .. nt + 1 exist
     issue_next(0);
     issue_next(1);
     wait_vmcnt<IPW>();
@@ -1246,9 +1224,9 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_sp_kernel(const AttnParams p)
     // (Measured and dropped: rotating the schedule of waves 4-7 by the tail -- block(i) sync(i+1) tail(i) -- so that one wave's barrier / test /
     // seed section lies beside its SIMD partner's MFMA block: +5 % time, profiles/r06_attention_sp_ablation.txt.)
     float ps[4];
-    int i = 1, jv = nt0 > 0 ? nk0 : nk1;
-    auto next_valid = [&](int ii) { jv -= 64; if (ii == nt0 && nt1 > 0) jv = nk1; };   // called after iteration ii: tile ii's count
-    for (; i + 1 <= nt; i += 2) {
+    int i = 1, jv = sf.nt0 > 0 ? sf.nk0 : sf.nk1;
+    auto next_valid = [&](int ii) { jv -= 64; if (ii == sf.nt0 && sf.nt1 > 0) jv = sf.nk1; };   // called after iteration ii: tile ii's count
+    for (; i + 1 <= sf.nt; i += 2) {
         const char* buf = sync_stage(i);
         block(jv, buf, sA, sB, ps);
         tail(sA, sB, ps);
@@ -1258,14 +1236,14 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_sp_kernel(const AttnParams p)
         tail(sB, sA, ps);
         next_valid(i + 1);
     }
-    if (i <= nt) {                                        // one iteration left
+    if (i <= sf.nt) {                                        // one iteration left
         const char* buf = sync_stage(i);
         block(jv, buf, sA, sB, ps);
         tail(sA, sB, ps);
     }
     // ---- iteration nt + 1: PV(nt-1) only, then normalise and store (lane holds O[q][h*64 + db*32 + 8g + 4u + j]) ----
-    if (nt > 0) {
-        const char* buf = sync_stage(nt + 1);
+    if (sf.nt > 0) {
+        const char* buf = sync_stage(sf.nt + 1);
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
             oacc[0] = VT<T>::mfma(v_frag(buf, 0, ks), P[ks], oacc[0]);
@@ -1274,20 +1252,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_sp_kernel(const AttnParams p)
     }
     const float lt = xhalf_sum(l_run);
     const float inv = lt > 0.f ? 1.0f / lt : 0.f;
-    if (q_row < p.Nq) {
-        T* op = (T*)p.out + ((size_t)b * p.Nq + q_row) * p.ldo + h * 64 + 8 * u;
-#pragma unroll
-        for (int db = 0; db < 2; ++db)
-#pragma unroll
-            for (int gp = 0; gp < 2; ++gp) {
-                v4 o[2];
-#pragma unroll
-                for (int k = 0; k < 2; ++k)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) o[k][j] = (T)(oacc[db][8 * gp + 4 * k + j] * inv);
-                store_cols8(op + db * 32 + 16 * gp, o[0], o[1]);
-            }
-    }
+    finalise_store<T>(p, b, h, q_row, u, oacc, inv);
 }
 
 template <typename T, int MODE>
@@ -1312,111 +1277,82 @@ static int launch_attn(AttnParams& p, int tune, hipStream_t st) {
     } else if (MODE == IDMVTON_ATTN_SELF && bh * ((p.Nq + 255) / 256) >= 200 && p.Nq >= 1024) {
         tune = (2 << 16) | (2 << 8) | 8; nw = 8; stg = 2;   // measured (profiles/r02_probe_attn_*): the ping-pong kernel wins on the long walks
     }
-    if (((tune >> 16) & 0xff) == 2 || ((tune >> 16) & 0xff) == 3) {   // ping-pong kernel (3: one workgroup per CU, deep fragment prefetch)
-        const bool deep = ((tune >> 16) & 0xff) == 3 && p.q_prescaled;   // the deep build needs q pre-multiplied (see NEGM)
-        if (MODE != IDMVTON_ATTN_SELF || nw != 8 || (stg != 2 && stg != 3))
-            return idmvton_set_error(IDMVTON_E_ARG, "attn_fwd: the ping-pong kernel needs SELF mode, 8 waves, 2 or 3 stages");
-        static const float thr_tab[4] = {4.f, 0.f, 8.f, 2.f};
-        p.pp_flags = (tune >> 24) & 3;
-        p.pp_thr = thr_tab[(tune >> 26) & 3];
-        dim3 gridp;
-        attn_grid(p, 256, gridp);
-        const dim3 blockp(512);
-        // (s_setprio around the MFMA block was measured: no effect in this structure; the 128-register build exists with 2 stages)
-        if (!deep) hipLaunchKernelGGL((attn_pp_kernel<T, 2, false>), gridp, blockp, 0, st, p);
-        else if (stg == 2) hipLaunchKernelGGL((attn_pp_kernel<T, 2, true>), gridp, blockp, 0, st, p);
-        else hipLaunchKernelGGL((attn_pp_kernel<T, 3, true>), gridp, blockp, 0, st, p);
+    const int kern = (tune >> 16) & 0xff, flags = (tune >> 24) & 3, sel = (tune >> 26) & 3;
+    static const float thr_tab[4] = {4.f, 0.f, 8.f, 2.f};          // rescale thresholds of the ping-pong kernels (tune bits 26-27), log2 units
+    typedef void (*kernel_t)(const AttnParams);
+    auto launch = [&](kernel_t k, bool sp, int qrows) -> int {     // 32 query rows per wave: qrows * 2 threads
+        dim3 grid;
+        if (sp) sp_grid(p, qrows, grid); else attn_grid(p, qrows, grid);
+        hipLaunchKernelGGL(k, grid, dim3(qrows * 2), 0, st, p);
         CHECK_LAUNCH("attn_fwd");
         return IDMVTON_OK;
+    };
+    if (kern == 2 || kern == 3) {   // ping-pong kernel (3: one workgroup per CU, deep fragment prefetch)
+        const bool deep = kern == 3 && p.q_prescaled;   // the deep build needs q pre-multiplied (see NEGM)
+        if (MODE != IDMVTON_ATTN_SELF || nw != 8 || (stg != 2 && stg != 3))
+            return idmvton_set_error(IDMVTON_E_ARG, "attn_fwd: the ping-pong kernel needs SELF mode, 8 waves, 2 or 3 stages");
+        p.pp_flags = flags;
+        p.pp_thr = thr_tab[sel];
+        // (s_setprio around the MFMA block was measured: no effect in this structure; the 128-register build exists with 2 stages)
+        return launch(!deep ? attn_pp_kernel<T, 2, false> : stg == 2 ? attn_pp_kernel<T, 2, true> : attn_pp_kernel<T, 3, true>, false, 256);
     }
-    if (((tune >> 16) & 0xff) >= 4 && ((tune >> 16) & 0xff) <= 6) {   // ablation builds of the ping-pong kernel (timing only)
+    if (kern >= 4 && kern <= 6) {   // ablation builds of the ping-pong kernel (timing only)
         p.pp_flags = 0; p.pp_thr = 4.f;
-        dim3 gridp;
-        attn_grid(p, 256, gridp);
         if (MODE != IDMVTON_ATTN_SELF) return idmvton_set_error(IDMVTON_E_ARG, "attn_fwd: ablation kernels are SELF mode only");
         if (nw != 8 || stg != 2)
             return idmvton_set_error(IDMVTON_E_ARG, "attn_fwd: the ablation kernels are 8 waves, 2 stages (tune waves=%d stages=%d)", nw, stg);
-        if (((tune >> 16) & 0xff) == 4) hipLaunchKernelGGL((attn_pp_kernel<T, 2, false, 1>), gridp, dim3(512), 0, st, p);
-        else if (((tune >> 16) & 0xff) == 5) hipLaunchKernelGGL((attn_pp_kernel<T, 2, false, 2>), gridp, dim3(512), 0, st, p);
-        else hipLaunchKernelGGL((attn_pp_kernel<T, 2, false, 3>), gridp, dim3(512), 0, st, p);
-        CHECK_LAUNCH("attn_fwd");
-        return IDMVTON_OK;
+        return launch(kern == 4 ? attn_pp_kernel<T, 2, false, 1> : kern == 5 ? attn_pp_kernel<T, 2, false, 2> : attn_pp_kernel<T, 2, false, 3>, false, 256);
     }
-    if (((tune >> 16) & 0xff) == 7 || ((tune >> 16) & 0xff) == 8) {   // attn_pf_kernel: fragments prefetched a phase early (7: row sums on the matrix pipe)
+    if (kern == 7 || kern == 8) {   // attn_pf_kernel: fragments prefetched a phase early (7: row sums on the matrix pipe)
         if (MODE != IDMVTON_ATTN_SELF || !p.q_prescaled)
             return idmvton_set_error(IDMVTON_E_ARG, "attn_fwd: the prefetch kernel needs SELF mode and a pre-multiplied q");
         if (nw != 8 || stg != 3)                         // the one build there is: another word would run it under a name it does not have
             return idmvton_set_error(IDMVTON_E_ARG, "attn_fwd: the prefetch kernel is 8 waves, 3 stages (tune waves=%d stages=%d)", nw, stg);
-        static const float thr_tab[4] = {4.f, 0.f, 8.f, 2.f};
         p.pp_flags = 0;
-        p.pp_thr = thr_tab[(tune >> 26) & 3];
-        dim3 gridp;
-        attn_grid(p, 256, gridp);
-        if (((tune >> 16) & 0xff) == 7) hipLaunchKernelGGL((attn_pf_kernel<T, true>), gridp, dim3(512), 0, st, p);
-        else hipLaunchKernelGGL((attn_pf_kernel<T, false>), gridp, dim3(512), 0, st, p);
-        CHECK_LAUNCH("attn_fwd");
-        return IDMVTON_OK;
+        p.pp_thr = thr_tab[sel];
+        return launch(kern == 7 ? attn_pf_kernel<T, true> : attn_pf_kernel<T, false>, false, 256);
     }
-    if (((tune >> 16) & 0xff) == 16) {   // attn_sp_kernel (software-pipelined, speculative exponentials, row-sum overflow test)
+    if (kern == 16) {   // attn_sp_kernel (software-pipelined, speculative exponentials, row-sum overflow test)
         if (MODE != IDMVTON_ATTN_SELF || !p.q_prescaled)
             return idmvton_set_error(IDMVTON_E_ARG, "attn_fwd: the software-pipelined kernel needs SELF mode and a pre-multiplied q");
         if ((nw != 4 && nw != 8) || stg != 3)
             return idmvton_set_error(IDMVTON_E_ARG, "attn_fwd: the software-pipelined kernel is 4 or 8 waves, 3 stages (tune waves=%d stages=%d)", nw, stg);
         static const float lim_tab[4] = {512.f, 32.f, 8192.f, 128.f};   // row-sum limits (tune bits 26-27): P <= limit while the max is kept
-        p.pp_thr = lim_tab[(tune >> 26) & 3];
-        dim3 gridp;
-        if (nw == 4) {                                   // 128 query rows per workgroup, two workgroups per CU: finer units for short / uneven walks
-            sp_grid(p, 128, gridp);
-            hipLaunchKernelGGL((attn_sp_kernel<T, 4>), gridp, dim3(256), 0, st, p);
-        } else {
-            sp_grid(p, 256, gridp);
-            hipLaunchKernelGGL((attn_sp_kernel<T, 8>), gridp, dim3(512), 0, st, p);
-        }
-        CHECK_LAUNCH("attn_fwd");
-        return IDMVTON_OK;
+        p.pp_thr = lim_tab[sel];
+        // 4 waves: 128 query rows per workgroup, two workgroups per CU: finer units for short / uneven walks
+        return nw == 4 ? launch(attn_sp_kernel<T, 4>, true, 128) : launch(attn_sp_kernel<T, 8>, true, 256);
     }
 #ifdef ATTN_DBG
-    if (((tune >> 16) & 0xff) >= 32 && ((tune >> 16) & 0xff) < 160) {   // ablation builds of attn_sp_kernel<row sums on the VALU> (timing only): selector - 32 = mask
+    if (kern >= 32 && kern < 160) {   // ablation builds of attn_sp_kernel<row sums on the VALU> (timing only): selector - 32 = mask
         p.pp_flags = 0; p.pp_thr = 512.f;                               // 1 no exponentials, 2 no MFMA, 4 no LDS reads, 8 no in-loop DMA, 16 no barrier
-        dim3 gridp;
-        sp_grid(p, 256, gridp);
-        switch (((tune >> 16) & 0xff) - 32) {                            // + 32 / + 64: every wave on group 0's / group 1's schedule (no rotation)
-#define SPA(m) case m: hipLaunchKernelGGL((attn_sp_kernel<T, 8, m>), gridp, dim3(512), 0, st, p); break;
+        switch (kern - 32) {                                            // + 32 / + 64: every wave on group 0's / group 1's schedule (no rotation)
+#define SPA(m) case m: return launch(attn_sp_kernel<T, 8, m>, true, 256);
         SPA(0) SPA(1) SPA(2) SPA(3) SPA(4) SPA(8) SPA(12) SPA(15) SPA(16) SPA(31) SPA(29)
 #undef SPA
         default: return idmvton_set_error(IDMVTON_E_ARG, "attn_fwd: ablation mask not built");
         }
-        CHECK_LAUNCH("attn_fwd");
-        return IDMVTON_OK;
     }
-    if (((tune >> 16) & 0xff) >= 9 && ((tune >> 16) & 0xff) <= 14) {   // anatomy builds of attn_pf_kernel<LSUM>: ABL = selector - 8
+    if (kern >= 9 && kern <= 14) {   // anatomy builds of attn_pf_kernel<LSUM>: ABL = selector - 8
         p.pp_flags = 0; p.pp_thr = 4.f;
-        dim3 gridp;
-        attn_grid(p, 256, gridp);
-        switch ((tune >> 16) & 0xff) {
-        case 9: hipLaunchKernelGGL((attn_pf_kernel<T, true, 1>), gridp, dim3(512), 0, st, p); break;
-        case 10: hipLaunchKernelGGL((attn_pf_kernel<T, true, 2>), gridp, dim3(512), 0, st, p); break;
-        case 11: hipLaunchKernelGGL((attn_pf_kernel<T, true, 3>), gridp, dim3(512), 0, st, p); break;
-        case 12: hipLaunchKernelGGL((attn_pf_kernel<T, true, 4>), gridp, dim3(512), 0, st, p); break;
-        case 13: hipLaunchKernelGGL((attn_pf_kernel<T, true, 5>), gridp, dim3(512), 0, st, p); break;
-        default: hipLaunchKernelGGL((attn_pf_kernel<T, true, 6>), gridp, dim3(512), 0, st, p); break;
+        switch (kern) {
+        case 9: return launch(attn_pf_kernel<T, true, 1>, false, 256);
+        case 10: return launch(attn_pf_kernel<T, true, 2>, false, 256);
+        case 11: return launch(attn_pf_kernel<T, true, 3>, false, 256);
+        case 12: return launch(attn_pf_kernel<T, true, 4>, false, 256);
+        case 13: return launch(attn_pf_kernel<T, true, 5>, false, 256);
+        default: return launch(attn_pf_kernel<T, true, 6>, false, 256);
         }
-        CHECK_LAUNCH("attn_fwd");
-        return IDMVTON_OK;
     }
 #endif
-    if ((tune >> 16) & 0xff) return idmvton_set_error(IDMVTON_E_ARG, "attn_fwd: unknown kernel selector in tune");
-    dim3 grid;
-    attn_grid(p, 32 * nw, grid);
-    const dim3 block(nw * 64);
-#define ATTN_CASE(NW_, ST_) if (nw == NW_ && stg == ST_) { hipLaunchKernelGGL((attn_kernel<T, MODE, NW_, ST_>), grid, block, 0, st, p); } else
+    if (kern) return idmvton_set_error(IDMVTON_E_ARG, "attn_fwd: unknown kernel selector in tune");
+    kernel_t k = nullptr;
+#define ATTN_CASE(NW_, ST_) if (nw == NW_ && stg == ST_) k = attn_kernel<T, MODE, NW_, ST_>;
     ATTN_CASE(2, 2) ATTN_CASE(4, 2) ATTN_CASE(8, 2)
     ATTN_CASE(2, 3) ATTN_CASE(4, 3) ATTN_CASE(8, 3)
     ATTN_CASE(2, 4) ATTN_CASE(4, 4) ATTN_CASE(8, 4)
-    return idmvton_set_error(IDMVTON_E_ARG, "attn_fwd: unsupported tune (waves=%d stages=%d)", nw, stg);
 #undef ATTN_CASE
-    CHECK_LAUNCH("attn_fwd");
-    return IDMVTON_OK;
+    if (!k) return idmvton_set_error(IDMVTON_E_ARG, "attn_fwd: unsupported tune (waves=%d stages=%d)", nw, stg);
+    return launch(k, false, 32 * nw);
 }
 
 // One implementation behind both entry points.  seg_nb[s] > 0: segment s holds seg_nb[s] batch elements and query batch b >= seg_b0[s] reads

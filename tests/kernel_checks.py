@@ -1173,10 +1173,17 @@ def all_checks(dev="cuda"):
                 add(f"attn_self_1seg_N1000_{tag}", lambda dt=dt, tn=tn: check_attn_self(1, 3, 1000, dt, dev, tune=tn))
                 add(f"attn_cross_77_16_N768_{tag}", lambda dt=dt, tn=tn: check_attn_cross(4, 4, 768, dt, dev, tune=tn))
                 add(f"attn_cross_scale0.5_N200_{tag}", lambda dt=dt, tn=tn: check_attn_cross(2, 2, 200, dt, dev, ip_scale=0.5, tune=tn))
+                # the pool entry point on every instantiation (tests/test_kernel_frames_gpu.py names three of the nine): a segment of 4 slots of
+                # capacity 136 read by index, per-batch key counts 75 | 75 | 136 (batch 0 absent: 75 keys in closed form), 200 query rows
+                add(f"attn_self_pool_ragged_N200_g136_{tag}", lambda dt=dt, tn=tn: check_attn_product(dt, dev, tune=tn, entry="ragged", n_garm=136, g_rows=136))
+        # ... and through the library's own rule with a pre-multiplied q (Nq >= 128: attn_sp_kernel)
+        add("attn_self_pool_ragged_N200_g136_auto_prescaled", lambda dt=dt: check_attn_product(dt, dev, entry="ragged", n_garm=136, g_rows=136, prescaled=True))
         # ping-pong kernel (attn_pp_kernel): every instantiation (stages x priority x prefetch depth), both wave pairings,
         # every rescale threshold; incl. inputs that FORCE the deferred-rescale branch late in the key walk (spike)
         for stg in (2, 3):
             for deep in (0, 1):                          # deep builds are only launched with a pre-multiplied q (else: the 128-register build)
+                # the pool entry point (as above) on every build: tests/test_kernel_frames_gpu.py has it on two of the three, not on <2 stages, deep>
+                add(f"attn_self_pool_ragged_N200_g136_pp_s{stg}d{deep}", lambda dt=dt, tn=pp_tune(stg, deep): check_attn_product(dt, dev, tune=tn, entry="ragged", n_garm=136, g_rows=136))
                 for pre in (False, True):
                     tn, tag = pp_tune(stg, deep), f"pp_s{stg}d{deep}{'q' if pre else ''}"
                     add(f"attn_self_2seg_cfg_N768_{tag}", lambda dt=dt, tn=tn, pre=pre: check_attn_self(4, 4, 768, dt, dev, n_garm=768, b0=2, tune=tn, prescaled=pre))
