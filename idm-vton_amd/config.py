@@ -257,8 +257,11 @@ def vae_param_shapes(cfg: VAEConfig):
 
 def random_state_dict(shapes, seed, dtype, device, std=0.02):
     """Seeded random-init weights (there are no trained weights anywhere: SURVEY.md 0.2): N(0, std) for matrices / conv
-    kernels, N(0, std) biases, norm gains 1 + N(0, std), so activations stay bounded through 70 blocks and every
-    parameter influences the output.  Generated per tensor on the CPU generator so oracle and HIP see identical bytes."""
+    kernels, N(0, std) biases, norm gains 1 + N(0, std), so activations stay bounded through 70 blocks.  This distribution does NOT
+    establish that every parameter influences the output measurably: at std 0.02 a Linear has a gain of 0.16..0.32, softmaxes are near
+    uniform and each attention branch is a few percent of the residual stream.  That is established by the audit on the "loud" set
+    derived from this draw (tests/parity_utils.py `loud_`, tests/test_parity_audit_cpu.py).
+    Generated per tensor on the CPU generator so oracle and HIP see identical bytes."""
     import torch
     g = torch.Generator(device="cpu").manual_seed(seed)
     sd = {}

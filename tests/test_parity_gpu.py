@@ -13,8 +13,7 @@ pytestmark = pytest.mark.gpu
 # doubles a relative latent difference.  The decode itself runs the split-precision path (idm_vton_amd/vae.py) and is held to its own bar on
 # IDENTICAL latents (`decode`), so the image bar only has to cover the amplified latent drift: round 4 took it back to the round-2 values
 # (round 3 had widened it to 1.5e-2 / 1e-1 together with numeric changes -- ADVICE r3).
-TOL = {torch.float16: dict(stage=4e-3, latents=5e-3, image=1e-2, decode=2e-4),
-       torch.bfloat16: dict(stage=3e-2, latents=4e-2, image=6e-2, decode=2e-4)}
+from tests.parity_checks import TOL  # noqa: E402  (one table of bars, shared with tests/test_parity_audit_cpu.py; values unchanged)
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
@@ -205,3 +204,101 @@ def test_fp8_attention_engine_matches_oracle_within_its_stated_tolerance():
     for kw in (dict(), dict(use_graph=True, overlap=True)):
         r = parity_checks.run("tiny", torch.float16, B=2, H=128, W=128, steps=3, unet_kw=dict(attn_fp8=True), **kw)
         assert r["garment_feat_max"] <= 8e-2 and r["tryon_eps"] <= 8e-2 and r["latents_final"] <= 8e-2, r
+
+
+# ---- the same checks on the "loud" weights (tests/parity_utils.py: every matrix of the two UNets at fan-in scale) ----
+# On the committed N(0, 0.02) weights the softmaxes are near uniform and every attention branch is a few percent of the residual stream, so the
+# bars above cannot see most wiring defects.  tests/test_parity_audit_cpu.py shows on the CPU that on the loud weights each defect of
+# tests/parity_mutants.py moves a quantity compared here by >= 3 bars, and that 16-bit storage alone stays inside the bars.  Same assertions,
+# same TOL as the quiet cases above.  (The fp8-attention engine stays on the quiet weights: 3 x its stated 8e-2 is more than several defects
+# move the outputs -- DESIGN.md section 5.)
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
+def test_tiny_pipeline_parity_loud(dtype):
+    from tests import parity_checks
+    r = parity_checks.run("tiny", dtype, B=1, H=128, W=128, steps=4, weights="loud")
+    t = TOL[dtype]
+    for k in ("resampler", "vae_encode", "garment_feat_max", "tryon_eps", "tryon_eps_materialised_zeros",
+              "prep_masked_lat", "prep_pose_lat"):
+        assert r[k] <= t["stage"], (k, r)
+    assert r["vae_decode"] <= t["decode"], r
+    assert r["closed_form_vs_materialised"] <= t["stage"], r
+    assert r["latents_final"] <= t["latents"], r
+    assert r["image"] <= t["image"], r
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
+def test_mid_pipeline_parity_loud(dtype):
+    from tests import parity_checks
+    r = parity_checks.run("mid", dtype, B=1, H=128, W=128, steps=2, weights="loud")
+    t = TOL[dtype]
+    for k in ("resampler", "vae_encode", "vae_decode", "garment_feat_max", "tryon_eps", "tryon_eps_materialised_zeros"):
+        assert r[k] <= t["stage"], (k, r)
+    assert r["latents_final"] <= t["latents"] and r["image"] <= t["image"], r
+
+
+@pytest.mark.parametrize("H,W", [(1000, 760), (320, 320), (264, 200)], ids=["1000x760", "320x320", "264x200"])
+def test_sizes_the_reference_accepts_match_the_oracle_loud(H, W):
+    """320x320 (100 tokens at the coarsest level) and 264x200 (odd levels as well) are where unmasked filler keys would show: the audit holds
+    that defect at >= 3 bars at 320x320 on these weights."""
+    from tests import parity_checks
+    r = parity_checks.run("tiny", torch.float16, B=1, H=H, W=W, steps=2, weights="loud")
+    t = TOL[torch.float16]
+    for k in ("vae_encode", "garment_feat_max", "tryon_eps", "tryon_eps_materialised_zeros", "prep_masked_lat", "prep_pose_lat"):
+        assert r[k] <= t["stage"], (k, r)
+    assert r["vae_decode"] <= t["decode"] and r["latents_final"] <= t["latents"] and r["image"] <= t["image"], r
+
+
+def test_two_stream_overlap_graph_matches_serial_loud():
+    """B = 2 (two garments, two persons), hipGraph replay with the two-stream overlap: bit-equal to the serial loop, and within the bars."""
+    from tests import parity_checks
+    r = parity_checks.run("tiny", torch.float16, B=2, H=128, W=128, steps=3, use_graph=True, overlap=True, weights="loud")
+    assert r["overlap_vs_serial"] == 0.0 and r["overlap_second_call"] == 0.0, r
+    for k in ("garment_feat_max", "tryon_eps", "tryon_eps_materialised_zeros"):
+        assert r[k] <= TOL[torch.float16]["stage"], (k, r)
+    assert r["latents_final"] <= TOL[torch.float16]["latents"] and r["image"] <= TOL[torch.float16]["image"], r
+
+
+@pytest.mark.parametrize("case", ["strength0.6", "guidance1.0"])
+def test_strength_and_no_cfg_branches_match_oracle_loud(case):
+    """test_strength_and_no_cfg_branches_match_oracle on the loud weights."""
+    from idm_vton_amd.pipeline import TryonEngine
+    from oracle import pipeline as opipe
+    from oracle.scheduler import Scheduler
+    from tests import parity_utils as pu
+    strength = 0.6 if case == "strength0.6" else 1.0
+    g = 1.0 if case == "guidance1.0" else 2.0
+    dt, B, steps = torch.float16, 1, 5
+    m = pu.build("tiny", dt, "cuda", weights="loud")
+    o_t, o_g, o_v = m["oracle"]
+    p_t, p_g, p_v, p_r = m["product"]
+    inp = pu.make_inputs(B, 128, 128, m["xd"], m["pooled"], m["enc_dim"], steps, dt)
+    inp["noise"]["image"] = torch.randn(B, 4, 16, 16, generator=torch.Generator().manual_seed(77))
+    n_exec = min(int(steps * strength), steps)
+    inp["noise"]["steps"] = inp["noise"]["steps"][:n_exec]
+    o_inp = dict(inp)
+    p_inp = dict(inp)
+    if g <= 1:                                            # the reference hands the pipeline the conditional rows only
+        o_inp["ip_hidden_states"] = inp["ip_hidden_states"][B:]
+        p_inp["ip_hidden_states"] = inp["ip_hidden_states"][B:]
+        p_inp["negative_prompt_embeds"] = p_inp["negative_pooled_prompt_embeds"] = None
+    tr = {}
+    lat_o = opipe.run(o_t, o_g, o_v, Scheduler("ddpm"), num_inference_steps=steps, guidance_scale=g, strength=strength,
+                      return_latents=True, trace=tr, **o_inp)
+    assert len(tr["step_latents"]) == n_exec
+    eng = TryonEngine(p_t, p_g, p_v, p_r, dt, "cuda")
+    for kw in (dict(), dict(use_graph=True, overlap=True)):
+        st = eng.prepare(num_inference_steps=steps, guidance_scale=g, scheduler="ddpm", strength=strength, **p_inp)
+        assert len(st["timesteps"]) == n_exec
+        assert pu.relerr(st["latents"], tr["latents0"]) < 2e-3, "start latents (add_noise of the encoded image)"
+        lat_p = eng.denoise(st, **kw)
+        assert pu.relerr(lat_p, lat_o) <= TOL[dt]["latents"], (case, kw, pu.relerr(lat_p, lat_o))
+
+
+def test_engine_options_match_oracle_loud():
+    """stream_f32 (the fp32 residual stream) in fp16 on the loud weights, same bars as the default engine."""
+    from tests import parity_checks
+    t = TOL[torch.float16]
+    r = parity_checks.run("tiny", torch.float16, B=2, H=128, W=128, steps=3, unet_kw=dict(stream_f32=True), weights="loud")
+    for k in ("garment_feat_max", "tryon_eps", "tryon_eps_materialised_zeros"):
+        assert r[k] <= t["stage"], (k, r)
+    assert r["latents_final"] <= t["latents"] and r["image"] <= t["image"], r
