@@ -338,6 +338,10 @@ def check_attn_self(B, heads, N, dtype, dev, n_garm=0, b0=0, scale=1.0, seed=0, 
 
 
 ENTRIES = ("plain", "shared", "indexed", "ragged")
+# idmvton_attn_args.tune = (flags << 24) | (kernel << 16) | (stages << 8) | waves: every attention kernel `tune` can select
+TUNES = {"auto": 0, "k0_2stage_4w": 0x0204, "k0_ring3_4w": 0x0304, "k0_2stage_8w": 0x0208, "k2_pingpong": (2 << 16) | (2 << 8) | 8,
+         "k3_pingpong_deep": (3 << 16) | (3 << 8) | 8, "k7_prefetch_mfma_sums": (7 << 16) | (3 << 8) | 8,
+         "k8_prefetch_valu_sums": (8 << 16) | (3 << 8) | 8, "k16_sp_4w": (16 << 16) | (3 << 8) | 4, "k16_sp_8w": (16 << 16) | (3 << 8) | 8}
 
 
 def _f8_slot_key(n, dev):

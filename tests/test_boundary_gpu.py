@@ -1,11 +1,11 @@
 """-m gpu: the drop-in boundary on the GPU -- the reference's plugin API (attention processors, Resampler) against plain
 PyTorch fp32 references of the reference's arithmetic (ip_adapter/attention_processor.py:203-278,1907-2010), and the
 `StableDiffusionXLInpaintPipeline` call surface end to end against the engine it wraps (bit-exact) and the oracle."""
-from types import SimpleNamespace
-
 import pytest
 import torch
 import torch.nn.functional as F
+
+from tests.engine_support import boundary_pipeline, ip_states, mk_attn, reference_draws
 
 pytestmark = pytest.mark.gpu
 DT, DEV = torch.float16, "cuda"
@@ -21,17 +21,10 @@ def _heads(t, h):
     return t.float().view(t.shape[0], t.shape[1], h, 64).transpose(1, 2)
 
 
-def _mk_attn(query_dim, cross_dim, heads, processor, seed):
-    from idm_vton_amd.boundary.modules import Attention
-    torch.manual_seed(seed)
-    a = Attention(query_dim, cross_dim, heads, 64, processor=processor).to(DEV, DT)
-    return a
-
-
 @pytest.mark.parametrize("four_d", [False, True], ids=["tokens", "nchw"])
 def test_attn_processor_self_attention(four_d):
     from ip_adapter.attention_processor import AttnProcessor2_0
-    attn = _mk_attn(128, None, 2, AttnProcessor2_0(), 0)
+    attn = mk_attn(128, None, 2, AttnProcessor2_0(), 0)
     x = (torch.randn(2, 128, 10, 10) if four_d else torch.randn(2, 100, 128)).to(DEV, DT)
     out = attn(x)
     t = x.view(2, 128, 100).transpose(1, 2) if four_d else x
@@ -45,7 +38,7 @@ def test_attn_processor_self_attention(four_d):
 
 def test_attn_processor_cross_attention_ragged_keys():
     from ip_adapter.attention_processor import AttnProcessor2_0
-    attn = _mk_attn(128, 192, 2, AttnProcessor2_0(), 1)
+    attn = mk_attn(128, 192, 2, AttnProcessor2_0(), 1)
     x, enc = torch.randn(2, 72, 128).to(DEV, DT), torch.randn(2, 77, 192).to(DEV, DT)
     out = attn(x, encoder_hidden_states=enc)
     q = F.linear(x.float(), attn.to_q.weight.float())
@@ -58,7 +51,7 @@ def test_attn_processor_cross_attention_ragged_keys():
 def test_ip_attn_processor_text_plus_image_tokens():
     from ip_adapter.attention_processor import IPAttnProcessor2_0
     proc = IPAttnProcessor2_0(hidden_size=128, cross_attention_dim=192, scale=0.75, num_tokens=16)
-    attn = _mk_attn(128, 192, 2, proc, 2)
+    attn = mk_attn(128, 192, 2, proc, 2)
     assert "processor.to_k_ip.weight" in attn.state_dict()                       # reference key layout (Appendix C)
     x, enc = torch.randn(2, 64, 128).to(DEV, DT), torch.randn(2, 77 + 16, 192).to(DEV, DT)
     out = attn(x, encoder_hidden_states=enc)
@@ -96,40 +89,10 @@ def test_resampler_boundary_matches_oracle():
         b(x)                                                                       # CPU tensor: no fallback
 
 
-class _FakeCLIPVision(torch.nn.Module):
-    """Stand-in for CLIPVisionModelWithProjection: deterministic 257-token hidden states from the pixels."""
-
-    def __init__(self, dim):
-        super().__init__()
-        self.proj = torch.nn.Linear(3, dim)
-
-    def forward(self, pixel_values, output_hidden_states=False):
-        p = F.adaptive_avg_pool2d(pixel_values.float(), (16, 16)).flatten(2).transpose(1, 2)            # [B,256,3]
-        t = torch.cat([p.mean(1, keepdim=True), p], dim=1)
-        h = self.proj(t.to(self.proj.weight.dtype))
-        return SimpleNamespace(hidden_states=[h * 0.5, h, h * 2.0], image_embeds=h[:, 0])
-
-
 def test_pipeline_boundary_end_to_end():
-    from idm_vton_amd import config as pc
-    from idm_vton_amd.boundary.scheduler import DDPMScheduler
-    from idm_vton_amd.boundary.vae import AutoencoderKL
-    from src.tryon_pipeline import StableDiffusionXLInpaintPipeline
-    from src.unet_hacked_garmnet import UNet2DConditionModel as G
-    from src.unet_hacked_tryon import UNet2DConditionModel as T
     from tests import parity_utils as pu
-    kw = dict(pu.TINY)
-    tcfg = pc.UNetConfig(mode="tryon", in_channels=13, sample_size=16, **kw)
-    gcfg = pc.UNetConfig(mode="garmnet", in_channels=4, addition_embed_type=None, encoder_hid_dim_type=None, sample_size=16, **kw)
-    vcfg = pc.VAEConfig(**pu.TINY_VAE)
-    rnd = lambda sd: {k: v.to(DT) for k, v in sd.items()}
-    t = T(tcfg, torch_dtype=DT); t.load_state_dict(rnd(pc.random_state_dict(pc.unet_param_shapes(tcfg), 1, torch.float32, "cpu")))
-    g = G(gcfg, torch_dtype=DT); g.load_state_dict(rnd(pc.random_state_dict(pc.unet_param_shapes(gcfg), 2, torch.float32, "cpu")))
-    v = AutoencoderKL(vcfg, torch_dtype=DT); v.load_state_dict(rnd(pc.random_state_dict(pc.vae_param_shapes(vcfg), 3, torch.float32, "cpu", std=0.05)))
-    torch.manual_seed(5)
-    enc = _FakeCLIPVision(kw["encoder_hid_dim"]).to(DT)
-    pipe = StableDiffusionXLInpaintPipeline(vae=v, text_encoder=None, text_encoder_2=None, tokenizer=None, tokenizer_2=None, unet=t,
-                                            unet_encoder=g, scheduler=DDPMScheduler(), image_encoder=enc).to(DEV)
+    pipe, enc, kw = boundary_pipeline(DT)
+    t, g = pipe.unet, pipe.unet_encoder
     assert str(pipe.device) == "cuda"
     B, H, W, steps = 2, 128, 128, 3
     inp = pu.make_inputs(B, H, W, kw["cross_attention_dim"], 64, kw["encoder_hid_dim"], steps, DT)
@@ -146,20 +109,12 @@ def test_pipeline_boundary_end_to_end():
     img_pt = pipe(generator=torch.Generator(DEV).manual_seed(7), output_type="pt", **call)[0]
     # the same through the engine the pipeline wraps, with the noise drawn in the reference's order
     eng = pipe.hip_engine()
-    gen = torch.Generator(DEV).manual_seed(7)
-    torch.manual_seed(123)
-    # dtypes as the reference draws them (randn_tensor): latents in the prompt dtype, VAE posterior samples in fp32 (upcast VAE),
-    # DDPM variance noise in the model-output dtype
-    draw = lambda gg, dt_: torch.randn((B, 4, H // 8, W // 8), generator=gg, device=DEV, dtype=dt_).float()
-    n_lat, n_masked, n_pose, n_cloth = draw(gen, DT), draw(gen, torch.float32), draw(None, torch.float32), draw(gen, torch.float32)
-    n_steps = torch.stack([draw(gen, DT) for _ in range(steps)])
-    with torch.no_grad():
-        pos = enc(clip_pix.to(DEV, DT), output_hidden_states=True).hidden_states[-2]
-        neg = enc(torch.zeros_like(clip_pix).to(DEV, DT), output_hidden_states=True).hidden_states[-2]
+    _, noise = reference_draws(7, 123, B, H, W, steps, DT)
+    neg, pos = ip_states(enc, clip_pix)
     ref = eng(image=inp["image"], mask_image=inp["mask_image"], pose_img=inp["pose_img"], cloth=inp["cloth"],
               prompt_embeds=inp["prompt_embeds"], negative_prompt_embeds=inp["negative_prompt_embeds"],
               pooled_prompt_embeds=inp["pooled_prompt_embeds"], negative_pooled_prompt_embeds=inp["negative_pooled_prompt_embeds"],
-              text_embeds_cloth=inp["text_embeds_cloth"], noise=dict(latents=n_lat, masked=n_masked, pose=n_pose, cloth=n_cloth, steps=n_steps),
+              text_embeds_cloth=inp["text_embeds_cloth"], noise=noise,
               num_inference_steps=steps, guidance_scale=2.0, ip_hidden_states=torch.cat([neg, pos]), scheduler="ddpm")
     assert torch.equal(img_pt, ref)
     # per-step callbacks and `interrupt` (/root/reference/src/tryon_pipeline.py:1766-1767,1840-1863) run the engine's serial un-captured loop:
@@ -190,6 +145,7 @@ def test_pipeline_boundary_end_to_end():
     img2 = pipe(generator=torch.Generator(DEV).manual_seed(7), output_type="pt", **{**call, "strength": 0.6, "guidance_scale": 1.0, "num_inference_steps": 5})[0]
     gen = torch.Generator(DEV).manual_seed(7)
     torch.manual_seed(123)
+    draw = lambda gg, dt_: torch.randn((B, 4, H // 8, W // 8), generator=gg, device=DEV, dtype=dt_).float()
     n_img, n_lat = draw(gen, torch.float32), draw(gen, DT)
     n_masked, n_pose, n_cloth = draw(gen, torch.float32), draw(None, torch.float32), draw(gen, torch.float32)
     n_steps = torch.stack([draw(gen, DT) for _ in range(3)])

@@ -5,6 +5,8 @@ Tolerances: relative Frobenius error of 16-bit storage through 2..4 pre-LN layer
 import pytest
 import torch
 
+from tests.engine_support import clip_ids, clip_text
+
 pytestmark = pytest.mark.gpu
 BAR = {torch.float16: 6e-3, torch.bfloat16: 3e-2}
 
@@ -22,38 +24,14 @@ def maxrel(x, ref):
 MAXREL_BAR = {torch.float16: 1.2e-2, torch.bfloat16: 8e-2}          # through 3 layers; per-layer values printed with -s
 
 
-def _text(hidden, heads, layers, act, proj, vocab=1000, eos=999, seed=0):
-    from transformers import CLIPTextConfig, CLIPTextModel, CLIPTextModelWithProjection
-    torch.manual_seed(seed)
-    cfg = CLIPTextConfig(vocab_size=vocab, hidden_size=hidden, intermediate_size=4 * hidden, num_hidden_layers=layers, num_attention_heads=heads,
-                         max_position_embeddings=77, projection_dim=proj or 64, hidden_act=act, bos_token_id=vocab - 2, eos_token_id=eos, pad_token_id=eos)
-    m = (CLIPTextModelWithProjection if proj else CLIPTextModel)(cfg).eval()
-    with torch.no_grad():                                  # default init is tiny (std 0.02): widen so every op matters numerically
-        for n, p in m.named_parameters():
-            if p.dim() == 2 and "embedding" not in n:
-                p.mul_(3.0)
-            if n.endswith("bias"):
-                p.normal_(0, 0.1)
-    return m
-
-
-def _ids(B, L, vocab, eos, seed):
-    g = torch.Generator().manual_seed(seed)
-    ids = torch.randint(0, vocab - 2, (B, L), generator=g)
-    ids[:, 0] = vocab - 2
-    for b in range(B):                                      # EOS at a different place per row, padding (== EOS id) after it
-        ids[b, 5 + 7 * b:] = eos
-    return ids
-
-
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
 @pytest.mark.parametrize("case", ["L_quickgelu", "bigG_proj", "legacy_eos2"])
 def test_text_tower_matches_transformers(dtype, case):
     from idm_vton_amd.clip import HipCLIPText
     hidden, heads, layers, act, proj, eos = dict(L_quickgelu=(768, 12, 3, "quick_gelu", 0, 999), bigG_proj=(1280, 20, 3, "gelu", 1280, 999),
                                                  legacy_eos2=(128, 2, 2, "quick_gelu", 64, 2))[case]
-    m = _text(hidden, heads, layers, act, proj, eos=eos)
-    ids = _ids(3, 77, 1000, 999, 1)                         # legacy (eos_token_id == 2) configs pool at argmax(ids): the first 999
+    m = clip_text(hidden, heads, layers, act, proj, eos=eos)
+    ids = clip_ids(3, 77, 1000, 999, 1)                         # legacy (eos_token_id == 2) configs pool at argmax(ids): the first 999
     with torch.no_grad():
         ref = m(ids, output_hidden_states=True)
     hip = HipCLIPText(m.state_dict(), m.config, dtype, "cuda")
@@ -105,7 +83,7 @@ def test_pipeline_encoders_run_on_hip(tmp_path):
     from idm_vton_amd import ops
     from idm_vton_amd.boundary.tryon_pipeline import StableDiffusionXLInpaintPipeline as P
     from transformers import CLIPVisionConfig, CLIPVisionModelWithProjection
-    t1, t2 = _text(64, 1, 2, "quick_gelu", 0, seed=4).half().cuda(), _text(128, 2, 2, "gelu", 64, seed=5).half().cuda()
+    t1, t2 = clip_text(64, 1, 2, "quick_gelu", 0, seed=4).half().cuda(), clip_text(128, 2, 2, "gelu", 64, seed=5).half().cuda()
     vis = CLIPVisionModelWithProjection(CLIPVisionConfig(hidden_size=128, intermediate_size=256, num_hidden_layers=2, num_attention_heads=2,
                                                          image_size=224, patch_size=14, projection_dim=64)).half().cuda().eval()
 
@@ -113,7 +91,7 @@ def test_pipeline_encoders_run_on_hip(tmp_path):
         model_max_length = 77
 
         def __call__(self, text, **kw):
-            return type("E", (), {"input_ids": _ids(len(text), 77, 1000, 999, len(text[0]))})()
+            return type("E", (), {"input_ids": clip_ids(len(text), 77, 1000, 999, len(text[0]))})()
 
     pipe = P.__new__(P)
     pipe.text_encoder, pipe.text_encoder_2, pipe.tokenizer, pipe.tokenizer_2, pipe.image_encoder = t1, t2, Tok(), Tok(), vis
@@ -126,7 +104,7 @@ def test_pipeline_encoders_run_on_hip(tmp_path):
         ops.RECORD = None
     # tower 1 stops after its penultimate layer (4 GEMMs), tower 2 runs 2 layers + text_projection (9), vision patch GEMM + 1 layer (5)
     assert sum(r[0] == "gemm" for r in rec) == 18, "the CLIP towers did not run on the HIP GEMM"
-    ids = _ids(1, 77, 1000, 999, 1).cuda()
+    ids = clip_ids(1, 77, 1000, 999, 1).cuda()
     with torch.no_grad():
         r1, r2 = t1(ids, output_hidden_states=True), t2(ids, output_hidden_states=True)
     ref = torch.cat([r1.hidden_states[-2], r2.hidden_states[-2]], -1)
@@ -154,8 +132,8 @@ def test_full_depth_towers_match_transformers(tower):
         cls = HipCLIPVision
     else:
         hidden, heads, layers, act, proj = (1280, 20, 32, "gelu", 1280) if "bigG" in tower else (768, 12, 12, "quick_gelu", 0)
-        m = _text(hidden, heads, layers, act, proj)
-        x = _ids(2, 77, 1000, 999, 1)
+        m = clip_text(hidden, heads, layers, act, proj)
+        x = clip_ids(2, 77, 1000, 999, 1)
         cls = HipCLIPText
     with torch.no_grad():
         ref = m.cuda()(x.cuda(), output_hidden_states=True)

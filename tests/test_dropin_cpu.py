@@ -14,23 +14,15 @@ import sys
 
 import pytest
 
+from tests.dropin_support import make_assets
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference/inference.py"
 
 
-def _make_assets(tmp_path, size=256, n=2):
-    ck, dd = str(tmp_path / "ckpt"), str(tmp_path / "data")
-    env = {k: v for k, v in os.environ.items() if k != "PYTHONPATH"}
-    for cmd in ([sys.executable, os.path.join(ROOT, "tools", "make_synth_ckpt.py"), ck],
-                [sys.executable, os.path.join(ROOT, "tools", "make_synth_vitonhd.py"), dd, "--n", str(n), "--width", str(size), "--height", str(size)]):
-        r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
-        assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
-    return ck, dd
-
-
 @pytest.mark.skipif(not os.path.exists(REF), reason="reference checkout not present (GPU box)")
 def test_unmodified_inference_py_runs_against_this_repository(tmp_path):
-    ck, dd = _make_assets(tmp_path)
+    ck, dd = make_assets(tmp_path)
     out, rec = str(tmp_path / "out"), str(tmp_path / "rec.json")
     env = {k: v for k, v in os.environ.items() if k != "PYTHONPATH"}
     env["IDMVTON_DROPIN_RECORD"] = rec
@@ -56,7 +48,7 @@ def test_unmodified_inference_py_runs_against_this_repository(tmp_path):
 def test_dropin_driver_matches_the_call_surface_of_inference_py(tmp_path):
     """The repo-local driver (used on the GPU box, where /root/reference is absent) reaches the engine with the same keys, shapes
     and dtypes as the unmodified script."""
-    ck, dd = _make_assets(tmp_path)
+    ck, dd = make_assets(tmp_path)
     out, rec = str(tmp_path / "out"), str(tmp_path / "rec.json")
     env = {k: v for k, v in os.environ.items() if k != "PYTHONPATH"}
     env["IDMVTON_DROPIN_RECORD"] = rec
@@ -79,7 +71,7 @@ def test_unmodified_inference_dc_py_runs_against_this_repository(tmp_path):
     """the DressCode script (same model call as inference.py:550; its own DresscodeTestDataset + get_agnostic mask
     synthesis, inference_dc.py:96-352) unmodified.  It hard-codes the hub id "yisol/IDM-VTON-DC" for the UNet (:391), so the run
     directory holds that relative path pointing at the synthetic TryonNet; cv2.dilate comes from the name shim."""
-    ck, _ = _make_assets(tmp_path, n=1)
+    ck, _ = make_assets(tmp_path, n=1)
     dd = str(tmp_path / "dc")
     env = {k: v for k, v in os.environ.items() if k != "PYTHONPATH"}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "make_synth_dresscode.py"), dd, "--width", "256", "--height", "256"],

@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.dropin_support import make_assets
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -27,9 +29,8 @@ def _run(tmp_path, tag, ck, dd):
 
 
 def test_inference_py_call_sequence_runs_to_pixels_on_the_hip_engine(tmp_path):
-    from tests.test_dropin_cpu import _make_assets
     from PIL import Image
-    ck, dd = _make_assets(tmp_path)
+    ck, dd = make_assets(tmp_path)
     out1, l1 = _run(tmp_path, "a", ck, dd)
     out2, l2 = _run(tmp_path, "b", ck, dd)
     assert sorted(os.listdir(out1)) == ["00000_00.jpg", "00001_00.jpg"]
@@ -64,9 +65,8 @@ def _launch(script, args, cwd, timeout=900, extra_env=None):
 def test_unmodified_inference_py_produces_pixels_on_the_mi355x(tmp_path):
     """inference.py:316-329 (from_pretrained of every component), :397-414 (pipe(...)), :415-419 (save) -- the script itself, on
     the HIP engine: CLIP towers, Resampler, VAE encodes, 4 denoising steps, decode, JPEG."""
-    from tests.test_dropin_cpu import _make_assets
     from PIL import Image
-    ck, dd = _make_assets(tmp_path)
+    ck, dd = make_assets(tmp_path)
     out = str(tmp_path / "out")
     r = _launch(_ref_script("inference.py"), ["--pretrained_model_name_or_path", ck, "--data_dir", dd, "--width", "256", "--height", "256",
                                               "--num_inference_steps", "4", "--output_dir", out, "--test_batch_size", "2"], str(tmp_path))
@@ -83,9 +83,8 @@ def test_unmodified_inference_dc_py_produces_pixels_on_the_mi355x(tmp_path, fp8)
     """SURVEY.md 8f-2 / BASELINE.json configs[4]: DresscodeTestDataset + get_agnostic (inference_dc.py:96-352), the hub id
     "yisol/IDM-VTON-DC" (:391) resolved relative to the run directory, upper_body; the second case is configs[4] as named --
     "DressCode upper_body ... fp16 + fp8 MFMA attention" -- selected by IDMVTON_ATTN_FP8=1 with the script untouched."""
-    from tests.test_dropin_cpu import _make_assets
     from PIL import Image
-    ck, _ = _make_assets(tmp_path, n=1)
+    ck, _ = make_assets(tmp_path, n=1)
     dd = str(tmp_path / "dc")
     env = {k: v for k, v in os.environ.items() if k != "PYTHONPATH"}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "make_synth_dresscode.py"), dd, "--width", "256", "--height", "256"],

@@ -5,6 +5,8 @@ import ctypes as C
 import pytest
 import torch
 
+from tests.garment_support import ask, attn_args, attn_f8_args
+
 
 def test_shared_entry_points_are_exported_and_the_abi_did_not_move():
     from idm_vton_amd import ffi
@@ -17,30 +19,7 @@ def test_shared_entry_points_are_exported_and_the_abi_did_not_move():
     assert L.idmvton_sizeof(b"idmvton_attn_f8_args") == 128 == C.sizeof(ffi.AttnF8Args)
 
 
-def _attn_args(mode, B=4, b0=2):
-    from idm_vton_amd import ffi
-    a = ffi.AttnArgs()
-    a.dtype, a.mode, a.B, a.heads, a.Nq = ffi.BF16, mode, B, 2, 64
-    a.q, a.ldq, a.out, a.ldo, a.nseg = 0x10000, 128, 0x20000, 128, 2
-    for s in range(2):                                   # (the pointers are never dereferenced: every call below is refused before a launch)
-        a.k[s], a.vt[s], a.ldk[s], a.ldvt[s], a.nk[s], a.k_rows[s] = 0x30000 + s * 0x10000, 0x50000 + s * 0x10000, 128, 64, 64, 64
-    a.seg_b0[0], a.seg_b0[1] = 0, b0
-    return a
-
-
-def _attn_f8_args(B=4, b0=2):
-    from idm_vton_amd import ffi
-    a = ffi.AttnF8Args()
-    a.out_dtype, a.B, a.heads, a.Nq = ffi.BF16, B, 2, 64
-    a.q8, a.ldq, a.out, a.ldo, a.nseg = 0x10000, 128, 0x20000, 128, 2
-    for s in range(2):
-        a.k8[s], a.vt8[s], a.ldk[s], a.ldvt[s], a.nk[s], a.k_rows[s] = 0x30000 + s * 0x10000, 0x50000 + s * 0x10000, 128, 64, 64, 64
-    a.seg_b0[0], a.seg_b0[1] = 0, b0
-    a.qk_scale_exp, a.v_scale_exp = -4, -2
-    return a
-
-
-@pytest.mark.parametrize("fn,make", [("idmvton_attn_fwd_shared", lambda: _attn_args(0)), ("idmvton_attn_f8_shared", _attn_f8_args)],
+@pytest.mark.parametrize("fn,make", [("idmvton_attn_fwd_shared", lambda: attn_args(0)), ("idmvton_attn_f8_shared", attn_f8_args)],
                          ids=["attn_fwd_shared", "attn_f8_shared"])
 def test_seg_nb_is_validated_on_the_host(fn, make):
     """seg_nb[s] >= 0 and, when non-zero, <= B - seg_b0[s]: refused with a message before any launch."""
@@ -61,9 +40,9 @@ def test_seg_nb_is_validated_on_the_host(fn, make):
 def test_cross_mode_takes_no_shared_segment():
     from idm_vton_amd import ffi
     with pytest.raises(RuntimeError, match=r"CROSS mode takes seg_nb = \{0, 0\}"):
-        ffi.call_shared("idmvton_attn_fwd_shared", _attn_args(ffi.ATTN_CROSS, b0=0), (0, 2), 0)
+        ffi.call_shared("idmvton_attn_fwd_shared", attn_args(ffi.ATTN_CROSS, b0=0), (0, 2), 0)
     with pytest.raises(RuntimeError, match=r"CROSS mode takes seg_nb = \{0, 0\}"):
-        ffi.call_shared("idmvton_attn_fwd_shared", _attn_args(ffi.ATTN_CROSS, b0=0), (1, 0), 0)
+        ffi.call_shared("idmvton_attn_fwd_shared", attn_args(ffi.ATTN_CROSS, b0=0), (1, 0), 0)
 
 
 def test_ops_segment_dicts_route_nb_to_the_shared_entry_point():
@@ -73,7 +52,7 @@ def test_ops_segment_dicts_route_nb_to_the_shared_entry_point():
     assert ops._seg_nb([dict(nk=4), dict(nk=4, b0=2, nb=0)]) is None
     assert ops._seg_nb([dict(nk=4), dict(nk=4, b0=2, nb=1)]) == [0, 1]
     assert ops._seg_nb([dict(nk=4, nb=2)]) == [2, 0]
-    a, b = _attn_args(0), _attn_args(0)
+    a, b = attn_args(0), attn_args(0)
     assert ops.attn_key(a) == ops.attn_key(b) == "1,0,4,2,64,2,64,64,2"
 
 
@@ -88,18 +67,12 @@ def _cache(G=2, ts=(900, 700, 500, 300, 100), h=16, w=12, dtype=torch.float16, a
     return GarmentCache(G=G, timesteps=ts, h=h, w=w, dtype=dtype, attn_fp8=attn_fp8, f8_exp=f8_exp, weights_id=wid, kv=kv)
 
 
-def _ask(c, **over):
-    kw = dict(timesteps=c.timesteps, h=c.h, w=c.w, dtype=c.dtype, attn_fp8=c.attn_fp8, f8_exp=c.f8_exp, weights_id=c.weights_id, persons=c.G)
-    kw.update(over)
-    return c.check(**kw)
-
-
 def test_cache_lookup_is_by_timestep_value():
     c = _cache()
-    assert _ask(c) == [0, 1, 2, 3, 4]
-    assert _ask(c, timesteps=[500, 300, 100]) == [2, 3, 4]           # strength = 0.6 of the same schedule: its last three timesteps
-    assert _ask(c, timesteps=torch.tensor([300, 900])) == [3, 0]
-    assert _ask(c, persons=6) == [0, 1, 2, 3, 4]                     # P = 3 G
+    assert ask(c) == [0, 1, 2, 3, 4]
+    assert ask(c, timesteps=[500, 300, 100]) == [2, 3, 4]           # strength = 0.6 of the same schedule: its last three timesteps
+    assert ask(c, timesteps=torch.tensor([300, 900])) == [3, 0]
+    assert ask(c, persons=6) == [0, 1, 2, 3, 4]                     # P = 3 G
     G, n = c.G, len(c.timesteps)
     for f, (k, vt) in enumerate(c.kv):
         r = k.shape[0] // n
@@ -118,15 +91,15 @@ def test_cache_lookup_is_by_timestep_value():
                                         ("weights", dict(weights_id="w1")), ("persons", dict(persons=3))])
 def test_cache_refuses_a_call_it_was_not_built_for(field, over):
     with pytest.raises(ValueError, match=f"GarmentCache {field} mismatch"):
-        _ask(_cache(), **over)
+        ask(_cache(), **over)
 
 
 def test_cache_refuses_other_fp8_exponents_and_bad_construction():
     from idm_vton_amd.garment_cache import GarmentCache
     c = _cache(attn_fp8=True)
-    assert _ask(c) == [0, 1, 2, 3, 4]
+    assert ask(c) == [0, 1, 2, 3, 4]
     with pytest.raises(ValueError, match="GarmentCache f8_exp mismatch"):
-        _ask(c, f8_exp=(2, 3, 2))
+        ask(c, f8_exp=(2, 3, 2))
     with pytest.raises(ValueError, match="distinct timesteps"):
         _cache(ts=(5, 5))
     with pytest.raises(ValueError, match="feature 0"):

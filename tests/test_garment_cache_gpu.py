@@ -1,40 +1,18 @@
 """-m gpu: the garment cache on the GPU.  Kernel level: the shared (broadcast) key segment of idmvton_attn_fwd_shared / idmvton_attn_f8_shared
 against the old entry points fed the same K / V^T materialised once per person -- same kernel, same tiles, same values, so EQUALITY, no
 tolerance.  Engine level: a call on a GarmentCache against the uncached call (bit for bit, every execution form), shared against
-materialised (bit for bit), against the oracle (the bars of tests/test_parity_gpu.py, imported), and the boundary pipeline."""
-from types import SimpleNamespace
-
+materialised (bit for bit), against the oracle (the bars of tests/parity_checks.py, which tests/test_parity_gpu.py is held to), and the boundary pipeline."""
 import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.engine_support import (DEV, boundary_inputs, boundary_pipeline, engine_inputs, engine_reference, f8_operands, garment_kw, ip_states, pair,
+                                  reference_draws, self_attn_operands)
+from tests.garment_support import DTYPES, FORMS, HEADS, SHAPES
+from tests.kernel_checks import TUNES
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-DTYPES = pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
-
-# idmvton_attn_args.tune = (flags << 24) | (kernel << 16) | (stages << 8) | waves: every attention kernel `tune` can select
-TUNES = {"auto": 0, "k0_2stage_4w": 0x0204, "k0_ring3_4w": 0x0304, "k0_2stage_8w": 0x0208, "k2_pingpong": (2 << 16) | (2 << 8) | 8,
-         "k3_pingpong_deep": (3 << 16) | (3 << 8) | 8, "k7_prefetch_mfma_sums": (7 << 16) | (3 << 8) | 8,
-         "k8_prefetch_valu_sums": (8 << 16) | (3 << 8) | 8, "k16_sp_4w": (16 << 16) | (3 << 8) | 4, "k16_sp_8w": (16 << 16) | (3 << 8) | 8}
-# (Nq, garment keys): 320 query rows are not a multiple of any kernel's 64 / 128 / 256 workgroup rows; 200 keys are not a multiple of 64
-SHAPES = [(320, 200), (256, 320)]
 PERSONS_GARMENTS = [(2, 1), (4, 1), (2, 2), (4, 2)]
-HEADS = 2
-
-
-def _r(*shape, dtype, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, generator=g).to(dtype).to(DEV)
-
-
-def _self_attn_operands(P, G, Nq, nkg, dtype, seed):
-    """Two-segment SELF launch of B = 2P query batches: own tokens + a garment segment from batch P on, held for G garments."""
-    from tests.kernel_checks import _key_order_padded
-    B, Cc = 2 * P, HEADS * 64
-    q = _r(B, Nq, Cc, dtype=dtype, seed=seed)
-    k1, v1 = _r(B, Nq, Cc, dtype=dtype, seed=seed + 1), _r(B, Nq, Cc, dtype=dtype, seed=seed + 2)
-    k2, v2 = _r(G, nkg, Cc, dtype=dtype, seed=seed + 3), _r(G, nkg, Cc, dtype=dtype, seed=seed + 4)
-    return q, k1, v1, k2, v2, _key_order_padded
 
 
 @DTYPES
@@ -44,7 +22,7 @@ def test_shared_segment_equals_materialised_copies(tune, dtype):
     from tests.kernel_checks import TOL as KTOL
     for Nq, nkg in SHAPES:
         for P, G in PERSONS_GARMENTS:
-            q, k1, v1, k2, v2, ko = _self_attn_operands(P, G, Nq, nkg, dtype, seed=7 * P + G)
+            q, k1, v1, k2, v2, ko = self_attn_operands(P, G, Nq, nkg, dtype, seed=7 * P + G)
             B, Cc = 2 * P, HEADS * 64
             pres = tune != "auto"                        # kernels 3, 7, 8, 16 need a pre-multiplied q; `auto` runs the library's rule for a raw q
             qq = (q.float() * ops.QSCALE).to(dtype) if pres else q
@@ -69,28 +47,13 @@ def test_shared_segment_equals_materialised_copies(tune, dtype):
                 assert err <= KTOL[dtype], (tune, err)  # the bar tests/kernel_checks.py holds check_attn_self to (imported)
 
 
-def _f8_operands(P, G, Nq, nkg, dtype, seed):
-    from idm_vton_amd import ops
-    q, k1, v1, k2, v2, ko = _self_attn_operands(P, G, Nq, nkg, dtype, seed)
-    B, Cc = 2 * P, HEADS * 64
-    q8 = ops.quant_f8((q.float() * ops.QSCALE).to(dtype).view(B * Nq, Cc), 4.0)
-
-    def seg(kx, vx, nk):
-        Bx = kx.shape[0]
-        k8 = ops.quant_f8(kx.view(Bx * nk, Cc), 4.0)
-        vt16, ld16 = ko(vx, nk)
-        vt8 = ops.quant_f8(vt16.view(Bx * Cc, ld16)[:, :ops.round16(nk)], 4.0, mode=1)
-        return k8, vt8
-    return q8, seg(k1, v1, Nq), seg(k2, v2, nkg)
-
-
 @DTYPES
 def test_shared_segment_equals_materialised_copies_fp8(dtype):
     from idm_vton_amd import ops
     for Nq, nkg in SHAPES:
         for P, G in PERSONS_GARMENTS:
             B, Cc = 2 * P, HEADS * 64
-            q8, (k8a, vt8a), (k8b, vt8b) = _f8_operands(P, G, Nq, nkg, dtype, seed=5 * P + G)
+            q8, (k8a, vt8a), (k8b, vt8b) = f8_operands(P, G, Nq, nkg, dtype, seed=5 * P + G)
             ld = vt8b.shape[1]
             own = dict(k8=k8a, vt8=vt8a, nk=Nq, ldk=Cc, ldvt=vt8a.shape[1])
             shared = dict(k8=k8b, vt8=vt8b, nk=nkg, ldk=Cc, ldvt=ld, b0=P, nb=G)
@@ -113,12 +76,12 @@ def test_old_entry_points_equal_the_shared_ones_with_zero_seg_nb(dtype, monkeypa
     monkeypatch.setattr(ops.ffi, "call_shared", lambda fn, a, nb, st: (calls.append((fn, list(nb))), real_shared(fn, a, nb, st))[1])
     P, Nq, nkg = 2, 320, 200
     B, Cc = 2 * P, HEADS * 64
-    q, k1, v1, k2, v2, ko = _self_attn_operands(P, P, Nq, nkg, dtype, seed=3)
+    q, k1, v1, k2, v2, ko = self_attn_operands(P, P, Nq, nkg, dtype, seed=3)
     qq = (q.float() * ops.QSCALE).to(dtype)
     vt1, ld1 = ko(v1, Nq)
     vt2, ld2 = ko(v2, nkg)
     segs = [dict(k=k1, vt=vt1, nk=Nq, ldk=Cc, ldvt=ld1), dict(k=k2, vt=vt2, nk=nkg, ldk=Cc, ldvt=ld2, b0=P)]
-    q8, (k8a, vt8a), (k8b, vt8b) = _f8_operands(P, P, Nq, nkg, dtype, seed=3)
+    q8, (k8a, vt8a), (k8b, vt8b) = f8_operands(P, P, Nq, nkg, dtype, seed=3)
     segs8 = [dict(k8=k8a, vt8=vt8a, nk=Nq, ldk=Cc, ldvt=vt8a.shape[1]), dict(k8=k8b, vt8=vt8b, nk=nkg, ldk=Cc, ldvt=vt8b.shape[1], b0=P)]
     outs = {}
     for form in ("old", "shared0"):
@@ -138,31 +101,6 @@ def test_old_entry_points_equal_the_shared_ones_with_zero_seg_nb(dtype, monkeypa
 
 
 # ------------------------------------------------------------------------------------------------------------------ engine
-def _engine(dtype, B, steps, unet_kw=None, H=128, W=128):
-    from idm_vton_amd.pipeline import TryonEngine
-    from tests import parity_utils as pu
-    m = pu.build("tiny", dtype, DEV, unet_kw=unet_kw)
-    inp = pu.make_inputs(B, H, W, m["xd"], m["pooled"], m["enc_dim"], steps, dtype)
-    return TryonEngine(*m["product"], dtype, DEV), inp, m
-
-
-def _garment_kw(inp, G=None):
-    return dict(cloth=inp["cloth"][:G], text_embeds_cloth=inp["text_embeds_cloth"][:G], noise_cloth=inp["noise"]["cloth"][:G])
-
-
-FORMS = {"serial_eager": dict(), "overlap_eager": dict(overlap=True), "graph": dict(use_graph=True),
-         "graph_overlap": dict(use_graph=True, overlap=True), "on_step": dict(on_step=lambda i, t, lat: False)}
-
-
-def _pair(eng, kw, cache, form):
-    """Uncached and cached denoise of one call in one execution form.  The person-side VAE encodes of the cached prepare() ran at another
-    encoder batch size (2B images instead of 3B), which is not what is under test: start latents and conditioning are copied over."""
-    st = eng.prepare(**kw)
-    st_c = eng.prepare(**{**kw, "cloth": cache, "text_embeds_cloth": None, "noise": {**kw["noise"], "cloth": None}})
-    st_c["latents"].copy_(st["latents"])
-    st_c["cond"].copy_(st["cond"])
-    assert st_c["timesteps"] is not None and len(st_c["timesteps"]) == len(st["timesteps"])
-    return eng.denoise(st, **FORMS[form]).clone(), eng.denoise(st_c, **FORMS[form]).clone()
 
 
 @pytest.mark.parametrize("scheduler", ["ddpm", "ddim"])
@@ -171,24 +109,24 @@ def test_cached_loop_is_bit_identical_to_the_uncached_loop(dtype, scheduler):
     """n = 7 steps: blocks of 1, 2, 4 timesteps.  encode_garment runs the same GarmentNet batches an uncached call runs, so the cached K / V^T
     are that call's bits and every execution form must reproduce its latents exactly."""
     steps = 7
-    eng, inp, _ = _engine(dtype, 2, steps)
+    eng, inp, _ = engine_inputs(dtype, 2, steps)
     kw = dict(num_inference_steps=steps, guidance_scale=2.0, scheduler=scheduler, **inp)
-    cache = eng.encode_garment(num_inference_steps=steps, scheduler=scheduler, **_garment_kw(inp))
+    cache = eng.encode_garment(num_inference_steps=steps, scheduler=scheduler, **garment_kw(inp))
     assert cache.G == 2 and len(cache.timesteps) == steps and cache.nbytes > 0
     for form in FORMS:
-        lat_u, lat_c = _pair(eng, kw, cache, form)
+        lat_u, lat_c = pair(eng, kw, cache, form)
         print(f"{dtype} {scheduler} {form}: max|cached - uncached| = {(lat_u - lat_c).abs().max().item():.3e}")
         assert torch.isfinite(lat_u).all() and torch.equal(lat_u, lat_c), (form, (lat_u - lat_c).abs().max().item())
 
 
 def test_cached_loop_is_bit_identical_with_fp8_attention():
     steps = 7
-    eng, inp, _ = _engine(torch.float16, 2, steps, unet_kw=dict(attn_fp8=True))
+    eng, inp, _ = engine_inputs(torch.float16, 2, steps, fp8=True)
     kw = dict(num_inference_steps=steps, guidance_scale=2.0, scheduler="ddpm", **inp)
-    cache = eng.encode_garment(num_inference_steps=steps, **_garment_kw(inp))
+    cache = eng.encode_garment(num_inference_steps=steps, **garment_kw(inp))
     assert cache.attn_fp8 and {k.dtype for k, _ in cache.kv} == {torch.uint8, torch.float16}    # e4m3 where whole 64-key tiles, else 16-bit
     for form in ("serial_eager", "graph_overlap"):
-        lat_u, lat_c = _pair(eng, kw, cache, form)
+        lat_u, lat_c = pair(eng, kw, cache, form)
         print(f"fp8 {form}: max|cached - uncached| = {(lat_u - lat_c).abs().max().item():.3e}")
         assert torch.isfinite(lat_u).all() and torch.equal(lat_u, lat_c), form
 
@@ -197,13 +135,13 @@ def test_cached_loop_is_bit_identical_with_fp8_attention():
 def test_cache_built_at_full_strength_serves_strength_0_6(dtype):
     """The cache of the 7-step schedule serves strength = 0.6: the last int(7 * 0.6) = 4 of its timesteps, found by value."""
     steps = 7
-    eng, inp, _ = _engine(dtype, 2, steps)
+    eng, inp, _ = engine_inputs(dtype, 2, steps)
     inp["noise"]["image"] = torch.randn(2, 4, 16, 16, generator=torch.Generator().manual_seed(77))
     inp["noise"]["steps"] = inp["noise"]["steps"][:4]
     kw = dict(num_inference_steps=steps, guidance_scale=2.0, scheduler="ddpm", strength=0.6, **inp)
-    cache = eng.encode_garment(num_inference_steps=steps, **_garment_kw(inp))                    # strength = 1
+    cache = eng.encode_garment(num_inference_steps=steps, **garment_kw(inp))                    # strength = 1
     for form in ("serial_eager", "graph_overlap"):
-        lat_u, lat_c = _pair(eng, kw, cache, form)
+        lat_u, lat_c = pair(eng, kw, cache, form)
         print(f"{dtype} strength 0.6 {form}: max|cached - uncached| = {(lat_u - lat_c).abs().max().item():.3e}")
         assert torch.isfinite(lat_u).all() and torch.equal(lat_u, lat_c), (form, (lat_u - lat_c).abs().max().item())
 
@@ -213,8 +151,8 @@ def test_one_shared_garment_equals_the_garment_held_once_per_person(mode):
     """P = 2 persons, G = 1 garment: the shared key segment against a cache that holds the garment twice."""
     dtype = torch.bfloat16 if mode == "bf16" else torch.float16
     steps = 5
-    eng, inp, _ = _engine(dtype, 2, steps, unet_kw=dict(attn_fp8=True) if mode.endswith("fp8") else None)
-    cache1 = eng.encode_garment(num_inference_steps=steps, **_garment_kw(inp, 1))
+    eng, inp, _ = engine_inputs(dtype, 2, steps, fp8=mode.endswith("fp8"))
+    cache1 = eng.encode_garment(num_inference_steps=steps, **garment_kw(inp, 1))
     cache2 = cache1.repeat_garments(2)
     assert (cache1.G, cache2.G) == (1, 2) and cache2.nbytes == 2 * cache1.nbytes
     base = dict(num_inference_steps=steps, guidance_scale=2.0, scheduler="ddpm", **{**inp, "text_embeds_cloth": None})
@@ -222,7 +160,7 @@ def test_one_shared_garment_equals_the_garment_held_once_per_person(mode):
         lats = [eng.denoise(eng.prepare(**{**base, "cloth": c}), **FORMS[form]).clone() for c in (cache1, cache2)]
         assert torch.isfinite(lats[0]).all() and torch.equal(lats[0], lats[1]), form
     # and the second person really wears garment 0: a cache of two different garments gives other latents
-    other = eng.encode_garment(num_inference_steps=steps, **_garment_kw(inp, 2))
+    other = eng.encode_garment(num_inference_steps=steps, **garment_kw(inp, 2))
     assert not torch.equal(eng.denoise(eng.prepare(**{**base, "cloth": other})).clone(), lats[0])
 
 
@@ -231,14 +169,14 @@ def test_cached_call_against_the_oracle(dtype):
     """The whole cached call, decode included, at the size / step count of test_parity_gpu.test_tiny_pipeline_parity and held to its bars."""
     from oracle import pipeline as opipe
     from oracle.scheduler import Scheduler
-    from tests.test_parity_gpu import TOL
+    from tests.parity_checks import TOL
     from tests import parity_utils as pu
     steps = 4
-    eng, inp, m = _engine(dtype, 1, steps)
+    eng, inp, m = engine_inputs(dtype, 1, steps)
     o_t, o_g, o_v = m["oracle"]
     tr = {}
     img_o = opipe.run(o_t, o_g, o_v, Scheduler("ddpm"), num_inference_steps=steps, guidance_scale=2.0, trace=tr, **inp)
-    cache = eng.encode_garment(num_inference_steps=steps, **_garment_kw(inp))
+    cache = eng.encode_garment(num_inference_steps=steps, **garment_kw(inp))
     call = dict(num_inference_steps=steps, guidance_scale=2.0, scheduler="ddpm", **{**inp, "cloth": cache, "text_embeds_cloth": None})
     for kw in (dict(), dict(use_graph=True, overlap=True)):
         lat = eng(return_latents=True, **kw, **call).clone()
@@ -250,7 +188,7 @@ def test_cached_call_against_the_oracle(dtype):
 
 def test_a_call_on_a_cache_runs_no_garmentnet_batch_and_a_wrong_cache_is_refused():
     steps = 7
-    eng, inp, _ = _engine(torch.float16, 2, steps)
+    eng, inp, _ = engine_inputs(torch.float16, 2, steps)
     kw = dict(num_inference_steps=steps, guidance_scale=2.0, scheduler="ddpm", **inp)
     eng.denoise(eng.prepare(**kw), **FORMS["graph_overlap"])                         # (the first graph call also runs one warm-up batch)
     for form in ("serial_eager", "graph_overlap"):
@@ -258,7 +196,7 @@ def test_a_call_on_a_cache_runs_no_garmentnet_batch_and_a_wrong_cache_is_refused
         st = eng.prepare(**kw)
         eng.denoise(st, **FORMS[form])
         assert eng.stats["garment_batches"] - n0 == len(st["blocks"]) == 3          # 1 + 2 + 4 timesteps: launched, or replayed
-    cache = eng.encode_garment(num_inference_steps=steps, **_garment_kw(inp))
+    cache = eng.encode_garment(num_inference_steps=steps, **garment_kw(inp))
     n1 = eng.stats["garment_batches"]
     ckw = {**kw, "cloth": cache, "text_embeds_cloth": None}
     for form in FORMS:
@@ -274,7 +212,7 @@ def test_a_call_on_a_cache_runs_no_garmentnet_batch_and_a_wrong_cache_is_refused
     three = {k: (torch.cat([v, v[:1]]) if torch.is_tensor(v) and k != "ip_hidden_states" else v) for k, v in ckw.items()}
     with pytest.raises(ValueError, match="GarmentCache persons mismatch"):
         eng.prepare(**three)
-    eng2, _, _ = _engine(torch.bfloat16, 2, steps)
+    eng2, _, _ = engine_inputs(torch.bfloat16, 2, steps)
     with pytest.raises(ValueError, match="GarmentCache dtype mismatch"):
         eng2.prepare(**ckw)
 
@@ -285,66 +223,31 @@ def test_captured_graphs_do_not_keep_a_cache_alive():
     import gc
     import weakref
     steps = 3
-    eng, inp, _ = _engine(torch.float16, 2, steps)
+    eng, inp, _ = engine_inputs(torch.float16, 2, steps)
     call = lambda c: dict(num_inference_steps=steps, guidance_scale=2.0, scheduler="ddpm",
                           **{**inp, "cloth": c, "text_embeds_cloth": None, "noise": {**inp["noise"], "cloth": None}})
-    cache = eng.encode_garment(num_inference_steps=steps, **_garment_kw(inp))
+    cache = eng.encode_garment(num_inference_steps=steps, **garment_kw(inp))
     st = eng.prepare(**call(cache))
     first = eng.denoise(st, **FORMS["graph_overlap"]).clone()
     ref = weakref.ref(cache)
     del cache, st
     gc.collect()
     assert ref() is None, "the engine's graph state still refers to the first call's GarmentCache"
-    cache = eng.encode_garment(num_inference_steps=steps, **_garment_kw(inp))
+    cache = eng.encode_garment(num_inference_steps=steps, **garment_kw(inp))
     again = eng.denoise(eng.prepare(**call(cache)), **FORMS["graph_overlap"]).clone()
     serial = eng.denoise(eng.prepare(**call(cache)), **FORMS["serial_eager"]).clone()
     assert torch.isfinite(serial).all() and torch.equal(again, serial) and torch.equal(first, serial)
 
 
 # ------------------------------------------------------------------------------------------------------------------ boundary
-class _FakeCLIPVision(torch.nn.Module):
-    """Stand-in for CLIPVisionModelWithProjection: deterministic 257-token hidden states from the pixels."""
-
-    def __init__(self, dim):
-        super().__init__()
-        self.proj = torch.nn.Linear(3, dim)
-
-    def forward(self, pixel_values, output_hidden_states=False):
-        p = F.adaptive_avg_pool2d(pixel_values.float(), (16, 16)).flatten(2).transpose(1, 2)
-        t = torch.cat([p.mean(1, keepdim=True), p], dim=1)
-        h = self.proj(t.to(self.proj.weight.dtype))
-        return SimpleNamespace(hidden_states=[h * 0.5, h, h * 2.0], image_embeds=h[:, 0])
 
 
 def test_boundary_pipeline_takes_the_cache_as_cloth():
-    from idm_vton_amd import config as pc
-    from idm_vton_amd.boundary.scheduler import DDPMScheduler
-    from idm_vton_amd.boundary.vae import AutoencoderKL
     from idm_vton_amd.garment_cache import GarmentCache
-    from src.tryon_pipeline import StableDiffusionXLInpaintPipeline
-    from src.unet_hacked_garmnet import UNet2DConditionModel as G
-    from src.unet_hacked_tryon import UNet2DConditionModel as T
-    from tests import parity_utils as pu
     DT = torch.float16
-    kw = dict(pu.TINY)
-    tcfg = pc.UNetConfig(mode="tryon", in_channels=13, sample_size=16, **kw)
-    gcfg = pc.UNetConfig(mode="garmnet", in_channels=4, addition_embed_type=None, encoder_hid_dim_type=None, sample_size=16, **kw)
-    vcfg = pc.VAEConfig(**pu.TINY_VAE)
-    rnd = lambda sd: {k: v.to(DT) for k, v in sd.items()}
-    t = T(tcfg, torch_dtype=DT); t.load_state_dict(rnd(pc.random_state_dict(pc.unet_param_shapes(tcfg), 1, torch.float32, "cpu")))
-    g = G(gcfg, torch_dtype=DT); g.load_state_dict(rnd(pc.random_state_dict(pc.unet_param_shapes(gcfg), 2, torch.float32, "cpu")))
-    v = AutoencoderKL(vcfg, torch_dtype=DT); v.load_state_dict(rnd(pc.random_state_dict(pc.vae_param_shapes(vcfg), 3, torch.float32, "cpu", std=0.05)))
-    torch.manual_seed(5)
-    enc = _FakeCLIPVision(kw["encoder_hid_dim"]).to(DT)
-    pipe = StableDiffusionXLInpaintPipeline(vae=v, text_encoder=None, text_encoder_2=None, tokenizer=None, tokenizer_2=None, unet=t,
-                                            unet_encoder=g, scheduler=DDPMScheduler(), image_encoder=enc).to(DEV)
+    pipe, enc, kw = boundary_pipeline(DT)
     B, H, W, steps = 2, 128, 128, 3
-    inp = pu.make_inputs(B, H, W, kw["cross_attention_dim"], 64, kw["encoder_hid_dim"], steps, DT)
-    clip_pix = torch.randn(B, 3, 224, 224, generator=torch.Generator().manual_seed(9))
-    call = dict(prompt_embeds=inp["prompt_embeds"], negative_prompt_embeds=inp["negative_prompt_embeds"],
-                pooled_prompt_embeds=inp["pooled_prompt_embeds"], negative_pooled_prompt_embeds=inp["negative_pooled_prompt_embeds"],
-                num_inference_steps=steps, strength=1.0, pose_img=inp["pose_img"], mask_image=inp["mask_image"], image=inp["image"],
-                height=H, width=W, guidance_scale=2.0, ip_adapter_image=clip_pix, output_type="pt")
+    inp, clip_pix, call = boundary_inputs(kw, B, H, W, steps, DT)
     cache = pipe.encode_garment(inp["cloth"], inp["text_embeds_cloth"], steps, H, W, generator=torch.Generator(DEV).manual_seed(11))
     assert isinstance(cache, GarmentCache) and cache.G == B and len(cache.timesteps) == steps
     eng = pipe.hip_engine()
@@ -354,19 +257,9 @@ def test_boundary_pipeline_takes_the_cache_as_cloth():
     img_c = pipe(generator=gen_c, cloth=cache, text_embeds_cloth=None, **call)[0]
     assert eng.stats["garment_batches"] == n_garm
     # the engine-level cached call on the draws of the reference's order: the cloth draw is made and dropped
-    gen = torch.Generator(DEV).manual_seed(7)
-    torch.manual_seed(123)
-    draw = lambda gg, dt_: torch.randn((B, 4, H // 8, W // 8), generator=gg, device=DEV, dtype=dt_).float()
-    n_lat, n_masked, n_pose, _dropped = draw(gen, DT), draw(gen, torch.float32), draw(None, torch.float32), draw(gen, torch.float32)
-    n_steps = torch.stack([draw(gen, DT) for _ in range(steps)])
-    with torch.no_grad():
-        pos = enc(clip_pix.to(DEV, DT), output_hidden_states=True).hidden_states[-2]
-        neg = enc(torch.zeros_like(clip_pix).to(DEV, DT), output_hidden_states=True).hidden_states[-2]
-    ref = eng(image=inp["image"], mask_image=inp["mask_image"], pose_img=inp["pose_img"], cloth=cache,
-              prompt_embeds=inp["prompt_embeds"], negative_prompt_embeds=inp["negative_prompt_embeds"],
-              pooled_prompt_embeds=inp["pooled_prompt_embeds"], negative_pooled_prompt_embeds=inp["negative_pooled_prompt_embeds"],
-              text_embeds_cloth=None, noise=dict(latents=n_lat, masked=n_masked, pose=n_pose, cloth=None, steps=n_steps),
-              num_inference_steps=steps, guidance_scale=2.0, ip_hidden_states=torch.cat([neg, pos]), scheduler="ddpm")
+    gen, noise = reference_draws(7, 123, B, H, W, steps, DT)
+    ip = ip_states(enc, clip_pix)
+    ref = engine_reference(eng, inp, noise, ip, steps, cloth=cache)
     assert torch.isfinite(img_c).all() and torch.equal(img_c, ref)
     # an uncached call with the same generator leaves it in the same state: the cached call made every draw of it
     gen_u = torch.Generator(DEV).manual_seed(7)

@@ -3,22 +3,19 @@
 records kv_records makes of compact feature parts -- a data run and, exactly where a garment has fewer rows than the slot, a zero ROW run
 behind it -- and TryonEngine._cached_fill on a CPU engine: after every block the staging list holds each part's F in front of its slot and
 the bits 0x0000 behind, and the sets hold what _fill_set gives on the K / V^T cache a stand-in projection makes of the zero-padded features.
-No GPU: launches are recorded and interpreted on host memory (tests/test_garment_shelf_cpu.py's interpreter)."""
+No GPU: launches are recorded and interpreted on host memory (tests/garment_support.py's interpreter)."""
 import ctypes as C
 import types
 
 import pytest
 import torch
 
-from tests.test_garment_features_cpu import BLOCKS, DTYPE, GINDEX, K, META, N_T, ORDERS, P, _Event, _same, _standin_unet
-from tests.test_garment_shelf_cpu import _apply
-from tests.test_garment_stream_cpu import _fields
+from tests.garment_support import BLOCKS, DTYPE, GINDEX, K, META, N_T, ORDERS, P, PACKED, Event, apply_records, record_fields, same_features, standin_unet
 
 SLOT = [(48, 64), (16, 128)]                             # (N_f, C_f) of the slot's two features
 # per garment: its own latent size and rows per timestep of the two features -- smaller, smallest, the slot's size
 KINDS = {"a": ((8, 4), (32, 16)), "b": ((4, 4), (16, 16)), "c": ((12, 4), (48, 16))}
 SLOT_HW = (12, 4)
-PACKED = pytest.mark.parametrize("packed", [False, True], ids=["16bit", "packed"])
 TRANSPORTS = pytest.mark.parametrize("transport", ["kernel", "copy"])
 
 
@@ -122,11 +119,11 @@ def test_a_16bit_feature_garment_is_packed_on_its_way_in():
     shelf = GarmentShelf(_like_features(), storage="features-e4m3")
     shelf.add("a", _feat("a"))
     shelf.add("a2", _feat("a").pack())
-    _same(shelf._parts["a"], _feat("a").pack())
-    _same(shelf._parts["a2"], shelf._parts["a"])
+    same_features(shelf._parts["a"], _feat("a").pack())
+    same_features(shelf._parts["a2"], shelf._parts["a"])
     plain = GarmentShelf(_like_features(), storage="features")
     plain.add("a", _feat("a"))
-    _same(plain._parts["a"], _feat("a"))
+    same_features(plain._parts["a"], _feat("a"))
     assert plain._parts["a"].kv[0][0].data_ptr() != _feat("a").kv[0][0].data_ptr()
 
 
@@ -143,7 +140,7 @@ def test_shelved_feature_cache_methods(packed):
         t = cache.take(g)
         assert t.G == 1 and t.features and t.packed == packed and (t.gh, t.gw) == KINDS[key][0]
         assert t.kv[0][0].data_ptr() != cache.parts[g].kv[0][0].data_ptr()
-        _same(t, cache.parts[g])
+        same_features(t, cache.parts[g])
     sel = cache.select([2, 0, 2])
     assert sel.features and sel.G == 3 and sel.sizes == [(12, 4), (8, 4), (12, 4)] and sel.parts[0] is cache.parts[2] and sel.parts[2] is cache.parts[2]
     assert sel.nbytes == 2 * cache.parts[2].nbytes + cache.parts[0].nbytes
@@ -261,7 +258,7 @@ def test_records_of_compact_feature_parts(packed, garments):
         if len(step) % 2:
             step.append(min(step, key=lambda r: r[3] * (r[4] // 16)))
         want += step
-    got = _fields(rec)
+    got = record_fields(rec)
     assert [r[:5] + r[6:] for r in got] == [r[:5] + r[6:] for r in want]                     # (lds of a zero run is not looked at)
     assert all(g[5] == w[5] for g, w in zip(got, want) if g[0])
     zero = [r for r in got if r[0] == 0]
@@ -275,7 +272,7 @@ def test_records_of_compact_feature_parts(packed, garments):
     assert table.first_host[:per + 1].tolist() == [sum((it + 1023) // 1024 for it in items[:m]) for m in range(per + 1)]
     # the bytes a timestep loads are the compact parts' own (the pad record here is a zero run, the smallest)
     assert table.link_bytes(0, per) == sum(p.nbytes - (p.exps.numel() * 4 if packed else 0) for p in parts) / N_T
-    _apply(rec, packed, DTYPE)
+    apply_records(rec, packed, DTYPE)
     for i, j in zip(entries, tslots):
         for u in range(S):
             for f, ((d,), (N, Cc)) in enumerate(zip(dst, SLOT)):
@@ -305,7 +302,7 @@ def test_staged_plan_serves_feature_parts(packed):
     if packed:
         assert tuple(plan["exps"].shape) == (len(used), len(SLOT), 1)
     assert len(plan["copies"]([1, 2])) == len(used) * len(SLOT) and len(plan["copies"]([3, 1])) == 2 * len(used) * len(SLOT)
-    got = _fields(plan["rec"])
+    got = record_fields(plan["rec"])
     per = plan["per"]
     assert per == 6 and len(got) == 2 * k * per                                              # 2 + 3 records per timestep, padded
     zero = [r for r in got if r[0] == 0]
@@ -335,7 +332,7 @@ def test_cached_fill_stages_compact_features_with_zero_rows_and_projects_them(mo
     monkeypatch.setattr(ops, "stream_address", lambda t: t.data_ptr())
     monkeypatch.setattr(ops, "_stream", lambda: 0)
     monkeypatch.setattr(ops, "PROFILE", None)
-    monkeypatch.setattr(torch.cuda, "Event", _Event)
+    monkeypatch.setattr(torch.cuda, "Event", Event)
     for name in ("KvUnpackTable", "KvStreamTable", "KvFillTable", "KvPlaceTable"):
         cls = getattr(ops, name)
         monkeypatch.setattr(ops, name, type(name, (cls,), {"__init__": lambda self, *a, _c=cls, _n=name, **kw: (made.append(_n), tables.append(self),
@@ -344,12 +341,12 @@ def test_cached_fill_stages_compact_features_with_zero_rows_and_projects_them(mo
 
     def launched(name, a, desc):
         launches.append((name, getattr(a, "workgroups", None)))
-        _apply(records(desc, a.n), packed, DTYPE)
+        apply_records(records(desc, a.n), packed, DTYPE)
     monkeypatch.setattr(ffi, "call_kv_unpack", lambda a, desc, stream: launched("kv_unpack", a, desc))
     for name in ("kv_stream", "kv_fill", "kv_place"):
         monkeypatch.setattr(ffi, "call_" + name, lambda a, desc, first, stream, name=name: launched(name, a, desc))
 
-    eng, ref_eng = [TryonEngine(_standin_unet(calls if i == 0 else []), None, None, dtype=DTYPE, device="cpu") for i in range(2)]
+    eng, ref_eng = [TryonEngine(standin_unet(calls if i == 0 else []), None, None, dtype=DTYPE, device="cpu") for i in range(2)]
     S, G = P, cache.G
     st = dict(B=P, h=8, w=4, gh=SLOT_HW[0], gw=SLOT_HW[1], k=K, steps_noise=None, gcache=cache, gidx=ORDERS[order], gindex=GINDEX, blocks=BLOCKS,
               host_transport=transport)

@@ -1,7 +1,7 @@
 """-m gpu: the FEATURE SHELF on the GPU -- a GarmentShelf of storage "features" / "features-e4m3" (compact feature caches of many sizes in
 page-locked host memory) as `cloth=` with `garment_index=`.  Kernel level: the one record form the feature relies on, a compact data run in
 front of a destination and a zero ROW run over all rows behind it, through idmvton_kv_fill and idmvton_kv_place as they are, on framed
-operands (tests/frames.py).  Engine level, on the tiny engine and the three garment sizes of tests/test_garment_ragged_gpu.py (latent 8x12,
+operands (tests/frames.py).  Engine level, on the tiny engine and the three garment sizes of tests/engine_support.py (latent 8x12,
 16x16 = the slot's, 9x5 with padded token rows; 3 steps: blocks of 1 and 2): slot-sized garments against today's plain host-resident feature
 cache, mixed sizes against the K / V^T shelf that engine.project_garment makes of the same garments, packed against its unpacked values,
 slot reuse through one graph state whose staging lists and sets were filled with NaN in between, counters and link bytes, refusals, the
@@ -9,17 +9,12 @@ boundary pipeline.  Widening is exact: every bar is torch.equal plus isfinite.""
 import pytest
 import torch
 
-from tests.test_garment_cache_gpu import FORMS
-from tests.test_garment_packed_gpu import _assert_bits, _bytes
-from tests.test_garment_ragged_gpu import GARMENT_HW, H, STEPS, W, WEARS, _base, _engine, _inputs, _model, _oracle_latents
-from tests.test_garment_stream_gpu import _pinned
+from tests.engine_support import (DEV, GARMENT_HW, KEYS, STEPS, WEARS, H, W, assert_bits, base_call, boundary_inputs, boundary_pipeline, e4m3_bytes,
+                                  encode_three, engine, engine_reference, gpu_shelf, ip_states, model, oracle_latents, pin_frame, reference_draws,
+                                  run_on, three_garments)
+from tests.garment_support import DTYPES, FORMS, PACKED, TRANSPORTS
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-DTYPES = pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
-PACKED = pytest.mark.parametrize("packed", [False, True], ids=["16bit", "packed"])
-TRANSPORTS = ("kernel", "copy")
-KEYS = ["g0", "g1", "g2"]                                # the garments of GARMENT_HW: latent 8x12, 16x16 (the slot's), 9x5
 NBLOCKS = 2
 
 
@@ -39,9 +34,9 @@ def test_a_compact_run_and_the_zero_row_run_behind_it(dtype, entry, workgroups, 
     from tests import frames
     out = frames.framed_out((ROWS, WIDTH), dtype, DEV, WIDTH)
     e = -3
-    x = torch.randn(FRONT, WIDTH, generator=torch.Generator().manual_seed(5)).to(dtype) if copy else _bytes(FRONT, WIDTH, seed=5)
+    x = torch.randn(FRONT, WIDTH, generator=torch.Generator().manual_seed(5)).to(dtype) if copy else e4m3_bytes(FRONT, WIDTH, seed=5)
     on_host = entry == "kv_fill"                         # kv_fill reads page-locked host memory, kv_place a staging arena in HBM
-    src = _pinned(frames.framed(x, WIDTH + 16)) if on_host else frames.framed(x.to(DEV), WIDTH + 16)
+    src = pin_frame(frames.framed(x, WIDTH + 16)) if on_host else frames.framed(x.to(DEV), WIDTH + 16)
     exps = torch.tensor([e], dtype=torch.int32)
     exps = exps.pin_memory() if on_host else exps.to(DEV)
     descs = [(src, out[:FRONT], None if copy else exps[0:1]), (None, out[FRONT:], None)]
@@ -57,28 +52,12 @@ def test_a_compact_run_and_the_zero_row_run_behind_it(dtype, entry, workgroups, 
     if copy:
         assert torch.equal(frames.ints(out[:FRONT].cpu().contiguous()), frames.ints(x)), "the data run is not the source's bits"
     else:
-        _assert_bits(out[:FRONT], unpack_values(x, torch.tensor(e), dtype), x, "the data run is not the format's bits")
+        assert_bits(out[:FRONT], unpack_values(x, torch.tensor(e), dtype), x, "the data run is not the format's bits")
     tail = frames.ints(out[FRONT:].cpu().contiguous())
     assert (tail == 0).all(), f"a zero run's bits are 0x0000, got {sorted(set(tail.flatten().tolist()))[:4]}"
 
 
 # ------------------------------------------------------------------------------------------------------------------ engine
-def _run(eng, base, cache, form, index, transport="kernel"):
-    return eng.denoise(eng.prepare(**{**base, "cloth": cache, "garment_index": index}), host_transport=transport, **FORMS[form]).clone()
-
-
-def _encode(eng, garments, storage="features", which=(0, 1, 2)):
-    return [eng.encode_garment(num_inference_steps=STEPS, height=H, width=W, storage=storage, **garments[j]) for j in which]
-
-
-def _shelf(eng, ones, storage, keys=KEYS):
-    from idm_vton_amd.garment_cache import GarmentShelf
-    shelf = GarmentShelf(eng.empty_garment_cache(1, H, W, STEPS, height=H, width=W), storage=storage)
-    for key, one in zip(keys, ones):
-        shelf.add(key, one)
-    assert all(t.is_pinned() for p in shelf._parts.values() for e in p.kv for t in e)
-    assert all(p.features and p.packed == storage.endswith("e4m3") and (not p.packed or p.exps.is_pinned()) for p in shelf._parts.values())
-    return shelf
 
 
 def _storage(packed):
@@ -101,22 +80,22 @@ def test_slot_sized_garments_equal_the_plain_host_resident_feature_cache(dtype, 
     """Three garments of the slot's own size: no zero run anywhere, and the shelf call moves what the call on cat(parts), pinned in host
     memory, moves -- today's path (idmvton_kv_stream, a plain indexed segment) -- into the same S slots."""
     from idm_vton_amd.garment_cache import GarmentCache
-    eng = _engine(_model(dtype), dtype)
-    inp, garments = _inputs(dtype)
+    eng = engine(model(dtype), dtype)
+    inp, garments = three_garments(dtype)
     g = torch.Generator().manual_seed(31)
     same = [dict(cloth=torch.randn(1, 3, H, W, generator=g).clamp(-1, 1), noise_cloth=torch.randn(1, 4, H // 8, W // 8, generator=g),
                  text_embeds_cloth=garments[j]["text_embeds_cloth"]) for j in range(3)]
-    shelf = _shelf(eng, _encode(eng, same), _storage(packed))
+    shelf = gpu_shelf(eng, encode_three(eng, same, storage="features"), _storage(packed))
     shelved, index = shelf.get([KEYS[j] for j in WEARS])
     assert shelved.features and shelved.sizes == [(16, 16)] * 3 and index == [0, 1, 2]
     plain = GarmentCache.cat(shelved.parts).to("cpu", pin_memory=True)
     assert plain.features and plain.sizes is None and plain.packed == packed and plain.host_resident and plain.nbytes == shelved.nbytes
-    base = _base(inp)
+    base = base_call(inp, STEPS)
     for form in FORMS:
         for transport in TRANSPORTS:
-            lat_p = _run(eng, base, plain, form, index, transport)
+            lat_p = run_on(eng, base, plain, form, index, transport)
             s0 = dict(eng.stats)
-            lat_s = _run(eng, base, shelved, form, index, transport)
+            lat_s = run_on(eng, base, shelved, form, index, transport)
             d = _delta(eng, s0)
             assert torch.isfinite(lat_p).all() and torch.equal(lat_s, lat_p), (form, transport, (lat_s - lat_p).abs().max().item())
             # (a graph state's first call adds its warm-up fill to the launch counter of its transport, as ever)
@@ -133,10 +112,10 @@ def test_mixed_sizes_equal_the_kv_shelf_of_the_same_garments(dtype, packed):
     on a GEMM row not depending on M, asserted here with the difference printed; the per-person fp32 oracle bounds both at the bar of
     tests/test_garment_ragged_gpu.py (16-bit storage: the packed form is lossy by its format, not by this path)."""
     from tests import parity_utils as pu
-    from tests.test_parity_gpu import TOL
-    eng = _engine(_model(dtype), dtype)
-    inp, garments = _inputs(dtype)
-    shelf = _shelf(eng, _encode(eng, garments), _storage(packed))
+    from tests.parity_checks import TOL
+    eng = engine(model(dtype), dtype)
+    inp, garments = three_garments(dtype)
+    shelf = gpu_shelf(eng, encode_three(eng, garments, storage="features"), _storage(packed))
     assert shelf.nbytes == sum(p.nbytes for p in shelf._parts.values()) < 3 * shelf._parts["g1"].nbytes
     shelved, index = shelf.get([KEYS[j] for j in WEARS])
     assert index == [0, 1, 2] and shelved.sizes == [(9, 5), (8, 12), (16, 16)] and shelved.features and shelved.packed == packed
@@ -145,19 +124,19 @@ def test_mixed_sizes_equal_the_kv_shelf_of_the_same_garments(dtype, packed):
     assert all(t.is_pinned() for p in kv.parts for e in p.kv for t in e)
     if not packed:
         assert kv.nbytes == 2 * shelved.nbytes           # exactly half the bytes of the compact K / V^T parts
-    base = _base(inp)
+    base = base_call(inp, STEPS)
     for form in FORMS:
         for transport in TRANSPORTS:
-            lat_k = _run(eng, base, kv, form, index, transport)
+            lat_k = run_on(eng, base, kv, form, index, transport)
             states = len(eng._graphs)
-            lat_f = _run(eng, base, shelved, form, index, transport)
+            lat_f = run_on(eng, base, shelved, form, index, transport)
             print(f"{dtype} {'packed' if packed else '16bit'} {form} {transport}: max|feature shelf - kv shelf| = {(lat_f - lat_k).abs().max().item():.3e}")
             assert torch.isfinite(lat_k).all() and torch.isfinite(lat_f).all(), (form, transport)
             assert torch.equal(lat_f, lat_k), (form, transport, (lat_f - lat_k).abs().max().item())
             assert len(eng._graphs) == states, (form, transport)         # one graph state serves both kinds of shelf
-    assert not torch.equal(_run(eng, base, shelved, "serial_eager", [0, 0, 1]), lat_k)       # and the assignment is read
+    assert not torch.equal(run_on(eng, base, shelved, "serial_eager", [0, 0, 1]), lat_k)       # and the assignment is read
     if not packed:
-        for i, ref in enumerate(_oracle_latents(dtype)):
+        for i, ref in enumerate(oracle_latents(dtype)):
             err = pu.relerr(lat_f[i:i + 1], ref)
             print(f"{dtype} person {i} in garment {WEARS[i]} ({GARMENT_HW[WEARS[i]]}): feature shelf against the oracle {err:.3e} (bar {TOL[dtype]['latents']:.1e})")
             assert err <= TOL[dtype]["latents"], (i, err)
@@ -167,10 +146,10 @@ def test_mixed_sizes_equal_the_kv_shelf_of_the_same_garments(dtype, packed):
 @DTYPES
 def test_packed_shelf_equals_the_16bit_shelf_of_its_unpacked_parts(dtype):
     from idm_vton_amd.garment_cache import GarmentShelf
-    eng = _engine(_model(dtype), dtype)
-    inp, garments = _inputs(dtype)
-    ones = _encode(eng, garments)
-    packed_shelf = _shelf(eng, ones, "features-e4m3")
+    eng = engine(model(dtype), dtype)
+    inp, garments = three_garments(dtype)
+    ones = encode_three(eng, garments, storage="features")
+    packed_shelf = gpu_shelf(eng, ones, "features-e4m3")
     wide = GarmentShelf(packed_shelf._parts["g1"], storage="features")    # (`like`: a G = 1 feature cache of the slot's size)
     assert wide.slot_shapes == packed_shelf.slot_shapes
     for key in KEYS:
@@ -179,10 +158,10 @@ def test_packed_shelf_equals_the_16bit_shelf_of_its_unpacked_parts(dtype):
     keys = [KEYS[j] for j in WEARS]
     (cp, index), (cw, index_w) = packed_shelf.get(keys), wide.get(keys)
     assert index == index_w and cp.packed and not cw.packed and cp.nbytes == cw.nbytes // 2 + 4 * 3 * len(cp.slot_shapes)
-    base = _base(inp)
+    base = base_call(inp, STEPS)
     for form in FORMS:
         for transport in TRANSPORTS:
-            lat_p, lat_w = _run(eng, base, cp, form, index, transport), _run(eng, base, cw, form, index, transport)
+            lat_p, lat_w = run_on(eng, base, cp, form, index, transport), run_on(eng, base, cw, form, index, transport)
             assert torch.isfinite(lat_w).all() and torch.equal(lat_p, lat_w), (form, transport, (lat_p - lat_w).abs().max().item())
 
 
@@ -193,17 +172,17 @@ def test_slot_reuse_through_one_graph_state_poisoned_between_calls(packed):
     the smallest.  Without the zero-row run the rows behind the small garment's F would keep NaN, its K rows and V^T tail would be NaN, and
     a NaN times a zero probability is NaN: the latents show it, where stale finite rows would not."""
     dtype = torch.float16
-    eng, fresh = _engine(_model(dtype), dtype), _engine(_model(dtype), dtype)
-    inp, garments = _inputs(dtype)
-    shelf = _shelf(eng, _encode(eng, garments), _storage(packed))
-    base = _base(inp)
+    eng, fresh = engine(model(dtype), dtype), engine(model(dtype), dtype)
+    inp, garments = three_garments(dtype)
+    shelf = gpu_shelf(eng, encode_three(eng, garments, storage="features"), _storage(packed))
+    base = base_call(inp, STEPS)
     nan = float("nan")
     for transport in TRANSPORTS:
         for form in ("graph", "graph_overlap"):
             for keys in (["g1"] * 3, ["g2"] * 3, ["g2", "g1", "g0"]):        # 16x16, then 9x5 in the same slot, then all three
                 shelved, index = shelf.get(keys)
-                lat = _run(eng, base, shelved, form, index, transport)
-                ref = _run(fresh, base, shelved, "serial_eager", index)
+                lat = run_on(eng, base, shelved, form, index, transport)
+                ref = run_on(fresh, base, shelved, "serial_eager", index)
                 assert torch.isfinite(lat).all() and torch.equal(lat, ref), (transport, form, keys, (lat - ref).abs().max().item())
                 torch.cuda.synchronize()
                 assert len(eng._graphs) == 1
@@ -222,11 +201,11 @@ def test_counters_link_bytes_and_refusals(packed, monkeypatch):
     from idm_vton_amd import ops
     from idm_vton_amd.garment_cache import ShelvedGarmentCache
     dtype = torch.float16
-    eng = _engine(_model(dtype), dtype)
-    inp, garments = _inputs(dtype)
-    shelf = _shelf(eng, _encode(eng, garments), _storage(packed))
+    eng = engine(model(dtype), dtype)
+    inp, garments = three_garments(dtype)
+    shelf = gpu_shelf(eng, encode_three(eng, garments, storage="features"), _storage(packed))
     shelved, index = shelf.get([KEYS[j] for j in WEARS])
-    base = _base(inp)
+    base = base_call(inp, STEPS)
     tables = []
     for name in ("KvFillTable", "KvPlaceTable"):
         cls = getattr(ops, name)
@@ -240,7 +219,7 @@ def test_counters_link_bytes_and_refusals(packed, monkeypatch):
         for form in ("serial_eager", "overlap_eager"):
             del tables[:]
             s0 = dict(eng.stats)
-            lat = _run(eng, base, shelved, form, index, transport)
+            lat = run_on(eng, base, shelved, form, index, transport)
             assert torch.isfinite(lat).all()
             assert _delta(eng, s0) == _per_block(transport), (form, transport)
             if transport == "copy":                      # one copy per part tensor and block (the call's entries are consecutive)
@@ -273,7 +252,7 @@ def test_counters_link_bytes_and_refusals(packed, monkeypatch):
     with pytest.raises(ValueError, match="slotted: features"):
         shelved.slotted(DEV)
     assert eng.stats == stats and launched == []
-    eng8 = _engine(_model(dtype, True), dtype)
+    eng8 = engine(model(dtype, True), dtype)
     stats8 = dict(eng8.stats)
     with pytest.raises(ValueError, match="attn_fp8"):
         eng8.prepare(**{**base, "cloth": shelved, "garment_index": index})
@@ -284,35 +263,11 @@ def test_counters_link_bytes_and_refusals(packed, monkeypatch):
 
 # ---- 7 ------------------------------------------------------------------------------------------------------------------------------------
 def test_boundary_pipeline_passes_a_feature_shelf_cache_through():
-    from idm_vton_amd import config as pc
-    from idm_vton_amd.boundary.scheduler import DDPMScheduler
-    from idm_vton_amd.boundary.vae import AutoencoderKL
     from idm_vton_amd.garment_cache import GarmentShelf, ShelvedGarmentCache
-    from src.tryon_pipeline import StableDiffusionXLInpaintPipeline
-    from src.unet_hacked_garmnet import UNet2DConditionModel as G
-    from src.unet_hacked_tryon import UNet2DConditionModel as T
-    from tests import parity_utils as pu
-    from tests.test_garment_cache_gpu import _FakeCLIPVision
     DT = torch.float16
-    kw = dict(pu.TINY)
-    tcfg = pc.UNetConfig(mode="tryon", in_channels=13, sample_size=16, **kw)
-    gcfg = pc.UNetConfig(mode="garmnet", in_channels=4, addition_embed_type=None, encoder_hid_dim_type=None, sample_size=16, **kw)
-    vcfg = pc.VAEConfig(**pu.TINY_VAE)
-    rnd = lambda sd: {k: v.to(DT) for k, v in sd.items()}
-    t = T(tcfg, torch_dtype=DT); t.load_state_dict(rnd(pc.random_state_dict(pc.unet_param_shapes(tcfg), 1, torch.float32, "cpu")))
-    g = G(gcfg, torch_dtype=DT); g.load_state_dict(rnd(pc.random_state_dict(pc.unet_param_shapes(gcfg), 2, torch.float32, "cpu")))
-    v = AutoencoderKL(vcfg, torch_dtype=DT); v.load_state_dict(rnd(pc.random_state_dict(pc.vae_param_shapes(vcfg), 3, torch.float32, "cpu", std=0.05)))
-    torch.manual_seed(5)
-    enc = _FakeCLIPVision(kw["encoder_hid_dim"]).to(DT)
-    pipe = StableDiffusionXLInpaintPipeline(vae=v, text_encoder=None, text_encoder_2=None, tokenizer=None, tokenizer_2=None, unet=t,
-                                            unet_encoder=g, scheduler=DDPMScheduler(), image_encoder=enc).to(DEV)
+    pipe, enc, kw = boundary_pipeline(DT)
     B, steps = 3, 3
-    inp = pu.make_inputs(B, H, W, kw["cross_attention_dim"], 64, kw["encoder_hid_dim"], steps, DT)
-    clip_pix = torch.randn(B, 3, 224, 224, generator=torch.Generator().manual_seed(9))
-    call = dict(prompt_embeds=inp["prompt_embeds"], negative_prompt_embeds=inp["negative_prompt_embeds"],
-                pooled_prompt_embeds=inp["pooled_prompt_embeds"], negative_pooled_prompt_embeds=inp["negative_pooled_prompt_embeds"],
-                num_inference_steps=steps, strength=1.0, pose_img=inp["pose_img"], mask_image=inp["mask_image"], image=inp["image"],
-                height=H, width=W, guidance_scale=2.0, ip_adapter_image=clip_pix, output_type="pt")
+    inp, clip_pix, call = boundary_inputs(kw, B, H, W, steps, DT)
     small = torch.randn(1, 3, 64, 96, generator=torch.Generator().manual_seed(13)).clamp(-1, 1)
     cloths = {"small": (small, inp["text_embeds_cloth"][:1]), "full": (inp["cloth"][1:2], inp["text_embeds_cloth"][1:2])}
     encode = lambda key: pipe.encode_garment(cloths[key][0], cloths[key][1], steps, H, W, generator=torch.Generator(DEV).manual_seed(11), storage="features")
@@ -321,19 +276,9 @@ def test_boundary_pipeline_passes_a_feature_shelf_cache_through():
     assert isinstance(cache, ShelvedGarmentCache) and cache.features and cache.packed and idx == [0, 1, 0] and cache.sizes == [(16, 16), (8, 12)]
     eng = pipe.hip_engine()
     # the engine-level call on the draws of the reference's order, on the same cache
-    gen = torch.Generator(DEV).manual_seed(7)
-    torch.manual_seed(123)
-    draw = lambda gg, dt_: torch.randn((B, 4, H // 8, W // 8), generator=gg, device=DEV, dtype=dt_).float()
-    n_lat, n_masked, n_pose, _dropped = draw(gen, DT), draw(gen, torch.float32), draw(None, torch.float32), draw(gen, torch.float32)
-    n_steps = torch.stack([draw(gen, DT) for _ in range(steps)])
-    with torch.no_grad():
-        pos = enc(clip_pix.to(DEV, DT), output_hidden_states=True).hidden_states[-2]
-        neg = enc(torch.zeros_like(clip_pix).to(DEV, DT), output_hidden_states=True).hidden_states[-2]
-    ref = eng(image=inp["image"], mask_image=inp["mask_image"], pose_img=inp["pose_img"], cloth=cache, garment_index=idx,
-              prompt_embeds=inp["prompt_embeds"], negative_prompt_embeds=inp["negative_prompt_embeds"],
-              pooled_prompt_embeds=inp["pooled_prompt_embeds"], negative_pooled_prompt_embeds=inp["negative_pooled_prompt_embeds"],
-              text_embeds_cloth=None, noise=dict(latents=n_lat, masked=n_masked, pose=n_pose, cloth=None, steps=n_steps),
-              num_inference_steps=steps, guidance_scale=2.0, ip_hidden_states=torch.cat([neg, pos]), scheduler="ddpm").clone()
+    gen, noise = reference_draws(7, 123, B, H, W, steps, DT)
+    ip = ip_states(enc, clip_pix)
+    ref = engine_reference(eng, inp, noise, ip, steps, cloth=cache, garment_index=idx).clone()
     assert torch.isfinite(ref).all()
     for transport, counter in (("kernel", "garment_stream_launches"), ("copy", "garment_stage_launches")):
         pipe.host_transport = transport

@@ -2,7 +2,7 @@
 K / V^T that TryonNet's attn1.to_k / to_v make of them -- its sizes, the container primitives, the packed form, the file format, the
 refusals, and TryonEngine._cached_fill on a CPU engine: which table class and entry point each kind of feature cache selects, and that
 after every block the staging list and the sets hold what _fill_set gives on the K / V^T cache a stand-in projection makes of the same
-features.  No GPU: launches are recorded and interpreted on host memory (tests/test_garment_shelf_cpu.py's interpreter)."""
+features.  No GPU: launches are recorded and interpreted on host memory (tests/garment_support.py's interpreter)."""
 import ctypes as C
 import json
 import types
@@ -10,13 +10,8 @@ import types
 import pytest
 import torch
 
-from tests.test_garment_shelf_cpu import _apply
+from tests.garment_support import BLOCKS, DTYPE, FEATS, GINDEX, K, META, N_T, ORDERS, P, PACKED, Event, apply_records, same_features, standin_unet
 
-FEATS = [(32, 64), (16, 128)]                            # (N_f, C_f) of the two features
-N_T, K, P, BLOCKS, GINDEX, DTYPE = 4, 3, 3, [(0, 1), (1, 2), (3, 1)], [2, 2, 0], torch.float16
-ORDERS = {"consecutive": [0, 1, 2, 3], "by value": [3, 1, 0, 2]}
-TS = list(range(900, 900 - 200 * N_T, -200))
-META = dict(timesteps=TS, h=8, w=4, gh=8, gw=4, dtype=DTYPE, attn_fp8=False, f8_exp=(2, 2, 2), weights_id="w0")
 
 
 def _features(G, seed, feats=FEATS):
@@ -29,19 +24,6 @@ def _native(G, seed):
     from idm_vton_amd.garment_cache import GarmentCache
     g = torch.Generator().manual_seed(seed)
     return GarmentCache(G=G, kv=[(torch.randn(N_T * G * N, Cc, generator=g).to(DTYPE), torch.randn(N_T * G, Cc, N, generator=g).to(DTYPE)) for N, Cc in FEATS], **META)
-
-
-def _same(a, b):
-    assert (a.G, a.features, a.packed, a.timesteps, a.h, a.w, a.gh, a.gw, a.dtype, a.weights_id) == \
-           (b.G, b.features, b.packed, b.timesteps, b.h, b.w, b.gh, b.gw, b.dtype, b.weights_id)
-    assert len(a.kv) == len(b.kv)
-    for ea, eb in zip(a.kv, b.kv):
-        assert len(ea) == len(eb) == 1 and ea[0].dtype == eb[0].dtype and torch.equal(ea[0], eb[0])
-    if a.packed:
-        assert torch.equal(a.exps, b.exps)
-
-
-BOTH = pytest.mark.parametrize("packed", [False, True], ids=["16bit", "packed"])
 
 
 # ---- sizes -------------------------------------------------------------------------------------------------------------------------------
@@ -67,21 +49,21 @@ def test_nbytes_is_half_the_native_cache_and_a_quarter_packed():
 
 
 # ---- container operations -----------------------------------------------------------------------------------------------------------------
-@BOTH
+@PACKED
 def test_select_cat_put_take_to_round_trips_are_bit_equal(packed):
     mk = (lambda G, s: _features(G, s).pack()) if packed else _features
     pool = mk(3, 1)
     ones = [pool.take(g) for g in range(3)]
     assert all(o.G == 1 and o.features and o.packed == packed for o in ones)
     assert sum(o.nbytes for o in ones) == pool.nbytes
-    _same(type(pool).cat(ones), pool)
-    _same(pool.select([0, 1, 2]), pool)
+    same_features(type(pool).cat(ones), pool)
+    same_features(pool.select([0, 1, 2]), pool)
     sel = pool.select([2, 0, 2])
-    _same(sel.take(0), ones[2]); _same(sel.take(1), ones[0]); _same(sel.take(2), ones[2])
+    same_features(sel.take(0), ones[2]); same_features(sel.take(1), ones[0]); same_features(sel.take(2), ones[2])
     other = mk(1, 7)
     before = [e[0].data_ptr() for e in pool.kv]
     assert pool.put(1, other) is pool and [e[0].data_ptr() for e in pool.kv] == before     # in place
-    _same(pool.take(1), other); _same(pool.take(0), ones[0]); _same(pool.take(2), ones[2])
+    same_features(pool.take(1), other); same_features(pool.take(0), ones[0]); same_features(pool.take(2), ones[2])
     moved = pool.to("cpu", pin_memory=False)
     assert moved is pool
     d = pool.for_person_size(16, 16)
@@ -90,10 +72,10 @@ def test_select_cat_put_take_to_round_trips_are_bit_equal(packed):
     (f0,), (f1,) = pool.run(1, 2)
     assert f0.shape == (2 * 3 * 32, 64) and f0.data_ptr() == pool.kv[0][0][3 * 32:].data_ptr() and f1.shape == (2 * 3 * 16, 128)
     rp = ones[0].repeat_garments(2)
-    _same(rp.take(0), ones[0]); _same(rp.take(1), ones[0])
+    same_features(rp.take(0), ones[0]); same_features(rp.take(1), ones[0])
 
 
-@BOTH
+@PACKED
 def test_save_load_round_trip_writes_version_4(tmp_path, packed):
     from safetensors import safe_open
     from idm_vton_amd.garment_cache import GarmentCache
@@ -105,7 +87,7 @@ def test_save_load_round_trip_writes_version_4(tmp_path, packed):
         assert meta["version"] == 4 and meta["kind"] == "features" and meta.get("packed", False) == packed
         assert sorted(f.keys()) == sorted(["f.000", "f.001"] + (["exps"] if packed else []))
     back = GarmentCache.load(path)
-    _same(back, c)
+    same_features(back, c)
 
 
 def test_a_version_3_file_still_loads(tmp_path):
@@ -139,7 +121,7 @@ def test_mixing_kinds_is_refused_by_name():
     # the one exception, today's rule: a 16-bit feature garment put into a packed feature pool is packed first
     pool, g = _features(2, 2).pack(), _features(1, 9)
     pool.put(1, g)
-    _same(pool.take(1), g.pack())
+    same_features(pool.take(1), g.pack())
     # out of scope, each refused by name: slotted caches, mixed-size pools, shelves
     with pytest.raises(ValueError, match="features"):
         GarmentCache(G=1, kv=f.kv, features=True, sizes=[(8, 4)], **META)
@@ -154,7 +136,7 @@ def test_mixing_kinds_is_refused_by_name():
         GarmentCache(G=1, kv=f.kv, features=True, **dict(META, attn_fp8=True))
 
 
-@BOTH
+@PACKED
 @pytest.mark.parametrize("resident", ["device", "host"])
 def test_garment_pool_takes_a_feature_cache_as_like(packed, resident):
     from idm_vton_amd.garment_cache import GarmentPool
@@ -164,12 +146,12 @@ def test_garment_pool_takes_a_feature_cache_as_like(packed, resident):
     assert pool.cache.features and pool.cache.packed == packed and pool.cache.G == 2 and pool.cache.nbytes == 2 * made["a"].nbytes
     assert pool.get(["a", "b", "a"], encode=made.__getitem__) == [0, 1, 0]
     assert pool.get(["c", "b"], encode=made.__getitem__) == [0, 1]         # a, the least recently used, leaves (device: spilled to the host)
-    _same(pool.cache.take(0), made["c"]); _same(pool.cache.take(1), made["b"])
+    same_features(pool.cache.take(0), made["c"]); same_features(pool.cache.take(1), made["b"])
     if resident == "device":
         assert list(pool.host) == ["a"] and pool.host["a"].features
-        _same(pool.host["a"], made["a"])
+        same_features(pool.host["a"], made["a"])
         assert pool.get(["a", "c"]) == [1, 0] and pool.stats["restored"] == 1          # comes back without `encode`
-        _same(pool.cache.take(1), made["a"])
+        same_features(pool.cache.take(1), made["a"])
 
 
 # ---- pack / unpack ------------------------------------------------------------------------------------------------------------------------
@@ -193,8 +175,8 @@ def test_pack_and_unpack_are_the_formats_own_functions():
         assert b.dtype == torch.uint8 and torch.equal(b.view(N_T, G, -1), want_b)
         assert y.dtype == DTYPE and torch.equal(y.view(N_T, G, -1), unpack_values(want_b, e.view(1, G, 1), DTYPE))
     again = u.pack()                                        # idempotent on unpacked values
-    _same(again, p)
-    _same(again.unpack(), u)
+    same_features(again, p)
+    same_features(again.unpack(), u)
     with pytest.raises(ValueError, match="already"):
         p.pack()
 
@@ -207,37 +189,6 @@ CASES = [(False, "kernel", "device", None, None),
          (True, "kernel", "host", "KvStreamTable", "kv_stream"),
          (False, "copy", "host", "KvPlaceTable", "kv_place"),
          (True, "copy", "host", "KvPlaceTable", "kv_place")]
-
-
-class _Event:
-    def record(self, *a):
-        pass
-
-    def query(self):
-        return True
-
-
-def _standin_unet(calls):
-    """project_garment_kv as plain torch: K = F W_k^T, V^T = (F W_v^T)^T per batch element, rounded once -- one weight pair per feature, the
-    rows of `out` beyond the batch untouched (unet.project_garment_kv's contract).  Weights in {-1, 0, 1} and fp64 accumulation: every sum of
-    at most 128 fp16 values is then exact, so a row's result cannot depend on the batch it is computed in or on the matmul's blocking."""
-    g = torch.Generator().manual_seed(99)
-    W = [tuple(torch.randint(-1, 2, (Cc, Cc), generator=g).double() for _ in range(2)) for _, Cc in FEATS]
-
-    def project_garment_kv(feats, out=None):
-        calls.append([tuple(f.shape) for f in feats])
-        res = []
-        for i, (f, (wk, wv)) in enumerate(zip(feats, W)):
-            Bg, N, Cc = f.shape
-            k = (f.reshape(Bg * N, Cc).double() @ wk.t()).to(f.dtype)
-            vt = (f.double() @ wv.t()).transpose(1, 2).to(f.dtype)
-            if out is not None:
-                out[i][0][:Bg * N].copy_(k)
-                out[i][1][:Bg].copy_(vt)
-                k, vt = out[i][0][:Bg * N], out[i][1][:Bg]
-            res.append((k, vt))
-        return res
-    return types.SimpleNamespace(project_garment_kv=project_garment_kv, attn_fp8=False, f8_exp=(2, 2, 2))
 
 
 @pytest.mark.parametrize("indexed", [True, False], ids=["index", "noindex"])
@@ -266,7 +217,7 @@ def test_cached_fill_stages_the_features_and_projects_them(monkeypatch, packed, 
     monkeypatch.setattr(ops, "stream_address", lambda t: t.data_ptr())
     monkeypatch.setattr(ops, "_stream", lambda: 0)
     monkeypatch.setattr(ops, "PROFILE", None)
-    monkeypatch.setattr(torch.cuda, "Event", _Event)
+    monkeypatch.setattr(torch.cuda, "Event", Event)
     for name in ("KvUnpackTable", "KvStreamTable", "KvFillTable", "KvPlaceTable"):
         cls = getattr(ops, name)
         monkeypatch.setattr(ops, name, type(name, (cls,), {"__init__": lambda self, *a, _c=cls, _n=name, **kw: (made.append(_n), _c.__init__(self, *a, **kw))[1]}))
@@ -274,12 +225,12 @@ def test_cached_fill_stages_the_features_and_projects_them(monkeypatch, packed, 
 
     def launched(name, a, desc):
         launches.append((name, getattr(a, "workgroups", None)))
-        _apply(records(desc, a.n), packed, DTYPE)
+        apply_records(records(desc, a.n), packed, DTYPE)
     monkeypatch.setattr(ffi, "call_kv_unpack", lambda a, desc, stream: launched("kv_unpack", a, desc))
     for name in ("kv_stream", "kv_fill", "kv_place"):
         monkeypatch.setattr(ffi, "call_" + name, lambda a, desc, first, stream, name=name: launched(name, a, desc))
 
-    eng, ref_eng = [TryonEngine(_standin_unet(calls if i == 0 else []), None, None, dtype=DTYPE, device="cpu") for i in range(2)]
+    eng, ref_eng = [TryonEngine(standin_unet(calls if i == 0 else []), None, None, dtype=DTYPE, device="cpu") for i in range(2)]
     gindex = GINDEX if indexed else None
     S = P if indexed else G
     st = dict(B=P, h=8, w=4, gh=8, gw=4, k=K, steps_noise=None, gcache=cache, gidx=ORDERS[order], gindex=gindex, blocks=BLOCKS, host_transport=transport)

@@ -1,45 +1,17 @@
 """-m gpu: the FEATURE cache on the GPU.  encode_garment(storage="features") keeps GarmentNet's features F in place of their K / V^T; a
 call on it fills a staging list per block and projects it with the launches an uncached call makes, so EQUALITY (torch.equal) with the
 uncached call and with the K / V^T-cached call is the bar everywhere but the packed form's oracle test.  Tiny engines: latent 16x16, 3 steps
-(blocks of 1 and 2 timesteps), the helpers of tests/test_garment_cache_gpu.py and its neighbours."""
-import functools
-
+(blocks of 1 and 2 timesteps), the helpers of tests/engine_support.py."""
 import pytest
 import torch
 
-from tests.test_garment_cache_gpu import FORMS, _FakeCLIPVision, _garment_kw, _pair
-from tests.test_garment_index_gpu import _base
+from tests.engine_support import (DEV, base_call, boundary_inputs, boundary_pipeline, engine_inputs, engine_reference, garment_kw, inputs, ip_states, pair,
+                                  reference_draws, run_on, to_host)
+from tests.garment_support import DTYPES, FORMS, IDX, TRANSPORTS
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-DTYPES = pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
+
 STEPS, NBLOCKS = 3, 2
-IDX = [2, 0, 2, 1]
-TRANSPORTS = ("kernel", "copy")
-
-
-@functools.lru_cache(maxsize=None)
-def _model(dtype, fp8=False):
-    """One tiny model per storage dtype, shared by the tests of this file; nothing in it is changed by a call."""
-    from tests import parity_utils as pu
-    return pu.build("tiny", dtype, DEV, unet_kw=dict(attn_fp8=True) if fp8 else None)
-
-
-def _engine(dtype, B, steps=STEPS, fp8=False, H=128, W=128):
-    from idm_vton_amd.pipeline import TryonEngine
-    from tests import parity_utils as pu
-    m = _model(dtype, fp8)
-    return TryonEngine(*m["product"], dtype, DEV), pu.make_inputs(B, H, W, m["xd"], m["pooled"], m["enc_dim"], steps, dtype), m
-
-
-def _run(eng, base, cache, form, index=None, transport="kernel"):
-    return eng.denoise(eng.prepare(**{**base, "cloth": cache, "garment_index": index}), host_transport=transport, **FORMS[form]).clone()
-
-
-def _host(cache):
-    h = cache.to("cpu", pin_memory=True)
-    assert h.host_resident and h.features and all(t.is_pinned() for e in h.kv for t in e) and (not h.packed or h.exps.is_pinned())
-    return h
 
 
 def _kv_equal(a, b):
@@ -56,15 +28,15 @@ def _kv_equal(a, b):
 @DTYPES
 def test_feature_cached_call_equals_the_uncached_and_the_kv_cached_call(dtype, scheduler):
     """B = G = 2: the four execution forms and on_step.  No GarmentNet batch, one projection per block."""
-    eng, inp, _ = _engine(dtype, 2)
+    eng, inp, _ = engine_inputs(dtype, 2, STEPS)
     kw = dict(num_inference_steps=STEPS, guidance_scale=2.0, scheduler=scheduler, **inp)
-    feats = eng.encode_garment(num_inference_steps=STEPS, scheduler=scheduler, storage="features", **_garment_kw(inp))
-    native = eng.encode_garment(num_inference_steps=STEPS, scheduler=scheduler, **_garment_kw(inp))
+    feats = eng.encode_garment(num_inference_steps=STEPS, scheduler=scheduler, storage="features", **garment_kw(inp))
+    native = eng.encode_garment(num_inference_steps=STEPS, scheduler=scheduler, **garment_kw(inp))
     assert feats.features and not native.features and feats.G == 2 and 2 * feats.nbytes == native.nbytes
     assert len(eng._block_schedule(STEPS)[1]) == NBLOCKS
-    base = _base(inp, STEPS, scheduler)
+    base = base_call(inp, STEPS, scheduler)
     for form in FORMS:
-        # _pair's two calls, with the counters read around the feature-cached one (start latents and conditioning copied over: the person-side
+        # pair's two calls, with the counters read around the feature-cached one (start latents and conditioning copied over: the person-side
         # VAE encodes of a cached prepare() run at another encoder batch size, which is not what is under test)
         st = eng.prepare(**kw)
         st_f = eng.prepare(**{**base, "cloth": feats})
@@ -74,9 +46,9 @@ def test_feature_cached_call_equals_the_uncached_and_the_kv_cached_call(dtype, s
         b0, p0 = eng.stats["garment_batches"], eng.stats["garment_projections"]
         lat_f = eng.denoise(st_f, **FORMS[form]).clone()
         assert (eng.stats["garment_batches"], eng.stats["garment_projections"]) == (b0, p0 + NBLOCKS), form
-        lat_k = _run(eng, base, native, form)
+        lat_k = run_on(eng, base, native, form)
         b1, p1 = eng.stats["garment_batches"], eng.stats["garment_projections"]
-        lat_f2 = _run(eng, base, feats, form)                            # (through the state the K / V^T call left, where there is one)
+        lat_f2 = run_on(eng, base, feats, form)                            # (through the state the K / V^T call left, where there is one)
         assert (eng.stats["garment_batches"], eng.stats["garment_projections"]) == (b1, p1 + NBLOCKS), form
         print(f"{dtype} {scheduler} {form}: max|features - uncached| = {(lat_u - lat_f).abs().max().item():.3e}")
         assert torch.isfinite(lat_u).all() and torch.equal(lat_f, lat_u), (form, (lat_u - lat_f).abs().max().item())
@@ -87,9 +59,9 @@ def test_feature_cached_call_equals_the_uncached_and_the_kv_cached_call(dtype, s
 @pytest.mark.parametrize("G", [1, 2])
 @DTYPES
 def test_project_garment_gives_the_native_cache_bit_for_bit(dtype, G):
-    eng, inp, _ = _engine(dtype, 2)
-    feats = eng.encode_garment(num_inference_steps=STEPS, storage="features", **_garment_kw(inp, G))
-    native = eng.encode_garment(num_inference_steps=STEPS, **_garment_kw(inp, G))
+    eng, inp, _ = engine_inputs(dtype, 2, STEPS)
+    feats = eng.encode_garment(num_inference_steps=STEPS, storage="features", **garment_kw(inp, G))
+    native = eng.encode_garment(num_inference_steps=STEPS, **garment_kw(inp, G))
     p0 = eng.stats["garment_batches"]
     proj = eng.project_garment(feats)
     assert eng.stats["garment_batches"] == p0 and not proj.features and not proj.packed
@@ -104,12 +76,12 @@ def test_project_garment_gives_the_native_cache_bit_for_bit(dtype, G):
 
 # ---- 3 ------------------------------------------------------------------------------------------------------------------------------------
 def test_shared_segment_of_four_persons_on_two_feature_garments():
-    eng, inp, _ = _engine(torch.float16, 4)
-    feats = eng.encode_garment(num_inference_steps=STEPS, storage="features", **_garment_kw(inp, 2))
-    native = eng.encode_garment(num_inference_steps=STEPS, **_garment_kw(inp, 2))
-    base = _base(inp, STEPS)
+    eng, inp, _ = engine_inputs(torch.float16, 4, STEPS)
+    feats = eng.encode_garment(num_inference_steps=STEPS, storage="features", **garment_kw(inp, 2))
+    native = eng.encode_garment(num_inference_steps=STEPS, **garment_kw(inp, 2))
+    base = base_call(inp, STEPS)
     for form in FORMS:
-        lat_k, lat_f = _run(eng, base, native, form), _run(eng, base, feats, form)
+        lat_k, lat_f = run_on(eng, base, native, form), run_on(eng, base, feats, form)
         assert torch.isfinite(lat_k).all() and torch.equal(lat_f, lat_k), form
 
 
@@ -125,40 +97,40 @@ def test_indexed_call_on_a_pool_of_feature_garments(dtype):
     staging lists), against the call on cat of the three native G = 1 caches.  The projection then runs over M = c * 4 * N_f rows where
     the native garments were projected over c * N_f: equality rests on a GEMM row not depending on M, which is measured here, not implied."""
     from idm_vton_amd.garment_cache import GarmentCache
-    eng, inp, _ = _engine(dtype, 4)
+    eng, inp, _ = engine_inputs(dtype, 4, STEPS)
     pool, ref = GarmentCache.cat(_ones(eng, inp, "features")), GarmentCache.cat(_ones(eng, inp, "native"))
     assert pool.features and pool.G == 3 and 2 * pool.nbytes == ref.nbytes
-    base = _base(inp, STEPS)
+    base = base_call(inp, STEPS)
     for form in FORMS:
-        lat_k, lat_f = _run(eng, base, ref, form, IDX), _run(eng, base, pool, form, IDX)
+        lat_k, lat_f = run_on(eng, base, ref, form, IDX), run_on(eng, base, pool, form, IDX)
         print(f"{dtype} {form}: max|features - kv| = {(lat_k - lat_f).abs().max().item():.3e}")
         assert torch.isfinite(lat_k).all() and torch.equal(lat_f, lat_k), (form, (lat_k - lat_f).abs().max().item())
-    assert not torch.equal(_run(eng, base, pool, "serial_eager", [0, 0, 0, 0]), lat_k)     # the index is read
+    assert not torch.equal(run_on(eng, base, pool, "serial_eager", [0, 0, 0, 0]), lat_k)     # the index is read
 
 
 def test_one_graph_state_serves_two_indices_and_a_put_in_place():
     from idm_vton_amd.garment_cache import GarmentCache
-    eng, inp, _ = _engine(torch.float16, 4)
+    eng, inp, _ = engine_inputs(torch.float16, 4, STEPS)
     f_ones, k_ones = _ones(eng, inp, "features", (0, 1, 2, 3)), _ones(eng, inp, "native", (0, 1, 2, 3))
     pool, ref = GarmentCache.cat(f_ones[:3]), GarmentCache.cat(k_ones[:3])
     swapped = GarmentCache.cat([k_ones[0], k_ones[3], k_ones[2]])
-    base = _base(inp, STEPS)
+    base = base_call(inp, STEPS)
     a, b = [2, 0, 2, 1], [1, 1, 0, 2]
-    want = {(name, tuple(i)): _run(eng, base, c, "serial_eager", i) for name, c in (("before", ref), ("after", swapped)) for i in (a, b)}
+    want = {(name, tuple(i)): run_on(eng, base, c, "serial_eager", i) for name, c in (("before", ref), ("after", swapped)) for i in (a, b)}
     assert len({tuple(v.flatten().tolist()) for v in want.values()}) == 4
-    _run(eng, base, ref, "graph_overlap", a)                             # the state is captured on the K / V^T cache ...
+    run_on(eng, base, ref, "graph_overlap", a)                             # the state is captured on the K / V^T cache ...
     states, n_garm = len(eng._graphs), eng.stats["garment_batches"]
     captured = sum(len(g["graphs"]) for g in eng._graphs.values())
     for form in ("graph", "graph_overlap"):                              # ... and serves the feature pool
         for i in (a, b, a):
-            assert torch.equal(_run(eng, base, pool, form, i), want[("before", tuple(i))]), (form, i)
+            assert torch.equal(run_on(eng, base, pool, form, i), want[("before", tuple(i))]), (form, i)
     ptr = pool.kv[0][0].data_ptr()
     pool.put(1, f_ones[3])
     assert pool.kv[0][0].data_ptr() == ptr
     for form in ("graph", "graph_overlap", "serial_eager"):
         for i in (a, b):
-            assert torch.equal(_run(eng, base, pool, form, i), want[("after", tuple(i))]), (form, i)
-    assert torch.equal(_run(eng, base, swapped, "graph_overlap", b), want[("after", tuple(b))])      # and the reverse: K / V^T through it again
+            assert torch.equal(run_on(eng, base, pool, form, i), want[("after", tuple(i))]), (form, i)
+    assert torch.equal(run_on(eng, base, swapped, "graph_overlap", b), want[("after", tuple(b))])      # and the reverse: K / V^T through it again
     assert len(eng._graphs) == states == 1 and eng.stats["garment_batches"] == n_garm
     assert sum(len(g["graphs"]) for g in eng._graphs.values()) >= captured
 
@@ -170,13 +142,13 @@ def test_feature_cache_built_at_full_strength_serves_strength_0_6(dtype):
     uncached 0.6 call's own M, on features that GarmentNet made in batches of 1, 2, 4 timesteps -- a measured equality, like its precedent
     tests/test_garment_cache_gpu.py::test_cache_built_at_full_strength_serves_strength_0_6."""
     steps = 7
-    eng, inp, _ = _engine(dtype, 2, steps)
+    eng, inp, _ = engine_inputs(dtype, 2, steps)
     inp["noise"]["image"] = torch.randn(2, 4, 16, 16, generator=torch.Generator().manual_seed(77))
     inp["noise"]["steps"] = inp["noise"]["steps"][:4]
     kw = dict(num_inference_steps=steps, guidance_scale=2.0, scheduler="ddpm", strength=0.6, **inp)
-    feats = eng.encode_garment(num_inference_steps=steps, storage="features", **_garment_kw(inp))
+    feats = eng.encode_garment(num_inference_steps=steps, storage="features", **garment_kw(inp))
     for form in ("serial_eager", "graph_overlap"):
-        lat_u, lat_f = _pair(eng, kw, feats, form)
+        lat_u, lat_f = pair(eng, kw, feats, form)
         assert torch.isfinite(lat_u).all() and torch.equal(lat_u, lat_f), (form, (lat_u - lat_f).abs().max().item())
 
 
@@ -185,29 +157,28 @@ def test_feature_cache_built_at_full_strength_serves_strength_0_6(dtype):
 def test_a_garment_at_its_own_size(cloth):
     """A 128x128 person; 72x40 is the odd latent 9x5: 15 and 6 tokens in 16 rows (64x96: 24 in 32, and 6), so the features carry pad rows,
     whose filler is the live call's."""
-    from tests.test_garment_size_gpu import _inputs
     dtype = torch.float16
-    eng, _, m = _engine(dtype, 2)
-    inp = _inputs(m, 2, 128, 128, *cloth, STEPS, dtype)
+    eng, _, m = engine_inputs(dtype, 2, STEPS)
+    inp = inputs(m, 2, 128, 128, *cloth, STEPS, dtype)
     kw = dict(num_inference_steps=STEPS, guidance_scale=2.0, scheduler="ddpm", **inp)
-    feats = eng.encode_garment(num_inference_steps=STEPS, storage="features", height=128, width=128, **_garment_kw(inp))
+    feats = eng.encode_garment(num_inference_steps=STEPS, storage="features", height=128, width=128, **garment_kw(inp))
     assert (feats.h, feats.w, feats.gh, feats.gw) == (16, 16, cloth[0] // 8, cloth[1] // 8)
     tokens = eng.unet.feature_tokens(feats.gh, feats.gw)
     assert [e[0].shape[0] // (STEPS * 2) for e in feats.kv] == [(n + 15) // 16 * 16 for n in tokens]
     assert any(n % 16 for n in tokens)                                   # 24 and 6 tokens (8x12), 15 and 6 (9x5): pad rows either way
     for form in FORMS:
-        lat_u, lat_f = _pair(eng, kw, feats, form)
+        lat_u, lat_f = pair(eng, kw, feats, form)
         assert torch.isfinite(lat_u).all() and torch.equal(lat_u, lat_f), (form, (lat_u - lat_f).abs().max().item())
-    _kv_equal(eng.project_garment(feats), eng.encode_garment(num_inference_steps=STEPS, height=128, width=128, **_garment_kw(inp)))
+    _kv_equal(eng.project_garment(feats), eng.encode_garment(num_inference_steps=STEPS, height=128, width=128, **garment_kw(inp)))
 
 
 # ---- 7 ------------------------------------------------------------------------------------------------------------------------------------
 @DTYPES
 def test_packed_feature_call_equals_the_call_on_the_unpacked_cache(dtype):
     from idm_vton_amd.garment_cache import GarmentCache
-    eng, inp, _ = _engine(dtype, 4)
-    feats = eng.encode_garment(num_inference_steps=STEPS, storage="features", **_garment_kw(inp, 3))
-    packed = eng.encode_garment(num_inference_steps=STEPS, storage="features-e4m3", **_garment_kw(inp, 3))
+    eng, inp, _ = engine_inputs(dtype, 4, STEPS)
+    feats = eng.encode_garment(num_inference_steps=STEPS, storage="features", **garment_kw(inp, 3))
+    packed = eng.encode_garment(num_inference_steps=STEPS, storage="features-e4m3", **garment_kw(inp, 3))
     assert packed.features and packed.packed and tuple(packed.exps.shape) == (3, len(feats.kv), 1)
     assert packed.nbytes == feats.nbytes // 2 + 4 * 3 * len(feats.kv)
     again = feats.pack()
@@ -215,16 +186,16 @@ def test_packed_feature_call_equals_the_call_on_the_unpacked_cache(dtype):
     assert torch.equal(packed.exps, again.exps)
     unpacked = packed.unpack()
     assert unpacked.features and not unpacked.packed and not all(torch.equal(a[0], b[0]) for a, b in zip(unpacked.kv, feats.kv))   # lossy
-    base = _base(inp, STEPS)
+    base = base_call(inp, STEPS)
     two, two_u = packed.select([0, 1]), unpacked.select([0, 1])
     for form in FORMS:
         c0, p0 = eng.stats["garment_set_copies"], eng.stats["garment_projections"]
-        lat_p = _run(eng, base, packed, form, IDX)
+        lat_p = run_on(eng, base, packed, form, IDX)
         # one unpack launch and one projection per block (a graph state's first call adds its warm-up fill to garment_set_copies, as ever)
         assert eng.stats["garment_set_copies"] - c0 in (NBLOCKS, NBLOCKS + 1) and eng.stats["garment_projections"] - p0 == NBLOCKS, form
-        lat_u = _run(eng, base, unpacked, form, IDX)
+        lat_u = run_on(eng, base, unpacked, form, IDX)
         assert torch.isfinite(lat_u).all() and torch.equal(lat_p, lat_u), ("index", form)
-        lat_p, lat_u = _run(eng, base, two, form), _run(eng, base, two_u, form)              # P = 4 on G = 2, no index
+        lat_p, lat_u = run_on(eng, base, two, form), run_on(eng, base, two_u, form)              # P = 4 on G = 2, no index
         assert torch.isfinite(lat_u).all() and torch.equal(lat_p, lat_u), ("no index", form)
     _kv_equal(eng.project_garment(packed), eng.project_garment(unpacked))
     assert isinstance(again, GarmentCache)
@@ -236,17 +207,17 @@ def test_host_resident_feature_cache_equals_the_device_resident_call(packed):
     """Page-locked host memory, both transports, every form, with an index (P = 4 on G = 3) and without (P = 4 on G = 2): one
     idmvton_kv_stream launch per block ("kernel"), one idmvton_kv_place launch per block ("copy"), one projection per block either way."""
     dtype = torch.float16
-    eng, inp, _ = _engine(dtype, 4)
-    device = eng.encode_garment(num_inference_steps=STEPS, storage="features-e4m3" if packed else "features", **_garment_kw(inp, 3))
-    base = _base(inp, STEPS)
+    eng, inp, _ = engine_inputs(dtype, 4, STEPS)
+    device = eng.encode_garment(num_inference_steps=STEPS, storage="features-e4m3" if packed else "features", **garment_kw(inp, 3))
+    base = base_call(inp, STEPS)
     for dev_c, index in ((device, IDX), (device.select([0, 1]), None)):
-        host = _host(dev_c)
+        host = to_host(dev_c, features=True)
         for form in FORMS:
-            lat_d = _run(eng, base, dev_c, form, index)
+            lat_d = run_on(eng, base, dev_c, form, index)
             states = len(eng._graphs)
             for transport in TRANSPORTS:
                 s0 = dict(eng.stats)
-                lat_h = _run(eng, base, host, form, index, transport)
+                lat_h = run_on(eng, base, host, form, index, transport)
                 assert torch.isfinite(lat_d).all() and torch.equal(lat_h, lat_d), (form, transport, index, (lat_h - lat_d).abs().max().item())
                 delta = {key: eng.stats[key] - s0.get(key, 0) for key in eng.stats if key != "garment_stage_copies"}
                 assert delta == dict(garment_batches=0, garment_set_copies=0, garment_projections=NBLOCKS,
@@ -267,12 +238,12 @@ def test_refusals_come_before_anything_is_launched():
     from idm_vton_amd import ops
     from idm_vton_amd.garment_cache import GarmentPool, GarmentShelf
     dtype = torch.float16
-    eng, inp, _ = _engine(dtype, 2)
-    eng8, _, _ = _engine(dtype, 2, fp8=True)
-    feats = eng.encode_garment(num_inference_steps=STEPS, storage="features", **_garment_kw(inp, 1))
-    native = eng.encode_garment(num_inference_steps=STEPS, **_garment_kw(inp, 1))
+    eng, inp, _ = engine_inputs(dtype, 2, STEPS)
+    eng8, _, _ = engine_inputs(dtype, 2, STEPS, fp8=True)
+    feats = eng.encode_garment(num_inference_steps=STEPS, storage="features", **garment_kw(inp, 1))
+    native = eng.encode_garment(num_inference_steps=STEPS, **garment_kw(inp, 1))
     slotted = eng.empty_garment_cache(2, garment_height=128, garment_width=128, num_inference_steps=STEPS)
-    base = _base(inp, STEPS)
+    base = base_call(inp, STEPS)
     torch.cuda.synchronize()
     stats, stats8, launched = dict(eng.stats), dict(eng8.stats), []
     real = ops._call
@@ -280,7 +251,7 @@ def test_refusals_come_before_anything_is_launched():
     try:
         for storage in ("features", "features-e4m3"):                    # an attn_fp8 engine neither encodes ...
             with pytest.raises(ValueError, match="attn_fp8"):
-                eng8.encode_garment(num_inference_steps=STEPS, storage=storage, **_garment_kw(inp, 1))
+                eng8.encode_garment(num_inference_steps=STEPS, storage=storage, **garment_kw(inp, 1))
         with pytest.raises(ValueError, match="attn_fp8"):                # ... nor takes ...
             eng8.prepare(**{**base, "cloth": feats.repeat_garments(2)})
         with pytest.raises(ValueError, match="attn_fp8"):                # ... nor projects a feature cache
@@ -294,7 +265,7 @@ def test_refusals_come_before_anything_is_launched():
         with pytest.raises(ValueError, match="features"):                # kinds do not mix
             native.put(0, feats)
         with pytest.raises(ValueError, match="storage"):
-            eng.encode_garment(num_inference_steps=STEPS, storage="feature", **_garment_kw(inp, 1))
+            eng.encode_garment(num_inference_steps=STEPS, storage="feature", **garment_kw(inp, 1))
     finally:
         ops._call = real
     assert launched == [] and eng.stats == stats and eng8.stats == stats8 and not eng._graphs and not eng8._graphs
@@ -302,33 +273,10 @@ def test_refusals_come_before_anything_is_launched():
 
 # ---- 10 -----------------------------------------------------------------------------------------------------------------------------------
 def test_boundary_pipeline_encodes_and_takes_a_feature_cache():
-    from idm_vton_amd import config as pc
-    from idm_vton_amd.boundary.scheduler import DDPMScheduler
-    from idm_vton_amd.boundary.vae import AutoencoderKL
-    from src.tryon_pipeline import StableDiffusionXLInpaintPipeline
-    from src.unet_hacked_garmnet import UNet2DConditionModel as G
-    from src.unet_hacked_tryon import UNet2DConditionModel as T
-    from tests import parity_utils as pu
     DT = torch.float16
-    kw = dict(pu.TINY)
-    tcfg = pc.UNetConfig(mode="tryon", in_channels=13, sample_size=16, **kw)
-    gcfg = pc.UNetConfig(mode="garmnet", in_channels=4, addition_embed_type=None, encoder_hid_dim_type=None, sample_size=16, **kw)
-    vcfg = pc.VAEConfig(**pu.TINY_VAE)
-    rnd = lambda sd: {k: v.to(DT) for k, v in sd.items()}
-    t = T(tcfg, torch_dtype=DT); t.load_state_dict(rnd(pc.random_state_dict(pc.unet_param_shapes(tcfg), 1, torch.float32, "cpu")))
-    g = G(gcfg, torch_dtype=DT); g.load_state_dict(rnd(pc.random_state_dict(pc.unet_param_shapes(gcfg), 2, torch.float32, "cpu")))
-    v = AutoencoderKL(vcfg, torch_dtype=DT); v.load_state_dict(rnd(pc.random_state_dict(pc.vae_param_shapes(vcfg), 3, torch.float32, "cpu", std=0.05)))
-    torch.manual_seed(5)
-    enc = _FakeCLIPVision(kw["encoder_hid_dim"]).to(DT)
-    pipe = StableDiffusionXLInpaintPipeline(vae=v, text_encoder=None, text_encoder_2=None, tokenizer=None, tokenizer_2=None, unet=t,
-                                            unet_encoder=g, scheduler=DDPMScheduler(), image_encoder=enc).to(DEV)
+    pipe, enc, kw = boundary_pipeline(DT)
     B, H, W, steps = 2, 128, 128, STEPS
-    inp = pu.make_inputs(B, H, W, kw["cross_attention_dim"], 64, kw["encoder_hid_dim"], steps, DT)
-    clip_pix = torch.randn(B, 3, 224, 224, generator=torch.Generator().manual_seed(9))
-    call = dict(prompt_embeds=inp["prompt_embeds"], negative_prompt_embeds=inp["negative_prompt_embeds"],
-                pooled_prompt_embeds=inp["pooled_prompt_embeds"], negative_pooled_prompt_embeds=inp["negative_pooled_prompt_embeds"],
-                num_inference_steps=steps, strength=1.0, pose_img=inp["pose_img"], mask_image=inp["mask_image"], image=inp["image"],
-                height=H, width=W, guidance_scale=2.0, ip_adapter_image=clip_pix, output_type="pt")
+    inp, clip_pix, call = boundary_inputs(kw, B, H, W, steps, DT)
     feats = pipe.encode_garment(inp["cloth"], inp["text_embeds_cloth"], steps, H, W, generator=torch.Generator(DEV).manual_seed(11), storage="features")
     native = pipe.encode_garment(inp["cloth"], inp["text_embeds_cloth"], steps, H, W, generator=torch.Generator(DEV).manual_seed(11))
     assert feats.features and feats.G == B and 2 * feats.nbytes == native.nbytes
@@ -340,19 +288,9 @@ def test_boundary_pipeline_encodes_and_takes_a_feature_cache():
     img_c = pipe(generator=gen_c, cloth=feats, text_embeds_cloth=None, **call)[0]
     assert eng.stats["garment_batches"] == n_garm and eng.stats["garment_projections"] > n_proj
     # the engine-level call on the draws of the reference's order: the cloth draw is made and dropped
-    gen = torch.Generator(DEV).manual_seed(7)
-    torch.manual_seed(123)
-    draw = lambda gg, dt_: torch.randn((B, 4, H // 8, W // 8), generator=gg, device=DEV, dtype=dt_).float()
-    n_lat, n_masked, n_pose, _dropped = draw(gen, DT), draw(gen, torch.float32), draw(None, torch.float32), draw(gen, torch.float32)
-    n_steps = torch.stack([draw(gen, DT) for _ in range(steps)])
-    with torch.no_grad():
-        pos = enc(clip_pix.to(DEV, DT), output_hidden_states=True).hidden_states[-2]
-        neg = enc(torch.zeros_like(clip_pix).to(DEV, DT), output_hidden_states=True).hidden_states[-2]
-    ref = eng(image=inp["image"], mask_image=inp["mask_image"], pose_img=inp["pose_img"], cloth=native,
-              prompt_embeds=inp["prompt_embeds"], negative_prompt_embeds=inp["negative_prompt_embeds"],
-              pooled_prompt_embeds=inp["pooled_prompt_embeds"], negative_pooled_prompt_embeds=inp["negative_pooled_prompt_embeds"],
-              text_embeds_cloth=None, noise=dict(latents=n_lat, masked=n_masked, pose=n_pose, cloth=None, steps=n_steps),
-              num_inference_steps=steps, guidance_scale=2.0, ip_hidden_states=torch.cat([neg, pos]), scheduler="ddpm")
+    gen, noise = reference_draws(7, 123, B, H, W, steps, DT)
+    ip = ip_states(enc, clip_pix)
+    ref = engine_reference(eng, inp, noise, ip, steps, cloth=native)
     assert torch.isfinite(img_c).all() and torch.equal(img_c, ref)
     gen_u = torch.Generator(DEV).manual_seed(7)
     torch.manual_seed(123)
@@ -372,15 +310,15 @@ def test_packed_feature_call_against_the_oracle():
     from oracle import pipeline as opipe
     from oracle.scheduler import Scheduler
     from tests import parity_utils as pu
-    eng, inp, m = _engine(torch.float16, 2)
+    eng, inp, m = engine_inputs(torch.float16, 2, STEPS)
     o_t, o_g, o_v = m["oracle"]
     tr = {}
     opipe.run(o_t, o_g, o_v, Scheduler("ddpm"), num_inference_steps=STEPS, guidance_scale=2.0, trace=tr, **inp)
-    feats = eng.encode_garment(num_inference_steps=STEPS, storage="features", **_garment_kw(inp))
-    packed = eng.encode_garment(num_inference_steps=STEPS, storage="features-e4m3", **_garment_kw(inp))
-    base = _base(inp, STEPS)
+    feats = eng.encode_garment(num_inference_steps=STEPS, storage="features", **garment_kw(inp))
+    packed = eng.encode_garment(num_inference_steps=STEPS, storage="features-e4m3", **garment_kw(inp))
+    base = base_call(inp, STEPS)
     for form in ("serial_eager", "graph_overlap"):
-        lat_n, lat_p = _run(eng, base, feats, form), _run(eng, base, packed, form)
+        lat_n, lat_p = run_on(eng, base, feats, form), run_on(eng, base, packed, form)
         e_n, e_p = pu.relerr(lat_n, tr["step_latents"][-1]), pu.relerr(lat_p, tr["step_latents"][-1])
         print(f"{form}: latents against the oracle: packed features {e_p:.3e}, 16-bit features {e_n:.3e}")
         assert torch.isfinite(lat_p).all() and not torch.equal(lat_p, lat_n), form

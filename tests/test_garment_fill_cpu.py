@@ -1,17 +1,15 @@
 """TryonEngine._cached_fill on a CPU engine: for every kind of cache, the table class / entry point it selects and what the slice it launches
-for (bi, p) does to set p -- interpreted on CPU tensors by tests/test_garment_shelf_cpu.py's interpreter -- against _fill_set on the 16-bit
+for (bi, p) does to set p -- interpreted on CPU tensors by tests/garment_support.py's interpreter -- against _fill_set on the 16-bit
 cache that holds the same values.  No GPU: ops.stream_address is data_ptr, launches are recorded and interpreted instead of made."""
 import ctypes as C
 
 import pytest
 import torch
 
-from tests.test_garment_shelf_cpu import _apply
+from tests.garment_support import BLOCKS, DTYPE, FEATS, GINDEX, K, N_T, ORDERS, P, Event, apply_records
 
-FEATS = [(32, 64), (16, 128)]                            # (N_f, C_f) of the slot's two features; ld_f = N_f
 SMALL = [(16, 64), (16, 128)]                            # a compact garment: half the K rows / V^T positions of feature 0, so ONE zero tail
-N_T, K, P, BLOCKS, GINDEX, DTYPE = 4, 3, 3, [(0, 1), (1, 2), (3, 1)], [2, 2, 0], torch.float16
-ORDERS = {"consecutive": [0, 1, 2, 3], "by value": [3, 1, 0, 2]}
+
 #         kind     packed  transport resident  table class      entry point
 CASES = [("plain", False, "kernel", "device", None, None),
          ("plain", True, "kernel", "device", "KvUnpackTable", "kv_unpack"),
@@ -50,14 +48,6 @@ def _source(kind, packed):
     return cache, cache.slotted("cpu"), [[N for N, _ in f] for f in (SMALL, SMALL, FEATS)]
 
 
-class _Event:
-    def record(self, *a):
-        pass
-
-    def query(self):
-        return True
-
-
 @pytest.mark.parametrize("order", list(ORDERS), ids=list(ORDERS))
 @pytest.mark.parametrize("kind,packed,transport,resident,table,entry", CASES, ids=[f"{c[0]}-{'packed' if c[1] else '16bit'}-{c[3]}-{c[2]}" for c in CASES])
 def test_cached_fill_selects_the_table_and_fills_the_sets_as_fill_set_does(monkeypatch, kind, packed, transport, resident, table, entry, order):
@@ -78,7 +68,7 @@ def test_cached_fill_selects_the_table_and_fills_the_sets_as_fill_set_does(monke
     monkeypatch.setattr(ops, "stream_address", lambda t: t.data_ptr())
     monkeypatch.setattr(ops, "_stream", lambda: 0)
     monkeypatch.setattr(ops, "PROFILE", None)
-    monkeypatch.setattr(torch.cuda, "Event", _Event)
+    monkeypatch.setattr(torch.cuda, "Event", Event)
     for name in ("KvUnpackTable", "KvStreamTable", "KvFillTable", "KvPlaceTable"):
         cls = getattr(ops, name)
         monkeypatch.setattr(ops, name, type(name, (cls,), {"__init__": lambda self, *a, _c=cls, _n=name, **kw: (made.append(_n), _c.__init__(self, *a, **kw))[1]}))
@@ -86,7 +76,7 @@ def test_cached_fill_selects_the_table_and_fills_the_sets_as_fill_set_does(monke
 
     def launched(name, a, desc):                         # the launch, recorded and carried out on host memory
         launches.append((name, getattr(a, "workgroups", None)))
-        _apply(records(desc, a.n), packed, DTYPE)
+        apply_records(records(desc, a.n), packed, DTYPE)
     monkeypatch.setattr(ffi, "call_kv_unpack", lambda a, desc, stream: launched("kv_unpack", a, desc))
     for name in ("kv_stream", "kv_fill", "kv_place"):
         monkeypatch.setattr(ffi, "call_" + name, lambda a, desc, first, stream, name=name: launched(name, a, desc))

@@ -8,33 +8,22 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tests.test_garment_cache_gpu import FORMS, HEADS, SHAPES, TUNES, _engine, _f8_operands, _garment_kw, _self_attn_operands
+from tests.engine_support import (DEV, base_call, boundary_inputs, boundary_pipeline, engine_inputs, engine_reference, f8_operands, garment_kw, int_table,
+                                  ip_states, model, nan_out, reference_draws, run_on, self_attn_operands)
+from tests.garment_support import DTYPES, F8_SDPA_BAR, FORMS, HEADS, IDX, SHAPES, pool_cache, same_values
+from tests.kernel_checks import TUNES
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-DTYPES = pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
 
 # (P, G, index): P % G != 0 with a repeated value, not monotone; a pool larger than the batch; one garment for all
 PATTERNS = [(4, 3, [2, 0, 2, 1]), (2, 5, [4, 4]), (3, 1, [0, 0, 0])]
 # index = [i % G]: what the shared segment reads
 MODULO = [(4, 2, [0, 1, 0, 1]), (3, 1, [0, 0, 0]), (3, 3, [0, 1, 2])]
-# The fp8 kernel against fp32 SDPA on the unquantised operands.  kernel_checks.TOL is the 16-bit kernels' bar (2e-3 / 1.6e-2: one 16-bit rounding
-# of the output); e4m3 operands carry 3 mantissa bits (relative step 2^-3), so no fp8 launch can meet it.  This is the bar include/idmvton_hip.h
-# states for idmvton_attn_f8 and tests/kernel_checks.py holds check_attn_f8 to (its `attn_f8_*` entries), written once here.
-F8_SDPA_BAR = 1.2e-1
-
-
-def _table(idx):
-    return torch.tensor(idx, dtype=torch.int32, device=DEV)
-
-
-def _nan(B, Nq, Cc, dtype):
-    return torch.full((B, Nq, Cc), float("nan"), dtype=dtype, device=DEV)
 
 
 def _segments16(P, G, Nq, nkg, dtype, seed, pres):
     from idm_vton_amd import ops
-    q, k1, v1, k2, v2, ko = _self_attn_operands(P, G, Nq, nkg, dtype, seed)
+    q, k1, v1, k2, v2, ko = self_attn_operands(P, G, Nq, nkg, dtype, seed)
     qq = (q.float() * ops.QSCALE).to(dtype) if pres else q
     vt1, ld1 = ko(v1, Nq)
     vt2, ld2 = ko(v2, nkg)
@@ -54,8 +43,8 @@ def test_indexed_segment_equals_materialised_copies(tune, dtype):
         for P, G, idx in PATTERNS:
             B, Cc = 2 * P, HEADS * 64
             qq, own, garment, (k1, v1, k2, v2, vt2) = _segments16(P, G, Nq, nkg, dtype, 11 * P + G, pres)
-            o_i, o_m = _nan(B, Nq, Cc, dtype), _nan(B, Nq, Cc, dtype)
-            ops.attention(qq, o_i, [own, garment(k2, vt2, nb=G, index=_table(idx))], HEADS, tune=TUNES[tune], q_prescaled=pres)
+            o_i, o_m = nan_out(B, Nq, Cc, dtype), nan_out(B, Nq, Cc, dtype)
+            ops.attention(qq, o_i, [own, garment(k2, vt2, nb=G, index=int_table(idx))], HEADS, tune=TUNES[tune], q_prescaled=pres)
             ops.attention(qq, o_m, [own, garment(k2[idx].contiguous(), vt2[idx].contiguous())], HEADS, tune=TUNES[tune], q_prescaled=pres)
             assert torch.isfinite(o_m).all(), (tune, Nq, nkg, idx)
             assert torch.equal(o_i, o_m), (tune, Nq, nkg, P, G, idx, (o_i.float() - o_m.float()).abs().max().item())
@@ -79,14 +68,14 @@ def test_the_modulo_table_equals_the_shared_segment(tune, dtype):
     for P, G, idx in MODULO:
         B, Cc = 2 * P, HEADS * 64
         qq, own, garment, (_, _, k2, _, vt2) = _segments16(P, G, Nq, nkg, dtype, 13 * P + G, pres)
-        o_i, o_s = _nan(B, Nq, Cc, dtype), _nan(B, Nq, Cc, dtype)
-        ops.attention(qq, o_i, [own, garment(k2, vt2, nb=G, index=_table(idx))], HEADS, tune=TUNES[tune], q_prescaled=pres)
+        o_i, o_s = nan_out(B, Nq, Cc, dtype), nan_out(B, Nq, Cc, dtype)
+        ops.attention(qq, o_i, [own, garment(k2, vt2, nb=G, index=int_table(idx))], HEADS, tune=TUNES[tune], q_prescaled=pres)
         ops.attention(qq, o_s, [own, garment(k2, vt2, nb=G if G < P else 0)], HEADS, tune=TUNES[tune], q_prescaled=pres)
         assert torch.isfinite(o_s).all() and torch.equal(o_i, o_s), (tune, P, G)
 
 
 def _segments8(P, G, Nq, nkg, dtype, seed):
-    q8, (k8a, vt8a), (k8b, vt8b) = _f8_operands(P, G, Nq, nkg, dtype, seed)
+    q8, (k8a, vt8a), (k8b, vt8b) = f8_operands(P, G, Nq, nkg, dtype, seed)
     Cc, ld = HEADS * 64, vt8b.shape[1]
     own = dict(k8=k8a, vt8=vt8a, nk=Nq, ldk=Cc, ldvt=vt8a.shape[1])
     garment = lambda kk, vv, **kw: dict(k8=kk, vt8=vv, nk=nkg, ldk=Cc, ldvt=ld, b0=P, **kw)
@@ -103,19 +92,19 @@ def test_indexed_segment_equals_materialised_copies_fp8(dtype):
             q8, own, garment, k8b, vt8b = _segments8(P, G, Nq, nkg, dtype, 5 * P + G)
             ld = vt8b.shape[1]
             kw = dict(qk_scale_exp=-4, v_scale_exp=-2, B=B, Nq=Nq, ldq=Cc, ldo=Cc)
-            o_i, o_m = _nan(B, Nq, Cc, dtype), _nan(B, Nq, Cc, dtype)
-            ops.attention_f8(q8, o_i, [own, garment(k8b, vt8b, nb=G, index=_table(idx))], HEADS, **kw)
+            o_i, o_m = nan_out(B, Nq, Cc, dtype), nan_out(B, Nq, Cc, dtype)
+            ops.attention_f8(q8, o_i, [own, garment(k8b, vt8b, nb=G, index=int_table(idx))], HEADS, **kw)
             k_m = k8b.view(G, nkg * Cc)[idx].reshape(P * nkg, Cc).contiguous()
             vt_m = vt8b.view(G, Cc * ld)[idx].reshape(P * Cc, ld).contiguous()
             ops.attention_f8(q8, o_m, [own, garment(k_m, vt_m)], HEADS, **kw)
             assert torch.isfinite(o_m).all() and torch.equal(o_i, o_m), (Nq, nkg, P, G, idx)
             if (P, G, idx) in MODULO:                    # ... and the shared segment's bits
-                o_s = _nan(B, Nq, Cc, dtype)
+                o_s = nan_out(B, Nq, Cc, dtype)
                 ops.attention_f8(q8, o_s, [own, garment(k8b, vt8b, nb=G if G < P else 0)], HEADS, **kw)
                 assert torch.equal(o_i, o_s), (Nq, nkg, P, G)
             if (P, G) == (2, 5):
                 # attention, not merely equal: held to F8_SDPA_BAR (see there why not KTOL)
-                q, k1, v1, k2, v2, _ = _self_attn_operands(P, G, Nq, nkg, dtype, 5 * P + G)
+                q, k1, v1, k2, v2, _ = self_attn_operands(P, G, Nq, nkg, dtype, 5 * P + G)
                 sp = lambda t: t.float().view(t.shape[0], t.shape[1], HEADS, 64).transpose(1, 2)
                 z = torch.zeros(P, HEADS, nkg, 64, device=DEV)
                 kk = torch.cat([sp(k1), torch.cat([z, sp(k2[idx])])], dim=2)
@@ -145,11 +134,11 @@ def test_null_tables_are_the_shared_rule_and_bad_combinations_are_refused(dtype,
         for nb in (G, 0):
             gk, gv = (k2, vt2) if nb else (k2.repeat(2, 1, 1).contiguous(), vt2.repeat(2, 1, 1).contiguous())
             for name, tune in TUNES.items():
-                o = _nan(B, Nq, Cc, dtype)
+                o = nan_out(B, Nq, Cc, dtype)
                 ops.attention(qq, o, [own, garment(gk, gv, nb=nb)], HEADS, tune=tune, q_prescaled=True)
                 outs[(form, nb, name)] = o
             g8k, g8v = (k8b, vt8b) if nb else (k8b.repeat(2, 1).contiguous(), vt8b.repeat(2, 1).contiguous())
-            o = _nan(B, Nq, Cc, dtype)
+            o = nan_out(B, Nq, Cc, dtype)
             ops.attention_f8(q8, o, [own8, garment8(g8k, g8v, nb=nb)], HEADS, **kw8)
             outs[(form, nb, "f8")] = o
         assert len(calls) == (0 if form == "shared" else 2 * (len(TUNES) + 1))
@@ -159,12 +148,12 @@ def test_null_tables_are_the_shared_rule_and_bad_combinations_are_refused(dtype,
             assert torch.isfinite(outs[("shared", nb, name)]).all() and torch.equal(outs[("shared", nb, name)], outs[("null_tables", nb, name)]), (nb, name)
     monkeypatch.undo()
     # refusals: nothing is launched, so the output keeps its NaN fill
-    o = _nan(B, Nq, Cc, dtype)
-    t = _table([0, 1, 0, 1])
+    o = nan_out(B, Nq, Cc, dtype)
+    t = int_table([0, 1, 0, 1])
     with pytest.raises(ValueError, match="needs nb="):
         ops.attention(qq, o, [own, garment(k2, vt2, index=t)], HEADS, q_prescaled=True)
     with pytest.raises(ValueError, match="int32 device tensor of B - b0 = 4 entries"):
-        ops.attention(qq, o, [own, garment(k2, vt2, nb=G, index=_table([0, 1]))], HEADS, q_prescaled=True)
+        ops.attention(qq, o, [own, garment(k2, vt2, nb=G, index=int_table([0, 1]))], HEADS, q_prescaled=True)
     monkeypatch.setattr(ops, "_seg_nb", lambda segs: [0, 0])                               # past the host op's own check: the C entry points'
     with pytest.raises(RuntimeError, match=r"idmvton_attn_fwd_indexed failed \(-1\).*needs seg_nb >= 1 \(0\)"):
         ops.attention(qq, o, [own, garment(k2, vt2, nb=G, index=t)], HEADS, q_prescaled=True)
@@ -174,21 +163,12 @@ def test_null_tables_are_the_shared_rule_and_bad_combinations_are_refused(dtype,
     q2 = qq[:, :, :Cc].contiguous()
     ctx = dict(k=k2.repeat(4, 1, 1).contiguous(), vt=vt2.repeat(4, 1, 1).contiguous(), nk=nkg, ldk=Cc, ldvt=vt2.shape[-1])
     with pytest.raises(RuntimeError, match=r"idmvton_attn_fwd_indexed failed \(-5\).*CROSS mode takes no table"):
-        ops.attention(q2, o, [ctx, dict(ctx, nb=1, index=_table(list(range(B))))], HEADS, mode=ffi.ATTN_CROSS)
+        ops.attention(q2, o, [ctx, dict(ctx, nb=1, index=int_table(list(range(B))))], HEADS, mode=ffi.ATTN_CROSS)
     torch.cuda.synchronize()
     assert torch.isnan(o).all()
 
 
 # ------------------------------------------------------------------------------------------------------------------ engine
-def _base(inp, steps, scheduler="ddpm"):
-    return dict(num_inference_steps=steps, guidance_scale=2.0, scheduler=scheduler, **{**inp, "text_embeds_cloth": None, "noise": {**inp["noise"], "cloth": None}})
-
-
-def _run(eng, base, cache, form, index=None):
-    return eng.denoise(eng.prepare(**{**base, "cloth": cache, "garment_index": index}), **FORMS[form]).clone()
-
-
-IDX = [2, 0, 2, 1]
 
 
 @pytest.mark.parametrize("scheduler", ["ddpm", "ddim"])
@@ -197,41 +177,41 @@ def test_indexed_call_equals_the_call_on_the_selected_cache(dtype, scheduler):
     """P = 4 persons on a G = 3 cache, garment_index = [2, 0, 2, 1], 4 steps (blocks of 1, 2, 1 timesteps), against the same call on
     cache.select([2, 0, 2, 1]) (G = P, no index): every execution form, and under on_step."""
     steps = 4
-    eng, inp, _ = _engine(dtype, 4, steps)
-    cache = eng.encode_garment(num_inference_steps=steps, scheduler=scheduler, **_garment_kw(inp, 3))
+    eng, inp, _ = engine_inputs(dtype, 4, steps)
+    cache = eng.encode_garment(num_inference_steps=steps, scheduler=scheduler, **garment_kw(inp, 3))
     sel = cache.select(IDX)
     assert (cache.G, sel.G) == (3, 4)
-    base = _base(inp, steps, scheduler)
+    base = base_call(inp, steps, scheduler)
     for form in FORMS:
-        lat_i, lat_s = _run(eng, base, cache, form, IDX), _run(eng, base, sel, form)
+        lat_i, lat_s = run_on(eng, base, cache, form, IDX), run_on(eng, base, sel, form)
         print(f"{dtype} {scheduler} {form}: max|indexed - selected| = {(lat_i - lat_s).abs().max().item():.3e}")
         assert torch.isfinite(lat_s).all() and torch.equal(lat_i, lat_s), (form, (lat_i - lat_s).abs().max().item())
     # and the index is read: another assignment gives other latents
-    assert not torch.equal(_run(eng, base, cache, "serial_eager", [0, 0, 0, 0]), lat_s)
+    assert not torch.equal(run_on(eng, base, cache, "serial_eager", [0, 0, 0, 0]), lat_s)
 
 
 def test_indexed_call_equals_the_selected_cache_with_fp8_attention():
     steps = 3
-    eng, inp, _ = _engine(torch.float16, 4, steps, unet_kw=dict(attn_fp8=True))
-    cache = eng.encode_garment(num_inference_steps=steps, **_garment_kw(inp, 3))
+    eng, inp, _ = engine_inputs(torch.float16, 4, steps, fp8=True)
+    cache = eng.encode_garment(num_inference_steps=steps, **garment_kw(inp, 3))
     assert cache.attn_fp8 and {k.dtype for k, _ in cache.kv} == {torch.uint8, torch.float16}    # both routes: e4m3 from the projection, quantised per launch
-    sel, base = cache.select(IDX), _base(inp, steps)
+    sel, base = cache.select(IDX), base_call(inp, steps)
     for form in FORMS:
-        lat_i, lat_s = _run(eng, base, cache, form, IDX), _run(eng, base, sel, form)
+        lat_i, lat_s = run_on(eng, base, cache, form, IDX), run_on(eng, base, sel, form)
         assert torch.isfinite(lat_s).all() and torch.equal(lat_i, lat_s), form
 
 
 def test_indexed_call_equals_the_selected_cache_with_a_garment_of_another_size():
     """Person 128x128, cloth 64x96: the garment segment has its own token count at both levels."""
     steps = 3
-    eng, inp, _ = _engine(torch.float16, 4, steps)
+    eng, inp, _ = engine_inputs(torch.float16, 4, steps)
     g = torch.Generator().manual_seed(21)
     cloth, nz = torch.randn(3, 3, 64, 96, generator=g).clamp(-1, 1), torch.randn(3, 4, 8, 12, generator=g)
     cache = eng.encode_garment(cloth=cloth, text_embeds_cloth=inp["text_embeds_cloth"][:3], noise_cloth=nz, num_inference_steps=steps, height=128, width=128)
     assert (cache.gh, cache.gw, cache.h, cache.w) == (8, 12, 16, 16)
-    sel, base = cache.select(IDX), _base(inp, steps)
+    sel, base = cache.select(IDX), base_call(inp, steps)
     for form in FORMS:
-        lat_i, lat_s = _run(eng, base, cache, form, IDX), _run(eng, base, sel, form)
+        lat_i, lat_s = run_on(eng, base, cache, form, IDX), run_on(eng, base, sel, form)
         assert torch.isfinite(lat_s).all() and torch.equal(lat_i, lat_s), form
 
 
@@ -239,7 +219,7 @@ def test_unet_forward_takes_the_table_on_the_garment_feats_route():
     """HipUNet.forward(garment_feats=..., garment_index=...): the per-launch projection route of _block, against the features gathered by hand."""
     from tests import parity_utils as pu
     dtype, P, G = torch.float16, 3, 2
-    m = pu.build("tiny", dtype, DEV)
+    m = model(dtype)
     t, g = m["product"][0], m["product"][1]
     inp = pu.make_inputs(P, 128, 128, m["xd"], m["pooled"], m["enc_dim"], 1, dtype)
     h = w = 16
@@ -255,7 +235,7 @@ def test_unet_forward_takes_the_table_on_the_garment_feats_route():
     ctx = t.encode_context(pe, m["product"][3](inp["ip_hidden_states"].to(DEV)))
     temb = t.time_embeddings([500], 2 * P, dict(text_embeds=add, time_ids=ids))[0]
     idx = [1, 0, 1]
-    e_i, _ = t.forward(x, temb, ctx, 2 * P, h, w, garment_feats=feats, garment_index=_table(idx))
+    e_i, _ = t.forward(x, temb, ctx, 2 * P, h, w, garment_feats=feats, garment_index=int_table(idx))
     e_m, _ = t.forward(x, temb, ctx, 2 * P, h, w, garment_feats=[f[idx].contiguous() for f in feats])
     assert torch.isfinite(e_m).all() and torch.equal(e_i, e_m)
 
@@ -265,35 +245,35 @@ def test_two_graph_calls_with_different_indices_and_a_garment_swapped_in_place()
     capture would repeat the first), also after cache.put(1, other) between them -- with no GarmentNet batch and no new graph state."""
     from idm_vton_amd.garment_cache import GarmentCache
     steps = 3
-    eng, inp, _ = _engine(torch.float16, 4, steps)
-    cache = eng.encode_garment(num_inference_steps=steps, **_garment_kw(inp, 3))
+    eng, inp, _ = engine_inputs(torch.float16, 4, steps)
+    cache = eng.encode_garment(num_inference_steps=steps, **garment_kw(inp, 3))
     other = eng.encode_garment(num_inference_steps=steps, cloth=inp["cloth"][3:], text_embeds_cloth=inp["text_embeds_cloth"][3:], noise_cloth=inp["noise"]["cloth"][3:])
     swapped = GarmentCache.cat([cache.select([0]), other, cache.select([2])])                # what the pool holds after the put, built apart from it
-    base = _base(inp, steps)
+    base = base_call(inp, steps)
     a, b = [2, 0, 2, 1], [1, 1, 0, 2]
-    ref = {(name, tuple(i)): _run(eng, base, c.select(i), "serial_eager") for name, c in (("before", cache), ("after", swapped)) for i in (a, b)}
+    ref = {(name, tuple(i)): run_on(eng, base, c.select(i), "serial_eager") for name, c in (("before", cache), ("after", swapped)) for i in (a, b)}
     assert len({tuple(v.flatten().tolist()) for v in ref.values()}) == 4                    # four different results to tell apart
     n_garm = eng.stats["garment_batches"]
     for form in ("graph", "graph_overlap"):
         for i in (a, b, a):
-            assert torch.equal(_run(eng, base, cache, form, i), ref[("before", tuple(i))]), (form, i)
+            assert torch.equal(run_on(eng, base, cache, form, i), ref[("before", tuple(i))]), (form, i)
     states = len(eng._graphs)
     ptr = cache.kv[0][0].data_ptr()
     cache.put(1, other)
     assert cache.kv[0][0].data_ptr() == ptr
     for form in ("graph", "graph_overlap", "serial_eager"):
         for i in (a, b):
-            assert torch.equal(_run(eng, base, cache, form, i), ref[("after", tuple(i))]), (form, i)
+            assert torch.equal(run_on(eng, base, cache, form, i), ref[("after", tuple(i))]), (form, i)
     assert eng.stats["garment_batches"] == n_garm and len(eng._graphs) == states
 
 
 def test_modulo_index_equals_the_call_without_an_index():
     steps = 3
-    eng, inp, _ = _engine(torch.bfloat16, 4, steps)
-    cache = eng.encode_garment(num_inference_steps=steps, **_garment_kw(inp, 2))
-    base = _base(inp, steps)
+    eng, inp, _ = engine_inputs(torch.bfloat16, 4, steps)
+    cache = eng.encode_garment(num_inference_steps=steps, **garment_kw(inp, 2))
+    base = base_call(inp, steps)
     for form in ("serial_eager", "graph_overlap"):
-        lat_i, lat_n = _run(eng, base, cache, form, [0, 1, 0, 1]), _run(eng, base, cache, form)
+        lat_i, lat_n = run_on(eng, base, cache, form, [0, 1, 0, 1]), run_on(eng, base, cache, form)
         assert torch.isfinite(lat_n).all() and torch.equal(lat_i, lat_n), form
 
 
@@ -301,12 +281,12 @@ def test_a_pool_larger_than_the_batch_fills_person_sized_sets():
     """G = 6 garments resident, P = 2 persons, graph form: the persistent sets have 2 slots per timestep, not 6, one fill per block, and
     pools of other sizes run through the same graph state."""
     steps = 3
-    eng, inp, _ = _engine(torch.float16, 2, steps)
-    cache2 = eng.encode_garment(num_inference_steps=steps, **_garment_kw(inp))
+    eng, inp, _ = engine_inputs(torch.float16, 2, steps)
+    cache2 = eng.encode_garment(num_inference_steps=steps, **garment_kw(inp))
     pool = cache2.repeat_garments(3)                                                       # g0 g1 g0 g1 g0 g1
     assert pool.G == 6
-    base = _base(inp, steps)
-    ref = _run(eng, base, pool.select([5, 2]), "serial_eager")
+    base = base_call(inp, steps)
+    ref = run_on(eng, base, pool.select([5, 2]), "serial_eager")
     n0 = eng.stats["garment_set_copies"]
     st = eng.prepare(**{**base, "cloth": pool, "garment_index": [5, 2]})
     lat = eng.denoise(st, **FORMS["graph_overlap"]).clone()
@@ -321,18 +301,13 @@ def test_a_pool_larger_than_the_batch_fills_person_sized_sets():
             N = pk.shape[0] // (steps * 6)
             assert vt.shape[0] == st["k"] * 2 and k.shape[0] == st["k"] * 2 * N, (tuple(k.shape), tuple(vt.shape))
     # the same state serves the 2-garment cache and another assignment; both persons on one garment use one slot
-    assert torch.equal(_run(eng, base, cache2, "graph_overlap", [1, 0]), ref)
-    assert torch.equal(_run(eng, base, pool, "graph_overlap", [3, 3]), _run(eng, base, pool.select([3, 3]), "serial_eager"))
+    assert torch.equal(run_on(eng, base, cache2, "graph_overlap", [1, 0]), ref)
+    assert torch.equal(run_on(eng, base, pool, "graph_overlap", [3, 3]), run_on(eng, base, pool.select([3, 3]), "serial_eager"))
     assert tuple(state["gix"].tolist()) == (0, 0) and [k for k in eng._graphs if "indexed" in k] == keys
 
 
 def _device_cache(G, seed, dtype=torch.float16):
-    from tests.test_garment_pool_cpu import _cache
-    return _cache(G=G, seed=seed, dtype=dtype).to(DEV)
-
-
-def _same(a, b):
-    return len(a.kv) == len(b.kv) and all(torch.equal(ka.cpu(), kb.cpu()) and torch.equal(va.cpu(), vb.cpu()) for (ka, va), (kb, vb) in zip(a.kv, b.kv))
+    return pool_cache(G=G, seed=seed, dtype=dtype).to(DEV)
 
 
 def test_host_offload_and_return_are_bit_equal_and_complete_on_return():
@@ -347,20 +322,20 @@ def test_host_offload_and_return_are_bit_equal_and_complete_on_return():
     host = big.to("cpu")                                                                   # unpinned: read immediately, no synchronize
     assert all(not k.is_cuda and torch.equal(k, rk.cpu()) and torch.equal(vt, rvt.cpu()) for (k, vt), (rk, rvt) in zip(host.kv, ref))
     pinned = big.to("cpu", pin_memory=True)
-    assert all(k.is_pinned() and vt.is_pinned() for k, vt in pinned.kv) and _same(pinned, host)
+    assert all(k.is_pinned() and vt.is_pinned() for k, vt in pinned.kv) and same_values(pinned, host)
     for src in (host, pinned):
         back = src.to(DEV)
-        assert all(k.is_cuda for k, _ in back.kv) and _same(back, big)
+        assert all(k.is_cuda for k, _ in back.kv) and same_values(back, big)
     one = big.take(5, "cpu", pin_memory=True)
-    assert one.G == 1 and all(k.is_pinned() for k, _ in one.kv) and _same(one, host.select([5]))
+    assert one.G == 1 and all(k.is_pinned() for k, _ in one.kv) and same_values(one, host.select([5]))
     other = _device_cache(32, 77)
     other.put(9, one)                                                                      # pinned host -> one slot of a device cache
-    assert _same(other.select([9]), one) and _same(other.select([8, 10]), _device_cache(32, 77).select([8, 10]))
+    assert same_values(other.select([9]), one) and same_values(other.select([8, 10]), _device_cache(32, 77).select([8, 10]))
     with tempfile.TemporaryDirectory() as d:
         path = os.path.join(d, "pool.safetensors")
         big.save(path)
         loaded = GarmentCache.load(path, device=DEV)
-        assert all(k.is_cuda for k, _ in loaded.kv) and _same(loaded, big) and (loaded.G, loaded.timesteps, loaded.weights_id) == (32, big.timesteps, "w0")
+        assert all(k.is_cuda for k, _ in loaded.kv) and same_values(loaded, big) and (loaded.G, loaded.timesteps, loaded.weights_id) == (32, big.timesteps, "w0")
 
 
 def test_pool_on_the_device_spills_to_pinned_host_memory_and_restores():
@@ -372,19 +347,19 @@ def test_pool_on_the_device_spills_to_pinned_host_memory_and_restores():
     ptr = pool.cache.kv[0][0].data_ptr()
     assert pool.get([1, 2, 1], encode) == [0, 1, 0]
     assert pool.get([3, 2], encode) == [0, 1] and list(pool.host) == [1] and all(k.is_pinned() for k, _ in pool.host[1].kv)
-    assert _same(pool.host[1], truth[1])
+    assert same_values(pool.host[1], truth[1])
     assert pool.get([1, 4], encode) == [0, 1] and made == [1, 2, 3, 4]                     # 1 came back from the host: not encoded again
     assert list(pool.host) == [3, 2] and pool.stats == dict(hits=1, encoded=4, restored=1, evicted=3)   # bound 2: 1's copy, the oldest, was dropped
     for key, slot in pool.slots().items():
-        assert _same(pool.cache.select([slot]), truth[key]), key
+        assert same_values(pool.cache.select([slot]), truth[key]), key
     assert pool.cache.kv[0][0].data_ptr() == ptr and pool.cache.kv[0][0].is_cuda
 
 
 def test_a_bad_index_is_refused_before_anything_is_launched():
     steps = 3
-    eng, inp, _ = _engine(torch.float16, 4, steps)
-    cache = eng.encode_garment(num_inference_steps=steps, **_garment_kw(inp, 3))
-    base = _base(inp, steps)
+    eng, inp, _ = engine_inputs(torch.float16, 4, steps)
+    cache = eng.encode_garment(num_inference_steps=steps, **garment_kw(inp, 3))
+    base = base_call(inp, steps)
     eng.denoise(eng.prepare(**{**base, "cloth": cache, "garment_index": IDX}), **FORMS["graph"])
     torch.cuda.synchronize()
     stats, graphs = dict(eng.stats), len(eng._graphs)
@@ -408,34 +383,10 @@ def test_a_bad_index_is_refused_before_anything_is_launched():
 
 # ------------------------------------------------------------------------------------------------------------------ boundary
 def test_boundary_pipeline_passes_the_index_to_the_engine():
-    from idm_vton_amd import config as pc
-    from idm_vton_amd.boundary.scheduler import DDPMScheduler
-    from idm_vton_amd.boundary.vae import AutoencoderKL
-    from src.tryon_pipeline import StableDiffusionXLInpaintPipeline
-    from src.unet_hacked_garmnet import UNet2DConditionModel as G
-    from src.unet_hacked_tryon import UNet2DConditionModel as T
-    from tests import parity_utils as pu
-    from tests.test_garment_cache_gpu import _FakeCLIPVision
     DT = torch.float16
-    kw = dict(pu.TINY)
-    tcfg = pc.UNetConfig(mode="tryon", in_channels=13, sample_size=16, **kw)
-    gcfg = pc.UNetConfig(mode="garmnet", in_channels=4, addition_embed_type=None, encoder_hid_dim_type=None, sample_size=16, **kw)
-    vcfg = pc.VAEConfig(**pu.TINY_VAE)
-    rnd = lambda sd: {k: v.to(DT) for k, v in sd.items()}
-    t = T(tcfg, torch_dtype=DT); t.load_state_dict(rnd(pc.random_state_dict(pc.unet_param_shapes(tcfg), 1, torch.float32, "cpu")))
-    g = G(gcfg, torch_dtype=DT); g.load_state_dict(rnd(pc.random_state_dict(pc.unet_param_shapes(gcfg), 2, torch.float32, "cpu")))
-    v = AutoencoderKL(vcfg, torch_dtype=DT); v.load_state_dict(rnd(pc.random_state_dict(pc.vae_param_shapes(vcfg), 3, torch.float32, "cpu", std=0.05)))
-    torch.manual_seed(5)
-    enc = _FakeCLIPVision(kw["encoder_hid_dim"]).to(DT)
-    pipe = StableDiffusionXLInpaintPipeline(vae=v, text_encoder=None, text_encoder_2=None, tokenizer=None, tokenizer_2=None, unet=t,
-                                            unet_encoder=g, scheduler=DDPMScheduler(), image_encoder=enc).to(DEV)
+    pipe, enc, kw = boundary_pipeline(DT)
     B, H, W, steps = 3, 128, 128, 3
-    inp = pu.make_inputs(B, H, W, kw["cross_attention_dim"], 64, kw["encoder_hid_dim"], steps, DT)
-    clip_pix = torch.randn(B, 3, 224, 224, generator=torch.Generator().manual_seed(9))
-    call = dict(prompt_embeds=inp["prompt_embeds"], negative_prompt_embeds=inp["negative_prompt_embeds"],
-                pooled_prompt_embeds=inp["pooled_prompt_embeds"], negative_pooled_prompt_embeds=inp["negative_pooled_prompt_embeds"],
-                num_inference_steps=steps, strength=1.0, pose_img=inp["pose_img"], mask_image=inp["mask_image"], image=inp["image"],
-                height=H, width=W, guidance_scale=2.0, ip_adapter_image=clip_pix, output_type="pt")
+    inp, clip_pix, call = boundary_inputs(kw, B, H, W, steps, DT)
     cache = pipe.encode_garment(inp["cloth"][:2], inp["text_embeds_cloth"][:2], steps, H, W, generator=torch.Generator(DEV).manual_seed(11))
     idx = [1, 0, 1]                                                                # P = 3 persons on G = 2 garments
     eng = pipe.hip_engine()
@@ -445,19 +396,9 @@ def test_boundary_pipeline_passes_the_index_to_the_engine():
     img_c = pipe(generator=gen_c, cloth=cache, text_embeds_cloth=None, garment_index=idx, **call)[0]
     assert eng.stats["garment_batches"] == n_garm
     # the engine-level call on the draws of the reference's order: the cloth draw is made and dropped, index or not
-    gen = torch.Generator(DEV).manual_seed(7)
-    torch.manual_seed(123)
-    draw = lambda gg, dt_: torch.randn((B, 4, H // 8, W // 8), generator=gg, device=DEV, dtype=dt_).float()
-    n_lat, n_masked, n_pose, _dropped = draw(gen, DT), draw(gen, torch.float32), draw(None, torch.float32), draw(gen, torch.float32)
-    n_steps = torch.stack([draw(gen, DT) for _ in range(steps)])
-    with torch.no_grad():
-        pos = enc(clip_pix.to(DEV, DT), output_hidden_states=True).hidden_states[-2]
-        neg = enc(torch.zeros_like(clip_pix).to(DEV, DT), output_hidden_states=True).hidden_states[-2]
-    ref = eng(image=inp["image"], mask_image=inp["mask_image"], pose_img=inp["pose_img"], cloth=cache, garment_index=idx,
-              prompt_embeds=inp["prompt_embeds"], negative_prompt_embeds=inp["negative_prompt_embeds"],
-              pooled_prompt_embeds=inp["pooled_prompt_embeds"], negative_pooled_prompt_embeds=inp["negative_pooled_prompt_embeds"],
-              text_embeds_cloth=None, noise=dict(latents=n_lat, masked=n_masked, pose=n_pose, cloth=None, steps=n_steps),
-              num_inference_steps=steps, guidance_scale=2.0, ip_hidden_states=torch.cat([neg, pos]), scheduler="ddpm")
+    gen, noise = reference_draws(7, 123, B, H, W, steps, DT)
+    ip = ip_states(enc, clip_pix)
+    ref = engine_reference(eng, inp, noise, ip, steps, cloth=cache, garment_index=idx)
     assert torch.isfinite(img_c).all() and torch.equal(img_c, ref)
     assert torch.equal(gen_c.get_state(), gen.get_state())                         # every draw of the call was made
     with pytest.raises(ValueError, match="GarmentCache persons mismatch"):         # 3 persons on 2 garments needs the index

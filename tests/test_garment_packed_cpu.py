@@ -8,8 +8,7 @@ import os
 import pytest
 import torch
 
-DTYPES = pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
-FINITE = torch.tensor([b for b in range(256) if b & 0x7f != 0x7f], dtype=torch.uint8)      # all but the two NaN bytes 0x7f / 0xff
+from tests.garment_support import DTYPES, FINITE, same_packed, scaled_cache
 
 
 # ------------------------------------------------------------------------------------------------------------------ the format
@@ -55,31 +54,12 @@ def test_error_bounds_on_random_tensors(scale, dtype):
 
 
 # ------------------------------------------------------------------------------------------------------------------ the cache
-def _cache(G=2, n=5, h=16, w=12, dtype=torch.float16, seed=0, **kw):
-    """The shape of tests/test_garment_cache_cpu.py::_cache -- two features of different (N, C) -- with random values of a scale of their own
-    per garment, feature and tensor (that one's values grow beyond fp16's range)."""
-    from idm_vton_amd.garment_cache import GarmentCache
-    g = torch.Generator().manual_seed(seed)
-    kv = []
-    for f, (N, Cc) in enumerate(((h * w, 64), (h * w // 4, 128))):
-        sk = torch.tensor([10.0 ** (gi - f) for gi in range(G)]).view(1, G, 1)
-        k = (torch.randn(n, G, N * Cc, generator=g) * sk).reshape(n * G * N, Cc).to(dtype)
-        vt = (torch.randn(n, G, Cc * N, generator=g) * sk * 300.0).reshape(n * G, Cc, N).to(dtype)
-        kv.append((k, vt))
-    args = dict(G=G, timesteps=list(range(900, 900 - 200 * n, -200)), h=h, w=w, dtype=dtype, attn_fp8=False, f8_exp=(2, 2, 2), weights_id="w0", kv=kv)
-    args.update(kw)
-    return GarmentCache(**args)
-
-
-def _same(a, b):
-    return (type(a) is type(b) and a.G == b.G and torch.equal(a.exps, b.exps) and
-            all(torch.equal(x, y) and torch.equal(u, v) and x.dtype == torch.uint8 for (x, u), (y, v) in zip(a.kv, b.kv)))
 
 
 @DTYPES
 def test_pack_unpack_round_trip_and_nbytes(dtype):
     from idm_vton_amd.garment_cache import PackedGarmentCache
-    c = _cache(dtype=dtype)
+    c = scaled_cache(dtype=dtype)
     p = c.pack()
     assert isinstance(p, PackedGarmentCache) and p.packed and not c.packed and p.dtype == dtype and not p.attn_fp8
     assert "e4m3-packed" in repr(p) and "e4m3-packed" not in repr(c)
@@ -96,24 +76,24 @@ def test_pack_unpack_round_trip_and_nbytes(dtype):
             normal = xd.abs() * sc >= 2.0 ** -6
             err = (yd - xd).abs()
             assert (err[normal] <= 2.0 ** -4 * xd.abs()[normal]).all() and (err <= torch.where(normal, err, 2.0 ** -10 / sc)).all()
-    assert _same(u.pack(), p)                            # pack . unpack . pack reproduces bytes and exponents
+    assert same_packed(u.pack(), p)                            # pack . unpack . pack reproduces bytes and exponents
 
 
 def test_primitives_carry_the_exponents():
     from idm_vton_amd.garment_cache import GarmentCache
-    c = _cache(G=3)
+    c = scaled_cache(G=3)
     p = c.pack()
     s = p.select([2, 0, 2])
-    assert s.G == 3 and torch.equal(s.exps, p.exps[[2, 0, 2]]) and _same(s, c.select([2, 0, 2]).pack())
+    assert s.G == 3 and torch.equal(s.exps, p.exps[[2, 0, 2]]) and same_packed(s, c.select([2, 0, 2]).pack())
     t = p.take(1)
-    assert t.G == 1 and t.packed and torch.equal(t.exps, p.exps[1:2]) and _same(t, c.take(1).pack())
-    assert _same(GarmentCache.cat([p.take(0), p.take(1), p.take(2)]), p)
+    assert t.G == 1 and t.packed and torch.equal(t.exps, p.exps[1:2]) and same_packed(t, c.take(1).pack())
+    assert same_packed(GarmentCache.cat([p.take(0), p.take(1), p.take(2)]), p)
     q = p.select([0, 1, 2])
     q.put(0, p.take(2))                                  # a packed source: bytes and exponents in place
     ptrs = [k.data_ptr() for k, _ in q.kv] + [q.exps.data_ptr()]
     q.put(1, c.take(0))                                  # a 16-bit source: packed first
     assert ptrs == [k.data_ptr() for k, _ in q.kv] + [q.exps.data_ptr()]
-    assert _same(q, p.select([2, 0, 2]))
+    assert same_packed(q, p.select([2, 0, 2]))
     shared = q.for_person_size(32, 24)
     assert shared.packed and shared.exps.data_ptr() == q.exps.data_ptr() and (shared.h, shared.w) == (32, 24)
     m = p.to("cpu", pin_memory=False)
@@ -126,7 +106,7 @@ def test_save_load_version_3_and_unpacked_still_version_1(tmp_path):
     import json
     from safetensors import safe_open
     from idm_vton_amd.garment_cache import GarmentCache
-    c = _cache()
+    c = scaled_cache()
     p = c.pack()
     p.save(str(tmp_path / "p.safetensors"))
     c.save(str(tmp_path / "c.safetensors"))
@@ -137,19 +117,19 @@ def test_save_load_version_3_and_unpacked_still_version_1(tmp_path):
         meta = {k: json.loads(v) for k, v in f.metadata().items()}
         assert meta["version"] == 1 and "packed" not in meta and "exps" not in f.keys()
     back = GarmentCache.load(str(tmp_path / "p.safetensors"))
-    assert _same(back, p) and back.timesteps == p.timesteps and back.dtype == p.dtype and back.weights_id == p.weights_id
+    assert same_packed(back, p) and back.timesteps == p.timesteps and back.dtype == p.dtype and back.weights_id == p.weights_id
     assert not GarmentCache.load(str(tmp_path / "c.safetensors")).packed
 
 
 def test_refusals():
     from idm_vton_amd.garment_cache import GarmentCache
-    c = _cache()
+    c = scaled_cache()
     with pytest.raises(ValueError, match="already e4m3-packed"):
         c.pack().pack()
     with pytest.raises(ValueError, match="attn_fp8 cache cannot be packed"):
-        _cache(attn_fp8=True).pack()
+        scaled_cache(attn_fp8=True).pack()
     with pytest.raises(ValueError, match="`sizes`.*cannot be packed"):
-        _cache(sizes=[(16, 12), (16, 12)]).pack()
+        scaled_cache(sizes=[(16, 12), (16, 12)]).pack()
     with pytest.raises(ValueError, match="GarmentCache cat: packed mismatch"):
         GarmentCache.cat([c.pack(), c])
     with pytest.raises(ValueError, match="GarmentCache cat: packed mismatch"):
@@ -168,7 +148,7 @@ def test_refusals():
 
 def test_pool_over_a_packed_cache_spills_and_restores_bit_identically():
     from idm_vton_amd.garment_cache import GarmentPool
-    ones = {key: _cache(G=1, seed=s) for s, key in enumerate("abc")}
+    ones = {key: scaled_cache(G=1, seed=s) for s, key in enumerate("abc")}
     packed = {key: one.pack() for key, one in ones.items()}
     calls = []
 
@@ -179,11 +159,11 @@ def test_pool_over_a_packed_cache_spills_and_restores_bit_identically():
     assert pool.cache.packed and pool.cache.G == 2 and pool.cache.nbytes == 2 * (packed["a"].nbytes - 16) + 32
     assert pool.get(["a", "b"], encode) == [0, 1]
     assert pool.get(["c", "b"], encode) == [0, 1]        # evicts a -> pinned-free host copy (CPU pool), packed bytes
-    assert list(pool.host) == ["a"] and pool.host["a"].packed and _same(pool.host["a"], packed["a"])
+    assert list(pool.host) == ["a"] and pool.host["a"].packed and same_packed(pool.host["a"], packed["a"])
     assert pool.host["a"].nbytes == packed["a"].nbytes
     assert pool.get(["a", "b"], encode) == [0, 1]        # evicts c, restores a from the host
     assert calls == ["a", "b", "c"] and pool.stats == dict(hits=2, encoded=3, restored=1, evicted=2)
-    assert _same(pool.cache.take(0), packed["a"]) and _same(pool.cache.take(1), packed["b"])
+    assert same_packed(pool.cache.take(0), packed["a"]) and same_packed(pool.cache.take(1), packed["b"])
     assert list(pool.host) == ["a"]                      # spill=1: the bound drops c's copy, never the one being restored
 
 
@@ -261,7 +241,7 @@ def test_fill_records_are_the_descriptors_of_the_layout_rule():
     set, one record per (timestep, garment, feature, K | V^T) in that order, each a valid idmvton_kv_unpack_desc."""
     from idm_vton_amd import ffi
     from idm_vton_amd.garment_cache import alloc_kv, fill_records, kv_shapes, slot_run
-    p = _cache(G=3).pack()
+    p = scaled_cache(G=3).pack()
     n, G, k, S = 5, 3, 4, 2
     dst = alloc_kv([((a[0] // G * S,) + a[1:], (b[0] // G * S,) + b[1:], torch.float16) for a, b, _ in kv_shapes(p.kv)], n, k, "cpu")
     entries, tslots, garments, gslots = [4, 1, 2], [0, 1, 2], [2, 0], [0, 1]

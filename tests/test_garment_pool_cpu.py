@@ -6,6 +6,8 @@ import ctypes as C
 import pytest
 import torch
 
+from tests.garment_support import POOL_FEATS, TABLE, ask, attn_args, attn_f8_args, caches_equal, pool_cache
+
 
 # ------------------------------------------------------------------------------------------------------------------ C ABI
 def test_indexed_entry_points_are_exported_and_the_abi_did_not_move():
@@ -18,33 +20,7 @@ def test_indexed_entry_points_are_exported_and_the_abi_did_not_move():
     assert L.idmvton_sizeof(b"idmvton_attn_f8_args") == 128 == C.sizeof(ffi.AttnF8Args)
 
 
-def _attn_args(mode, B=4, b0=2):
-    from idm_vton_amd import ffi
-    a = ffi.AttnArgs()
-    a.dtype, a.mode, a.B, a.heads, a.Nq = ffi.BF16, mode, B, 2, 64
-    a.q, a.ldq, a.out, a.ldo, a.nseg = 0x10000, 128, 0x20000, 128, 2
-    for s in range(2):                                   # (the pointers are never dereferenced: every call below is refused before a launch)
-        a.k[s], a.vt[s], a.ldk[s], a.ldvt[s], a.nk[s], a.k_rows[s] = 0x30000 + s * 0x10000, 0x50000 + s * 0x10000, 128, 64, 64, 64
-    a.seg_b0[0], a.seg_b0[1] = 0, b0
-    return a
-
-
-def _attn_f8_args(B=4, b0=2):
-    from idm_vton_amd import ffi
-    a = ffi.AttnF8Args()
-    a.out_dtype, a.B, a.heads, a.Nq = ffi.BF16, B, 2, 64
-    a.q8, a.ldq, a.out, a.ldo, a.nseg = 0x10000, 128, 0x20000, 128, 2
-    for s in range(2):
-        a.k8[s], a.vt8[s], a.ldk[s], a.ldvt[s], a.nk[s], a.k_rows[s] = 0x30000 + s * 0x10000, 0x50000 + s * 0x10000, 128, 64, 64, 64
-    a.seg_b0[0], a.seg_b0[1] = 0, b0
-    a.qk_scale_exp, a.v_scale_exp = -4, -2
-    return a
-
-
-TABLE = 0x70000                                          # a stand-in device address: never read on the host
-
-
-@pytest.mark.parametrize("fn,make", [("idmvton_attn_fwd_indexed", lambda **kw: _attn_args(0, **kw)), ("idmvton_attn_f8_indexed", _attn_f8_args)],
+@pytest.mark.parametrize("fn,make", [("idmvton_attn_fwd_indexed", lambda **kw: attn_args(0, **kw)), ("idmvton_attn_f8_indexed", attn_f8_args)],
                          ids=["attn_fwd_indexed", "attn_f8_indexed"])
 def test_indexed_arguments_are_validated_on_the_host(fn, make):
     from idm_vton_amd import ffi
@@ -72,9 +48,9 @@ def test_indexed_arguments_are_validated_on_the_host(fn, make):
 def test_cross_mode_takes_no_table():
     from idm_vton_amd import ffi
     with pytest.raises(RuntimeError, match=r"CROSS mode takes no table"):
-        ffi.call_indexed("idmvton_attn_fwd_indexed", _attn_args(ffi.ATTN_CROSS, b0=0), (0, 1), (0, TABLE), 0)
+        ffi.call_indexed("idmvton_attn_fwd_indexed", attn_args(ffi.ATTN_CROSS, b0=0), (0, 1), (0, TABLE), 0)
     with pytest.raises(RuntimeError, match=r"CROSS mode takes no table"):
-        ffi.call_indexed("idmvton_attn_fwd_indexed", _attn_args(ffi.ATTN_CROSS, b0=0), (1, 0), (TABLE, 0), 0)
+        ffi.call_indexed("idmvton_attn_fwd_indexed", attn_args(ffi.ATTN_CROSS, b0=0), (1, 0), (TABLE, 0), 0)
 
 
 def test_ops_segment_dicts_without_an_index_keep_their_entry_points():
@@ -86,23 +62,6 @@ def test_ops_segment_dicts_without_an_index_keep_their_entry_points():
 
 
 # ------------------------------------------------------------------------------------------------------------------ GarmentCache
-FEATS = ((12, 64), (6, 128))                             # (token rows, channels) of two features
-
-
-def _cache(G=2, ts=(900, 700, 500, 300, 100), h=4, w=3, dtype=torch.float16, attn_fp8=False, f8_exp=(2, 2, 2), wid="w0", seed=0):
-    """Every (timestep, garment, feature) block has values of its own (a seeded draw), so a misplaced block cannot compare equal."""
-    from idm_vton_amd.garment_cache import GarmentCache
-    n, kv = len(ts), []
-    g = torch.Generator().manual_seed(seed)
-    for N, Cc in FEATS:
-        if dtype == torch.uint8:
-            k = torch.randint(0, 256, (n * G * N, Cc), generator=g, dtype=torch.uint8)
-            vt = torch.randint(0, 256, (n * G, Cc, N), generator=g, dtype=torch.uint8)
-        else:
-            k, vt = torch.randn(n * G * N, Cc, generator=g).to(dtype), torch.randn(n * G, Cc, N, generator=g).to(dtype)
-        kv.append((k, vt))
-    return GarmentCache(G=G, timesteps=ts, h=h, w=w, dtype=torch.float16 if dtype == torch.uint8 else dtype, attn_fp8=attn_fp8, f8_exp=f8_exp,
-                        weights_id=wid, kv=kv)
 
 
 def _garment(c, i, g):
@@ -118,14 +77,8 @@ def _same_garment(a, b):
     return all(torch.equal(ka, kb) and torch.equal(va, vb) for (ka, va), (kb, vb) in zip(a, b))
 
 
-def _equal(a, b):
-    return (a.G, a.timesteps, a.h, a.w, a.gh, a.gw, a.dtype, a.attn_fp8, a.f8_exp, a.weights_id) == \
-           (b.G, b.timesteps, b.h, b.w, b.gh, b.gw, b.dtype, b.attn_fp8, b.f8_exp, b.weights_id) and len(a.kv) == len(b.kv) and \
-        all(ka.dtype == kb.dtype and torch.equal(ka, kb) and torch.equal(va, vb) for (ka, va), (kb, vb) in zip(a.kv, b.kv))
-
-
 def test_select_gathers_garments_in_the_order_asked():
-    c = _cache(G=3)
+    c = pool_cache(G=3)
     ids = [2, 0, 2, 1]
     s = c.select(ids)
     assert s.G == 4 and s.timesteps == c.timesteps and s.nbytes == c.nbytes // 3 * 4
@@ -133,23 +86,23 @@ def test_select_gathers_garments_in_the_order_asked():
         for j, g in enumerate(ids):
             assert _same_garment(_garment(s, i, j), _garment(c, i, g)), (i, j, g)
     assert all(ks.data_ptr() != kc.data_ptr() for (ks, _), (kc, _) in zip(s.kv, c.kv))     # a copy
-    assert _equal(c.select([0, 1, 2, 0, 1, 2]), c.repeat_garments(2))                      # what the modulo rule reads, materialised
-    assert _equal(c.select([0, 1, 2]), c)
+    assert caches_equal(c.select([0, 1, 2, 0, 1, 2]), c.repeat_garments(2))                      # what the modulo rule reads, materialised
+    assert caches_equal(c.select([0, 1, 2]), c)
     with pytest.raises(ValueError, match="GarmentCache garment_index mismatch"):
         c.select([0, 3])
 
 
 def test_cat_joins_caches_and_names_the_field_that_differs():
     from idm_vton_amd.garment_cache import GarmentCache
-    a, b, c = _cache(G=1, seed=1), _cache(G=2, seed=2), _cache(G=1, seed=3)
+    a, b, c = pool_cache(G=1, seed=1), pool_cache(G=2, seed=2), pool_cache(G=1, seed=3)
     j = GarmentCache.cat([a, b, c])
     assert j.G == 4 and j.nbytes == a.nbytes + b.nbytes + c.nbytes
     for i in range(len(a.timesteps)):
         for slot, (src, g) in enumerate([(a, 0), (b, 0), (b, 1), (c, 0)]):
             assert _same_garment(_garment(j, i, slot), _garment(src, i, g)), (i, slot)
-    assert _equal(GarmentCache.cat([b.select([0]), b.select([1])]), b)
-    for field, other in (("timesteps", _cache(G=1, ts=(900, 700, 500, 300, 99))), ("h", _cache(G=1, h=6, w=2)), ("dtype", _cache(G=1, dtype=torch.bfloat16)),
-                         ("attn_fp8", _cache(G=1, attn_fp8=True)), ("f8_exp", _cache(G=1, f8_exp=(2, 3, 2))), ("weights_id", _cache(G=1, wid="w1")),
+    assert caches_equal(GarmentCache.cat([b.select([0]), b.select([1])]), b)
+    for field, other in (("timesteps", pool_cache(G=1, ts=(900, 700, 500, 300, 99))), ("h", pool_cache(G=1, h=6, w=2)), ("dtype", pool_cache(G=1, dtype=torch.bfloat16)),
+                         ("attn_fp8", pool_cache(G=1, attn_fp8=True)), ("f8_exp", pool_cache(G=1, f8_exp=(2, 3, 2))), ("weights_id", pool_cache(G=1, wid="w1")),
                          ("gh", a.for_person_size(4, 3)._like(gh=2, gw=6))):
         with pytest.raises(ValueError, match=f"GarmentCache cat: {field} mismatch"):
             GarmentCache.cat([a, other])
@@ -161,7 +114,7 @@ def test_cat_joins_caches_and_names_the_field_that_differs():
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.uint8], ids=["f16", "e4m3_bytes"])
 def test_put_overwrites_exactly_one_slot_of_every_tensor_at_every_timestep(dtype):
-    c, one = _cache(G=3, dtype=dtype, seed=4), _cache(G=1, dtype=dtype, seed=5)
+    c, one = pool_cache(G=3, dtype=dtype, seed=4), pool_cache(G=1, dtype=dtype, seed=5)
     before = c.select([0, 1, 2])
     ptrs = [(k.data_ptr(), vt.data_ptr()) for k, vt in c.kv]
     assert c.put(1, one) is c
@@ -170,7 +123,7 @@ def test_put_overwrites_exactly_one_slot_of_every_tensor_at_every_timestep(dtype
         assert _same_garment(_garment(c, i, 1), _garment(one, i, 0)), i
         for g in (0, 2):
             assert _same_garment(_garment(c, i, g), _garment(before, i, g)), (i, g)
-    assert not _equal(c, before)
+    assert not caches_equal(c, before)
     # element for element: everything outside slot 1 is what it was
     for (k, vt), (k0, vt0) in zip(c.kv, before.kv):
         n, N = len(c.timesteps), k.shape[0] // (len(c.timesteps) * 3)
@@ -182,19 +135,19 @@ def test_put_overwrites_exactly_one_slot_of_every_tensor_at_every_timestep(dtype
     with pytest.raises(ValueError, match="put: G mismatch"):
         c.put(0, before)
     with pytest.raises(ValueError, match="put: weights_id mismatch"):
-        c.put(0, _cache(G=1, dtype=dtype, wid="w1"))
+        c.put(0, pool_cache(G=1, dtype=dtype, wid="w1"))
     with pytest.raises(ValueError, match="put: kv mismatch"):
-        c.put(0, _cache(G=1, dtype=torch.uint8 if dtype != torch.uint8 else torch.float16))
+        c.put(0, pool_cache(G=1, dtype=torch.uint8 if dtype != torch.uint8 else torch.float16))
 
 
 def test_take_copies_one_slot_out_and_put_brings_it_back():
-    c = _cache(G=3, seed=6)
+    c = pool_cache(G=3, seed=6)
     one = c.take(2)
     assert one.G == 1 and one.timesteps == c.timesteps and one.nbytes == c.nbytes // 3
     assert all(_same_garment(_garment(one, i, 0), _garment(c, i, 2)) for i in range(len(c.timesteps)))
     assert all(k1.data_ptr() != k.data_ptr() for (k1, _), (k, _) in zip(one.kv, c.kv))     # a copy
-    assert _equal(one, c.select([2])) and _equal(c.take(0, "cpu"), c.select([0]))
-    d = _cache(G=3, seed=7)
+    assert caches_equal(one, c.select([2])) and caches_equal(c.take(0, "cpu"), c.select([0]))
+    d = pool_cache(G=3, seed=7)
     d.put(0, one)
     assert all(_same_garment(_garment(d, i, 0), _garment(c, i, 2)) for i in range(len(c.timesteps)))
     with pytest.raises(ValueError, match="take: slot mismatch"):
@@ -202,10 +155,10 @@ def test_take_copies_one_slot_out_and_put_brings_it_back():
 
 
 def test_to_cpu_keeps_the_cache():
-    c = _cache(G=2)
+    c = pool_cache(G=2)
     assert c.to("cpu") is c                                                                # nothing to move
     d = c.to(torch.device("cpu"))
-    assert _equal(c, d)
+    assert caches_equal(c, d)
 
 
 @pytest.mark.parametrize("dtype,fp8", [(torch.float16, False), (torch.bfloat16, False), (torch.uint8, True)], ids=["f16", "bf16", "e4m3_bytes"])
@@ -213,11 +166,11 @@ def test_save_load_round_trip_is_bit_equal_with_all_metadata(tmp_path, dtype, fp
     import json
     from safetensors import safe_open
     from idm_vton_amd.garment_cache import GarmentCache
-    c = _cache(G=2, dtype=dtype, attn_fp8=fp8, f8_exp=(1, 2, 3), wid="abc:def", h=4, w=3)._like(gh=2, gw=6)
+    c = pool_cache(G=2, dtype=dtype, attn_fp8=fp8, f8_exp=(1, 2, 3), wid="abc:def", h=4, w=3)._like(gh=2, gw=6)
     path = str(tmp_path / "garments.safetensors")
     c.save(path)
     d = GarmentCache.load(path)
-    assert _equal(c, d) and (d.gh, d.gw) == (2, 6) and {k.dtype for k, _ in d.kv} == {dtype}
+    assert caches_equal(c, d) and (d.gh, d.gw) == (2, 6) and {k.dtype for k, _ in d.kv} == {dtype}
     with safe_open(path, framework="pt") as f:
         meta = {k: json.loads(v) for k, v in f.metadata().items()}
     assert meta == dict(format="idmvton_garment_cache", version=1, G=2, timesteps=list(c.timesteps), h=4, w=3, gh=2, gw=6, dtype=str(c.dtype),
@@ -239,41 +192,35 @@ def test_save_load_round_trip_is_bit_equal_with_all_metadata(tmp_path, dtype, fp
         GarmentCache.load(path2)
 
 
-def _ask(c, **over):
-    kw = dict(timesteps=c.timesteps, h=c.h, w=c.w, dtype=c.dtype, attn_fp8=c.attn_fp8, f8_exp=c.f8_exp, weights_id=c.weights_id, persons=c.G)
-    kw.update(over)
-    return c.check(**kw)
-
-
 def test_check_with_a_garment_index_replaces_the_modulo_rule():
-    c = _cache(G=3)
+    c = pool_cache(G=3)
     with pytest.raises(ValueError, match="GarmentCache persons mismatch"):
-        _ask(c, persons=4)                                                                 # without an index: P % G, as ever
+        ask(c, persons=4)                                                                 # without an index: P % G, as ever
     # with an index: (cache entries, the validated index as ints) -- what the engine needs
-    assert _ask(c, persons=4, garment_index=[2, 0, 2, 1]) == ([0, 1, 2, 3, 4], [2, 0, 2, 1])
-    assert _ask(c, persons=1, garment_index=(2,)) == ([0, 1, 2, 3, 4], [2])
-    assert _ask(c, persons=2, garment_index=torch.tensor([1, 1]), timesteps=[300, 900]) == ([3, 0], [1, 1])
-    assert _ask(c, persons=3) == [0, 1, 2, 3, 4]                                           # without: the entries alone, as ever
+    assert ask(c, persons=4, garment_index=[2, 0, 2, 1]) == ([0, 1, 2, 3, 4], [2, 0, 2, 1])
+    assert ask(c, persons=1, garment_index=(2,)) == ([0, 1, 2, 3, 4], [2])
+    assert ask(c, persons=2, garment_index=torch.tensor([1, 1]), timesteps=[300, 900]) == ([3, 0], [1, 1])
+    assert ask(c, persons=3) == [0, 1, 2, 3, 4]                                           # without: the entries alone, as ever
     assert c.garment_ids(torch.tensor([1, 2], dtype=torch.int32), 2) == [1, 2]
     for bad, persons, what in (([0, 1, 2], 4, "3 entries for P = 4 persons"), ([0, 1, 2, 0, 1], 4, "5 entries for P = 4"), ([0, 3, 1, 1], 4, r"\[3\] outside \[0, G = 3\)"),
                                ([0, -1], 2, r"\[-1\] outside"), ([], 0, "0 entries for P = 0"), (7, 1, "expected a sequence"), (["a"], 1, "expected a sequence")):
         with pytest.raises(ValueError, match=f"GarmentCache garment_index mismatch: .*{what}"):
-            _ask(c, persons=persons, garment_index=bad)
+            ask(c, persons=persons, garment_index=bad)
     # the other fields are held as before, index or not
     with pytest.raises(ValueError, match="GarmentCache weights mismatch"):
-        _ask(c, persons=4, garment_index=[2, 0, 2, 1], weights_id="w1")
+        ask(c, persons=4, garment_index=[2, 0, 2, 1], weights_id="w1")
     with pytest.raises(ValueError, match="GarmentCache timesteps mismatch"):
-        _ask(c, persons=4, garment_index=[2, 0, 2, 1], timesteps=[901])
+        ask(c, persons=4, garment_index=[2, 0, 2, 1], timesteps=[901])
 
 
 def test_slot_run_and_index_runs_follow_the_layout_rule():
     from idm_vton_amd.garment_cache import index_runs, slot_run
-    c = _cache(G=3)
+    c = pool_cache(G=3)
     n = len(c.timesteps)
     for i in (0, 3):
         two = slot_run(c.kv, n, 3, i, 1, 2)
         for f, (k, vt) in enumerate(two):
-            N = FEATS[f][0]
+            N = POOL_FEATS[f][0]
             assert torch.equal(k[:N], _garment(c, i, 1)[f][0]) and torch.equal(k[N:], _garment(c, i, 2)[f][0])
             assert torch.equal(vt[0], _garment(c, i, 1)[f][1]) and torch.equal(vt[1], _garment(c, i, 2)[f][1])
             assert k.data_ptr() == _garment(c, i, 1)[f][0].data_ptr()                      # views
@@ -290,10 +237,10 @@ def _pool(capacity, spill=False):
 
     def encode(key):
         made.append(key)
-        garments.setdefault(key, _cache(G=1, seed=100 + key))
+        garments.setdefault(key, pool_cache(G=1, seed=100 + key))
         return garments[key]
-    pool = GarmentPool(capacity, like=_cache(G=1, seed=99), spill=spill)
-    return pool, encode, made, lambda key: _cache(G=1, seed=100 + key)
+    pool = GarmentPool(capacity, like=pool_cache(G=1, seed=99), spill=spill)
+    return pool, encode, made, lambda key: pool_cache(G=1, seed=100 + key)
 
 
 def _holds(pool, slot, one):
@@ -338,7 +285,7 @@ def test_pool_spills_to_the_host_and_restores_without_encoding():
     pool, encode, made, truth = _pool(2, spill=True)
     pool.get([1, 2], encode)
     pool.get([3], encode)                                                                  # evicts 1 -> host
-    assert 1 not in pool and list(pool.host) == [1] and _equal(pool.host[1], truth(1))
+    assert 1 not in pool and list(pool.host) == [1] and caches_equal(pool.host[1], truth(1))
     n = len(made)
     assert pool.get([1], encode) == [1] and len(made) == n                                 # 2 was the oldest; 1 comes back from the host copy
     assert _holds(pool, 1, truth(1)) and pool.stats["restored"] == 1 and pool.stats["encoded"] == 3
@@ -353,7 +300,7 @@ def test_pool_bounds_its_host_copies_and_loses_no_slot_when_encode_fails():
     assert pool.host_capacity == 2
     for key in (1, 2, 3, 4):
         pool.get([key], encode)                                                            # each evicts its predecessor -> host
-    assert list(pool.host) == [2, 3] and all(_equal(pool.host[k], truth(k)) for k in (2, 3))   # 1, spilled longest ago, was dropped
+    assert list(pool.host) == [2, 3] and all(caches_equal(pool.host[k], truth(k)) for k in (2, 3))   # 1, spilled longest ago, was dropped
     n = len(made)
     assert pool.get([2], encode) == [0] and len(made) == n and _holds(pool, 0, truth(2))   # restored; 4 spilled, 3 stays, 2 is in use
     assert list(pool.host) == [2, 4]                                                       # 3 was the oldest copy not in use
@@ -371,9 +318,9 @@ def test_pool_bounds_its_host_copies_and_loses_no_slot_when_encode_fails():
     assert pool2.get([6, 7], encode2) == [0, 1]                                            # the pool still has both its slots
     from idm_vton_amd.garment_cache import GarmentPool
     with pytest.raises(ValueError, match="must hold one garment"):
-        GarmentPool(2, like=_cache(G=2))
+        GarmentPool(2, like=pool_cache(G=2))
     with pytest.raises(ValueError, match="capacity 0 < 1"):
-        GarmentPool(0, like=_cache(G=1))
+        GarmentPool(0, like=pool_cache(G=1))
 
 
 # ------------------------------------------------------------------------------------------------------------------ engine, host side
@@ -384,7 +331,7 @@ def test_fill_set_gathers_the_distinct_garments_of_a_call_into_person_sized_sets
     from idm_vton_amd.garment_cache import kv_shapes, timestep_run
     from idm_vton_amd.pipeline import TryonEngine
     eng = TryonEngine(None, None, None, dtype=torch.float16, device="cpu")
-    pool = _cache(G=6, seed=8)
+    pool = pool_cache(G=6, seed=8)
     n, P, k = len(pool.timesteps), 4, 3
     gindex = [5, 2, 5, 3]                                                                  # U = 3: garments 5, 2, 3 -> slots 0, 1, 2
     st = dict(B=P, h=4, w=3, gh=4, gw=3, k=k, steps_noise=None, gcache=pool, gidx=[1, 2, 4], gindex=gindex)      # timesteps not consecutive
@@ -398,8 +345,8 @@ def test_fill_set_gathers_the_distinct_garments_of_a_call_into_person_sized_sets
     assert eng.stats["garment_set_copies"] == 1
     for j, i in enumerate([2, 4]):
         for f, (kk, vt) in enumerate(timestep_run(fset["kv"], k, P, j)):
-            N = FEATS[f][0]
-            assert tuple(vt.shape) == (P, FEATS[f][1], N) and tuple(kk.shape) == (P * N, FEATS[f][1])
+            N = POOL_FEATS[f][0]
+            assert tuple(vt.shape) == (P, POOL_FEATS[f][1], N) and tuple(kk.shape) == (P * N, POOL_FEATS[f][1])
             for slot, g in enumerate([5, 2, 3]):
                 gk, gvt = _garment(pool, i, g)[f]
                 assert torch.equal(kk[slot * N:(slot + 1) * N], gk) and torch.equal(vt[slot], gvt), (j, f, slot)
@@ -408,6 +355,6 @@ def test_fill_set_gathers_the_distinct_garments_of_a_call_into_person_sized_sets
         assert (kk == -7.0).all() and (vt == -7.0).all()
     # one state for every pool size and assignment; never the state of the call without an index, nor a live one
     key = TryonEngine._graph_key(st, False)
-    assert key == TryonEngine._graph_key(dict(st, gcache=_cache(G=2), gindex=[0, 1, 1, 0]), False)
+    assert key == TryonEngine._graph_key(dict(st, gcache=pool_cache(G=2), gindex=[0, 1, 1, 0]), False)
     assert key != TryonEngine._graph_key(dict(st, gindex=None), False) and key != TryonEngine._graph_key(st, True)
     assert key != TryonEngine._graph_key(dict(st, B=2, gindex=[5, 2]), False)

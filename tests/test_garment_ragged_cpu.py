@@ -2,9 +2,14 @@
 put / take / select / cat / save / load and GarmentPool(mixed_sizes=True) on CPU tensors, no kernels -- and the two ragged attention entry
 points: exported, validating on the host (no launch), with the C ABI where it was."""
 import ctypes as C
+import functools
 
 import pytest
 import torch
+
+from tests.garment_support import TABLE, attn_args, attn_f8_args, caches_equal
+
+_equal = functools.partial(caches_equal, sizes=True)    # slotted caches: the slots' garment sizes are facts too
 
 
 # ------------------------------------------------------------------------------------------------------------------ C ABI
@@ -18,33 +23,7 @@ def test_ragged_entry_points_are_exported_and_the_abi_did_not_move():
     assert L.idmvton_sizeof(b"idmvton_attn_f8_args") == 128 == C.sizeof(ffi.AttnF8Args)
 
 
-def _attn_args(mode, B=4, b0=2):
-    from idm_vton_amd import ffi
-    a = ffi.AttnArgs()
-    a.dtype, a.mode, a.B, a.heads, a.Nq = ffi.BF16, mode, B, 2, 64
-    a.q, a.ldq, a.out, a.ldo, a.nseg = 0x10000, 128, 0x20000, 128, 2
-    for s in range(2):                                   # (the pointers are never dereferenced: every call below is refused before a launch)
-        a.k[s], a.vt[s], a.ldk[s], a.ldvt[s], a.nk[s], a.k_rows[s] = 0x30000 + s * 0x10000, 0x50000 + s * 0x10000, 128, 64, 64, 64
-    a.seg_b0[0], a.seg_b0[1] = 0, b0
-    return a
-
-
-def _attn_f8_args(B=4, b0=2):
-    from idm_vton_amd import ffi
-    a = ffi.AttnF8Args()
-    a.out_dtype, a.B, a.heads, a.Nq = ffi.BF16, B, 2, 64
-    a.q8, a.ldq, a.out, a.ldo, a.nseg = 0x10000, 128, 0x20000, 128, 2
-    for s in range(2):
-        a.k8[s], a.vt8[s], a.ldk[s], a.ldvt[s], a.nk[s], a.k_rows[s] = 0x30000 + s * 0x10000, 0x50000 + s * 0x10000, 128, 64, 64, 64
-    a.seg_b0[0], a.seg_b0[1] = 0, b0
-    a.qk_scale_exp, a.v_scale_exp = -4, -2
-    return a
-
-
-TABLE = 0x70000                                          # a stand-in device address: never read on the host
-
-
-@pytest.mark.parametrize("fn,make", [("idmvton_attn_fwd_ragged", lambda **kw: _attn_args(0, **kw)), ("idmvton_attn_f8_ragged", _attn_f8_args)],
+@pytest.mark.parametrize("fn,make", [("idmvton_attn_fwd_ragged", lambda **kw: attn_args(0, **kw)), ("idmvton_attn_f8_ragged", attn_f8_args)],
                          ids=["attn_fwd_ragged", "attn_f8_ragged"])
 def test_ragged_arguments_are_validated_on_the_host(fn, make):
     from idm_vton_amd import ffi
@@ -69,7 +48,7 @@ def test_cross_mode_takes_no_key_count_table():
     from idm_vton_amd import ffi
     for nk in ((0, TABLE), (TABLE, 0)):
         with pytest.raises(RuntimeError, match=r"attn_fwd_ragged: CROSS mode takes no table"):
-            ffi.call_ragged("idmvton_attn_fwd_ragged", _attn_args(ffi.ATTN_CROSS, b0=0), (0, 0), None, nk, 0)
+            ffi.call_ragged("idmvton_attn_fwd_ragged", attn_args(ffi.ATTN_CROSS, b0=0), (0, 0), None, nk, 0)
 
 
 def test_ops_segment_dicts_without_a_key_count_table_keep_their_entry_points(monkeypatch):
@@ -119,12 +98,6 @@ def _cache(size, G=1, sizes=None, dtype=torch.float16, seed=0, ts=TS, wid="w0", 
 
 def _slotted(G, fill=7.0):
     return _cache(SLOT, G=G, sizes=[SLOT] * G, fill=fill)
-
-
-def _equal(a, b):
-    return (a.G, a.timesteps, a.h, a.w, a.gh, a.gw, a.dtype, a.attn_fp8, a.f8_exp, a.weights_id, a.sizes) == \
-           (b.G, b.timesteps, b.h, b.w, b.gh, b.gw, b.dtype, b.attn_fp8, b.f8_exp, b.weights_id, b.sizes) and len(a.kv) == len(b.kv) and \
-        all(ka.dtype == kb.dtype and torch.equal(ka, kb) and torch.equal(va, vb) for (ka, va), (kb, vb) in zip(a.kv, b.kv))
 
 
 def _slot_views(c, i, g):

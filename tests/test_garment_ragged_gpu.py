@@ -4,41 +4,23 @@ same kernel, same grid, same tile walk, so EQUALITY, no tolerance -- with NaN wh
 against fp32 SDPA on per-person keys.  Engine level: persons wearing garments of three sizes in one call against the oracle run per person,
 every execution form, one graph state across assignments and across a put that changes a slot's size, a slotted cache of equal sizes
 against the plain cache, refusals, and the boundary pipeline.  No test hands a kernel a count outside [1, nk]: the kernels' clamp is a guard."""
-import functools
-
 import pytest
 import torch
 import torch.nn.functional as F
 
-from tests.test_garment_cache_gpu import FORMS, HEADS, TUNES, _f8_operands, _self_attn_operands
-from tests.test_garment_index_gpu import F8_SDPA_BAR
+from tests.engine_support import (DEV, GARMENT_HW, STEPS, WEARS, H, W, base_call, boundary_inputs, boundary_pipeline, encode_three, engine, engine_reference,
+                                  f8_operands, int_table, ip_states, model, nan_out, no_tune_table, oracle_latents, reference_draws, run_on,
+                                  self_attn_operands, slotted_pool, three_garments)
+from tests.garment_support import DTYPES, F8_SDPA_BAR, FORMS, HEADS
+from tests.kernel_checks import TUNES
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-DTYPES = pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
-
 CAP = 320                                                # keys a slot holds
 # (P, G, index, slot lengths): lengths below / at / between tile multiples, one of a single partial tile, one shorter than 16; a slot (length
 # 15) no person reads; two persons on one slot -- then a full and a 6-key slot -- then every length the capacity
 PATTERNS = [(3, 4, [2, 0, 2], [48, 320, 200, 15]), (2, 2, [1, 0], [64, 6]), (2, 2, [0, 1], [CAP, CAP])]
 NQS = [320, 256]                                         # 320 query rows are not a multiple of any kernel's 64 / 128 / 256 workgroup rows
 E4M3_NAN = 0x7f
-
-
-def _table(v):
-    return torch.tensor(v, dtype=torch.int32, device=DEV)
-
-
-def _nan(B, Nq, Cc, dtype):
-    return torch.full((B, Nq, Cc), float("nan"), dtype=dtype, device=DEV)
-
-
-@pytest.fixture
-def no_tune_table(monkeypatch):
-    """The tune table's key carries nk, which differs between a ragged launch (the capacity) and its reference (a person's count): with no
-    table, tune = 0 reaches the library's own rule, which does not look at nk, and every other tune value is passed explicitly."""
-    from idm_vton_amd import ops
-    monkeypatch.setattr(ops, "_TUNE", {"gemm": {}, "attn": {}})
 
 
 def _sp(t):
@@ -60,10 +42,10 @@ def _sdpa_per_person(q, k1, v1, k2, v2, idx, lens):
 
 
 def _ragged16(P, G, lens, Nq, dtype, seed, pres):
-    """Operands of tests/test_garment_cache_gpu.py with a garment segment of G slots of CAP keys; slot g holds lens[g] keys: its V^T is zero
+    """self_attn_operands with a garment segment of G slots of CAP keys; slot g holds lens[g] keys: its V^T is zero
     from there to round16 (the finite filler a real slot has there) and NaN beyond, its K rows NaN from lens[g] on."""
     from idm_vton_amd import ops
-    q, k1, v1, k2, v2, ko = _self_attn_operands(P, G, Nq, CAP, dtype, seed)
+    q, k1, v1, k2, v2, ko = self_attn_operands(P, G, Nq, CAP, dtype, seed)
     qq = (q.float() * ops.QSCALE).to(dtype) if pres else q
     k2, v2 = k2.clone(), v2.clone()
     for g, L in enumerate(lens):
@@ -81,7 +63,8 @@ def _ragged16(P, G, lens, Nq, dtype, seed, pres):
 
 @DTYPES
 @pytest.mark.parametrize("tune", list(TUNES), ids=list(TUNES))
-def test_ragged_segment_equals_the_indexed_launch_at_each_persons_count(tune, dtype, no_tune_table):
+def test_ragged_segment_equals_the_indexed_launch_at_each_persons_count(tune, dtype, monkeypatch):
+    no_tune_table(monkeypatch)
     from idm_vton_amd import ops
     from tests.kernel_checks import TOL as KTOL
     pres = tune != "auto"                                # kernels 3, 7, 8, 16 need a pre-multiplied q; `auto` runs the library's rule for a raw q
@@ -90,12 +73,12 @@ def test_ragged_segment_equals_the_indexed_launch_at_each_persons_count(tune, dt
             B, Cc = 2 * P, HEADS * 64
             q, qq, own, garment, (k1, v1, k2, v2) = _ragged16(P, G, lens, Nq, dtype, 17 * P + G, pres)
             per = [lens[g] for g in idx]
-            o_r = _nan(B, Nq, Cc, dtype)
-            ops.attention(qq, o_r, [own, garment(CAP, index=_table(idx), nk_table=_table(per * 2))], HEADS, tune=TUNES[tune], q_prescaled=pres)
+            o_r = nan_out(B, Nq, Cc, dtype)
+            ops.attention(qq, o_r, [own, garment(CAP, index=int_table(idx), nk_table=int_table(per * 2))], HEADS, tune=TUNES[tune], q_prescaled=pres)
             assert torch.isfinite(o_r).all(), (tune, Nq, idx, lens)
             for i, L in enumerate(per):                  # the _indexed entry point, launch-wide nk = this person's count, same strides, same tune
-                o_i = _nan(B, Nq, Cc, dtype)
-                ops.attention(qq, o_i, [own, garment(L, index=_table(idx))], HEADS, tune=TUNES[tune], q_prescaled=pres)
+                o_i = nan_out(B, Nq, Cc, dtype)
+                ops.attention(qq, o_i, [own, garment(L, index=int_table(idx))], HEADS, tune=TUNES[tune], q_prescaled=pres)
                 for b in (i, P + i):
                     assert torch.equal(o_r[b], o_i[b]), (tune, Nq, idx, lens, b, (o_r[b].float() - o_i[b].float()).abs().max().item())
             if P == 3:                                   # the values are attention, not merely equal
@@ -106,9 +89,9 @@ def test_ragged_segment_equals_the_indexed_launch_at_each_persons_count(tune, dt
 
 
 def _ragged8(P, G, lens, Nq, dtype, seed):
-    """_f8_operands with slot lengths: the garment V^T bytes are zero at the positions of keys >= lens[g] inside the last tile and e4m3 NaN from
+    """f8_operands with slot lengths: the garment V^T bytes are zero at the positions of keys >= lens[g] inside the last tile and e4m3 NaN from
     roundup64(lens[g]) on, the K rows e4m3 NaN from lens[g] on."""
-    q8, (k8a, vt8a), (k8b, vt8b) = _f8_operands(P, G, Nq, CAP, dtype, seed)
+    q8, (k8a, vt8a), (k8b, vt8b) = f8_operands(P, G, Nq, CAP, dtype, seed)
     Cc, ld = HEADS * 64, vt8b.shape[1]
     k8b, vt8b = k8b.clone().view(G, CAP, Cc), vt8b.clone().view(G, Cc, ld)
     pos = torch.arange(ld, device=DEV)
@@ -131,16 +114,16 @@ def test_ragged_segment_equals_the_indexed_launch_at_each_persons_count_fp8(dtyp
             q8, own, garment = _ragged8(P, G, lens, Nq, dtype, 5 * P + G)
             kw = dict(qk_scale_exp=-4, v_scale_exp=-2, B=B, Nq=Nq, ldq=Cc, ldo=Cc)
             per = [lens[g] for g in idx]
-            o_r = _nan(B, Nq, Cc, dtype)
-            ops.attention_f8(q8, o_r, [own, garment(CAP, index=_table(idx), nk_table=_table(per * 2))], HEADS, **kw)
+            o_r = nan_out(B, Nq, Cc, dtype)
+            ops.attention_f8(q8, o_r, [own, garment(CAP, index=int_table(idx), nk_table=int_table(per * 2))], HEADS, **kw)
             assert torch.isfinite(o_r).all(), (Nq, idx, lens)
             for i, L in enumerate(per):
-                o_i = _nan(B, Nq, Cc, dtype)
-                ops.attention_f8(q8, o_i, [own, garment(L, index=_table(idx))], HEADS, **kw)
+                o_i = nan_out(B, Nq, Cc, dtype)
+                ops.attention_f8(q8, o_i, [own, garment(L, index=int_table(idx))], HEADS, **kw)
                 for b in (i, P + i):
                     assert torch.equal(o_r[b], o_i[b]), (Nq, idx, lens, b)
             if P == 3:                                   # held to F8_SDPA_BAR, the bar the header states for this kernel (see there why not TOL)
-                q, k1, v1, k2, v2, _ = _self_attn_operands(P, G, Nq, CAP, dtype, 5 * P + G)
+                q, k1, v1, k2, v2, _ = self_attn_operands(P, G, Nq, CAP, dtype, 5 * P + G)
                 ref = _sdpa_per_person(q, k1, v1, k2, v2, idx, lens)
                 err = ((o_r.float() - ref).abs().max() / ref.abs().max()).item()
                 print(f"fp8 {dtype} Nq={Nq}: ragged against fp32 SDPA {err:.3e} (fp8 bar {F8_SDPA_BAR:.1e})")
@@ -148,10 +131,11 @@ def test_ragged_segment_equals_the_indexed_launch_at_each_persons_count_fp8(dtyp
 
 
 @DTYPES
-def test_capacity_tables_and_null_tables_are_the_indexed_launch(dtype, monkeypatch, no_tune_table):
+def test_capacity_tables_and_null_tables_are_the_indexed_launch(dtype, monkeypatch):
     """A table that holds the capacity for every batch, and {NULL, NULL} through the _ragged entry points, give the _indexed launch's bits,
     in every kernel; without nk_table nothing goes through _ragged."""
     from idm_vton_amd import ffi, ops
+    no_tune_table(monkeypatch)
     P, G, idx, lens = PATTERNS[2]
     Nq, B, Cc = NQS[0], 2 * P, HEADS * 64
     kw8 = dict(qk_scale_exp=-4, v_scale_exp=-2, B=B, Nq=Nq, ldq=Cc, ldo=Cc)
@@ -164,14 +148,14 @@ def test_capacity_tables_and_null_tables_are_the_indexed_launch(dtype, monkeypat
     def launch(**seg_kw):
         outs = {}
         for name, tune in TUNES.items():
-            outs[name] = _nan(B, Nq, Cc, dtype)
-            ops.attention(qq, outs[name], [own, garment(CAP, index=_table(idx), **seg_kw)], HEADS, tune=tune, q_prescaled=True)
-        outs["f8"] = _nan(B, Nq, Cc, dtype)
-        ops.attention_f8(q8, outs["f8"], [own8, garment8(CAP, index=_table(idx), **seg_kw)], HEADS, **kw8)
+            outs[name] = nan_out(B, Nq, Cc, dtype)
+            ops.attention(qq, outs[name], [own, garment(CAP, index=int_table(idx), **seg_kw)], HEADS, tune=tune, q_prescaled=True)
+        outs["f8"] = nan_out(B, Nq, Cc, dtype)
+        ops.attention_f8(q8, outs["f8"], [own8, garment8(CAP, index=int_table(idx), **seg_kw)], HEADS, **kw8)
         return outs
     indexed = launch()
     assert calls == []
-    full = launch(nk_table=_table([CAP] * B))
+    full = launch(nk_table=int_table([CAP] * B))
     assert len(calls) == len(TUNES) + 1 and all(nk[0] == 0 and nk[1] != 0 for _, nk in calls)
     monkeypatch.setattr(ops, "_seg_nk", lambda segs, B: [0, 0])
     null = launch()
@@ -179,9 +163,9 @@ def test_capacity_tables_and_null_tables_are_the_indexed_launch(dtype, monkeypat
     for name in indexed:
         assert torch.isfinite(indexed[name]).all() and torch.equal(full[name], indexed[name]) and torch.equal(null[name], indexed[name]), name
     monkeypatch.undo()
-    o = _nan(B, Nq, Cc, dtype)                           # refusals: nothing is launched, so the output keeps its NaN fill
+    o = nan_out(B, Nq, Cc, dtype)                           # refusals: nothing is launched, so the output keeps its NaN fill
     with pytest.raises(ValueError, match="nk_table must be a contiguous int32 device tensor of B = 4 entries"):
-        ops.attention(qq, o, [own, garment(CAP, index=_table(idx), nk_table=_table([CAP] * P))], HEADS, q_prescaled=True)
+        ops.attention(qq, o, [own, garment(CAP, index=int_table(idx), nk_table=int_table([CAP] * P))], HEADS, q_prescaled=True)
     with pytest.raises(ValueError, match="nk_table must be a contiguous int32 device tensor of B = 4 entries"):
         ops.attention_f8(q8, o, [own8, garment8(CAP, nk_table=torch.full((B,), CAP, device=DEV))], HEADS, **kw8)
     torch.cuda.synchronize()
@@ -189,90 +173,25 @@ def test_capacity_tables_and_null_tables_are_the_indexed_launch(dtype, monkeypat
 
 
 # ------------------------------------------------------------------------------------------------------------------ engine
-STEPS, H, W, P = 3, 128, 128, 3
-GARMENT_HW = [(64, 96), (128, 128), (72, 40)]            # A, B, C: latent 8x12, 16x16 (the slot's), 9x5 (odd: padded token rows)
-WEARS = [2, 0, 1]                                        # person i wears garment WEARS[i]
-
-
-def _model(dtype, fp8=False):
-    from tests.test_garment_size_gpu import _model as shared
-    return shared(dtype, fp8)
-
-
-def _engine(m, dtype):
-    from idm_vton_amd.pipeline import TryonEngine
-    return TryonEngine(*m["product"], dtype, DEV)
-
-
-@functools.lru_cache(maxsize=None)
-def _inputs(dtype):
-    """Persons' inputs (the garment keys dropped: every call here is on a cache) and the three garments' own inputs."""
-    from tests import parity_utils as pu
-    m = _model(dtype)
-    inp = pu.make_inputs(P, H, W, m["xd"], m["pooled"], m["enc_dim"], STEPS, dtype)
-    g = torch.Generator().manual_seed(77)
-    garments = [dict(cloth=torch.randn(1, 3, hg, wg, generator=g).clamp(-1, 1), noise_cloth=torch.randn(1, 4, hg // 8, wg // 8, generator=g),
-                     text_embeds_cloth=inp["text_embeds_cloth"][j:j + 1]) for j, (hg, wg) in enumerate(GARMENT_HW)]
-    return inp, garments
-
-
-def _base(inp, steps=STEPS):
-    return dict(num_inference_steps=steps, guidance_scale=2.0, scheduler="ddpm", **{**inp, "text_embeds_cloth": None, "noise": {**inp["noise"], "cloth": None}})
-
-
-def _run(eng, base, cache, form, index=None):
-    return eng.denoise(eng.prepare(**{**base, "cloth": cache, "garment_index": index}), **FORMS[form]).clone()
-
-
-def _encode(eng, garments, which=(0, 1, 2)):
-    return [eng.encode_garment(num_inference_steps=STEPS, height=H, width=W, **garments[j]) for j in which]
-
-
-def _slotted(eng, ones, hw=(H, W)):
-    pool = eng.empty_garment_cache(len(ones), hw[0], hw[1], STEPS, height=H, width=W)
-    for s, one in enumerate(ones):
-        pool.put(s, one)
-    return pool
-
-
-@functools.lru_cache(maxsize=None)
-def _oracle_latents(dtype):
-    """oracle.pipeline.run on each person alone (B = 1) with the cloth that person wears: the final latents, computed once per dtype."""
-    from oracle import pipeline as opipe
-    from oracle.scheduler import Scheduler
-    o_t, o_g, o_v = _model(dtype)["oracle"]
-    inp, garments = _inputs(dtype)
-    out = []
-    for i, j in enumerate(WEARS):
-        one = {k: v[i:i + 1] for k, v in inp.items() if k not in ("noise", "ip_hidden_states", "cloth", "text_embeds_cloth")}
-        one["ip_hidden_states"] = torch.cat([inp["ip_hidden_states"][i:i + 1], inp["ip_hidden_states"][P + i:P + i + 1]])
-        one["noise"] = {k: (v[:, i:i + 1] if k == "steps" else v[i:i + 1]) for k, v in inp["noise"].items() if k != "cloth"}
-        one["noise"]["cloth"] = garments[j]["noise_cloth"]
-        one.update(cloth=garments[j]["cloth"], text_embeds_cloth=garments[j]["text_embeds_cloth"])
-        tr = {}
-        with torch.no_grad():
-            opipe.run(o_t, o_g, o_v, Scheduler("ddpm"), num_inference_steps=STEPS, guidance_scale=2.0, trace=tr, **one)
-        out.append(tr["step_latents"][-1])
-    return out
 
 
 @DTYPES
 def test_persons_wearing_garments_of_three_sizes_match_the_oracle_per_person(dtype):
     from tests import parity_utils as pu
-    from tests.test_parity_gpu import TOL
-    m = _model(dtype)
-    eng = _engine(m, dtype)
-    inp, garments = _inputs(dtype)
-    ones = _encode(eng, garments)
-    pool = _slotted(eng, ones)
+    from tests.parity_checks import TOL
+    m = model(dtype)
+    eng = engine(m, dtype)
+    inp, garments = three_garments(dtype)
+    ones = encode_three(eng, garments)
+    pool = slotted_pool(eng, ones)
     assert pool.sizes == [(8, 12), (16, 16), (9, 5)] and (pool.gh, pool.gw) == (16, 16)
     # the analytic slot shapes are those of a garment encoded at the slot's size
     assert [(tuple(k.shape), tuple(vt.shape)) for k, vt in pool.select([1]).kv] == [(tuple(k.shape), tuple(vt.shape)) for k, vt in ones[1].kv]
-    st = eng.prepare(**{**_base(inp), "cloth": pool, "garment_index": WEARS})
+    st = eng.prepare(**{**base_call(inp, STEPS), "cloth": pool, "garment_index": WEARS})
     tokens = [m["product"][0].feature_tokens(*pool.sizes[g]) for g in WEARS]
     assert st["gnk"].dtype == torch.int32 and st["gnk"].tolist() == [[t[f] for t in tokens] * 2 for f in range(len(tokens[0]))]
     lat = eng.denoise(st)
-    for i, ref in enumerate(_oracle_latents(dtype)):
+    for i, ref in enumerate(oracle_latents(dtype)):
         err = pu.relerr(lat[i:i + 1], ref)
         print(f"{dtype} person {i} in garment {WEARS[i]} ({GARMENT_HW[WEARS[i]]}): latents against the oracle {err:.3e} (bar {TOL[dtype]['latents']:.1e})")
         assert err <= TOL[dtype]["latents"], (i, err)
@@ -286,9 +205,9 @@ def test_three_sizes_with_fp8_attention_match_the_oracle_within_the_variants_tol
     from idm_vton_amd.garment_cache import widen_f8
     from tests import parity_utils as pu
     dtype = torch.float16
-    eng = _engine(_model(dtype, True), dtype)
-    inp, garments = _inputs(dtype)
-    ones = _encode(eng, garments)
+    eng = engine(model(dtype, True), dtype)
+    inp, garments = three_garments(dtype)
+    ones = encode_three(eng, garments)
     assert {k.dtype for k, _ in ones[1].kv} == {torch.uint8, torch.float16} and {k.dtype for k, _ in ones[0].kv} == {torch.float16}
     _, ek, ev = eng.unet.f8_exp
     k8, vt8 = next((k, vt) for k, vt in ones[1].kv if k.dtype == torch.uint8)
@@ -296,74 +215,74 @@ def test_three_sizes_with_fp8_attention_match_the_oracle_within_the_variants_tol
     f8 = lambda t: t.view(torch.float8_e4m3fn).float()
     assert torch.equal(f8(ops.quant_f8(k16, 2.0 ** ek)), f8(k8))
     assert torch.equal(f8(ops.quant_f8(vt16.reshape(-1, vt16.shape[-1]), 2.0 ** ev, mode=1)), f8(vt8.reshape(-1, vt8.shape[-1])))
-    pool = _slotted(eng, ones)
+    pool = slotted_pool(eng, ones)
     assert {k.dtype for k, _ in pool.kv} == {torch.float16}
-    lat = _run(eng, _base(inp), pool, "serial_eager", WEARS)
-    for i, ref in enumerate(_oracle_latents(dtype)):
+    lat = run_on(eng, base_call(inp, STEPS), pool, "serial_eager", WEARS)
+    for i, ref in enumerate(oracle_latents(dtype)):
         err = pu.relerr(lat[i:i + 1], ref)
         print(f"fp8 attention, person {i} in garment {WEARS[i]}: latents against the oracle {err:.3e} (bar 8.0e-02)")
         assert err <= 8e-2, (i, err)
-    assert torch.equal(_run(eng, _base(inp), pool, "graph_overlap", WEARS), lat)
+    assert torch.equal(run_on(eng, base_call(inp, STEPS), pool, "graph_overlap", WEARS), lat)
 
 
 @DTYPES
 def test_every_execution_form_gives_the_bits_of_serial_eager_for_a_ragged_call(dtype):
-    eng = _engine(_model(dtype), dtype)
-    inp, garments = _inputs(dtype)
-    pool = _slotted(eng, _encode(eng, garments))
-    base = _base(inp)
-    ref = _run(eng, base, pool, "serial_eager", WEARS)
+    eng = engine(model(dtype), dtype)
+    inp, garments = three_garments(dtype)
+    pool = slotted_pool(eng, encode_three(eng, garments))
+    base = base_call(inp, STEPS)
+    ref = run_on(eng, base, pool, "serial_eager", WEARS)
     assert torch.isfinite(ref).all()
     for form in FORMS:
-        assert torch.equal(_run(eng, base, pool, form, WEARS), ref), form
-    assert not torch.equal(_run(eng, base, pool, "serial_eager", [0, 0, 0]), ref)          # and the assignment is read
+        assert torch.equal(run_on(eng, base, pool, form, WEARS), ref), form
+    assert not torch.equal(run_on(eng, base, pool, "serial_eager", [0, 0, 0]), ref)          # and the assignment is read
 
 
 def test_one_graph_state_serves_every_assignment_and_a_put_that_changes_a_slots_size():
     dtype = torch.float16
-    eng = _engine(_model(dtype), dtype)
-    inp, garments = _inputs(dtype)
-    ones = _encode(eng, garments)
-    pool = _slotted(eng, ones)
-    base = _base(inp)
+    eng = engine(model(dtype), dtype)
+    inp, garments = three_garments(dtype)
+    ones = encode_three(eng, garments)
+    pool = slotted_pool(eng, ones)
+    base = base_call(inp, STEPS)
     n_garm = eng.stats["garment_batches"]
     smallest = [2, 2, 2]                                 # every person in the 9x5 garment
     assign = [WEARS, smallest, [1, 1, 0]]
-    ref = {tuple(a): _run(eng, base, pool, "serial_eager", a) for a in assign}
+    ref = {tuple(a): run_on(eng, base, pool, "serial_eager", a) for a in assign}
     assert len({tuple(v.flatten().tolist()) for v in ref.values()}) == len(assign)
     for form in ("graph", "graph_overlap"):
         for a in assign + [WEARS]:
-            assert torch.equal(_run(eng, base, pool, form, a), ref[tuple(a)]), (form, a)
+            assert torch.equal(run_on(eng, base, pool, form, a), ref[tuple(a)]), (form, a)
     states = [k for k in eng._graphs if "ragged" in k]
     assert len(states) == 1 and len(eng._graphs) == 1
     ptr = pool.kv[0][0].data_ptr()
     pool.put(1, ones[2])                                 # the slot of the largest garment now holds the smallest
     assert pool.sizes == [(8, 12), (9, 5), (9, 5)] and pool.kv[0][0].data_ptr() == ptr
-    after = {tuple(a): _run(eng, base, pool, "serial_eager", a) for a in (WEARS, [1, 1, 0])}
-    assert torch.equal(_run(eng, base, pool, "serial_eager", [1, 1, 1]), ref[tuple(smallest)])    # slot 1 IS garment C now
+    after = {tuple(a): run_on(eng, base, pool, "serial_eager", a) for a in (WEARS, [1, 1, 0])}
+    assert torch.equal(run_on(eng, base, pool, "serial_eager", [1, 1, 1]), ref[tuple(smallest)])    # slot 1 IS garment C now
     assert not torch.equal(after[tuple(WEARS)], ref[tuple(WEARS)])
     for form in ("graph", "graph_overlap"):
         for a in (WEARS, [1, 1, 0]):
-            assert torch.equal(_run(eng, base, pool, form, a), after[tuple(a)]), (form, a)
+            assert torch.equal(run_on(eng, base, pool, form, a), after[tuple(a)]), (form, a)
     assert eng.stats["garment_batches"] == n_garm and list(eng._graphs) == states
 
 
 @DTYPES
 def test_a_slotted_cache_of_equal_sizes_gives_the_bits_of_the_plain_cache(dtype, monkeypatch):
     from idm_vton_amd import ffi, ops
-    eng = _engine(_model(dtype), dtype)
-    inp, _ = _inputs(dtype)
+    eng = engine(model(dtype), dtype)
+    inp, _ = three_garments(dtype)
     plain = eng.encode_garment(num_inference_steps=STEPS, cloth=inp["cloth"], text_embeds_cloth=inp["text_embeds_cloth"], noise_cloth=inp["noise"]["cloth"])
-    pool = _slotted(eng, [plain.select([g]) for g in range(3)])
+    pool = slotted_pool(eng, [plain.select([g]) for g in range(3)])
     assert pool.sizes == [(16, 16)] * 3 and plain.sizes is None and pool.rows == [None] * 3
     ragged = []
     real = ffi.call_ragged
     monkeypatch.setattr(ops.ffi, "call_ragged", lambda fn, *a: (ragged.append(fn), real(fn, *a))[1])
-    base = _base(inp)
+    base = base_call(inp, STEPS)
     for form in ("serial_eager", "graph_overlap"):
-        lat_p = _run(eng, base, plain, form, WEARS)
+        lat_p = run_on(eng, base, plain, form, WEARS)
         assert ragged == []                              # a plain cache: through _indexed, no table
-        lat_s = _run(eng, base, pool, form, WEARS)
+        lat_s = run_on(eng, base, pool, form, WEARS)
         assert len(ragged) > 0 and set(ragged) == {"idmvton_attn_fwd_ragged"}
         assert torch.isfinite(lat_p).all() and torch.equal(lat_s, lat_p), form
         del ragged[:]
@@ -373,17 +292,17 @@ def test_a_slotted_cache_of_equal_sizes_gives_the_bits_of_the_plain_cache(dtype,
 def test_refusals_come_before_anything_is_launched():
     from idm_vton_amd import ops
     dtype = torch.float16
-    eng = _engine(_model(dtype), dtype)
-    inp, garments = _inputs(dtype)
-    ones = _encode(eng, garments, which=(0, 1))
-    pool = _slotted(eng, [ones[0]] * 3)
+    eng = engine(model(dtype), dtype)
+    inp, garments = three_garments(dtype)
+    ones = encode_three(eng, garments, which=(0, 1))
+    pool = slotted_pool(eng, [ones[0]] * 3)
     torch.cuda.synchronize()
     launched = []
     real = ops._call
     ops._call = lambda *a, **kw: (launched.append(a[0]), real(*a, **kw))[1]
     try:
         with pytest.raises(ValueError, match="holds garments of several sizes: pass garment_index"):
-            eng.prepare(**{**_base(inp), "cloth": pool})
+            eng.prepare(**{**base_call(inp, STEPS), "cloth": pool})
         small = eng.empty_garment_cache(1, 64, 96, STEPS, height=H, width=W)
         with pytest.raises(ValueError, match="put: does not fit"):
             small.put(0, ones[1])                        # 128x128 into a 64x96 slot
@@ -396,35 +315,11 @@ def test_refusals_come_before_anything_is_launched():
 
 # ------------------------------------------------------------------------------------------------------------------ boundary
 def test_boundary_pipeline_passes_a_slotted_pool_through():
-    from idm_vton_amd import config as pc
-    from idm_vton_amd.boundary.scheduler import DDPMScheduler
-    from idm_vton_amd.boundary.vae import AutoencoderKL
     from idm_vton_amd.garment_cache import GarmentPool
-    from src.tryon_pipeline import StableDiffusionXLInpaintPipeline
-    from src.unet_hacked_garmnet import UNet2DConditionModel as G
-    from src.unet_hacked_tryon import UNet2DConditionModel as T
-    from tests import parity_utils as pu
-    from tests.test_garment_cache_gpu import _FakeCLIPVision
     DT = torch.float16
-    kw = dict(pu.TINY)
-    tcfg = pc.UNetConfig(mode="tryon", in_channels=13, sample_size=16, **kw)
-    gcfg = pc.UNetConfig(mode="garmnet", in_channels=4, addition_embed_type=None, encoder_hid_dim_type=None, sample_size=16, **kw)
-    vcfg = pc.VAEConfig(**pu.TINY_VAE)
-    rnd = lambda sd: {k: v.to(DT) for k, v in sd.items()}
-    t = T(tcfg, torch_dtype=DT); t.load_state_dict(rnd(pc.random_state_dict(pc.unet_param_shapes(tcfg), 1, torch.float32, "cpu")))
-    g = G(gcfg, torch_dtype=DT); g.load_state_dict(rnd(pc.random_state_dict(pc.unet_param_shapes(gcfg), 2, torch.float32, "cpu")))
-    v = AutoencoderKL(vcfg, torch_dtype=DT); v.load_state_dict(rnd(pc.random_state_dict(pc.vae_param_shapes(vcfg), 3, torch.float32, "cpu", std=0.05)))
-    torch.manual_seed(5)
-    enc = _FakeCLIPVision(kw["encoder_hid_dim"]).to(DT)
-    pipe = StableDiffusionXLInpaintPipeline(vae=v, text_encoder=None, text_encoder_2=None, tokenizer=None, tokenizer_2=None, unet=t,
-                                            unet_encoder=g, scheduler=DDPMScheduler(), image_encoder=enc).to(DEV)
+    pipe, enc, kw = boundary_pipeline(DT)
     B, steps = 3, 3
-    inp = pu.make_inputs(B, H, W, kw["cross_attention_dim"], 64, kw["encoder_hid_dim"], steps, DT)
-    clip_pix = torch.randn(B, 3, 224, 224, generator=torch.Generator().manual_seed(9))
-    call = dict(prompt_embeds=inp["prompt_embeds"], negative_prompt_embeds=inp["negative_prompt_embeds"],
-                pooled_prompt_embeds=inp["pooled_prompt_embeds"], negative_pooled_prompt_embeds=inp["negative_pooled_prompt_embeds"],
-                num_inference_steps=steps, strength=1.0, pose_img=inp["pose_img"], mask_image=inp["mask_image"], image=inp["image"],
-                height=H, width=W, guidance_scale=2.0, ip_adapter_image=clip_pix, output_type="pt")
+    inp, clip_pix, call = boundary_inputs(kw, B, H, W, steps, DT)
     small = torch.randn(1, 3, 64, 96, generator=torch.Generator().manual_seed(13)).clamp(-1, 1)
     cloths = {"small": (small, inp["text_embeds_cloth"][:1]), "full": (inp["cloth"][1:2], inp["text_embeds_cloth"][1:2])}
     encode = lambda key: pipe.encode_garment(cloths[key][0], cloths[key][1], steps, H, W, generator=torch.Generator(DEV).manual_seed(11))
@@ -438,19 +333,9 @@ def test_boundary_pipeline_passes_a_slotted_pool_through():
     img_c = pipe(generator=gen_c, cloth=pool.cache, text_embeds_cloth=None, garment_index=idx, **call)[0]
     assert eng.stats["garment_batches"] == n_garm
     # the engine-level call on the draws of the reference's order: the cloth draw (of the slot's latent size) is made and dropped
-    gen = torch.Generator(DEV).manual_seed(7)
-    torch.manual_seed(123)
-    draw = lambda gg, dt_: torch.randn((B, 4, H // 8, W // 8), generator=gg, device=DEV, dtype=dt_).float()
-    n_lat, n_masked, n_pose, _dropped = draw(gen, DT), draw(gen, torch.float32), draw(None, torch.float32), draw(gen, torch.float32)
-    n_steps = torch.stack([draw(gen, DT) for _ in range(steps)])
-    with torch.no_grad():
-        pos = enc(clip_pix.to(DEV, DT), output_hidden_states=True).hidden_states[-2]
-        neg = enc(torch.zeros_like(clip_pix).to(DEV, DT), output_hidden_states=True).hidden_states[-2]
-    ref = eng(image=inp["image"], mask_image=inp["mask_image"], pose_img=inp["pose_img"], cloth=pool.cache, garment_index=idx,
-              prompt_embeds=inp["prompt_embeds"], negative_prompt_embeds=inp["negative_prompt_embeds"],
-              pooled_prompt_embeds=inp["pooled_prompt_embeds"], negative_pooled_prompt_embeds=inp["negative_pooled_prompt_embeds"],
-              text_embeds_cloth=None, noise=dict(latents=n_lat, masked=n_masked, pose=n_pose, cloth=None, steps=n_steps),
-              num_inference_steps=steps, guidance_scale=2.0, ip_hidden_states=torch.cat([neg, pos]), scheduler="ddpm")
+    _, noise = reference_draws(7, 123, B, H, W, steps, DT)
+    ip = ip_states(enc, clip_pix)
+    ref = engine_reference(eng, inp, noise, ip, steps, cloth=pool.cache, garment_index=idx)
     assert torch.isfinite(img_c).all() and torch.equal(img_c, ref)
     with pytest.raises(ValueError, match="holds garments of several sizes: pass garment_index"):
         pipe(generator=gen_c, cloth=pool.cache, text_embeds_cloth=None, **call)

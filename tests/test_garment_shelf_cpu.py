@@ -8,9 +8,7 @@ import os
 import pytest
 import torch
 
-from tests.test_garment_stream_cpu import _fields
-
-PACKED = pytest.mark.parametrize("packed", [False, True], ids=["16bit", "packed"])
+from tests.garment_support import N_T, PACKED, SHELF_KINDS, SHELF_SLOT, apply_records, cpu_shelf, record_fields, same_packed, shelf_like, shelf_one
 
 
 # ------------------------------------------------------------------------------------------------------------------ ABI
@@ -96,38 +94,6 @@ def test_a_table_of_zero_runs_only_is_valid_up_to_its_last_check():
 
 
 # ------------------------------------------------------------------------------------------------------------------ garments
-SLOT = [(192, 64), (48, 128), (1040, 16)]                # (N_f, C_f) of the slot's three features; ld_f = N_f
-# A smaller, B the slot's size, C smaller with V^T row lengths that are no multiple of 64 (80, 16, 528)
-KINDS = {"a": ((8, 12), [(96, 64), (32, 128), (512, 16)]), "b": ((16, 12), SLOT), "c": ((9, 5), [(80, 64), (16, 128), (528, 16)])}
-N_T = 4
-
-
-def _one(kind, seed=0, dtype=torch.float16, **kw):
-    """A G = 1 cache of N_T timesteps at the compact size of KINDS[kind]: K [n * N'][C], V^T [n][C][N']."""
-    from idm_vton_amd.garment_cache import GarmentCache
-    (gh, gw), feats = KINDS[kind]
-    g = torch.Generator().manual_seed(100 * seed + ord(kind))
-    kv = [(torch.randn(N_T * N, Cc, generator=g).to(dtype), torch.randn(N_T, Cc, N, generator=g).to(dtype)) for N, Cc in feats]
-    args = dict(G=1, timesteps=list(range(900, 900 - 200 * N_T, -200)), h=16, w=12, gh=gh, gw=gw, dtype=dtype, attn_fp8=False, f8_exp=(2, 2, 2),
-                weights_id="w0", kv=kv)
-    args.update(kw)
-    return GarmentCache(**args)
-
-
-def _like(dtype=torch.float16):
-    """What TryonEngine.empty_garment_cache gives: one uninitialised slot of the slot's shapes, with `sizes`."""
-    from idm_vton_amd.garment_cache import GarmentCache
-    kv = [(torch.empty(N_T * N, Cc, dtype=dtype), torch.empty(N_T, Cc, N, dtype=dtype)) for N, Cc in SLOT]
-    return GarmentCache(G=1, timesteps=list(range(900, 900 - 200 * N_T, -200)), h=16, w=12, gh=16, gw=12, dtype=dtype, attn_fp8=False, f8_exp=(2, 2, 2),
-                        weights_id="w0", kv=kv, sizes=[(16, 12)])
-
-
-def _shelf(packed, dtype=torch.float16, **kw):
-    from idm_vton_amd.garment_cache import GarmentShelf
-    shelf = GarmentShelf(_like(dtype), storage="e4m3" if packed else "native", **kw)
-    for kind in "abc":
-        shelf.add(kind, _one(kind, dtype=dtype))
-    return shelf
 
 
 # ------------------------------------------------------------------------------------------------------------------ records
@@ -157,24 +123,6 @@ def _restated(parts, packed, dst, k, S, entries, tslots, gslots, address):
     return out
 
 
-def _apply(rec, packed, dtype):
-    """The interpreter: what idmvton_kv_fill does with a record table, on host memory, by address and by rows -- a byte copy, unpack_values
-    for a widening data run (the exponent read through its address), zeros for a zero run."""
-    from idm_vton_amd.garment_cache import unpack_values
-    for src, dst, exp, rows, cols, lds, ldd in _fields(rec):
-        ldd_bytes = ldd * 2 if packed else ldd
-        out_bytes = cols * 2 if packed else cols
-        for r in range(rows):
-            if src == 0:
-                C.memset(dst + r * ldd_bytes, 0, out_bytes)
-            elif not packed:
-                C.memmove(dst + r * ldd_bytes, src + r * lds, cols)
-            else:
-                b = torch.frombuffer(bytearray(C.string_at(src + r * lds, cols)), dtype=torch.uint8)
-                x = unpack_values(b, torch.tensor(C.c_int32.from_address(exp).value), dtype).contiguous()
-                C.memmove(dst + r * ldd_bytes, x.data_ptr(), out_bytes)
-
-
 @PACKED
 @pytest.mark.parametrize("garments", [[2, 0], [2, 1]], ids=["c,a", "c,b"])
 def test_shelf_records_against_a_restatement_and_an_interpreter(packed, garments):
@@ -185,7 +133,7 @@ def test_shelf_records_against_a_restatement_and_an_interpreter(packed, garments
     from idm_vton_amd import ffi, ops
     from idm_vton_amd.garment_cache import shelf_records, slot_run
     dtype = torch.float16
-    shelf = _shelf(packed)
+    shelf = cpu_shelf(packed)
     cache, index = shelf.get(["a", "b", "c"])
     assert index == [0, 1, 2] and cache.G == 3 and cache.packed == packed
     k, S, entries, tslots, gslots = 3, 3, [3, 1, 2], [0, 1, 2], [0, 1]
@@ -193,7 +141,7 @@ def test_shelf_records_against_a_restatement_and_an_interpreter(packed, garments
     ref = cache.slotted()
     n = len(ref.timesteps)
     for fill in (0x00, 0x7f):
-        dst = [(torch.empty(k * S * N, Cc, dtype=dtype), torch.empty(k * S, Cc, N, dtype=dtype)) for N, Cc in SLOT]
+        dst = [(torch.empty(k * S * N, Cc, dtype=dtype), torch.empty(k * S, Cc, N, dtype=dtype)) for N, Cc in SHELF_SLOT]
         for t in (t for kvf in dst for t in kvf):
             t.view(torch.uint8).fill_(fill)
         asked = []
@@ -205,22 +153,22 @@ def test_shelf_records_against_a_restatement_and_an_interpreter(packed, garments
         want = sorted(t.data_ptr() for p in parts for kvf in p.kv for t in kvf) + ([p.exps.data_ptr() for p in parts] if packed else [])
         assert sorted(asked) == sorted(want)                                                 # once per tensor
         assert rec.dtype == torch.int64 and rec.is_contiguous() and per % 2 == 0 and tuple(rec.shape) == (len(entries) * per, 5)
-        assert _fields(rec) == _restated(parts, packed, dst, k, S, entries, tslots, gslots, lambda t: t.data_ptr())
-        zero = [r for r in _fields(rec) if r[0] == 0]
+        assert record_fields(rec) == _restated(parts, packed, dst, k, S, entries, tslots, gslots, lambda t: t.data_ptr())
+        zero = [r for r in record_fields(rec) if r[0] == 0]
         assert zero and all(r[2] == 0 for r in zero)
-        raw = sum(3 if ld1 < ld else 2 for g in garments for (ld1, _), (ld, _) in zip(KINDS["abc"[g]][1], SLOT))
+        raw = sum(3 if ld1 < ld else 2 for g in garments for (ld1, _), (ld, _) in zip(SHELF_KINDS["abc"[g]][1], SHELF_SLOT))
         assert per == raw + raw % 2 and (raw % 2 == 1) == (garments == [2, 1])
         # every launched slice starts at an even record index, and the prefix tables count a zero run like a data run
         table = ops.KvFillTable(rec, "cpu", ffi.KVS_WIDEN_E4M3 if packed else ffi.KVS_COPY, [(t * per, per) for t in range(len(entries))])
         assert all(f % 2 == 0 for f, _ in table.slices) and table.ENTRY == "kv_fill"
-        items = [r[3] * (r[4] // 16) for r in _fields(rec)]
+        items = [r[3] * (r[4] // 16) for r in record_fields(rec)]
         assert table.items.tolist() == items
         assert table.first_host[:per + 1].tolist() == [sum((it + 1023) // 1024 for it in items[:m]) for m in range(per + 1)]
-        data = sum(it for it, r in zip(items, _fields(rec)) if r[0])
+        data = sum(it for it, r in zip(items, record_fields(rec)) if r[0])
         assert table.link_bytes() == 16.0 * data and table.bytes_moved(0, table.n) == 16.0 * data + (32.0 if packed else 16.0) * sum(items)
         with pytest.raises(ValueError, match="an even first index"):
             ops.KvFillTable(rec, "cpu", ffi.KVS_COPY, [(1, 2)])
-        _apply(rec, packed, dtype)
+        apply_records(rec, packed, dtype)
         pattern = torch.full((1,), fill, dtype=torch.uint8)
         for i, j in zip(entries, tslots):
             for u in range(S):
@@ -230,7 +178,7 @@ def test_shelf_records_against_a_restatement_and_an_interpreter(packed, garments
                         assert (dk.view(torch.uint8) == pattern).all() and (dv.view(torch.uint8) == pattern).all()
                         continue
                     rk, rv = slot_run(ref.kv, n, ref.G, i, g)[f]
-                    Nf = KINDS["abc"[g]][1][f][0]
+                    Nf = SHELF_KINDS["abc"[g]][1][f][0]
                     assert torch.equal(dv.view(torch.int16), rv.view(torch.int16)), (fill, i, u, f)
                     assert torch.equal(dk[:Nf].view(torch.int16), rk[:Nf].view(torch.int16)), (fill, i, u, f)
                     assert (dk[Nf:].view(torch.uint8) == pattern).all(), (fill, i, u, f)
@@ -267,24 +215,24 @@ def test_kv_pad_even_repeats_the_smallest_record():
 @PACKED
 def test_shelf_add_get_lru_and_eviction(packed):
     from idm_vton_amd.garment_cache import GarmentShelf, PackedGarmentCache, ShelvedGarmentCache
-    shelf = _shelf(packed)
+    shelf = cpu_shelf(packed)
     assert len(shelf) == 3 and "a" in shelf and "z" not in shelf and shelf.keys() == ["a", "b", "c"]
     sizes = {key: shelf._parts[key].nbytes for key in "abc"}
     assert shelf.nbytes == sum(sizes.values()) and sizes["a"] < sizes["b"] and sizes["c"] < sizes["b"]
     esz = 1 if packed else 2
     for key in "abc":                                    # compact: the garment's own rows and positions, nothing of the slot
-        want = sum(2 * N_T * N * Cc * esz for N, Cc in KINDS[key][1]) + (4 * 3 * 2 if packed else 0)
+        want = sum(2 * N_T * N * Cc * esz for N, Cc in SHELF_KINDS[key][1]) + (4 * 3 * 2 if packed else 0)
         assert sizes[key] == want and isinstance(shelf._parts[key], PackedGarmentCache) == packed
     cache, index = shelf.get(["c", "a", "c"])
     assert isinstance(cache, ShelvedGarmentCache) and index == [0, 1, 0] and cache.G == 2 and cache.sizes == [(9, 5), (8, 12)]
     assert (cache.gh, cache.gw) == (16, 12) and cache.host_resident and cache.packed == packed and cache.kv == []
-    assert cache.slot_shapes == [((N, Cc), (Cc, N)) for N, Cc in SLOT]
+    assert cache.slot_shapes == [((N, Cc), (Cc, N)) for N, Cc in SHELF_SLOT]
     assert cache.nbytes == sizes["a"] + sizes["c"] < 2 * sizes["b"]                           # smaller than G x slot bytes
     assert shelf.keys() == ["b", "c", "a"] and shelf.stats == dict(hits=2, encoded=0, restored=0, evicted=0)
     assert "slots of 16x12" in repr(cache) and "ShelvedGarmentCache(G=2" in repr(cache)
     # encode: once per missing distinct key; KeyError without one, before anything changes
     calls = []
-    enc = lambda key: (calls.append(key), _one("a", seed=ord(key)))[1]
+    enc = lambda key: (calls.append(key), shelf_one("a", seed=ord(key)))[1]
     with pytest.raises(KeyError, match="'x' is not on the shelf"):
         shelf.get(["a", "x"])
     cache2, index2 = shelf.get(["x", "b", "x", "y"], encode=enc)
@@ -298,16 +246,16 @@ def test_shelf_add_get_lru_and_eviction(packed):
         shelf.get(["c", "q"], encode=boom)
     assert (shelf.keys(), dict(shelf.stats), shelf.nbytes) == before
     # max_bytes: the least recently used garments the batch does not name go until the shelf fits
-    small = GarmentShelf(_like(), storage="e4m3" if packed else "native", max_bytes=2 * sizes["b"] + 100)
+    small = GarmentShelf(shelf_like(), storage="e4m3" if packed else "native", max_bytes=2 * sizes["b"] + 100)
     for key in "abc":
-        small.add(key, _one(key))
+        small.add(key, shelf_one(key))
     kept, _ = small.get(["a"])                               # a is now the most recently used
-    _, idx = small.get(["d", "b"], encode=lambda key: _one("c", seed=7))
+    _, idx = small.get(["d", "b"], encode=lambda key: shelf_one("c", seed=7))
     assert idx == [0, 1] and small.keys() == ["a", "d", "b"] and small.stats["evicted"] == 1 and small.nbytes <= small.max_bytes
-    _, idx = small.get(["e"], encode=lambda key: _one("b", seed=8))
+    _, idx = small.get(["e"], encode=lambda key: shelf_one("b", seed=8))
     assert small.keys() == ["b", "e"] and small.stats["evicted"] == 3                         # a and d went, in that order; never e
     with pytest.raises(ValueError, match="the batch alone holds"):
-        small.get(["f", "g", "b"], encode=lambda key: _one("b", seed=9))
+        small.get(["f", "g", "b"], encode=lambda key: shelf_one("b", seed=9))
     assert small.keys() == ["b", "e"]
     # the cache keeps its parts alive whatever the shelf does
     part = kept.parts[0]
@@ -317,43 +265,42 @@ def test_shelf_add_get_lru_and_eviction(packed):
 
 def test_shelf_packs_a_16bit_garment_on_its_way_in_and_takes_packed_ones():
     from idm_vton_amd.garment_cache import GarmentShelf
-    from tests.test_garment_packed_cpu import _same
-    shelf = GarmentShelf(_like(), storage="e4m3")
-    shelf.add("a", _one("a"))
-    shelf.add("a2", _one("a").pack())
-    assert _same(shelf._parts["a"], _one("a").pack()) and _same(shelf._parts["a2"], shelf._parts["a"])
-    one_slot = _like()                                   # a one-slot slotted cache holding a small garment: taken at its compact size
-    one_slot.put(0, _one("c"))
+    shelf = GarmentShelf(shelf_like(), storage="e4m3")
+    shelf.add("a", shelf_one("a"))
+    shelf.add("a2", shelf_one("a").pack())
+    assert same_packed(shelf._parts["a"], shelf_one("a").pack()) and same_packed(shelf._parts["a2"], shelf._parts["a"])
+    one_slot = shelf_like()                                   # a one-slot slotted cache holding a small garment: taken at its compact size
+    one_slot.put(0, shelf_one("c"))
     shelf.add("c", one_slot)
-    assert _same(shelf._parts["c"], _one("c").pack()) and (shelf._parts["c"].gh, shelf._parts["c"].gw) == (9, 5)
+    assert same_packed(shelf._parts["c"], shelf_one("c").pack()) and (shelf._parts["c"].gh, shelf._parts["c"].gw) == (9, 5)
 
 
 def test_shelf_refusals():
     from idm_vton_amd.garment_cache import GarmentCache, GarmentShelf
-    shelf = GarmentShelf(_like(), storage="native")
+    shelf = GarmentShelf(shelf_like(), storage="native")
     with pytest.raises(ValueError, match="storage='fp4'"):
-        GarmentShelf(_like(), storage="fp4")
+        GarmentShelf(shelf_like(), storage="fp4")
     for field, kw in (("timesteps", dict(timesteps=[900, 700, 500, 100])), ("h", dict(h=32)), ("w", dict(w=8)), ("f8_exp", dict(f8_exp=(1, 2, 2))),
                       ("weights_id", dict(weights_id="w1"))):
         with pytest.raises(ValueError, match=f"GarmentShelf add: {field} mismatch"):
-            shelf.add("x", _one("a", **kw))
+            shelf.add("x", shelf_one("a", **kw))
     with pytest.raises(ValueError, match="GarmentShelf add: dtype mismatch"):
-        shelf.add("x", _one("a", dtype=torch.bfloat16))
+        shelf.add("x", shelf_one("a", dtype=torch.bfloat16))
     with pytest.raises(ValueError, match="GarmentShelf add: attn_fp8 mismatch"):
-        shelf.add("x", _one("a", attn_fp8=True))
+        shelf.add("x", shelf_one("a", attn_fp8=True))
     with pytest.raises(ValueError, match="GarmentShelf add: packed mismatch"):
-        shelf.add("x", _one("a").pack())
+        shelf.add("x", shelf_one("a").pack())
     with pytest.raises(ValueError, match="GarmentShelf add: G mismatch"):
-        shelf.add("x", GarmentCache.cat([_one("a"), _one("a")]))
-    big = _one("b")
+        shelf.add("x", GarmentCache.cat([shelf_one("a"), shelf_one("a")]))
+    big = shelf_one("b")
     big.kv[2] = (torch.zeros(N_T * 1056, 16, dtype=torch.float16), torch.zeros(N_T, 16, 1056, dtype=torch.float16))
     with pytest.raises(ValueError, match=r"does not fit \(feature 2: .*K rows 1056 x 16.*holds 1040 x 16"):
         shelf.add("x", big)
-    wide = _one("a")
+    wide = shelf_one("a")
     wide.kv[0] = (torch.zeros(N_T * 96, 80, dtype=torch.float16), torch.zeros(N_T, 80, 96, dtype=torch.float16))
     with pytest.raises(ValueError, match=r"does not fit \(feature 0"):
         shelf.add("x", wide)
-    two = _one("a")
+    two = shelf_one("a")
     two.kv = two.kv[:2]
     with pytest.raises(ValueError, match=r"does not fit \(2 features against 3\)"):
         shelf.add("x", two)
@@ -363,7 +310,7 @@ def test_shelf_refusals():
 @PACKED
 def test_shelved_cache_methods(packed):
     from idm_vton_amd.garment_cache import GarmentCache
-    shelf = _shelf(packed)
+    shelf = cpu_shelf(packed)
     cache, _ = shelf.get(["a", "b", "c"])
     kw = dict(timesteps=[700, 300], h=16, w=12, dtype=torch.float16, attn_fp8=False, f8_exp=(2, 2, 2), weights_id="w0")
     assert cache.check(persons=4, garment_index=[2, 0, 2, 1], **kw) == ([1, 3], [2, 0, 2, 1])
@@ -376,14 +323,14 @@ def test_shelved_cache_methods(packed):
     assert (other.h, other.w) == (32, 24) and other.parts == cache.parts and other.sizes == cache.sizes
     assert other.check(persons=1, garment_index=[1], **{**kw, "h": 32, "w": 24}) == ([1, 3], [1])
     # methods that need one tensor list say so by name
-    for name, args in (("put", (0, _one("a"))), ("save", ("x.safetensors",)), ("pack", ()), ("unpack", ()), ("repeat_garments", (2,)), ("run", (0,)),
+    for name, args in (("put", (0, shelf_one("a"))), ("save", ("x.safetensors",)), ("pack", ()), ("unpack", ()), ("repeat_garments", (2,)), ("run", (0,)),
                        ("step", (0,)), ("to", ("cpu",)), ("cat", ([cache, cache],))):
         with pytest.raises(ValueError, match=f"ShelvedGarmentCache {name}:"):
             getattr(cache, name)(*args)
     # take: a copy of the part; select: the same parts in another order; slotted: empty slots + put(take(g))
     for g, key in enumerate("abc"):
         t = cache.take(g)
-        assert t.G == 1 and t.packed == packed and (t.gh, t.gw) == KINDS[key][0] and t.kv[0][0].data_ptr() != cache.parts[g].kv[0][0].data_ptr()
+        assert t.G == 1 and t.packed == packed and (t.gh, t.gw) == SHELF_KINDS[key][0] and t.kv[0][0].data_ptr() != cache.parts[g].kv[0][0].data_ptr()
         assert all(torch.equal(x, y) and torch.equal(u, v) for (x, u), (y, v) in zip(t.kv, cache.parts[g].kv))
         assert not packed or torch.equal(t.exps, cache.parts[g].exps)
     with pytest.raises(ValueError, match="take: slot mismatch"):
@@ -393,8 +340,8 @@ def test_shelved_cache_methods(packed):
     ref = cache.slotted()
     assert type(ref) is GarmentCache
     assert ref.sizes == cache.sizes and (ref.gh, ref.gw) == (16, 12) and ref.G == 3 and not ref.packed and ref.kv[0][0].dtype == torch.float16
-    by_hand = GarmentCache(**{**_like()._args(), "G": 3, "sizes": [(16, 12)] * 3, "rows": None,
-                              "kv": [(torch.zeros(N_T * 3 * N, Cc, dtype=torch.float16), torch.zeros(N_T * 3, Cc, N, dtype=torch.float16)) for N, Cc in SLOT]})
+    by_hand = GarmentCache(**{**shelf_like()._args(), "G": 3, "sizes": [(16, 12)] * 3, "rows": None,
+                              "kv": [(torch.zeros(N_T * 3 * N, Cc, dtype=torch.float16), torch.zeros(N_T * 3, Cc, N, dtype=torch.float16)) for N, Cc in SHELF_SLOT]})
     for g in range(3):
         one = cache.take(g)
         by_hand.put(g, one.unpack() if packed else one)
@@ -410,6 +357,6 @@ def test_shelved_cache_methods(packed):
 # ------------------------------------------------------------------------------------------------------------------ what stays
 def test_the_locked_refusals_still_hold():
     from idm_vton_amd.garment_cache import GarmentPool
-    one = _one("b")
+    one = shelf_one("b")
     with pytest.raises(ValueError, match=r'resident="host" cannot be combined with mixed_sizes'):
         GarmentPool(2, like=one, mixed_sizes=True, resident="host")

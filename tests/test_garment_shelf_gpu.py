@@ -7,24 +7,14 @@ graph state; the refusals; the boundary pipeline.  A chunk is 1024 16-byte items
 import pytest
 import torch
 
-from tests.test_garment_cache_gpu import FORMS
-from tests.test_garment_packed_gpu import _assert_bits, _bytes
-from tests.test_garment_ragged_gpu import H, STEPS, W, WEARS, _base, _encode, _engine, _inputs, _model, _run
-from tests.test_garment_stream_gpu import _pinned
+from tests.engine_support import (DEV, KEYS, MIXED_DSTS, MIXED_RUNS, STEPS, WEARS, H, W, base_call, boundary_inputs, boundary_pipeline, check_fill, e4m3_bytes,
+                                  encode_three, engine, engine_reference, gpu_shelf, ip_states, model, pin_frame, reference_draws, run_on, three_garments)
+from tests.garment_support import DTYPES, FORMS
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-DTYPES = pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
 
 
 # ------------------------------------------------------------------------------------------------------------------ kernel
-# destinations: (rows, width, row stride) in 16-bit elements; runs: ("d", rows, cols, source row stride, exponent, destination, first column)
-# or ("z", rows, cols, destination, first column), cols in elements
-MIXED_DSTS = [(5, 112, 128), (70, 256, 256), (33, 512, 520)]
-MIXED_RUNS = [("d", 5, 48, 64, -3, 0, 0),                # a compact run into the front of a wider destination ...
-              ("z", 5, 64, 0, 48),                       # ... and the zero tail behind it: together they cover its 112 columns
-              ("d", 70, 256, 256, 5, 1, 0),              # 1120 items when widening: one full chunk and one partial chunk
-              ("z", 33, 512, 2, 0)]                      # 1056 items when widening
 
 
 def _fill(dsts, runs, dtype, workgroups, copy=False, on_device=()):
@@ -43,34 +33,13 @@ def _fill(dsts, runs, dtype, workgroups, copy=False, on_device=()):
             descs.append((None, outs[d][:rows, c0:c0 + cols], None))
             continue
         _, rows, cols, lds, e, d, c0 = run
-        x = torch.randn(rows, cols, generator=torch.Generator().manual_seed(i)).to(dtype) if copy else _bytes(rows, cols, seed=i)
-        s = frames.framed(x.to(DEV), lds) if i in on_device else _pinned(frames.framed(x, lds))
+        x = torch.randn(rows, cols, generator=torch.Generator().manual_seed(i)).to(dtype) if copy else e4m3_bytes(rows, cols, seed=i)
+        s = frames.framed(x.to(DEV), lds) if i in on_device else pin_frame(frames.framed(x, lds))
         srcs[i], vals[i] = s, x
         descs.append((s, outs[d][:rows, c0:c0 + cols], None if copy else (exps_d if i in on_device else exps_h)[i:i + 1]))
     table = ops.kv_fill(descs, dtype, mode=ffi.KVS_COPY if copy else ffi.KVS_WIDEN_E4M3, workgroups=workgroups)
     torch.cuda.synchronize()
     return outs, srcs, vals, table
-
-
-def _check(dsts, runs, outs, srcs, vals, dtype, copy=False):
-    from idm_vton_amd.garment_cache import unpack_values
-    from tests import frames
-    for d, o in enumerate(outs):
-        frames.assert_all_written(o, f"destination {d}")
-        frames.assert_frame_intact(o, f"destination {d}")    # guard bands and the gap columns [width, ld)
-    for i, run in enumerate(runs):
-        if run[0] == "z":
-            _, rows, cols, d, c0 = run
-            got = frames.ints(outs[d][:rows, c0:c0 + cols].cpu().contiguous())
-            assert (got == 0).all(), f"run {i}: a zero run's bits are 0x0000, got {sorted(set(got.flatten().tolist()))[:4]}"
-            continue
-        _, rows, cols, lds, e, d, c0 = run
-        frames.assert_untouched(srcs[i], f"run {i} source")
-        got = outs[d][:rows, c0:c0 + cols]
-        if copy:
-            assert torch.equal(frames.ints(got.cpu().contiguous()), frames.ints(vals[i])), f"run {i}: not the source's bits"
-        else:
-            _assert_bits(got, unpack_values(vals[i], torch.tensor(e), dtype), vals[i], f"run {i}: not the format's bits")
 
 
 @DTYPES
@@ -82,7 +51,7 @@ def test_kv_fill_widens_data_runs_and_writes_zero_runs_in_one_table(dtype, workg
     assert table.host[:, 0].ne(0).tolist() == [True, False, True, False] and table.host[1, 2] == 0
     assert all(not s.is_cuda and s.is_pinned() for s in srcs.values())
     assert table.link_bytes() == 16.0 * (15 + 1120)
-    _check(MIXED_DSTS, MIXED_RUNS, outs, srcs, vals, dtype)
+    check_fill(MIXED_DSTS, MIXED_RUNS, outs, srcs, vals, dtype)
 
 
 ORDERINGS = {"zdz": "zdz", "dzd": "dzd", "zdzd": "zdzd", "zzz": "zzz"}
@@ -103,7 +72,7 @@ def test_kv_fill_orderings_of_single_chunk_runs_with_one_workgroup(order):
     assert table.first_host.tolist() == list(range(len(runs) + 1))
     if order == "zzz":
         assert not srcs and (table.host[:, 0] == 0).all() and (table.host[:, 2] == 0).all() and table.link_bytes() == 0.0
-    _check(dsts, runs, outs, srcs, vals, dtype)
+    check_fill(dsts, runs, outs, srcs, vals, dtype)
 
 
 @DTYPES
@@ -112,13 +81,13 @@ def test_kv_fill_copy_mode(dtype, workgroups):
     """The same table with 16-bit sources in pinned memory: byte units (30, 40, 2240 and 2112 items), zero BYTES."""
     outs, srcs, vals, table = _fill(MIXED_DSTS, MIXED_RUNS, dtype, workgroups, copy=True)
     assert table.items.tolist() == [30, 40, 2240, 2112] and table.first_host.tolist() == [0, 1, 2, 5, 8]
-    _check(MIXED_DSTS, MIXED_RUNS, outs, srcs, vals, dtype, copy=True)
+    check_fill(MIXED_DSTS, MIXED_RUNS, outs, srcs, vals, dtype, copy=True)
 
 
 def test_kv_fill_one_table_mixes_host_and_device_sources_with_zero_runs():
     outs, srcs, vals, _ = _fill(MIXED_DSTS, MIXED_RUNS, torch.bfloat16, 8, on_device=(2,))
     assert [srcs[i].is_cuda for i in sorted(srcs)] == [False, True]
-    _check(MIXED_DSTS, MIXED_RUNS, outs, srcs, vals, torch.bfloat16)
+    check_fill(MIXED_DSTS, MIXED_RUNS, outs, srcs, vals, torch.bfloat16)
 
 
 def test_kv_fill_wrapper_refuses_a_malformed_run():
@@ -135,44 +104,34 @@ def test_kv_fill_wrapper_refuses_a_malformed_run():
 
 
 # ------------------------------------------------------------------------------------------------------------------ engine
-KEYS = ["g0", "g1", "g2"]                                # the three garments of tests/test_garment_ragged_gpu.py: latent 8x12, 16x16 (the slot's), 9x5
-
-
-def _shelf(eng, ones, storage):
-    from idm_vton_amd.garment_cache import GarmentShelf
-    shelf = GarmentShelf(eng.empty_garment_cache(1, H, W, STEPS, height=H, width=W), storage=storage)
-    for key, one in zip(KEYS, ones):
-        shelf.add(key, one)
-    assert all(k.is_pinned() and vt.is_pinned() for p in shelf._parts.values() for k, vt in p.kv)
-    return shelf
 
 
 def _against_the_slotted_device_cache(dtype, storage):
-    eng = _engine(_model(dtype), dtype)
-    inp, garments = _inputs(dtype)
-    shelf = _shelf(eng, _encode(eng, garments), storage)
+    eng = engine(model(dtype), dtype)
+    inp, garments = three_garments(dtype)
+    shelf = gpu_shelf(eng, encode_three(eng, garments), storage)
     assert shelf.nbytes == sum(p.nbytes for p in shelf._parts.values()) < 3 * shelf._parts["g1"].nbytes       # compact: less than 3 slots
     shelved, index = shelf.get([KEYS[j] for j in WEARS])
     assert index == [0, 1, 2] and shelved.sizes == [(9, 5), (8, 12), (16, 16)] and shelved.packed == (storage == "e4m3") and shelved.host_resident
     device = shelved.slotted(DEV)
     assert device.sizes == shelved.sizes and not device.host_resident and not device.packed
-    base = _base(inp)
+    base = base_call(inp, STEPS)
     nblocks = len(eng._block_schedule(STEPS)[1])
     assert nblocks == 2
     for form in FORMS:                                   # (the device call first: a graph form's state then exists and must serve the shelved call)
-        lat_d = _run(eng, base, device, form, index)
+        lat_d = run_on(eng, base, device, form, index)
         states, n0, c0 = len(eng._graphs), eng.stats["garment_stream_launches"], eng.stats["garment_set_copies"]
-        lat_s = _run(eng, base, shelved, form, index)
+        lat_s = run_on(eng, base, shelved, form, index)
         assert torch.isfinite(lat_d).all() and torch.isfinite(lat_s).all(), form
         assert torch.equal(lat_s, lat_d), (form, (lat_s - lat_d).abs().max().item())
         assert eng.stats["garment_stream_launches"] - n0 == nblocks, form
         assert eng.stats["garment_set_copies"] == c0 and len(eng._graphs) == states, form
-    assert not torch.equal(_run(eng, base, shelved, "serial_eager", [0, 0, 1]), lat_d)        # and the assignment is read
+    assert not torch.equal(run_on(eng, base, shelved, "serial_eager", [0, 0, 1]), lat_d)        # and the assignment is read
     # the reverse: a state built by a shelved call serves the device-resident slotted cache
-    fresh = _engine(_model(dtype), dtype)
-    lat_s = _run(fresh, base, shelved, "graph_overlap", index)
+    fresh = engine(model(dtype), dtype)
+    lat_s = run_on(fresh, base, shelved, "graph_overlap", index)
     states = len(fresh._graphs)
-    assert torch.equal(_run(fresh, base, device, "graph_overlap", index), lat_s) and len(fresh._graphs) == states == 1 and torch.equal(lat_s, lat_d)
+    assert torch.equal(run_on(fresh, base, device, "graph_overlap", index), lat_s) and len(fresh._graphs) == states == 1 and torch.equal(lat_s, lat_d)
 
 
 @DTYPES
@@ -189,19 +148,19 @@ def test_slot_reuse_through_one_graph_state():
     """Set slot 0 holds the largest garment, then the smallest (its zero tail has to replace the larger garment's values), then the call's
     three; a fourth call names a garment `get` has to encode.  Each against the slotted device call of that assignment."""
     dtype = torch.float16
-    eng = _engine(_model(dtype), dtype)
-    fresh = _engine(_model(dtype), dtype)                # the reference runs apart: its sets never held another garment
-    inp, garments = _inputs(dtype)
-    ones = _encode(eng, garments)
-    shelf = _shelf(eng, ones[1:], "e4m3")                # g0 = ones[1] (16x16), g1 = ones[2] (9x5): KEYS[:2]
-    base = _base(inp)
+    eng = engine(model(dtype), dtype)
+    fresh = engine(model(dtype), dtype)                # the reference runs apart: its sets never held another garment
+    inp, garments = three_garments(dtype)
+    ones = encode_three(eng, garments)
+    shelf = gpu_shelf(eng, ones[1:], "e4m3")                # g0 = ones[1] (16x16), g1 = ones[2] (9x5): KEYS[:2]
+    base = base_call(inp, STEPS)
     encoded = []
     enc = lambda key: (encoded.append(key), ones[0])[1]
     for form in ("graph", "graph_overlap"):
         for keys in (["g0"] * 3, ["g1"] * 3, ["g1", "g0", "g1"], ["new", "g0", "new"]):
             shelved, index = shelf.get(keys, encode=enc)
-            lat = _run(eng, base, shelved, form, index)
-            ref = _run(fresh, base, shelved.slotted(DEV), "serial_eager", index)
+            lat = run_on(eng, base, shelved, form, index)
+            ref = run_on(fresh, base, shelved.slotted(DEV), "serial_eager", index)
             assert torch.isfinite(lat).all() and torch.equal(lat, ref), (form, keys, (lat - ref).abs().max().item())
     assert encoded == ["new"] and "new" in shelf and len(eng._graphs) == 1
 
@@ -210,12 +169,12 @@ def test_shelved_refusals_come_before_anything_is_launched():
     from idm_vton_amd import ops
     from idm_vton_amd.garment_cache import ShelvedGarmentCache
     dtype = torch.float16
-    eng = _engine(_model(dtype), dtype)
-    inp, garments = _inputs(dtype)
-    ones = _encode(eng, garments, which=(0, 1))
-    shelf = _shelf(eng, ones, "e4m3")
+    eng = engine(model(dtype), dtype)
+    inp, garments = three_garments(dtype)
+    ones = encode_three(eng, garments, which=(0, 1))
+    shelf = gpu_shelf(eng, ones, "e4m3")
     good, index = shelf.get(["g0", "g1", "g0"])
-    base = _base(inp)
+    base = base_call(inp, STEPS)
     torch.cuda.synchronize()
     stats, launched = dict(eng.stats), []
     real = ops._call
@@ -238,7 +197,7 @@ def test_shelved_refusals_come_before_anything_is_launched():
     finally:
         ops._call = real
     assert eng.stats == stats and not eng._graphs and launched == []
-    eng8 = _engine(_model(dtype, True), dtype)
+    eng8 = engine(model(dtype, True), dtype)
     stats8 = dict(eng8.stats)
     with pytest.raises(ValueError, match="attn_fp8 mismatch"):
         eng8.prepare(**{**base, "cloth": good, "garment_index": index})
@@ -250,35 +209,11 @@ def test_shelved_refusals_come_before_anything_is_launched():
 
 # ------------------------------------------------------------------------------------------------------------------ boundary
 def test_boundary_pipeline_passes_a_shelved_cache_through():
-    from idm_vton_amd import config as pc
-    from idm_vton_amd.boundary.scheduler import DDPMScheduler
-    from idm_vton_amd.boundary.vae import AutoencoderKL
     from idm_vton_amd.garment_cache import GarmentShelf, ShelvedGarmentCache
-    from src.tryon_pipeline import StableDiffusionXLInpaintPipeline
-    from src.unet_hacked_garmnet import UNet2DConditionModel as G
-    from src.unet_hacked_tryon import UNet2DConditionModel as T
-    from tests import parity_utils as pu
-    from tests.test_garment_cache_gpu import _FakeCLIPVision
     DT = torch.float16
-    kw = dict(pu.TINY)
-    tcfg = pc.UNetConfig(mode="tryon", in_channels=13, sample_size=16, **kw)
-    gcfg = pc.UNetConfig(mode="garmnet", in_channels=4, addition_embed_type=None, encoder_hid_dim_type=None, sample_size=16, **kw)
-    vcfg = pc.VAEConfig(**pu.TINY_VAE)
-    rnd = lambda sd: {k: v.to(DT) for k, v in sd.items()}
-    t = T(tcfg, torch_dtype=DT); t.load_state_dict(rnd(pc.random_state_dict(pc.unet_param_shapes(tcfg), 1, torch.float32, "cpu")))
-    g = G(gcfg, torch_dtype=DT); g.load_state_dict(rnd(pc.random_state_dict(pc.unet_param_shapes(gcfg), 2, torch.float32, "cpu")))
-    v = AutoencoderKL(vcfg, torch_dtype=DT); v.load_state_dict(rnd(pc.random_state_dict(pc.vae_param_shapes(vcfg), 3, torch.float32, "cpu", std=0.05)))
-    torch.manual_seed(5)
-    enc = _FakeCLIPVision(kw["encoder_hid_dim"]).to(DT)
-    pipe = StableDiffusionXLInpaintPipeline(vae=v, text_encoder=None, text_encoder_2=None, tokenizer=None, tokenizer_2=None, unet=t,
-                                            unet_encoder=g, scheduler=DDPMScheduler(), image_encoder=enc).to(DEV)
+    pipe, enc, kw = boundary_pipeline(DT)
     B, steps = 3, 3
-    inp = pu.make_inputs(B, H, W, kw["cross_attention_dim"], 64, kw["encoder_hid_dim"], steps, DT)
-    clip_pix = torch.randn(B, 3, 224, 224, generator=torch.Generator().manual_seed(9))
-    call = dict(prompt_embeds=inp["prompt_embeds"], negative_prompt_embeds=inp["negative_prompt_embeds"],
-                pooled_prompt_embeds=inp["pooled_prompt_embeds"], negative_pooled_prompt_embeds=inp["negative_pooled_prompt_embeds"],
-                num_inference_steps=steps, strength=1.0, pose_img=inp["pose_img"], mask_image=inp["mask_image"], image=inp["image"],
-                height=H, width=W, guidance_scale=2.0, ip_adapter_image=clip_pix, output_type="pt")
+    inp, clip_pix, call = boundary_inputs(kw, B, H, W, steps, DT)
     small = torch.randn(1, 3, 64, 96, generator=torch.Generator().manual_seed(13)).clamp(-1, 1)
     cloths = {"small": (small, inp["text_embeds_cloth"][:1]), "full": (inp["cloth"][1:2], inp["text_embeds_cloth"][1:2])}
     encode = lambda key: pipe.encode_garment(cloths[key][0], cloths[key][1], steps, H, W, generator=torch.Generator(DEV).manual_seed(11))
@@ -292,19 +227,9 @@ def test_boundary_pipeline_passes_a_shelved_cache_through():
     img_c = pipe(generator=gen_c, cloth=cache, text_embeds_cloth=None, garment_index=idx, **call)[0]
     assert eng.stats["garment_batches"] == n_garm and eng.stats["garment_stream_launches"] > n0
     # the engine-level call on the draws of the reference's order, on the device-resident slotted cache the same garments give
-    gen = torch.Generator(DEV).manual_seed(7)
-    torch.manual_seed(123)
-    draw = lambda gg, dt_: torch.randn((B, 4, H // 8, W // 8), generator=gg, device=DEV, dtype=dt_).float()
-    n_lat, n_masked, n_pose, _dropped = draw(gen, DT), draw(gen, torch.float32), draw(None, torch.float32), draw(gen, torch.float32)
-    n_steps = torch.stack([draw(gen, DT) for _ in range(steps)])
-    with torch.no_grad():
-        pos = enc(clip_pix.to(DEV, DT), output_hidden_states=True).hidden_states[-2]
-        neg = enc(torch.zeros_like(clip_pix).to(DEV, DT), output_hidden_states=True).hidden_states[-2]
-    ref = eng(image=inp["image"], mask_image=inp["mask_image"], pose_img=inp["pose_img"], cloth=cache.slotted(DEV), garment_index=idx,
-              prompt_embeds=inp["prompt_embeds"], negative_prompt_embeds=inp["negative_prompt_embeds"],
-              pooled_prompt_embeds=inp["pooled_prompt_embeds"], negative_pooled_prompt_embeds=inp["negative_pooled_prompt_embeds"],
-              text_embeds_cloth=None, noise=dict(latents=n_lat, masked=n_masked, pose=n_pose, cloth=None, steps=n_steps),
-              num_inference_steps=steps, guidance_scale=2.0, ip_hidden_states=torch.cat([neg, pos]), scheduler="ddpm")
+    _, noise = reference_draws(7, 123, B, H, W, steps, DT)
+    ip = ip_states(enc, clip_pix)
+    ref = engine_reference(eng, inp, noise, ip, steps, cloth=cache.slotted(DEV), garment_index=idx)
     assert torch.isfinite(img_c).all() and torch.equal(img_c, ref)
     with pytest.raises(ValueError, match="holds garments of several sizes: pass garment_index"):
         pipe(generator=gen_c, cloth=cache, text_embeds_cloth=None, **call)

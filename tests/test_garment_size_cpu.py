@@ -4,6 +4,8 @@ sets and captured graphs (the key functions alone: no kernels, no device)."""
 import pytest
 import torch
 
+from tests.garment_support import ask
+
 
 def _cache(G=2, ts=(900, 500, 100), h=16, w=16, gh=8, gw=12, dtype=torch.float16, levels=((1, 64), (2, 128))):
     """A hand-built cache shaped like the engine's: per (level, channels) one feature whose token rows are round16 of the garment's token
@@ -21,12 +23,6 @@ def _cache(G=2, ts=(900, 500, 100), h=16, w=16, gh=8, gw=12, dtype=torch.float16
     return GarmentCache(G=G, timesteps=ts, h=h, w=w, gh=gh, gw=gw, dtype=dtype, attn_fp8=False, f8_exp=(2, 2, 2), weights_id="w0", kv=kv), rows
 
 
-def _ask(c, **over):
-    kw = dict(timesteps=c.timesteps, h=c.h, w=c.w, dtype=c.dtype, attn_fp8=c.attn_fp8, f8_exp=c.f8_exp, weights_id=c.weights_id, persons=c.G)
-    kw.update(over)
-    return c.check(**kw)
-
-
 def test_garment_size_defaults_to_the_person_size_and_shows_in_the_repr_only_when_it_differs():
     from idm_vton_amd.garment_cache import GarmentCache
     kv = [(torch.zeros(2 * 16, 64), torch.zeros(2, 64, 16))]
@@ -40,10 +36,10 @@ def test_check_is_still_the_person_size_check():
     """A cache of an 8x12 garment declared for 16x16 persons: the call's PERSON size is what `check` compares; the garment's own size is not
     a size a call may run at unless it is declared."""
     c, _ = _cache()
-    assert _ask(c) == [0, 1, 2]
+    assert ask(c) == [0, 1, 2]
     for h, w in ((32, 32), (8, 12), (16, 12)):
         with pytest.raises(ValueError, match="GarmentCache resolution mismatch"):
-            _ask(c, h=h, w=w)
+            ask(c, h=h, w=w)
 
 
 def test_for_person_size_shares_storage_and_then_passes():
@@ -52,10 +48,10 @@ def test_for_person_size_shares_storage_and_then_passes():
     assert (d.h, d.w, d.gh, d.gw, d.G, d.timesteps) == (32, 32, 8, 12, c.G, c.timesteps)
     for (k, vt), (k2, vt2) in zip(c.kv, d.kv):
         assert k.data_ptr() == k2.data_ptr() and vt.data_ptr() == vt2.data_ptr()
-    assert _ask(d, h=32, w=32) == [0, 1, 2]
+    assert ask(d, h=32, w=32) == [0, 1, 2]
     with pytest.raises(ValueError, match="GarmentCache resolution mismatch"):
-        _ask(d, h=16, w=16)                                # the re-declared cache is as strict as the first
-    assert _ask(c) == [0, 1, 2] and (c.h, c.w) == (16, 16)  # and the first is unchanged
+        ask(d, h=16, w=16)                                # the re-declared cache is as strict as the first
+    assert ask(c) == [0, 1, 2] and (c.h, c.w) == (16, 16)  # and the first is unchanged
     assert d.nbytes == c.nbytes
 
 

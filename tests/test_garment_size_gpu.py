@@ -2,19 +2,17 @@
 on that latent (:1787) and joins the garment tokens to the person's along the token axis only (src/attentionhacked_tryon.py:334,348), so the
 garment's token count need not be the person's.  Kernel level: two-segment self-attention whose garment segment is shorter or longer than
 the own segment and no multiple of 16, on every kernel `tune` selects, against fp32 SDPA.  Engine level: against the oracle (the bars of
-tests/test_parity_gpu.py and tests/kernel_checks.py, imported), cached against uncached (bit for bit), graph states per garment size,
+tests/parity_checks.py and tests/kernel_checks.py, imported), cached against uncached (bit for bit), graph states per garment size,
 GarmentCache.for_person_size, the fp8 attention variant, and the boundary pipeline."""
-import functools
-
 import pytest
 import torch
 import torch.nn.functional as F
 
-from tests.test_garment_cache_gpu import FORMS, HEADS, TUNES, _FakeCLIPVision, _pair, _r
+from tests.engine_support import DEV, boundary_inputs, boundary_pipeline, engine, garment_kw, inputs, model, pair, randn
+from tests.garment_support import DTYPES, FORMS, HEADS
+from tests.kernel_checks import TUNES
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-DTYPES = pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
 
 # (Nq, garment keys): the level-1 / level-2 launches of the engine tests below -- 256 query rows x 15 keys (person 256x256, cloth 72x40),
 # 64 x 6 (person 128x128, cloth 72x40 at level 1 ... and 64x96 at level 2), 64 x 192 (cloth 256x192: more garment keys than own), 320 x 48
@@ -28,7 +26,7 @@ def _garment_segment(G, nkg, dtype, seed):
     to round16 FINITE FILLER, not zeros (GarmentNet's padded token rows go through the same projections) -- nk must be what masks them."""
     from idm_vton_amd import ops
     Cc, ld = HEADS * 64, ops.round16(nkg)
-    k, v = _r(G, ld, Cc, dtype=dtype, seed=seed), _r(G, ld, Cc, dtype=dtype, seed=seed + 1)
+    k, v = randn(G, ld, Cc, dtype=dtype, seed=seed), randn(G, ld, Cc, dtype=dtype, seed=seed + 1)
     return k, v, ops.key_order(v.transpose(1, 2).contiguous()), ld
 
 
@@ -41,8 +39,8 @@ def test_self_attention_with_a_garment_segment_of_its_own_length(tune, dtype):
     B, Cc = 2 * P, HEADS * 64
     sp = lambda t: t.float().view(t.shape[0], t.shape[1], HEADS, 64).transpose(1, 2)
     for Nq, nkg in SHAPES:
-        q = _r(B, Nq, Cc, dtype=dtype, seed=Nq + nkg)
-        k1, v1 = _r(B, Nq, Cc, dtype=dtype, seed=Nq + nkg + 1), _r(B, Nq, Cc, dtype=dtype, seed=Nq + nkg + 2)
+        q = randn(B, Nq, Cc, dtype=dtype, seed=Nq + nkg)
+        k1, v1 = randn(B, Nq, Cc, dtype=dtype, seed=Nq + nkg + 1), randn(B, Nq, Cc, dtype=dtype, seed=Nq + nkg + 2)
         vt1, ld1 = _key_order_padded(v1, Nq)
         pres = tune != "auto"                            # kernels 3, 7, 8, 16 need a pre-multiplied q; `auto` runs the library's rule for a raw q
         qq = (q.float() * ops.QSCALE).to(dtype) if pres else q
@@ -77,31 +75,6 @@ def test_fp8_self_attention_with_a_garment_segment_of_its_own_length(Nq, nkg, dt
 
 
 # ------------------------------------------------------------------------------------------------------------------ engine
-@functools.lru_cache(maxsize=None)
-def _model(dtype, fp8=False):
-    """One tiny model (oracle + product) per storage dtype, shared by the tests of this file; nothing in it is changed by a call."""
-    from tests import parity_utils as pu
-    return pu.build("tiny", dtype, DEV, unet_kw=dict(attn_fp8=True) if fp8 else None)
-
-
-def _inputs(m, B, H, W, Hg, Wg, steps, dtype):
-    """parity_utils.make_inputs with a cloth image (and its posterior draw) of another size."""
-    from tests import parity_utils as pu
-    inp = pu.make_inputs(B, H, W, m["xd"], m["pooled"], m["enc_dim"], steps, dtype)
-    if (Hg, Wg) != (H, W):
-        g = torch.Generator().manual_seed(1000 + Hg + Wg)
-        inp["cloth"] = torch.randn(B, 3, Hg, Wg, generator=g).clamp(-1, 1)
-        inp["noise"]["cloth"] = torch.randn(B, 4, Hg // 8, Wg // 8, generator=g)
-    return inp
-
-
-def _engine(m, dtype):
-    from idm_vton_amd.pipeline import TryonEngine
-    return TryonEngine(*m["product"], dtype, DEV)
-
-
-def _garment_kw(inp, G=None):
-    return dict(cloth=inp["cloth"][:G], text_embeds_cloth=inp["text_embeds_cloth"][:G], noise_cloth=inp["noise"]["cloth"][:G])
 
 
 @torch.no_grad()
@@ -114,7 +87,7 @@ def _parity(m, dtype, B, H, W, Hg, Wg, steps, forms=(dict(),)):
     from tests import parity_utils as pu
     o_t, o_g, o_v = m["oracle"]
     p_t, p_g, p_v, p_r = m["product"]
-    inp = _inputs(m, B, H, W, Hg, Wg, steps, dtype)
+    inp = inputs(m, B, H, W, Hg, Wg, steps, dtype)
     h, w, gh, gw = H // 8, W // 8, Hg // 8, Wg // 8
     res, t = {}, 481
     z_o = o_v.encode_sample(inp["cloth"], inp["noise"]["cloth"]) * o_v.cfg.scaling_factor
@@ -138,7 +111,7 @@ def _parity(m, dtype, B, H, W, Hg, Wg, steps, forms=(dict(),)):
     res["tryon_eps"] = pu.relerr(eps_p.view(2 * B, h, w, -1)[..., :4].permute(0, 3, 1, 2), eps_o)
     tr = {}
     img_o = opipe.run(o_t, o_g, o_v, Scheduler("ddpm"), num_inference_steps=steps, guidance_scale=2.0, trace=tr, **inp)
-    eng = _engine(m, dtype)
+    eng = engine(m, dtype)
     for i, kw in enumerate(forms):
         st = eng.prepare(num_inference_steps=steps, guidance_scale=2.0, scheduler="ddpm", **inp)
         assert (st["gh"], st["gw"]) == (gh, gw) and tuple(st["trace"]["cloth_lat"].shape[-2:]) == (gh, gw)
@@ -156,8 +129,8 @@ def _parity(m, dtype, B, H, W, Hg, Wg, steps, forms=(dict(),)):
 def test_garment_of_another_size_matches_the_oracle(person, cloth, dtype):
     """Garment tokens (level 1, level 2): 72x40 -> 15, 6; 64x96 -> 24, 6; 256x192 -> 192, 48 (more than the 64 / 16 own tokens of a 128x128
     person).  At 256x256 the level-1 launches have 256 query rows -- the software-pipelined kernel's workgroup -- against 15 garment keys."""
-    from tests.test_parity_gpu import TOL
-    r = _parity(_model(dtype), dtype, 1, *person, *cloth, steps=2)
+    from tests.parity_checks import TOL
+    r = _parity(model(dtype), dtype, 1, *person, *cloth, steps=2)
     print(person, cloth, dtype, {k: f"{v:.3e}" for k, v in r.items()})
     t = TOL[dtype]
     assert r["garment_feat_max"] <= t["stage"] and r["tryon_eps"] <= t["stage"] and r["cloth_lat"] <= t["stage"], r
@@ -171,18 +144,18 @@ def test_cached_loop_is_bit_identical_to_the_uncached_loop_at_another_garment_si
     -- the cloth's own VAE pass, the same GarmentNet batches at the garment's latent size --, so every execution form reproduces the uncached
     latents exactly; and P = 2 persons on a G = 1 cache (shared segment) equal the cache that holds the garment twice."""
     steps = 7
-    m = _model(dtype)
-    eng, inp = _engine(m, dtype), _inputs(m, 2, 128, 128, 64, 96, steps, dtype)
+    m = model(dtype)
+    eng, inp = engine(m, dtype), inputs(m, 2, 128, 128, 64, 96, steps, dtype)
     kw = dict(num_inference_steps=steps, guidance_scale=2.0, scheduler=scheduler, **inp)
-    cache = eng.encode_garment(num_inference_steps=steps, scheduler=scheduler, height=128, width=128, **_garment_kw(inp))
+    cache = eng.encode_garment(num_inference_steps=steps, scheduler=scheduler, height=128, width=128, **garment_kw(inp))
     assert (cache.h, cache.w, cache.gh, cache.gw, cache.G) == (16, 16, 8, 12, 2)
     tokens = m["product"][0].feature_tokens(8, 12)
     assert [vt.shape[2] for _, vt in cache.kv] == [(n + 15) // 16 * 16 for n in tokens]      # round16 rows of the GARMENT's token counts
     for form in FORMS:
-        lat_u, lat_c = _pair(eng, kw, cache, form)
+        lat_u, lat_c = pair(eng, kw, cache, form)
         print(f"{dtype} {scheduler} {form}: max|cached - uncached| = {(lat_u - lat_c).abs().max().item():.3e}")
         assert torch.isfinite(lat_u).all() and torch.equal(lat_u, lat_c), (form, (lat_u - lat_c).abs().max().item())
-    cache1 = eng.encode_garment(num_inference_steps=steps, scheduler=scheduler, height=128, width=128, **_garment_kw(inp, 1))
+    cache1 = eng.encode_garment(num_inference_steps=steps, scheduler=scheduler, height=128, width=128, **garment_kw(inp, 1))
     cache2 = cache1.repeat_garments(2)
     assert (cache2.G, cache2.gh, cache2.gw) == (2, 8, 12)
     base = {**kw, "text_embeds_cloth": None}
@@ -196,10 +169,10 @@ def test_graph_state_is_kept_per_garment_size():
     captured graphs are keyed by the garment's size, so each call gives the serial eager result of its own inputs and the last call -- back
     on the first call's state -- its bits."""
     dtype, steps = torch.float16, 5
-    m = _model(dtype)
-    eng = _engine(m, dtype)
+    m = model(dtype)
+    eng = engine(m, dtype)
     sizes = [(128, 128), (64, 96), (256, 192), (128, 128)]
-    calls = [dict(num_inference_steps=steps, guidance_scale=2.0, scheduler="ddpm", **_inputs(m, 2, 128, 128, Hg, Wg, steps, dtype)) for Hg, Wg in sizes]
+    calls = [dict(num_inference_steps=steps, guidance_scale=2.0, scheduler="ddpm", **inputs(m, 2, 128, 128, Hg, Wg, steps, dtype)) for Hg, Wg in sizes]
     graph = [eng.denoise(eng.prepare(**kw), **FORMS["graph_overlap"]).clone() for kw in calls]
     assert len(eng._graphs) == 3 and len(eng._set_shapes) == 3
     serial = [eng.denoise(eng.prepare(**kw), **FORMS["serial_eager"]).clone() for kw in calls]
@@ -214,12 +187,12 @@ def test_one_encoded_garment_serves_another_person_size_once_declared():
     256x256 call through for_person_size(32, 32), with the latents of the uncached 256x256 call on that cloth (whole call: both encode
     the two person-side images in one 2B pass); undeclared, it is refused."""
     dtype, steps = torch.float16, 3
-    m = _model(dtype)
-    eng = _engine(m, dtype)
-    small, big = _inputs(m, 1, 128, 128, 64, 96, steps, dtype), _inputs(m, 1, 256, 256, 64, 96, steps, dtype)
+    m = model(dtype)
+    eng = engine(m, dtype)
+    small, big = inputs(m, 1, 128, 128, 64, 96, steps, dtype), inputs(m, 1, 256, 256, 64, 96, steps, dtype)
     small["text_embeds_cloth"] = big["text_embeds_cloth"]                          # one garment: the same image, posterior draw and caption
     assert torch.equal(small["cloth"], big["cloth"]) and torch.equal(small["noise"]["cloth"], big["noise"]["cloth"])
-    cache = eng.encode_garment(num_inference_steps=steps, height=128, width=128, **_garment_kw(small))
+    cache = eng.encode_garment(num_inference_steps=steps, height=128, width=128, **garment_kw(small))
     kw = dict(num_inference_steps=steps, guidance_scale=2.0, scheduler="ddpm", return_latents=True)
     with pytest.raises(ValueError, match="GarmentCache resolution mismatch"):
         eng(**kw, **{**big, "cloth": cache, "text_embeds_cloth": None})
@@ -238,44 +211,22 @@ def test_fp8_attention_engine_with_a_larger_garment_matches_the_oracle_within_it
     the projection) against 64 own, 48 at level 2 (projected in 16 bits, quantised per launch) against 16 own.  The bar of
     tests/test_parity_gpu.py::test_fp8_attention_engine_matches_oracle_within_its_stated_tolerance."""
     dtype = torch.float16
-    r = _parity(_model(dtype, fp8=True), dtype, 2, 128, 128, 256, 192, steps=3, forms=(dict(), dict(use_graph=True, overlap=True)))
+    r = _parity(model(dtype, fp8=True), dtype, 2, 128, 128, 256, 192, steps=3, forms=(dict(), dict(use_graph=True, overlap=True)))
     print({k: f"{v:.3e}" for k, v in r.items()})
     assert r["garment_feat_max"] <= 8e-2 and r["tryon_eps"] <= 8e-2 and r["latents_final"] <= 8e-2 and r["latents_final_1"] <= 8e-2, r
 
 
 # ------------------------------------------------------------------------------------------------------------------ boundary
 def test_boundary_pipeline_takes_a_cloth_of_another_size():
-    from idm_vton_amd import config as pc
-    from idm_vton_amd.boundary.scheduler import DDPMScheduler
-    from idm_vton_amd.boundary.vae import AutoencoderKL
     from oracle import pipeline as opipe
     from oracle.scheduler import Scheduler
-    from src.tryon_pipeline import StableDiffusionXLInpaintPipeline
-    from src.unet_hacked_garmnet import UNet2DConditionModel as G
-    from src.unet_hacked_tryon import UNet2DConditionModel as T
     from tests import parity_utils as pu
-    from tests.test_parity_gpu import TOL
+    from tests.parity_checks import TOL
     DT = torch.float16
-    kw = dict(pu.TINY)
-    tcfg = pc.UNetConfig(mode="tryon", in_channels=13, sample_size=16, **kw)
-    gcfg = pc.UNetConfig(mode="garmnet", in_channels=4, addition_embed_type=None, encoder_hid_dim_type=None, sample_size=16, **kw)
-    vcfg = pc.VAEConfig(**pu.TINY_VAE)
-    rnd = lambda sd: {k: v.to(DT) for k, v in sd.items()}
-    t = T(tcfg, torch_dtype=DT); t.load_state_dict(rnd(pc.random_state_dict(pc.unet_param_shapes(tcfg), 1, torch.float32, "cpu")))
-    g = G(gcfg, torch_dtype=DT); g.load_state_dict(rnd(pc.random_state_dict(pc.unet_param_shapes(gcfg), 2, torch.float32, "cpu")))
-    v = AutoencoderKL(vcfg, torch_dtype=DT); v.load_state_dict(rnd(pc.random_state_dict(pc.vae_param_shapes(vcfg), 3, torch.float32, "cpu", std=0.05)))
-    torch.manual_seed(5)
-    enc = _FakeCLIPVision(kw["encoder_hid_dim"]).to(DT)
-    pipe = StableDiffusionXLInpaintPipeline(vae=v, text_encoder=None, text_encoder_2=None, tokenizer=None, tokenizer_2=None, unet=t,
-                                            unet_encoder=g, scheduler=DDPMScheduler(), image_encoder=enc).to(DEV)
+    pipe, _, kw = boundary_pipeline(DT)
     B, H, W, Hg, Wg, steps = 2, 128, 128, 64, 96, 3
-    m = _model(DT)                                       # the same seeds and rounding as above: the oracle holds the pipeline's weights
-    inp = _inputs(m, B, H, W, Hg, Wg, steps, DT)
-    clip_pix = torch.randn(B, 3, 224, 224, generator=torch.Generator().manual_seed(9))
-    call = dict(prompt_embeds=inp["prompt_embeds"], negative_prompt_embeds=inp["negative_prompt_embeds"],
-                pooled_prompt_embeds=inp["pooled_prompt_embeds"], negative_pooled_prompt_embeds=inp["negative_pooled_prompt_embeds"],
-                num_inference_steps=steps, strength=1.0, pose_img=inp["pose_img"], mask_image=inp["mask_image"], image=inp["image"],
-                height=H, width=W, guidance_scale=2.0, ip_adapter_image=clip_pix, output_type="pt")
+    m = model(DT)                                       # the same seeds and rounding as above: the oracle holds the pipeline's weights
+    inp, clip_pix, call = boundary_inputs(kw, B, H, W, steps, DT, inp=inputs(m, B, H, W, Hg, Wg, steps, DT))
     o_t, o_g, o_v = m["oracle"]
 
     def oracle_of(traced, cloth_lat_noise):

@@ -1,7 +1,7 @@
 """CPU tests of the copy-engine transport of host-resident garment caches: the host side of idmvton_kv_place -- exported, additive to ABI version
 9, every refusal raised before a launch (no GPU: the pointers are made up and never dereferenced) --, KvPlaceTable's launch, and
 garment_cache.staged_plan -- the staging arena, the copy list and the place tables of pipeline.py's _staged_fill -- carried out on CPU tensors:
-the copies as tensor copies, the tables by the record interpreter of tests/test_garment_shelf_cpu.py, against the tables today's kernel
+the copies as tensor copies, the tables by the record interpreter of tests/garment_support.py, against the tables today's kernel
 transport (_stream_fill / _shelf_fill) builds, interpreted the same way."""
 import ctypes as C
 import os
@@ -9,10 +9,7 @@ import os
 import pytest
 import torch
 
-from tests.test_garment_shelf_cpu import KINDS, SLOT, _apply, _shelf
-from tests.test_garment_stream_cpu import _cache3, _fields
-
-PACKED = pytest.mark.parametrize("packed", [False, True], ids=["16bit", "packed"])
+from tests.garment_support import PACKED, SHELF_KINDS, SHELF_SLOT, apply_records, cache3, cpu_shelf, record_fields
 
 
 # ------------------------------------------------------------------------------------------------------------------ ABI
@@ -140,7 +137,7 @@ def _stage_and_place(plan, packed, dtype, idx, p, k):
             d.data_ptr() + d.numel() * d.element_size() <= plan["arena"].data_ptr() + plan["nbytes"]
         d.copy_(s)
     f0 = p * k * plan["per"]
-    _apply(plan["rec"][f0:f0 + len(idx) * plan["per"]], packed, dtype)
+    apply_records(plan["rec"][f0:f0 + len(idx) * plan["per"]], packed, dtype)
     return len(pairs)
 
 
@@ -157,7 +154,7 @@ def test_staged_plain_cache_with_an_index_fills_the_sets_as_the_kernel_transport
     from idm_vton_amd import ffi, ops
     from idm_vton_amd.garment_cache import fill_records, staged_plan
     dtype, n, G, k, S, gindex = torch.float16, 4, 3, 3, 3, [1, 1, 0]
-    cache = _cache3(G, n, dtype)
+    cache = cache3(G, n, dtype)
     if packed:
         cache = cache.pack()
         cache.exps.copy_(torch.arange(-3, -3 + cache.exps.numel(), dtype=torch.int32).view_as(cache.exps) % 9 - 2)   # distinct per (garment, feature, K | V^T)
@@ -175,7 +172,7 @@ def test_staged_plain_cache_with_an_index_fills_the_sets_as_the_kernel_transport
         assert len(plan["exps_copies"]) == 2 and torch.equal(plan["exps"], cache.exps[[1, 0]])
     # every source address of the table lies in the arena, every exponent address in the staged exponents
     lo, hi = plan["arena"].data_ptr(), plan["arena"].data_ptr() + plan["nbytes"]
-    for src, _, exp, rows, cols, lds, _ in _fields(plan["rec"]):
+    for src, _, exp, rows, cols, lds, _ in record_fields(plan["rec"]):
         assert lo <= src and src + (rows - 1) * lds + cols <= hi and src % 16 == 0
         assert (exp == 0) if not packed else plan["exps"].data_ptr() <= exp < plan["exps"].data_ptr() + 4 * plan["exps"].numel()
     table = ops.KvPlaceTable(plan["rec"], "cpu", ffi.KVS_WIDEN_E4M3 if packed else ffi.KVS_COPY,
@@ -184,7 +181,7 @@ def test_staged_plain_cache_with_an_index_fills_the_sets_as_the_kernel_transport
     garments = [1, 0]
     for bi, idx in enumerate(BLOCKS[order]):
         p = bi & 1
-        _apply(fill_records(cache.kv, n, G, want[p], k, S, cache.exps if packed else None, idx, list(range(len(idx))), garments, [0, 1]), packed, dtype)
+        apply_records(fill_records(cache.kv, n, G, want[p], k, S, cache.exps if packed else None, idx, list(range(len(idx))), garments, [0, 1]), packed, dtype)
         ncopies = _stage_and_place(plan, packed, dtype, idx, p, k)
         assert ncopies == len(idx) * 2 * 3 * 2                                             # per timestep and run of consecutive garments: [1], [0]
         assert _same_bytes(got[p], want[p]) and _same_bytes(got[1 - p], want[1 - p]), (order, bi)
@@ -198,27 +195,27 @@ def test_staged_plain_cache_without_an_index_copies_once_per_tensor():
     """No index, P = G = 2: a block of consecutive entries is ONE copy per cache tensor, a block by value one per timestep."""
     from idm_vton_amd.garment_cache import fill_records, staged_plan
     dtype, n, G, k = torch.bfloat16, 4, 2, 3
-    cache = _cache3(G, n, dtype)
+    cache = cache3(G, n, dtype)
     shapes = [(192, 64), (48, 128), (1040, 16)]
     want, got = _sets(shapes, k, G, dtype, 0x7f), _sets(shapes, k, G, dtype, 0x7f)
     plan = staged_plan(cache, None, k, G, [got], "cpu")
     assert plan["nbytes"] == k * G * sum(2 * N * Cc * 2 for N, Cc in shapes) == cache.nbytes * k // n and plan["exps"] is None and not plan["exps_copies"]
     for idx, ncopies in (([1, 2, 3], 6), ([2, 0], 12), ([3], 6)):
-        _apply(fill_records(cache.kv, n, G, want, k, G, None, idx, list(range(len(idx))), [0, 1], [0, 1]), False, dtype)
+        apply_records(fill_records(cache.kv, n, G, want, k, G, None, idx, list(range(len(idx))), [0, 1], [0, 1]), False, dtype)
         assert _stage_and_place(plan, False, dtype, idx, 0, k) == ncopies
         assert _same_bytes(got, want), idx
 
 
 @PACKED
 def test_staged_shelf_of_three_sizes_fills_the_sets_as_the_kernel_transport_does(packed):
-    """The three garments of tests/test_garment_shelf_cpu.py (smaller, the slot's size, smaller with ld' no multiple of 64), index [2, 0, 2, 1]:
+    """The three garments of tests/garment_support.py's shelf (smaller, the slot's size, smaller with ld' no multiple of 64), index [2, 0, 2, 1]:
     U = 3 parts in first-use order c, a, b into slots 0..2 of 4-slot sets.  Then a second call through the SAME sets and the same arena with
     the small garment c where the slot-sized b was: its zero tail has to replace b's values.  Against shelf_records from the parts (_shelf_fill's
     table), interpreted the same way."""
     from idm_vton_amd.garment_cache import shelf_records, staged_plan
     dtype, k, S = torch.float16, 3, 4
-    shelf = _shelf(packed)
-    want, got = [_sets(SLOT, k, S, dtype, 0x7f) for _ in range(2)], [_sets(SLOT, k, S, dtype, 0x7f) for _ in range(2)]
+    shelf = cpu_shelf(packed)
+    want, got = [_sets(SHELF_SLOT, k, S, dtype, 0x7f) for _ in range(2)], [_sets(SHELF_SLOT, k, S, dtype, 0x7f) for _ in range(2)]
     arena = exps = None
     esz = 1 if packed else 2
     sizes = []
@@ -226,21 +223,21 @@ def test_staged_shelf_of_three_sizes_fills_the_sets_as_the_kernel_transport_does
         cache, index = shelf.get(keys)
         U = cache.G
         plan = staged_plan(cache, index, k, S, got, "cpu", arena, exps if exps is not None and exps.shape[0] == U else None)
-        need = k * sum(2 * N * Cc * esz for key in dict.fromkeys(keys) for N, Cc in KINDS[key][1])
+        need = k * sum(2 * N * Cc * esz for key in dict.fromkeys(keys) for N, Cc in SHELF_KINDS[key][1])
         assert plan["nbytes"] == need < cache.nbytes and plan["arena"].numel() >= need
         sizes.append(plan["arena"].numel())
         arena, exps = plan["arena"], plan["exps"]
         for d, s in plan["exps_copies"]:
             d.copy_(s)
         assert len(plan["exps_copies"]) == (U if packed else 0)
-        zero = [r for r in _fields(plan["rec"]) if r[0] == 0]
+        zero = [r for r in record_fields(plan["rec"]) if r[0] == 0]
         assert zero and all(r[2] == 0 for r in zero) and plan["per"] % 2 == 0
         parts = [cache.parts[g] for g in dict.fromkeys(index)]
         for bi, idx in enumerate([[0], [1, 2], [3], [3, 1]]):
             p = bi & 1
             rec, per = shelf_records(parts, packed, want[p], k, S, idx, list(range(len(idx))), list(range(U)))
             assert per == plan["per"]
-            _apply(rec, packed, dtype)
+            apply_records(rec, packed, dtype)
             ncopies = _stage_and_place(plan, packed, dtype, idx, p, k)
             assert ncopies == U * 3 * 2 * (1 if idx != [3, 1] else 2)                    # one per part tensor; by value: per timestep
             assert _same_bytes(got[p], want[p]), (keys, bi)

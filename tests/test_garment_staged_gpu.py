@@ -7,21 +7,17 @@ host_transport="kernel": the sets receive the same bits, so EQUALITY in every ex
 import pytest
 import torch
 
-from tests import test_garment_ragged_gpu as ragged
-from tests.test_garment_cache_gpu import FORMS, _engine, _garment_kw
-from tests.test_garment_index_gpu import _base
-from tests.test_garment_packed_gpu import _bytes
-from tests.test_garment_shelf_gpu import KEYS, MIXED_DSTS, MIXED_RUNS, _check, _shelf
-from tests.test_garment_stream_gpu import _host, _pinned
+from tests.engine_support import (DEV, KEYS, MIXED_DSTS, MIXED_RUNS, STEPS, WEARS, base_call, boundary_inputs, boundary_pipeline, check_fill, e4m3_bytes,
+                                  encode_three, engine, engine_inputs, engine_reference, garment_kw, gpu_shelf, ip_states, model, pin_frame,
+                                  reference_draws, run_on, three_garments, to_host)
+from tests.garment_support import DTYPES, FORMS
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-DTYPES = pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
 COPY = pytest.mark.parametrize("copy", [False, True], ids=["widen", "copy"])
 
 
 # ------------------------------------------------------------------------------------------------------------------ kernel
-# (the notation of tests/test_garment_shelf_gpu.py) the edges of a one-chunk-per-workgroup grid: a run of exactly 1024 items when widening (64 rows
+# (the notation of MIXED_RUNS in tests/engine_support.py) the edges of a one-chunk-per-workgroup grid: a run of exactly 1024 items when widening (64 rows
 # x 256 bytes: no lane of its workgroup is clamped; 2048 = two full chunks when copying), a run of ONE item (1 x 16 bytes widening), a run of
 # exactly 1024 items when copying (64 x 128 elements), a zero run
 EDGE_DSTS = [(64, 256, 264), (1, 16, 24), (64, 128, 136), (3, 32, 40)]
@@ -45,8 +41,8 @@ def _place(dsts, runs, dtype, copy=False, on_host=()):
             descs.append((None, outs[d][:rows, c0:c0 + cols], None))
             continue
         _, rows, cols, lds, e, d, c0 = run
-        x = torch.randn(rows, cols, generator=torch.Generator().manual_seed(i)).to(dtype) if copy else _bytes(rows, cols, seed=i)
-        s = _pinned(frames.framed(x, lds)) if i in on_host else frames.framed(x.to(DEV), lds)
+        x = torch.randn(rows, cols, generator=torch.Generator().manual_seed(i)).to(dtype) if copy else e4m3_bytes(rows, cols, seed=i)
+        s = pin_frame(frames.framed(x, lds)) if i in on_host else frames.framed(x.to(DEV), lds)
         srcs[i], vals[i] = s, x
         descs.append((s, outs[d][:rows, c0:c0 + cols], None if copy else (exps_h if i in on_host else exps_d)[i:i + 1]))
     table = ops.kv_place(descs, dtype, mode=ffi.KVS_COPY if copy else ffi.KVS_WIDEN_E4M3)
@@ -80,7 +76,7 @@ def test_kv_place_mixed_table_from_device_memory(dtype, copy):
     assert table.items.tolist() == ([30, 40, 2240, 2112] if copy else [15, 20, 1120, 1056])
     assert table.first_host.tolist() == ([0, 1, 2, 5, 8] if copy else [0, 1, 2, 4, 6]) and all(s.is_cuda for s in srcs.values())
     assert table.host[:, 0].ne(0).tolist() == [True, False, True, False] and table.host[1, 2] == 0
-    _check(MIXED_DSTS, MIXED_RUNS, outs, srcs, vals, dtype, copy)
+    check_fill(MIXED_DSTS, MIXED_RUNS, outs, srcs, vals, dtype, copy)
     _same_as_kv_fill(outs, table, dtype)
 
 
@@ -90,7 +86,7 @@ def test_kv_place_edges_of_a_one_chunk_per_workgroup_grid(dtype, copy):
     outs, srcs, vals, table = _place(EDGE_DSTS, EDGE_RUNS, dtype, copy)
     assert table.items.tolist() == ([2048, 2, 1024, 12] if copy else [1024, 1, 512, 6])
     assert table.first_host.tolist() == ([0, 2, 3, 4, 5] if copy else [0, 1, 2, 3, 4])
-    _check(EDGE_DSTS, EDGE_RUNS, outs, srcs, vals, dtype, copy)
+    check_fill(EDGE_DSTS, EDGE_RUNS, outs, srcs, vals, dtype, copy)
     _same_as_kv_fill(outs, table, dtype)
 
 
@@ -100,14 +96,14 @@ def test_kv_place_table_of_zero_runs_only(copy):
     outs, srcs, vals, table = _place(ZERO_DSTS, ZERO_RUNS, dtype, copy)
     assert not srcs and (table.host[:, 0] == 0).all() and (table.host[:, 2] == 0).all() and table.link_bytes() == 0.0
     assert table.first_host.tolist() == [0, 1, 2, 3]
-    _check(ZERO_DSTS, ZERO_RUNS, outs, srcs, vals, dtype, copy)
+    check_fill(ZERO_DSTS, ZERO_RUNS, outs, srcs, vals, dtype, copy)
     _same_as_kv_fill(outs, table, dtype)
 
 
 def test_kv_place_one_table_mixes_device_and_pinned_host_sources():
     outs, srcs, vals, table = _place(MIXED_DSTS, MIXED_RUNS, torch.bfloat16, on_host=(0,))
     assert [srcs[i].is_cuda for i in sorted(srcs)] == [False, True] and srcs[0].is_pinned()
-    _check(MIXED_DSTS, MIXED_RUNS, outs, srcs, vals, torch.bfloat16)
+    check_fill(MIXED_DSTS, MIXED_RUNS, outs, srcs, vals, torch.bfloat16)
     _same_as_kv_fill(outs, table, torch.bfloat16)
 
 
@@ -128,8 +124,6 @@ def test_kv_place_wrapper_refuses_a_malformed_run():
 
 
 # ------------------------------------------------------------------------------------------------------------------ engine
-def _run(eng, base, cache, form, index=None, transport="kernel"):
-    return eng.denoise(eng.prepare(**{**base, "cloth": cache, "garment_index": index}), host_transport=transport, **FORMS[form]).clone()
 
 
 def _forms(dtype):
@@ -146,10 +140,10 @@ def _three_ways(eng, base, device, host, index, forms, nblocks, copies_per_block
     copy transport -- equal latents, no new state or capture, and the copy call's counters."""
     lat_d = None
     for form in forms:
-        lat_d = _run(eng, base, device, form, index)
-        lat_k = _run(eng, base, host, form, index, "kernel")
+        lat_d = run_on(eng, base, device, form, index)
+        lat_k = run_on(eng, base, host, form, index, "kernel")
         graphs, s0 = _graphs(eng), dict(eng.stats)
-        lat_c = _run(eng, base, host, form, index, "copy")
+        lat_c = run_on(eng, base, host, form, index, "copy")
         assert torch.isfinite(lat_d).all() and torch.isfinite(lat_c).all(), form
         assert torch.equal(lat_c, lat_d), (form, (lat_c - lat_d).abs().max().item())
         assert torch.equal(lat_c, lat_k), (form, (lat_c - lat_k).abs().max().item())
@@ -175,57 +169,57 @@ def test_copy_transport_equals_the_device_resident_call_and_the_kernel_transport
     persons on a G = 3 cache, garment_index [2, 0, 2, 0] (repeats; U = 2 < G: garment 1 is never copied), 4 steps (blocks of 1, 2, 1).
     16bit_index: a 16-bit G = 4 cache (copy mode), [2, 0, 2, 1]: U = 3 in the runs [2], [0, 1]."""
     storage, P, G, index, steps = CASES[case]
-    eng, inp, _ = _engine(dtype, P, steps)
-    device = eng.encode_garment(num_inference_steps=steps, storage=storage, **_garment_kw(inp, G))
-    host = _host(device)
+    eng, inp, _ = engine_inputs(dtype, P, steps)
+    device = eng.encode_garment(num_inference_steps=steps, storage=storage, **garment_kw(inp, G))
+    host = to_host(device)
     assert host.packed == (storage == "e4m3") and host.G == G
     k, blocks = eng._block_schedule(steps)
     assert [c for _, c in blocks] == ([1, 2, 4] if steps == 7 else [1, 2, 1])
     F = len(host.kv)
     runs = 1 if index is None else 2
     copies = [2 * F if index is None else c * runs * 2 * F for _, c in blocks]
-    lat = _three_ways(eng, _base(inp, steps), device, host, index, _forms(dtype), len(blocks), copies)
+    lat = _three_ways(eng, base_call(inp, steps), device, host, index, _forms(dtype), len(blocks), copies)
     # the arena: k timesteps of the U used garments in the source's storage -- derived, and never the size of the cache
     U = G if index is None else len(set(index))
     arena = _arena(eng)
     assert arena.dtype == torch.uint8 and arena.numel() == k * U * sum(t.numel() * t.element_size() for kv in host.kv for t in kv) // (steps * G)
     assert arena.numel() < host.nbytes
     if index is not None:                                # the assignment is read
-        assert not torch.equal(_run(eng, _base(inp, steps), host, "serial_eager", index[::-1], "copy"), lat)
+        assert not torch.equal(run_on(eng, base_call(inp, steps), host, "serial_eager", index[::-1], "copy"), lat)
 
 
 @pytest.mark.parametrize("storage", ["e4m3", "native"], ids=["packed", "16bit"])
 @DTYPES
 def test_copy_transport_of_a_shelf_of_three_sizes(dtype, storage):
     """Compact garments of latent 9x5, 8x12 and 16x16 in pinned host memory against slotted("cuda"): one copy per part tensor and block."""
-    eng = ragged._engine(ragged._model(dtype), dtype)
-    inp, garments = ragged._inputs(dtype)
-    shelf = _shelf(eng, ragged._encode(eng, garments), storage)
-    shelved, index = shelf.get([KEYS[j] for j in ragged.WEARS])
+    eng = engine(model(dtype), dtype)
+    inp, garments = three_garments(dtype)
+    shelf = gpu_shelf(eng, encode_three(eng, garments), storage)
+    shelved, index = shelf.get([KEYS[j] for j in WEARS])
     assert index == [0, 1, 2] and shelved.sizes == [(9, 5), (8, 12), (16, 16)] and shelved.host_resident
     device = shelved.slotted(DEV)
-    k, blocks = eng._block_schedule(ragged.STEPS)
+    k, blocks = eng._block_schedule(STEPS)
     assert len(blocks) == 2
     F = len(shelved.parts[0].kv)
-    _three_ways(eng, ragged._base(inp), device, shelved, index, _forms(dtype), len(blocks), [3 * 2 * F] * len(blocks))
+    _three_ways(eng, base_call(inp, STEPS), device, shelved, index, _forms(dtype), len(blocks), [3 * 2 * F] * len(blocks))
     arena = _arena(eng)
-    assert arena.numel() == k * sum(t.numel() * t.element_size() for p in shelved.parts for kv in p.kv for t in kv) // ragged.STEPS < device.nbytes   # compact
+    assert arena.numel() == k * sum(t.numel() * t.element_size() for p in shelved.parts for kv in p.kv for t in kv) // STEPS < device.nbytes   # compact
 
 
 def test_two_copy_calls_through_one_state_use_the_arena_again():
     """A packed G = 3 host cache, two assignments through one graph state and one arena; each against a fresh engine's serial call on the
     device-resident cache."""
     dtype, steps = torch.float16, 4
-    eng, inp, _ = _engine(dtype, 4, steps)
-    fresh, _, _ = _engine(dtype, 4, steps)
-    device = eng.encode_garment(num_inference_steps=steps, storage="e4m3", **_garment_kw(inp, 3))
-    host = _host(device)
-    base = _base(inp, steps)
+    eng, inp, _ = engine_inputs(dtype, 4, steps)
+    fresh, _, _ = engine_inputs(dtype, 4, steps)
+    device = eng.encode_garment(num_inference_steps=steps, storage="e4m3", **garment_kw(inp, 3))
+    host = to_host(device)
+    base = base_call(inp, steps)
     seen = []
     for index in ([2, 0, 2, 0], [1, 2, 2, 1]):
         for form in ("graph_overlap", "serial_eager"):
-            lat = _run(eng, base, host, form, index, "copy")
-            assert torch.equal(lat, _run(fresh, base, device, "serial_eager", index)), (index, form)
+            lat = run_on(eng, base, host, form, index, "copy")
+            assert torch.equal(lat, run_on(fresh, base, device, "serial_eager", index)), (index, form)
             seen.append(_arena(eng).data_ptr())
     assert len(set(seen)) == 1 and len(eng._graphs) == 1 and eng.stats["garment_stream_launches"] == 0
     assert not eng._streaming or all(h[0] is host for h in eng._streaming)
@@ -238,18 +232,18 @@ def test_shelf_slot_reuse_under_the_copy_transport():
     """Set slot 0 holds the largest garment, then the smallest -- its zero tail has to replace the larger garment's values, and the arena the
     larger call sized serves the smaller --, then a mix.  Each against the slotted device call of that assignment on a fresh engine."""
     dtype = torch.float16
-    eng = ragged._engine(ragged._model(dtype), dtype)
-    fresh = ragged._engine(ragged._model(dtype), dtype)
-    inp, garments = ragged._inputs(dtype)
-    ones = ragged._encode(eng, garments)
-    shelf = _shelf(eng, ones[1:], "e4m3")                # g0 = ones[1] (16x16), g1 = ones[2] (9x5): KEYS[:2]
-    base = ragged._base(inp)
+    eng = engine(model(dtype), dtype)
+    fresh = engine(model(dtype), dtype)
+    inp, garments = three_garments(dtype)
+    ones = encode_three(eng, garments)
+    shelf = gpu_shelf(eng, ones[1:], "e4m3")                # g0 = ones[1] (16x16), g1 = ones[2] (9x5): KEYS[:2]
+    base = base_call(inp, STEPS)
     seen = []
     for form in ("graph", "graph_overlap"):
         for keys in (["g0"] * 3, ["g1"] * 3, ["g0"] * 3, ["g1", "g0", "g1"]):
             shelved, index = shelf.get(keys)
-            lat = _run(eng, base, shelved, form, index, "copy")
-            ref = _run(fresh, base, shelved.slotted(DEV), "serial_eager", index)
+            lat = run_on(eng, base, shelved, form, index, "copy")
+            ref = run_on(fresh, base, shelved.slotted(DEV), "serial_eager", index)
             assert torch.isfinite(lat).all() and torch.equal(lat, ref), (form, keys, (lat - ref).abs().max().item())
             seen.append({key: a.data_ptr() for key, (a, _) in eng._arenas.items()})
     assert len(eng._graphs) == 1 and eng.stats["garment_stream_launches"] == 0
@@ -259,65 +253,41 @@ def test_shelf_slot_reuse_under_the_copy_transport():
 
 def test_copy_transport_refusals_come_before_anything_is_launched():
     steps = 3
-    eng, inp, _ = _engine(torch.float16, 2, steps)
-    base = _base(inp, steps)
-    cache = eng.encode_garment(num_inference_steps=steps, **_garment_kw(inp))
+    eng, inp, _ = engine_inputs(torch.float16, 2, steps)
+    base = base_call(inp, steps)
+    cache = eng.encode_garment(num_inference_steps=steps, **garment_kw(inp))
     packed = cache.pack()
     stats = dict(eng.stats)
     for pageable in (cache.to("cpu"), packed.to("cpu")):
         with pytest.raises(ValueError, match="kv mismatch.*pageable.*pin_memory"):
             eng(return_latents=True, host_transport="copy", **{**base, "cloth": pageable})
     with pytest.raises(ValueError, match="host_transport='dma'"):
-        eng(return_latents=True, host_transport="dma", **{**base, "cloth": _host(packed)})
+        eng(return_latents=True, host_transport="dma", **{**base, "cloth": to_host(packed)})
     with pytest.raises(ValueError, match="host_transport='dma'"):
-        eng.denoise(eng.prepare(**{**base, "cloth": _host(packed)}), host_transport="dma")
+        eng.denoise(eng.prepare(**{**base, "cloth": to_host(packed)}), host_transport="dma")
     assert eng.stats == stats and not eng._graphs and not eng._arenas
-    eng8, inp8, _ = _engine(torch.float16, 2, steps, unet_kw=dict(attn_fp8=True))
-    cache8 = eng8.encode_garment(num_inference_steps=steps, **_garment_kw(inp8))
+    eng8, inp8, _ = engine_inputs(torch.float16, 2, steps, fp8=True)
+    cache8 = eng8.encode_garment(num_inference_steps=steps, **garment_kw(inp8))
     stats8 = dict(eng8.stats)
     with pytest.raises(ValueError, match="attn_fp8 mismatch.*does not stream"):
-        eng8(return_latents=True, host_transport="copy", **{**_base(inp8, steps), "cloth": _host(cache8)})
+        eng8(return_latents=True, host_transport="copy", **{**base_call(inp8, steps), "cloth": to_host(cache8)})
     assert eng8.stats == stats8 and not eng8._graphs and not eng8._arenas
     # on a device-resident cache the keyword has no effect
-    lat = _run(eng, base, packed, "serial_eager", None, "copy")
-    assert torch.equal(lat, _run(eng, base, packed, "serial_eager")) and not eng._arenas and eng.stats["garment_stage_launches"] == 0
+    lat = run_on(eng, base, packed, "serial_eager", None, "copy")
+    assert torch.equal(lat, run_on(eng, base, packed, "serial_eager")) and not eng._arenas and eng.stats["garment_stage_launches"] == 0
 
 
 # ------------------------------------------------------------------------------------------------------------------ boundary
 def test_boundary_pipeline_passes_host_transport_through():
     """pipe.host_transport = "copy" on a packed cache in pinned host memory against the engine-level call on the same draws and the
     DEVICE-RESIDENT cache."""
-    from idm_vton_amd import config as pc
-    from idm_vton_amd.boundary.scheduler import DDPMScheduler
-    from idm_vton_amd.boundary.vae import AutoencoderKL
-    from src.tryon_pipeline import StableDiffusionXLInpaintPipeline
-    from src.unet_hacked_garmnet import UNet2DConditionModel as G
-    from src.unet_hacked_tryon import UNet2DConditionModel as T
-    from tests import parity_utils as pu
-    from tests.test_garment_cache_gpu import _FakeCLIPVision
     DT = torch.float16
-    kw = dict(pu.TINY)
-    tcfg = pc.UNetConfig(mode="tryon", in_channels=13, sample_size=16, **kw)
-    gcfg = pc.UNetConfig(mode="garmnet", in_channels=4, addition_embed_type=None, encoder_hid_dim_type=None, sample_size=16, **kw)
-    vcfg = pc.VAEConfig(**pu.TINY_VAE)
-    rnd = lambda sd: {k: v.to(DT) for k, v in sd.items()}
-    t = T(tcfg, torch_dtype=DT); t.load_state_dict(rnd(pc.random_state_dict(pc.unet_param_shapes(tcfg), 1, torch.float32, "cpu")))
-    g = G(gcfg, torch_dtype=DT); g.load_state_dict(rnd(pc.random_state_dict(pc.unet_param_shapes(gcfg), 2, torch.float32, "cpu")))
-    v = AutoencoderKL(vcfg, torch_dtype=DT); v.load_state_dict(rnd(pc.random_state_dict(pc.vae_param_shapes(vcfg), 3, torch.float32, "cpu", std=0.05)))
-    torch.manual_seed(5)
-    enc = _FakeCLIPVision(kw["encoder_hid_dim"]).to(DT)
-    pipe = StableDiffusionXLInpaintPipeline(vae=v, text_encoder=None, text_encoder_2=None, tokenizer=None, tokenizer_2=None, unet=t,
-                                            unet_encoder=g, scheduler=DDPMScheduler(), image_encoder=enc).to(DEV)
+    pipe, enc, kw = boundary_pipeline(DT)
     assert pipe.host_transport == "kernel"
     B, H, W, steps = 2, 128, 128, 3
-    inp = pu.make_inputs(B, H, W, kw["cross_attention_dim"], 64, kw["encoder_hid_dim"], steps, DT)
-    clip_pix = torch.randn(B, 3, 224, 224, generator=torch.Generator().manual_seed(9))
-    call = dict(prompt_embeds=inp["prompt_embeds"], negative_prompt_embeds=inp["negative_prompt_embeds"],
-                pooled_prompt_embeds=inp["pooled_prompt_embeds"], negative_pooled_prompt_embeds=inp["negative_pooled_prompt_embeds"],
-                num_inference_steps=steps, strength=1.0, pose_img=inp["pose_img"], mask_image=inp["mask_image"], image=inp["image"],
-                height=H, width=W, guidance_scale=2.0, ip_adapter_image=clip_pix, output_type="pt")
+    inp, clip_pix, call = boundary_inputs(kw, B, H, W, steps, DT)
     device = pipe.encode_garment(inp["cloth"], inp["text_embeds_cloth"], steps, H, W, generator=torch.Generator(DEV).manual_seed(11), storage="e4m3")
-    cache = _host(device)
+    cache = to_host(device)
     index = [1, 1]
     eng = pipe.hip_engine()
     pipe.host_transport = "copy"
@@ -325,19 +295,9 @@ def test_boundary_pipeline_passes_host_transport_through():
     torch.manual_seed(123)                                                         # the pose posterior uses the GLOBAL generator
     img_c = pipe(generator=torch.Generator(DEV).manual_seed(7), cloth=cache, text_embeds_cloth=None, garment_index=index, **call)[0]
     assert eng.stats["garment_stream_launches"] == s0["garment_stream_launches"] and eng.stats["garment_stage_launches"] > s0["garment_stage_launches"]
-    gen = torch.Generator(DEV).manual_seed(7)
-    torch.manual_seed(123)
-    draw = lambda gg, dt_: torch.randn((B, 4, H // 8, W // 8), generator=gg, device=DEV, dtype=dt_).float()
-    n_lat, n_masked, n_pose, _dropped = draw(gen, DT), draw(gen, torch.float32), draw(None, torch.float32), draw(gen, torch.float32)
-    n_steps = torch.stack([draw(gen, DT) for _ in range(steps)])
-    with torch.no_grad():
-        pos = enc(clip_pix.to(DEV, DT), output_hidden_states=True).hidden_states[-2]
-        neg = enc(torch.zeros_like(clip_pix).to(DEV, DT), output_hidden_states=True).hidden_states[-2]
-    ref = eng(image=inp["image"], mask_image=inp["mask_image"], pose_img=inp["pose_img"], cloth=device, garment_index=index,
-              prompt_embeds=inp["prompt_embeds"], negative_prompt_embeds=inp["negative_prompt_embeds"],
-              pooled_prompt_embeds=inp["pooled_prompt_embeds"], negative_pooled_prompt_embeds=inp["negative_pooled_prompt_embeds"],
-              text_embeds_cloth=None, noise=dict(latents=n_lat, masked=n_masked, pose=n_pose, cloth=None, steps=n_steps),
-              num_inference_steps=steps, guidance_scale=2.0, ip_hidden_states=torch.cat([neg, pos]), scheduler="ddpm")
+    _, noise = reference_draws(7, 123, B, H, W, steps, DT)
+    ip = ip_states(enc, clip_pix)
+    ref = engine_reference(eng, inp, noise, ip, steps, cloth=device, garment_index=index)
     assert torch.isfinite(img_c).all() and torch.equal(img_c, ref)
     pipe.host_transport = "bogus"
     with pytest.raises(ValueError, match="host_transport='bogus'"):

@@ -8,7 +8,7 @@ import os
 import pytest
 import torch
 
-from tests.test_garment_packed_cpu import _same
+from tests.garment_support import cache3, record_fields, same_packed
 
 
 # ------------------------------------------------------------------------------------------------------------------ ABI
@@ -106,12 +106,6 @@ def test_copy_mode_ignores_the_exponent_pointer():
 
 
 # ------------------------------------------------------------------------------------------------------------------ records
-def _cache3(G=3, n=4, dtype=torch.float16, seed=0):
-    """Three features of different (N, C): K [n * G * N][C], V^T [n * G][C][N]."""
-    from idm_vton_amd.garment_cache import GarmentCache
-    g = torch.Generator().manual_seed(seed)
-    kv = [(torch.randn(n * G * N, Cc, generator=g).to(dtype), torch.randn(n * G, Cc, N, generator=g).to(dtype)) for N, Cc in ((192, 64), (48, 128), (1040, 16))]
-    return GarmentCache(G=G, timesteps=list(range(900, 900 - 200 * n, -200)), h=16, w=12, dtype=dtype, attn_fp8=False, f8_exp=(2, 2, 2), weights_id="w0", kv=kv)
 
 
 def _restated(src, dst, exps, n, G, k, S, entries, tslots, garments, gslots, address):
@@ -131,17 +125,13 @@ def _restated(src, dst, exps, n, G, k, S, entries, tslots, garments, gslots, add
     return out
 
 
-def _fields(rec):
-    return [(int(r[0]), int(r[1]), int(r[2]), int(r[3]) & 0xffffffff, int(r[3]) >> 32, int(r[4]) & 0xffffffff, int(r[4]) >> 32) for r in rec]
-
-
 def test_copy_mode_records_and_prefix_table_against_a_restatement():
     """A 3-feature synthetic cache, P = 4 persons with garment_index [2, 0, 2, 1]: the U = 3 distinct garments in first-use order into slots
     0..2 of 4-slot sets, entries by value.  Copy form (16-bit source: byte units, no exponent) and widening form, with an `address` of the
     caller's (asked once per source tensor); the prefix table and KvStreamTable's per-slice tables against ceil(items / 1024) summed up."""
     from idm_vton_amd import ffi, ops
     from idm_vton_amd.garment_cache import alloc_kv, fill_records, kv_shapes, slot_run
-    c = _cache3()
+    c = cache3()
     n, G, k, S = 4, 3, 3, 4
     garments = list(dict.fromkeys([2, 0, 2, 1]))
     assert garments == [2, 0, 1]
@@ -155,7 +145,7 @@ def test_copy_mode_records_and_prefix_table_against_a_restatement():
     rec = fill_records(c.kv, n, G, dst, k, S, None, entries, tslots, garments, gslots, address=address)
     assert rec.dtype == torch.int64 and tuple(rec.shape) == (3 * 3 * 3 * 2, 5) and rec.is_contiguous()
     assert sorted(asked) == sorted(t.data_ptr() for kvf in c.kv for t in kvf)                # once per tensor
-    assert _fields(rec) == _restated(c.kv, dst, None, n, G, k, S, entries, tslots, garments, gslots, lambda t: t.data_ptr() + 0x10000000)
+    assert record_fields(rec) == _restated(c.kv, dst, None, n, G, k, S, entries, tslots, garments, gslots, lambda t: t.data_ptr() + 0x10000000)
     # the default address is data_ptr(): the records name slot_run's views, in bytes
     rec0 = fill_records(c.kv, n, G, dst, k, S, None, entries, tslots, garments, gslots)
     descs = (ffi.KvStreamDesc * rec0.shape[0]).from_address(rec0.data_ptr())
@@ -173,11 +163,11 @@ def test_copy_mode_records_and_prefix_table_against_a_restatement():
     asked.clear()
     recw = fill_records(p.kv, n, G, dst, k, S, p.exps, entries, tslots, garments, gslots, address=address)
     assert len(asked) == 2 * len(p.kv) + 1
-    assert _fields(recw) == _restated(p.kv, dst, p.exps, n, G, k, S, entries, tslots, garments, gslots, lambda t: t.data_ptr() + 0x10000000)
-    assert _fields(fill_records(p.kv, n, G, dst, k, S, p.exps, entries, tslots, garments, gslots)) == \
+    assert record_fields(recw) == _restated(p.kv, dst, p.exps, n, G, k, S, entries, tslots, garments, gslots, lambda t: t.data_ptr() + 0x10000000)
+    assert record_fields(fill_records(p.kv, n, G, dst, k, S, p.exps, entries, tslots, garments, gslots)) == \
         _restated(p.kv, dst, p.exps, n, G, k, S, entries, tslots, garments, gslots, lambda t: t.data_ptr())
     # prefix tables: 16-byte items per record -> chunks of 1024
-    items = [r[3] * (r[4] // 16) for r in _fields(rec)]
+    items = [r[3] * (r[4] // 16) for r in record_fields(rec)]
     chunks = [(it + 1023) // 1024 for it in items]
     assert max(chunks) > 1 and min(chunks) == 1
     want = [0]
@@ -205,7 +195,7 @@ def test_a_pageable_tensor_never_gets_an_address():
 
 # ------------------------------------------------------------------------------------------------------------------ cache and pool
 def test_host_resident_flag_and_put_on_cpu_tensors():
-    c = _cache3()
+    c = cache3()
     assert c.host_resident and c.pack().host_resident and c.select([1]).host_resident and c.take(0).host_resident
     q = c.select([0, 1, 2])
     ptrs = [k.data_ptr() for k, _ in q.kv]
@@ -214,13 +204,13 @@ def test_host_resident_flag_and_put_on_cpu_tensors():
     assert all(torch.equal(a, b) and torch.equal(x, y) for (a, x), (b, y) in zip(q.kv, c.select([2, 1, 2]).kv))
     p = c.pack().select([0, 1, 2])
     p.put(1, c.take(0))                                  # a 16-bit source into a packed host cache: packed first
-    assert _same(p, c.select([0, 0, 2]).pack())
+    assert same_packed(p, c.select([0, 0, 2]).pack())
 
 
 @pytest.mark.parametrize("packed", [False, True], ids=["16bit", "packed"])
 def test_host_pool_lru_equals_the_device_style_pool(packed):
     from idm_vton_amd.garment_cache import GarmentPool
-    ones = {key: _cache3(G=1, seed=s) for s, key in enumerate("abcde")}
+    ones = {key: cache3(G=1, seed=s) for s, key in enumerate("abcde")}
     if packed:
         ones = {key: one.pack() for key, one in ones.items()}
     pools = [GarmentPool(3, like=ones["a"]), GarmentPool(3, like=ones["a"], resident="host")]
@@ -246,7 +236,7 @@ def test_host_pool_lru_equals_the_device_style_pool(packed):
 
 def test_host_pool_refuses_spill_and_mixed_sizes():
     from idm_vton_amd.garment_cache import GarmentPool
-    one = _cache3(G=1)
+    one = cache3(G=1)
     with pytest.raises(ValueError, match=r'resident="host" cannot be combined with spill'):
         GarmentPool(2, like=one, spill=True, resident="host")
     with pytest.raises(ValueError, match=r'resident="host" cannot be combined with spill'):

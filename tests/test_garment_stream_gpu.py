@@ -8,25 +8,14 @@ import ctypes as C
 import pytest
 import torch
 
-from tests.test_garment_cache_gpu import FORMS, _engine, _garment_kw
-from tests.test_garment_index_gpu import _base, _run
-from tests.test_garment_packed_gpu import RUNS, _assert_bits, _bytes
+from tests.engine_support import (DEV, RUNS, assert_bits, base_call, boundary_inputs, boundary_pipeline, e4m3_bytes, engine_inputs, engine_reference,
+                                  garment_kw, ip_states, pin_frame, reference_draws, run_on, to_host)
+from tests.garment_support import DTYPES, FORMS, IDX
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-DTYPES = pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
 
 
 # ------------------------------------------------------------------------------------------------------------------ kernel
-def _pinned(view):
-    """A framed CPU view (tests/frames.py) -> the same frame in page-locked memory."""
-    from tests import frames
-    fr = view._frame
-    buf = fr.buf.pin_memory()
-    v = buf.as_strided(view.shape, view.stride(), view.storage_offset())
-    v._frame = frames._Frame(buf, fr.start, fr.shape, fr.ld, fr.interior_bits)
-    assert v.is_pinned()
-    return v
 
 
 def _widen(runs, dtype, workgroups, on_device=()):
@@ -38,8 +27,8 @@ def _widen(runs, dtype, workgroups, on_device=()):
     exps_d = exps_h.to(DEV)
     srcs, dsts, descs = [], [], []
     for i, (rows, cols, lds, ldd, _) in enumerate(runs):
-        b = _bytes(rows, cols, seed=i)
-        s = frames.framed(b.to(DEV), lds) if i in on_device else _pinned(frames.framed(b, lds))   # gap columns and guard bands: 0x7f, e4m3's NaN
+        b = e4m3_bytes(rows, cols, seed=i)
+        s = frames.framed(b.to(DEV), lds) if i in on_device else pin_frame(frames.framed(b, lds))   # gap columns and guard bands: 0x7f, e4m3's NaN
         d = frames.framed_out((rows, cols), dtype, DEV, ldd)
         srcs.append(s); dsts.append(d)
         descs.append((s, d, (exps_d if i in on_device else exps_h)[i:i + 1]))
@@ -52,11 +41,11 @@ def _check_widen(runs, srcs, dsts, dtype):
     from idm_vton_amd.garment_cache import unpack_values
     from tests import frames
     for i, ((rows, cols, lds, ldd, e), s, d) in enumerate(zip(runs, srcs, dsts)):
-        b = _bytes(rows, cols, seed=i)
+        b = e4m3_bytes(rows, cols, seed=i)
         frames.assert_all_written(d, f"run {i}")
         frames.assert_frame_intact(d, f"run {i}")        # guard bands and the gap columns [cols, ldd)
         frames.assert_untouched(s, f"run {i} source")
-        _assert_bits(d, unpack_values(b, torch.tensor(e), dtype), b, f"run {i}: not the format's bits")
+        assert_bits(d, unpack_values(b, torch.tensor(e), dtype), b, f"run {i}: not the format's bits")
 
 
 @DTYPES
@@ -94,7 +83,7 @@ def test_kv_stream_copy_mode_from_pinned_memory(dtype):
     srcs, dsts, vals, descs = [], [], [], []
     for i, (rows, cols, lds, ldd) in enumerate(COPY_RUNS):
         x = torch.randn(rows, cols, generator=torch.Generator().manual_seed(i)).to(dtype)
-        s, d = _pinned(frames.framed(x, lds)), frames.framed_out((rows, cols), dtype, DEV, ldd)
+        s, d = pin_frame(frames.framed(x, lds)), frames.framed_out((rows, cols), dtype, DEV, ldd)
         srcs.append(s); dsts.append(d); vals.append(x)
         descs.append((s, d, None))
     table = ops.kv_stream(descs, dtype, mode=ffi.KVS_COPY, workgroups=3)
@@ -145,13 +134,6 @@ def test_kv_stream_wrapper_refuses_a_malformed_run():
 
 
 # ------------------------------------------------------------------------------------------------------------------ engine
-IDX = [2, 0, 2, 1]
-
-
-def _host(cache):
-    h = cache.to("cpu", pin_memory=True)
-    assert h.host_resident and not cache.host_resident and all(k.is_pinned() and vt.is_pinned() for k, vt in h.kv)
-    return h
 
 
 @DTYPES
@@ -160,21 +142,21 @@ def test_packed_host_cache_equals_the_device_resident_call(dtype):
     execution form against the same call on the device-resident cache, and one idmvton_kv_stream launch per block.  (The device call of a
     form runs first, so a graph form's state exists when the host call starts: a state built on a device cache serves the host one.)"""
     steps = 4
-    eng, inp, _ = _engine(dtype, 4, steps)
-    packed = eng.encode_garment(num_inference_steps=steps, storage="e4m3", **_garment_kw(inp, 3))
-    host = _host(packed)
+    eng, inp, _ = engine_inputs(dtype, 4, steps)
+    packed = eng.encode_garment(num_inference_steps=steps, storage="e4m3", **garment_kw(inp, 3))
+    host = to_host(packed)
     assert host.packed and host.exps.is_pinned() and host.G == 3
-    base = _base(inp, steps)
+    base = base_call(inp, steps)
     nblocks = len(eng._block_schedule(steps)[1])
     assert nblocks == 3
     for form in FORMS:
-        lat_d = _run(eng, base, packed, form, IDX)
+        lat_d = run_on(eng, base, packed, form, IDX)
         states, n0, c0 = len(eng._graphs), eng.stats["garment_stream_launches"], eng.stats["garment_set_copies"]
-        lat_h = _run(eng, base, host, form, IDX)
+        lat_h = run_on(eng, base, host, form, IDX)
         assert torch.isfinite(lat_d).all() and torch.equal(lat_h, lat_d), (form, (lat_h - lat_d).abs().max().item())
         assert eng.stats["garment_stream_launches"] - n0 == nblocks, form
         assert eng.stats["garment_set_copies"] == c0 and len(eng._graphs) == states, form
-    assert not torch.equal(_run(eng, base, host, "serial_eager", [0, 0, 1, 2]), lat_d)    # another index gives other latents
+    assert not torch.equal(run_on(eng, base, host, "serial_eager", [0, 0, 1, 2]), lat_d)    # another index gives other latents
 
 
 @DTYPES
@@ -182,51 +164,51 @@ def test_16bit_host_cache_equals_the_device_resident_call(dtype):
     """A 16-bit cache in pinned host memory (copy mode), P = G = 2, 7 steps (blocks of 1, 2, 4 timesteps), and the strength-0.6 call on the
     same 7-step cache (its entries found by value)."""
     steps = 7
-    eng, inp, _ = _engine(dtype, 2, steps)
-    cache = eng.encode_garment(num_inference_steps=steps, **_garment_kw(inp))
-    host = _host(cache)
+    eng, inp, _ = engine_inputs(dtype, 2, steps)
+    cache = eng.encode_garment(num_inference_steps=steps, **garment_kw(inp))
+    host = to_host(cache)
     assert not host.packed
-    base = _base(inp, steps)
+    base = base_call(inp, steps)
     part = dict(base, strength=0.6, noise={**base["noise"], "image": torch.randn(2, 4, 16, 16, generator=torch.Generator().manual_seed(77)),
                                            "steps": inp["noise"]["steps"][:4]})
     for what, call, nblocks in (("full", base, 3), ("strength 0.6", part, len(eng._block_schedule(4)[1]))):
         for form in FORMS:                               # (the device call first: a graph form's state then exists and serves the host call)
-            lat_d = _run(eng, call, cache, form)
+            lat_d = run_on(eng, call, cache, form)
             states, n0, c0 = len(eng._graphs), eng.stats["garment_stream_launches"], eng.stats["garment_set_copies"]
-            lat_h = _run(eng, call, host, form)
+            lat_h = run_on(eng, call, host, form)
             assert torch.isfinite(lat_d).all() and torch.equal(lat_h, lat_d), (what, form, (lat_h - lat_d).abs().max().item())
             assert eng.stats["garment_stream_launches"] - n0 == nblocks, (what, form)
             assert eng.stats["garment_set_copies"] == c0 and len(eng._graphs) == states, (what, form)
-    assert not torch.equal(lat_d, _run(eng, base, cache, "serial_eager"))
+    assert not torch.equal(lat_d, run_on(eng, base, cache, "serial_eager"))
 
 
 def test_refusals_before_anything_is_launched():
     from idm_vton_amd.garment_cache import GarmentCache
     steps = 3
-    eng, inp, _ = _engine(torch.float16, 2, steps)
-    base = _base(inp, steps)
-    cache = eng.encode_garment(num_inference_steps=steps, **_garment_kw(inp))
+    eng, inp, _ = engine_inputs(torch.float16, 2, steps)
+    base = base_call(inp, steps)
+    cache = eng.encode_garment(num_inference_steps=steps, **garment_kw(inp))
     packed = cache.pack()
     stats = dict(eng.stats)
     with pytest.raises(ValueError, match="kv mismatch.*pageable.*pin_memory"):
         eng.prepare(**{**base, "cloth": cache.to("cpu")})
     with pytest.raises(ValueError, match="kv mismatch.*pageable.*pin_memory"):
         eng.prepare(**{**base, "cloth": packed.to("cpu")})
-    half = _host(packed)
+    half = to_host(packed)
     half.exps = half.exps.clone()                        # pinned bytes, pageable exponents
     assert not half.exps.is_pinned()
     with pytest.raises(ValueError, match="exps mismatch.*pageable.*pin_memory"):
         eng.prepare(**{**base, "cloth": half})
-    slotted = _host(eng.empty_garment_cache(2, garment_height=128, garment_width=128, num_inference_steps=steps))
+    slotted = to_host(eng.empty_garment_cache(2, garment_height=128, garment_width=128, num_inference_steps=steps))
     assert slotted.sizes is not None
     with pytest.raises(ValueError, match="sizes mismatch.*not streamed"):
         eng.prepare(**{**base, "cloth": slotted, "garment_index": [0, 1]})
     assert eng.stats == stats and not eng._graphs
-    eng8, inp8, _ = _engine(torch.float16, 2, steps, unet_kw=dict(attn_fp8=True))
-    cache8 = eng8.encode_garment(num_inference_steps=steps, **_garment_kw(inp8))
+    eng8, inp8, _ = engine_inputs(torch.float16, 2, steps, fp8=True)
+    cache8 = eng8.encode_garment(num_inference_steps=steps, **garment_kw(inp8))
     stats8 = dict(eng8.stats)
     with pytest.raises(ValueError, match="attn_fp8 mismatch.*does not stream"):
-        eng8.prepare(**{**_base(inp8, steps), "cloth": _host(cache8)})
+        eng8.prepare(**{**base_call(inp8, steps), "cloth": to_host(cache8)})
     assert eng8.stats == stats8 and not eng8._graphs
     assert isinstance(cache8, GarmentCache)
 
@@ -236,78 +218,44 @@ def test_host_pool_swaps_a_garment_between_two_graph_calls():
     equals a fresh engine's call on the swapped cache built apart on the device, and no graph state or graph was added."""
     from idm_vton_amd.garment_cache import GarmentCache, GarmentPool
     steps = 3
-    eng, inp, _ = _engine(torch.float16, 4, steps)
+    eng, inp, _ = engine_inputs(torch.float16, 4, steps)
     enc = lambda i: eng.encode_garment(num_inference_steps=steps, storage="e4m3", cloth=inp["cloth"][i:i + 1],
                                        text_embeds_cloth=inp["text_embeds_cloth"][i:i + 1], noise_cloth=inp["noise"]["cloth"][i:i + 1])
     ones = {f"g{i}": enc(i) for i in range(4)}
     pool = GarmentPool(3, like=ones["g0"], resident="host")
     assert pool.cache.host_resident and pool.cache.packed and pool.cache.exps.is_pinned() and all(k.is_pinned() for k, _ in pool.cache.kv)
     assert pool.get(["g0", "g1", "g2"], encode=ones.get) == [0, 1, 2]
-    base = _base(inp, steps)
-    fresh, _, _ = _engine(torch.float16, 4, steps)
+    base = base_call(inp, steps)
+    fresh, _, _ = engine_inputs(torch.float16, 4, steps)
     before = GarmentCache.cat([ones["g0"], ones["g1"], ones["g2"]])
     swapped = GarmentCache.cat([ones["g0"], ones["g3"], ones["g2"]])
-    ref_before, ref_after = _run(fresh, base, before, "serial_eager", IDX), _run(fresh, base, swapped, "serial_eager", IDX)
+    ref_before, ref_after = run_on(fresh, base, before, "serial_eager", IDX), run_on(fresh, base, swapped, "serial_eager", IDX)
     assert not torch.equal(ref_before, ref_after)
     for form in ("graph", "graph_overlap"):
-        assert torch.equal(_run(eng, base, pool.cache, form, IDX), ref_before), form
+        assert torch.equal(run_on(eng, base, pool.cache, form, IDX), ref_before), form
     states, graphs = len(eng._graphs), sum(len(g["graphs"]) for g in eng._graphs.values())
     ptrs = [k.data_ptr() for k, _ in pool.cache.kv] + [pool.cache.exps.data_ptr()]
     assert pool.get(["g0", "g3", "g2"], encode=ones.get) == [0, 1, 2]            # g1 is the least recently used garment the batch does not name
     assert ptrs == [k.data_ptr() for k, _ in pool.cache.kv] + [pool.cache.exps.data_ptr()] and pool.stats["evicted"] == 1
     for form in ("graph", "graph_overlap"):
-        assert torch.equal(_run(eng, base, pool.cache, form, IDX), ref_after), form
+        assert torch.equal(run_on(eng, base, pool.cache, form, IDX), ref_after), form
     assert len(eng._graphs) == states and sum(len(g["graphs"]) for g in eng._graphs.values()) == graphs
 
 
 def test_boundary_pipeline_takes_a_host_resident_packed_cache():
     """pipe(cloth=<packed cache in pinned host memory>, garment_index=...) against the engine-level call on the same draws."""
-    from idm_vton_amd import config as pc
-    from idm_vton_amd.boundary.scheduler import DDPMScheduler
-    from idm_vton_amd.boundary.vae import AutoencoderKL
-    from src.tryon_pipeline import StableDiffusionXLInpaintPipeline
-    from src.unet_hacked_garmnet import UNet2DConditionModel as G
-    from src.unet_hacked_tryon import UNet2DConditionModel as T
-    from tests import parity_utils as pu
-    from tests.test_garment_cache_gpu import _FakeCLIPVision
     DT = torch.float16
-    kw = dict(pu.TINY)
-    tcfg = pc.UNetConfig(mode="tryon", in_channels=13, sample_size=16, **kw)
-    gcfg = pc.UNetConfig(mode="garmnet", in_channels=4, addition_embed_type=None, encoder_hid_dim_type=None, sample_size=16, **kw)
-    vcfg = pc.VAEConfig(**pu.TINY_VAE)
-    rnd = lambda sd: {k: v.to(DT) for k, v in sd.items()}
-    t = T(tcfg, torch_dtype=DT); t.load_state_dict(rnd(pc.random_state_dict(pc.unet_param_shapes(tcfg), 1, torch.float32, "cpu")))
-    g = G(gcfg, torch_dtype=DT); g.load_state_dict(rnd(pc.random_state_dict(pc.unet_param_shapes(gcfg), 2, torch.float32, "cpu")))
-    v = AutoencoderKL(vcfg, torch_dtype=DT); v.load_state_dict(rnd(pc.random_state_dict(pc.vae_param_shapes(vcfg), 3, torch.float32, "cpu", std=0.05)))
-    torch.manual_seed(5)
-    enc = _FakeCLIPVision(kw["encoder_hid_dim"]).to(DT)
-    pipe = StableDiffusionXLInpaintPipeline(vae=v, text_encoder=None, text_encoder_2=None, tokenizer=None, tokenizer_2=None, unet=t,
-                                            unet_encoder=g, scheduler=DDPMScheduler(), image_encoder=enc).to(DEV)
+    pipe, enc, kw = boundary_pipeline(DT)
     B, H, W, steps = 2, 128, 128, 3
-    inp = pu.make_inputs(B, H, W, kw["cross_attention_dim"], 64, kw["encoder_hid_dim"], steps, DT)
-    clip_pix = torch.randn(B, 3, 224, 224, generator=torch.Generator().manual_seed(9))
-    call = dict(prompt_embeds=inp["prompt_embeds"], negative_prompt_embeds=inp["negative_prompt_embeds"],
-                pooled_prompt_embeds=inp["pooled_prompt_embeds"], negative_pooled_prompt_embeds=inp["negative_pooled_prompt_embeds"],
-                num_inference_steps=steps, strength=1.0, pose_img=inp["pose_img"], mask_image=inp["mask_image"], image=inp["image"],
-                height=H, width=W, guidance_scale=2.0, ip_adapter_image=clip_pix, output_type="pt")
-    cache = _host(pipe.encode_garment(inp["cloth"], inp["text_embeds_cloth"], steps, H, W, generator=torch.Generator(DEV).manual_seed(11), storage="e4m3"))
+    inp, clip_pix, call = boundary_inputs(kw, B, H, W, steps, DT)
+    cache = to_host(pipe.encode_garment(inp["cloth"], inp["text_embeds_cloth"], steps, H, W, generator=torch.Generator(DEV).manual_seed(11), storage="e4m3"))
     index = [1, 1]
     eng = pipe.hip_engine()
     n0 = eng.stats["garment_stream_launches"]
     torch.manual_seed(123)                                                         # the pose posterior uses the GLOBAL generator
     img_c = pipe(generator=torch.Generator(DEV).manual_seed(7), cloth=cache, text_embeds_cloth=None, garment_index=index, **call)[0]
     assert eng.stats["garment_stream_launches"] > n0 and cache.host_resident
-    gen = torch.Generator(DEV).manual_seed(7)
-    torch.manual_seed(123)
-    draw = lambda gg, dt_: torch.randn((B, 4, H // 8, W // 8), generator=gg, device=DEV, dtype=dt_).float()
-    n_lat, n_masked, n_pose, _dropped = draw(gen, DT), draw(gen, torch.float32), draw(None, torch.float32), draw(gen, torch.float32)
-    n_steps = torch.stack([draw(gen, DT) for _ in range(steps)])
-    with torch.no_grad():
-        pos = enc(clip_pix.to(DEV, DT), output_hidden_states=True).hidden_states[-2]
-        neg = enc(torch.zeros_like(clip_pix).to(DEV, DT), output_hidden_states=True).hidden_states[-2]
-    ref = eng(image=inp["image"], mask_image=inp["mask_image"], pose_img=inp["pose_img"], cloth=cache, garment_index=index,
-              prompt_embeds=inp["prompt_embeds"], negative_prompt_embeds=inp["negative_prompt_embeds"],
-              pooled_prompt_embeds=inp["pooled_prompt_embeds"], negative_pooled_prompt_embeds=inp["negative_pooled_prompt_embeds"],
-              text_embeds_cloth=None, noise=dict(latents=n_lat, masked=n_masked, pose=n_pose, cloth=None, steps=n_steps),
-              num_inference_steps=steps, guidance_scale=2.0, ip_hidden_states=torch.cat([neg, pos]), scheduler="ddpm")
+    _, noise = reference_draws(7, 123, B, H, W, steps, DT)
+    ip = ip_states(enc, clip_pix)
+    ref = engine_reference(eng, inp, noise, ip, steps, cloth=cache, garment_index=index)
     assert torch.isfinite(img_c).all() and torch.equal(img_c, ref)

@@ -121,7 +121,7 @@ def test_undefined_attention_tune_words_are_refused_on_the_host():
         with pytest.raises(RuntimeError, match="unknown kernel selector"):
             ffi.call("idmvton_attn_fwd", args(word(kern, 3, 8)), 0)
     # every word the suite's kernel list and the committed table spell is a defined one
-    from tests.test_garment_cache_gpu import TUNES
+    from tests.kernel_checks import TUNES
 
     def defined(t):
         kern, stg, nw = (t >> 16) & 0xff, (t >> 8) & 0xff, t & 0xff

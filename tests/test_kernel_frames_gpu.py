@@ -12,8 +12,9 @@ import torch
 from hypothesis import HealthCheck, given, settings, strategies as st
 
 from tests import kernel_checks as kc
+from tests.engine_support import no_tune_table
 from tests.frames import Framed, Tight
-from tests.test_garment_cache_gpu import TUNES
+from tests.kernel_checks import TUNES
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -207,19 +208,15 @@ def test_fused_cross_attention_nan_key_rows_large_vt_filler(hint, dtype):
 
 
 # ------------------------------------------------------------------------------------------------------------------ Family B: attention
-@pytest.fixture
-def no_tune_table(monkeypatch):
-    """tune = 0 reaches the library's own rule, whatever the committed table holds for a shape."""
-    from idm_vton_amd import ops
-    monkeypatch.setattr(ops, "_TUNE", {"gemm": {}, "attn": {}})
 
 
 @DTYPES
 @pytest.mark.parametrize("entry", kc.ENTRIES)
 @pytest.mark.parametrize("tune", list(TUNES), ids=list(TUNES))
-def test_self_attention_in_the_products_geometry(tune, entry, dtype, no_tune_table):
+def test_self_attention_in_the_products_geometry(tune, entry, dtype, monkeypatch):
     """q | k column halves of one buffer (ldq = ldk = 2C), out at ldo = C + 8, own segment B = 3, 2 heads, 200 queries, nk = 200 of k_rows = 208,
     garment segment 72 keys of 80 rows from batch 1 on, ldvt > round16(nk); NaN key rows, 1.0e4 in V^T beyond nk; through every entry point."""
+    no_tune_table(monkeypatch)
     run_both(kc.check_attn_product, kc.TOL[dtype], Framed(pads=dict(out=8, kg=8)), named=bool(TUNES[tune]), dtype=dtype, dev=DEV, tune=TUNES[tune], entry=entry)
 
 
@@ -228,9 +225,10 @@ RAW_Q = [t for t in TUNES if ((TUNES[t] >> 16) & 0xff) not in (7, 8, 16)]       
 
 @DTYPES
 @pytest.mark.parametrize("tune", RAW_Q, ids=RAW_Q)
-def test_self_attention_in_the_resamplers_geometry(tune, dtype, no_tune_table):
+def test_self_attention_in_the_resamplers_geometry(tune, dtype, monkeypatch):
     """16 raw latent queries against 257 keys in 272 rows plus the 16 latent keys (Nq != round16(nk), q not pre-multiplied): key rows 257..271
     NaN -- in the Resampler they hold the projection of zero rows through a LayerNorm: finite, non-zero --, V^T 1.0e4 beyond the keys."""
+    no_tune_table(monkeypatch)
     run_both(kc.check_attn_product, kc.TOL[dtype], Framed(pads=dict(out=8, kg=8)), named=bool(TUNES[tune]), dtype=dtype, dev=DEV, tune=TUNES[tune],
              **kc.RESAMPLER_GEOMETRY)
 
@@ -244,8 +242,9 @@ def test_fp8_attention_in_the_products_geometry(entry, dtype):
 
 @DTYPES
 @pytest.mark.parametrize("tune", ["auto", "k0_2stage_4w", "k0_ring3_4w", "k0_2stage_8w"])
-def test_cross_attention_key_rows_96_and_32(tune, dtype, no_tune_table):
+def test_cross_attention_key_rows_96_and_32(tune, dtype, monkeypatch):
     """77 / 16 keys in K tables of 96 / 32 rows (rows from nk on NaN), V^T 1.0e4 beyond nk at ldvt = round16(nk) + 16, q / K / out strided."""
+    no_tune_table(monkeypatch)
     run_both(kc.check_attn_cross, kc.TOL[dtype], Framed(pads=dict(q=8, out=8, k0=8, k1=8)), named=bool(TUNES[tune]), B=2, heads=2, N=200, dtype=dtype,
              dev=DEV, ip_scale=0.5, tune=TUNES[tune], k_rows=(96, 32))
 

@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from tests import kernel_checks as kc
+from tests.engine_support import clip_ids, clip_text, mk_attn
 from tests.launch_forms import describe, gemm_form
 
 pytestmark = pytest.mark.gpu
@@ -128,17 +129,15 @@ def _engine_call(H, W, steps=1, vae16=False, garment_cache=False, **unet_kw):
 
 
 def _clip(kind):
-    from tests.test_clip_gpu import _ids, _text
-
     def run():
         if kind == "text_quick_gelu":
             from idm_vton_amd.clip import HipCLIPText
-            m = _text(128, 2, 2, "quick_gelu", 64, eos=2)
-            HipCLIPText(m.state_dict(), m.config, DT, DEV)(_ids(3, 77, 1000, 999, 1))
+            m = clip_text(128, 2, 2, "quick_gelu", 64, eos=2)
+            HipCLIPText(m.state_dict(), m.config, DT, DEV)(clip_ids(3, 77, 1000, 999, 1))
         elif kind == "text_gelu":
             from idm_vton_amd.clip import HipCLIPText
-            m = _text(128, 2, 2, "gelu", 64)
-            HipCLIPText(m.state_dict(), m.config, DT, DEV)(_ids(3, 77, 1000, 999, 1))
+            m = clip_text(128, 2, 2, "gelu", 64)
+            HipCLIPText(m.state_dict(), m.config, DT, DEV)(clip_ids(3, 77, 1000, 999, 1))
         else:
             from transformers import CLIPVisionConfig, CLIPVisionModelWithProjection
             from idm_vton_amd.clip import HipCLIPVision
@@ -154,14 +153,13 @@ def _boundary():
     """The attention processors by the route of tests/test_boundary_gpu.py: self-attention on tokens (a multiple of 16 and not) and on NCHW, cross
     attention with 77 keys, text + image tokens."""
     from ip_adapter.attention_processor import AttnProcessor2_0, IPAttnProcessor2_0
-    from tests.test_boundary_gpu import _mk_attn
-    a = _mk_attn(128, None, 2, AttnProcessor2_0(), 0)
+    a = mk_attn(128, None, 2, AttnProcessor2_0(), 0)
     a(torch.randn(2, 100, 128).to(DEV, DT))
     a(torch.randn(2, 96, 128).to(DEV, DT))
     a(torch.randn(2, 128, 10, 10).to(DEV, DT))
-    _mk_attn(128, 192, 2, AttnProcessor2_0(), 1)(torch.randn(2, 72, 128).to(DEV, DT), encoder_hidden_states=torch.randn(2, 77, 192).to(DEV, DT))
+    mk_attn(128, 192, 2, AttnProcessor2_0(), 1)(torch.randn(2, 72, 128).to(DEV, DT), encoder_hidden_states=torch.randn(2, 77, 192).to(DEV, DT))
     proc = IPAttnProcessor2_0(hidden_size=128, cross_attention_dim=192, scale=0.75, num_tokens=16)
-    _mk_attn(128, 192, 2, proc, 2)(torch.randn(2, 64, 128).to(DEV, DT), encoder_hidden_states=torch.randn(2, 93, 192).to(DEV, DT))
+    mk_attn(128, 192, 2, proc, 2)(torch.randn(2, 64, 128).to(DEV, DT), encoder_hidden_states=torch.randn(2, 93, 192).to(DEV, DT))
 
 
 def _resampler():
