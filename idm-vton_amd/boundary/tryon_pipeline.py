@@ -12,9 +12,11 @@ they are transformers CLIP towers living on the GPU their forward is executed by
 hipGraph replay) and the decode.  RNG draws follow the reference's order with the caller's generator.
 
 guidance_scale <= 1 (no CFG) runs the batched step with guidance 1 (the conditional prediction to one fp32 rounding, at the cost of
-the unused half); strength < 1 starts from the noised image latents as the reference does.
+the unused half) -- or, with `pipe.skip_uncond = True`, the conditional branch alone, as the reference does (:1229-1230); strength < 1
+starts from the noised image latents as the reference does.  `guidance_scale` and `guidance_rescale` (:1818-1820) take a float or a list
+of one value per person: the persons of a batch are independent requests.
 Loud differences: `padding_mask_crop`, `masked_image_latents=`, `timesteps=`,
-`denoising_start/end`, `guidance_rescale`, `cross_attention_kwargs`, step callbacks, `num_images_per_prompt != 1` and
+`denoising_start/end`, `cross_attention_kwargs`, step callbacks, `num_images_per_prompt != 1` and
 schedulers other than DDPM/DDIM raise NotImplementedError: the reference scripts use none of them.
 """
 import json
@@ -29,6 +31,7 @@ from ..clip import HipCLIPText, HipCLIPVision
 from ..garment_cache import GarmentCache
 from ..pipeline import TryonEngine
 from .modules import params_version
+from ..scheduler import per_person
 from .scheduler import DDIMScheduler, DDPMScheduler
 from .unet import GarmentUNet2DConditionModel, TryonUNet2DConditionModel
 from .vae import AutoencoderKL
@@ -94,6 +97,8 @@ class StableDiffusionXLInpaintPipeline:
         self._engine, self._engine_key = None, None
         self._clip = {}                                     # name -> (params_version, HipCLIPText | HipCLIPVision)
         self._guidance_scale = 7.5
+        self._guidance_rescale = 0.0
+        self.skip_uncond = False                            # True: a call in which no person has guidance_scale > 1 runs the conditional branch alone
         self.use_graph, self.overlap = True, True          # engine execution mode (hipGraph replay, two-stream loop)
         self.host_transport = "kernel"                      # how a host-resident GarmentCache crosses the host link ("kernel" | "copy": TryonEngine.denoise)
 
@@ -170,8 +175,15 @@ class StableDiffusionXLInpaintPipeline:
         return self._guidance_scale
 
     @property
+    def guidance_rescale(self):
+        return self._guidance_rescale
+
+    @property
     def do_classifier_free_guidance(self):
-        return self._guidance_scale > 1 and self.unet.config.time_cond_proj_dim is None
+        """True when any person's guidance_scale is > 1 (a float, or a list of one value per person)."""
+        g = self._guidance_scale
+        seq = hasattr(g, "__len__") and getattr(g, "ndim", 1) != 0
+        return max(per_person(g, len(g), "guidance_scale")[0] if seq else [float(g)]) > 1 and self.unet.config.time_cond_proj_dim is None
 
     # ------------------------------------------------------------------------------------------ conditioning encoders
     def _hip_clip(self, name):
@@ -414,8 +426,6 @@ class StableDiffusionXLInpaintPipeline:
                                    ("clip_skip", clip_skip, None)):
             if val is not default:
                 raise NotImplementedError(f"`{name}` is not used by the try-on scripts and not supported by the HIP engine")
-        if guidance_rescale != 0.0:
-            raise NotImplementedError("guidance_rescale != 0 is not supported")
         if num_images_per_prompt != 1:
             raise NotImplementedError("num_images_per_prompt != 1 is not supported")
         if self.config.requires_aesthetics_score:
@@ -437,8 +447,8 @@ class StableDiffusionXLInpaintPipeline:
         self.check_inputs(prompt, prompt_2, image, mask_image, height, width, strength, callback_steps, output_type,
                           negative_prompt, negative_prompt_2, prompt_embeds, negative_prompt_embeds,
                           callback_on_step_end_tensor_inputs, padding_mask_crop)
-        self._guidance_scale = guidance_scale
-        cfg = self.do_classifier_free_guidance              # guidance_scale <= 1: the engine runs its batched step with guidance 1
+        self._guidance_scale, self._guidance_rescale = guidance_scale, guidance_rescale
+        cfg = self.do_classifier_free_guidance              # no person above 1: the engine runs its batched step with guidance 1, or (skip_uncond) the conditional branch alone
         # strength < 1 (reference :987-995, 883-893): the last int(n*strength) timesteps, from the noised image latents (the signature
         # default 0.9999 already drops one step; inference.py:404 and gradio_demo/app.py:225 pass 1.0)
         n_exec = min(int(num_inference_steps * strength), num_inference_steps)
@@ -503,6 +513,11 @@ class StableDiffusionXLInpaintPipeline:
                                latents_given=latents is not None),
                     num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, ip_hidden_states=image_states,
                     strength=strength, scheduler=kind, height=height, width=width)
+        # passed only when they say something: a call without them is, keyword for keyword, the call it always was (trace_call below)
+        if hasattr(guidance_rescale, "__len__") or guidance_rescale != 0.0:
+            call["guidance_rescale"] = guidance_rescale                                          # :1818-1820
+        if self.skip_uncond and not cfg:
+            call["uncond"] = "skip"                                                              # the conditional branch alone (:1229-1230)
         if garment_index is not None:
             call["garment_index"] = garment_index
         if isinstance(getattr(self, "trace_call", None), dict):    # test hook: what crossed the engine boundary (an oracle can replay it)

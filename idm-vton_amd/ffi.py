@@ -68,6 +68,11 @@ class CfgStepArgs(C.Structure):
                 ("noise", vp), ("coef", vp)]
 
 
+class GuidedStepArgs(C.Structure):
+    _fields_ = [("dtype", i32), ("B", i32), ("hw", i32), ("ldc", i32), ("branches", i32), ("work_floats", i32), ("eps_nhwc", vp),
+                ("latents", vp), ("noise", vp), ("coef", vp), ("work", vp)]
+
+
 class LayoutArgs(C.Structure):
     _fields_ = [("dtype", i32), ("B", i32), ("C", i32), ("HW", i32), ("cpad", i32), ("to_nhwc", i32), ("src", vp),
                 ("dst", vp), ("scale", f32), ("shift", f32), ("flags", i32)]
@@ -123,7 +128,8 @@ STRUCTS = {"idmvton_seg": Seg, "idmvton_gemm_conv_args": GemmConvArgs, "idmvton_
            "idmvton_layout_args": LayoutArgs, "idmvton_vae_sample_args": VaeSampleArgs, "idmvton_softmax_args": SoftmaxArgs,
            "idmvton_attn_small_args": AttnSmallArgs, "idmvton_attn_f8_args": AttnF8Args, "idmvton_quant_f8_args": QuantF8Args,
            "idmvton_split_args": SplitArgs, "idmvton_xattn": XAttn, "idmvton_kv_unpack_desc": KvUnpackDesc,
-           "idmvton_kv_unpack_args": KvUnpackArgs, "idmvton_kv_stream_desc": KvStreamDesc, "idmvton_kv_stream_args": KvStreamArgs}
+           "idmvton_kv_unpack_args": KvUnpackArgs, "idmvton_kv_stream_desc": KvStreamDesc, "idmvton_kv_stream_args": KvStreamArgs,
+           "idmvton_guided_step_args": GuidedStepArgs}
 
 # every symbol include/idmvton_hip.h declares
 SYMBOLS = ["idmvton_last_error", "idmvton_abi_version", "idmvton_sizeof", "idmvton_gemm_conv", "idmvton_attn_fwd",
@@ -133,7 +139,8 @@ SYMBOLS = ["idmvton_last_error", "idmvton_abi_version", "idmvton_sizeof", "idmvt
            "idmvton_rccl_comm_destroy", "idmvton_attn_f8", "idmvton_quant_f8", "idmvton_split", "idmvton_attn_fwd_shared",
            "idmvton_attn_f8_shared", "idmvton_attn_fwd_indexed", "idmvton_attn_f8_indexed",
            "idmvton_attn_fwd_ragged", "idmvton_attn_f8_ragged", "idmvton_kv_unpack", "idmvton_kv_stream",
-           "idmvton_host_device_ptr", "idmvton_kv_fill", "idmvton_kv_place"]
+           "idmvton_host_device_ptr", "idmvton_kv_fill", "idmvton_kv_place", "idmvton_guided_step", "idmvton_guided_step_work_floats",
+           "idmvton_pack_input_cond"]
 
 _lib = None
 
@@ -167,7 +174,7 @@ def lib():
             raise HipLibraryMissing(f"ABI drift: sizeof({name}) is {n} in the library, {C.sizeof(st)} in ffi.py")
     for s in ("idmvton_gemm_conv", "idmvton_attn_fwd", "idmvton_layernorm", "idmvton_groupnorm",
               "idmvton_pack_input", "idmvton_cfg_step", "idmvton_layout", "idmvton_vae_sample", "idmvton_softmax_rows",
-              "idmvton_attn_small", "idmvton_attn_f8", "idmvton_quant_f8", "idmvton_split"):
+              "idmvton_attn_small", "idmvton_attn_f8", "idmvton_quant_f8", "idmvton_split", "idmvton_guided_step", "idmvton_pack_input_cond"):
         getattr(L, s).argtypes = [vp, vp]
         getattr(L, s).restype = C.c_int
     for s in ("idmvton_attn_fwd_shared", "idmvton_attn_f8_shared"):          # (args*, const int32_t seg_nb[2], stream)
@@ -189,6 +196,8 @@ def lib():
     L.idmvton_probe_mfma.argtypes = [C.c_int, vp, vp, vp, vp]
     L.idmvton_groupnorm_stats_doubles.argtypes = [C.c_int] * 4
     L.idmvton_groupnorm_stats_doubles.restype = C.c_int
+    L.idmvton_guided_step_work_floats.argtypes = [C.c_int] * 2
+    L.idmvton_guided_step_work_floats.restype = C.c_int
     L.idmvton_rccl_unique_id.argtypes = [vp]
     L.idmvton_rccl_comm_init.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]
     L.idmvton_rccl_bcast_arena.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_uint64, vp]

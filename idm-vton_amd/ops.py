@@ -636,6 +636,46 @@ def cfg_step(eps_nhwc, latents, noise, coef):
     return latents
 
 
+def pack_input_cond(latents, cond, out):
+    """pack_input for the conditional branch alone: out NHWC [B][hw][cpad] from cond [B][hw][9] (idmvton_pack_input_cond)."""
+    a = ffi.PackInputArgs()
+    B, hw = latents.shape[0], latents.shape[2] * latents.shape[3] if latents.dim() == 4 else latents.shape[2]
+    if out.shape[0] != B or cond.shape[0] != B:
+        raise ValueError(f"pack_input_cond: {B} persons, cond of {cond.shape[0]} rows, out of {out.shape[0]} rows (B rows each)")
+    a.dtype, a.B, a.hw, a.cpad = _dt(out), B, hw, out.shape[-1]
+    a.latents, a.cond, a.out = _ptr(latents), _ptr(cond), _ptr(out)
+    _call("idmvton_pack_input_cond", a)
+    return out
+
+
+def guided_step_work_floats(B, hw):
+    """Floats of the `work` buffer of guided_step for B persons of hw pixels (idmvton_guided_step_work_floats)."""
+    n = ffi.lib().idmvton_guided_step_work_floats(int(B), int(hw))
+    if n < 0:
+        raise ValueError(f"guided_step_work_floats: B={B} hw={hw}")
+    return n
+
+
+def guided_step(eps_nhwc, latents, noise, coef_row, work, branches=2):
+    """The CFG combine + scheduler update with a guidance scale and a guidance_rescale per person (idmvton_guided_step).  eps_nhwc: NHWC
+    [branches * B][hw][ldc]; coef_row: float32 device tensor {c_x, c_eps, sigma, g[0..B), phi[0..B)}; work: float32 device tensor of at
+    least guided_step_work_floats(B, hw) elements (branches=1 takes None: the conditional rows alone, e = t).  Updates latents in place."""
+    a = ffi.GuidedStepArgs()
+    B = latents.shape[0]
+    hw = latents.numel() // (B * 4)
+    if coef_row.numel() != 3 + 2 * B or coef_row.dtype != torch.float32:
+        raise ValueError(f"guided_step: coef_row holds {coef_row.numel()} {coef_row.dtype} values, needs 3 + 2B = {3 + 2 * B} float32")
+    if eps_nhwc.shape[0] != branches * B:
+        raise ValueError(f"guided_step: eps of {eps_nhwc.shape[0]} rows for branches={branches} and {B} persons")
+    if work is not None and work.dtype != torch.float32:
+        raise ValueError(f"guided_step: work must be float32, got {work.dtype}")
+    a.dtype, a.B, a.hw, a.ldc, a.branches = _dt(eps_nhwc), B, hw, eps_nhwc.shape[-1], branches
+    a.work, a.work_floats = _ptr(work), 0 if work is None else work.numel()
+    a.eps_nhwc, a.latents, a.noise, a.coef = _ptr(eps_nhwc), _ptr(latents), _ptr(noise), _ptr(coef_row)
+    _call("idmvton_guided_step", a)
+    return latents
+
+
 def to_nhwc(src_nchw_f32, dtype, cpad=None, scale=1.0, shift=0.0, out=None, split=False):
     """fp32 NCHW -> NHWC [cpad] of `dtype`; split=True: NHWC [2*cpad] = [hi | lo] (the split-precision VAE path)."""
     B, Cc = src_nchw_f32.shape[:2]

@@ -49,6 +49,12 @@ A shelved cache may hold feature parts (GarmentShelf(storage="features")): the f
 With garment_index the two cache rows read through the table: eager on the cache's own views (nb = G, table = garment_index), graph on
 P-slot sets into which _fill_set gathers the U distinct garments of the call (table = person -> set slot, a persistent buffer of the state).
 
+Guidance is per person (prepare: guidance_scale / guidance_rescale as a float or one value per person).  A scalar scale without rescale is the
+PLAIN state ([steps][4] coef table, idmvton_cfg_step); anything else the GUIDED state ([steps][3 + 2B] table, a `work` buffer,
+idmvton_guided_step: the reference's rescale_noise_cfg fused into the step), with a graph state of its own.  uncond="skip" -- no person with
+guidance -- runs the conditional branch alone: B TryonNet rows, the garment segment from batch 0 on, e = t; every form and every kind of cache
+below serves it, since what they fill is the garment side.
+
 `denoise` asks once whether the call is live or on a cache, wraps the step in the per-step hooks (`trace`, `on_step`) and drives the
 blocks.  The K / V^T layout of sets and cache (timestep-major) has one owner, garment_cache.timestep_run.
 """
@@ -57,7 +63,7 @@ import torch
 from . import ops
 from .garment_cache import (GarmentCache, PackedGarmentCache, ShelvedGarmentCache, alloc_kv, cache_sources, index_runs, kv_records, kv_shapes,
                             slot_run, staged_plan, timestep_run)
-from .scheduler import StepScheduler
+from .scheduler import StepScheduler, per_person
 
 
 def drive_blocks(blocks, garment, tryon, main=None, side=None, ready=None, free=None):
@@ -188,19 +194,45 @@ class TryonEngine:
 
     @staticmethod
     def _set_key(st):
-        """What the shapes of a persistent garment set depend on: garments, the garment's latent size, timesteps per batch."""
-        return (st["B"], st["gh"], st["gw"], st["k"])
+        """What the shapes of a persistent garment set depend on: garments, the garment's latent size, timesteps per batch -- and an
+        element of its own for a call that runs the conditional branch alone (uncond="skip")."""
+        return (st["B"], st["gh"], st["gw"], st["k"]) + (("cond-only",) if st.get("branches", 2) == 1 else ())
 
     @staticmethod
     def _graph_key(st, live):
         """One persistent graph state per shape of a call: persons, person latent size, garment latent size, block size, step noise, and on a
         GarmentCache its garment count -- or, with garment_index, nothing more: the sets of an indexed state have one slot per PERSON, so one
         state serves every pool size and every assignment.  A cache with `sizes` adds "ragged" (its forwards read a key-count table that a plain
-        state's captures do not have); gh, gw are then the SLOT size, and the garments' own sizes are not in the key."""
+        state's captures do not have); gh, gw are then the SLOT size, and the garments' own sizes are not in the key.  A GUIDED state (per-person
+        guidance: another `cf` width, a `work` buffer, idmvton_guided_step in its captures) adds ("guided", branches) -- branches 1 being
+        uncond="skip", whose captures run B TryonNet rows; a plain state's key is what it always was."""
+        guided = (("guided", st.get("branches", 2)),) if st.get("guided") else ()
         if live:
-            return (st["B"], st["h"], st["w"], st["gh"], st["gw"], st["k"], st["steps_noise"] is not None)
+            return (st["B"], st["h"], st["w"], st["gh"], st["gw"], st["k"], st["steps_noise"] is not None) + guided
         return (st["B"], st["h"], st["w"], st["gh"], st["gw"], st["k"], st["steps_noise"] is not None, "cached",
-                "indexed" if st.get("gindex") is not None else st["gcache"].G) + (("ragged",) if st.get("gnk") is not None else ())
+                "indexed" if st.get("gindex") is not None else st["gcache"].G) + (("ragged",) if st.get("gnk") is not None else ()) + guided
+
+    UNCOND = ("run", "skip")
+
+    @staticmethod
+    def _guidance(B, guidance_scale, guidance_rescale, uncond):
+        """prepare's guidance arguments -> (g per person, phi per person, guided state?, skip the unconditional rows?): checked here, before
+        anything is launched.  A person with g <= 1 gets g = 1 and phi = 0 (no guidance, and the rescale is applied under CFG only)."""
+        if uncond not in TryonEngine.UNCOND:
+            raise ValueError(f"uncond={uncond!r}: \"run\" (the batched step, guidance 1 for a person without guidance) or \"skip\" (the "
+                             "conditional branch alone, when no person has guidance)")
+        g, g_seq = per_person(guidance_scale, B, "guidance_scale")
+        phi, phi_seq = per_person(guidance_rescale, B, "guidance_rescale")
+        if any(not 0.0 <= p <= 1.0 for p in phi):
+            raise ValueError(f"`guidance_rescale` lies in [0, 1], got {guidance_rescale!r}")
+        skip = uncond == "skip"
+        if skip and any(x > 1 for x in g):
+            raise ValueError(f"uncond=\"skip\" runs the conditional branch alone, which needs guidance_scale <= 1 for every person; got "
+                             f"{guidance_scale!r} (uncond=\"run\" runs both branches)")
+        phi = [p if x > 1 else 0.0 for x, p in zip(g, phi)]
+        g = [x if x > 1 else 1.0 for x in g]
+        guided = skip or g_seq or phi_seq or guidance_rescale != 0.0
+        return g, phi, guided, skip
 
     def weights_identity(self):
         """What a GarmentCache depends on besides its inputs: every GarmentNet weight, and TryonNet's attn1.to_k / to_v (the projections of
@@ -375,7 +407,7 @@ class TryonEngine:
     def prepare(self, *, image, mask_image, pose_img, cloth, prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds,
                 negative_pooled_prompt_embeds, text_embeds_cloth, noise, num_inference_steps, guidance_scale,
                 ip_hidden_states=None, image_embeds=None, scheduler="ddpm", height=None, width=None, strength=1.0,
-                image_dtype=None, garment_index=None):
+                image_dtype=None, garment_index=None, guidance_rescale=0.0, uncond="run"):
         """Everything before the loop (tryon_pipeline.py:1495-1762).  image in [0,1]; pose_img / cloth in [-1,1];
         noise: dict(latents, masked, pose [B,4,h,w] fp32; cloth [B,4,gh,gw] fp32; steps [n,B,4,h,w] fp32 or None; image [B,4,h,w] when
         strength < 1) -- RNG order SURVEY A.4.
@@ -396,7 +428,18 @@ class TryonEngine:
         packed cache's `exps` -- must be page-locked (pin_memory), the cache must not have `sizes`, and the engine must not be attn_fp8: each
         a ValueError naming the field, before anything is launched.  A ShelvedGarmentCache (GarmentShelf.get) is the host-resident cache WITH
         sizes: garment_index is required, every part and every part's `exps` must be page-locked, the engine must not be attn_fp8; its
-        parts are compact K / V^T caches or compact feature caches (GarmentShelf(storage="features" / "features-e4m3"))."""
+        parts are compact K / V^T caches or compact feature caches (GarmentShelf(storage="features" / "features-e4m3")).
+        guidance_scale / guidance_rescale: a float, or a sequence of B floats -- one per person, as the garment is (a service need not split
+        a batch by them).  guidance_rescale (rescale_noise_cfg, :101-113, applied as :1818-1820: under CFG only) lies in [0, 1].  A person
+        with g <= 1 runs with g = 1 and without rescale.  A scalar guidance_scale with guidance_rescale == 0 (a scalar) and uncond="run" gives
+        the PLAIN state: the [steps][4] coef table and idmvton_cfg_step, as ever.  Anything else gives the GUIDED state: a [steps][3 + 2B]
+        coef table, a `work` buffer and idmvton_guided_step (st["guided"]), with a graph state of its own.
+        uncond="skip" (only when every person has g <= 1): the reference's form of a call without guidance (:1229-1230) -- the conditional
+        branch ALONE: B TryonNet rows instead of 2B (x_in, cond, temb_t, ctx_t, the key-count table), the garment segment from batch 0 on,
+        e = t in the step.  negative_* are not read; ip_hidden_states / image_embeds may hold B rows or 2B (the first B are dropped).
+        uncond="run" (the default) keeps the batched step with guidance 1 for such a call.
+        A sequence of the wrong length, a rescale outside [0, 1], an unknown `uncond` or uncond="skip" with a g > 1 is a ValueError naming
+        the argument, before anything is launched."""
         dev, dt = self.device, self.dtype
         self._release_streamed()
         f32 = lambda t: t.to(dev, torch.float32).contiguous()
@@ -409,6 +452,7 @@ class TryonEngine:
         if gcache is not None and gcache.sizes is not None and garment_index is None:
             raise ValueError("a GarmentCache with `sizes` holds garments of several sizes: pass garment_index (person i wears garment "
                              "garment_index[i]; the i % G rule of a plain cache does not apply)")
+        g_b, phi_b, guided, skip = self._guidance(image.shape[0], guidance_scale, guidance_rescale, uncond)
         if gcache is not None:
             gidx = gcache.check(timesteps=self._timesteps(scheduler, num_inference_steps, strength)[1],
                                 h=(height or image.shape[-2]) // 8, w=(width or image.shape[-1]) // 8, dtype=dt, attn_fp8=self.unet.attn_fp8,
@@ -434,7 +478,12 @@ class TryonEngine:
                              "noise['image'] (the reference's first random draw, tryon_pipeline.py:883-889), or set noise['latents_given'] "
                              "when noise['latents'] already is the start (the reference's `latents=` argument)")
         sched, timesteps = self._timesteps(scheduler, num_inference_steps, strength)
-        if guidance_scale <= 1:                                                            # no CFG: see the docstring
+        if skip:                                             # the conditional branch alone: nothing unconditional is read
+            if ip_hidden_states is not None and ip_hidden_states.shape[0] == 2 * B:
+                ip_hidden_states = ip_hidden_states[B:]
+            if image_embeds is not None and image_embeds.shape[0] == 2 * B:
+                image_embeds = image_embeds[B:]
+        elif max(g_b) <= 1:                                                                # no CFG: see the docstring
             guidance_scale = 1.0
             if negative_prompt_embeds is None:
                 negative_prompt_embeds = torch.zeros_like(prompt_embeds)
@@ -469,15 +518,19 @@ class TryonEngine:
                 cloth_lat = self.vae.encode_sample(cloth, f32(noise["cloth"]))
         # step-invariant 9 conditioning channels of the 13-channel input, NHWC, both CFG halves (:955,977,1649-1652,1777)
         cond = torch.cat([mask_l, masked_lat, pose_lat], dim=1).permute(0, 2, 3, 1).reshape(B, h * w, 9)
-        cond = torch.cat([cond, cond], dim=0).to(dt).contiguous()
+        rows = B if skip else 2 * B                          # TryonNet rows: [uncond | cond], or the conditional branch alone
+        cond = (cond if skip else torch.cat([cond, cond], dim=0)).to(dt).contiguous()
 
-        pe = torch.cat([negative_prompt_embeds, prompt_embeds], dim=0).to(dev)             # :1710
-        add_text = torch.cat([negative_pooled_prompt_embeds, pooled_prompt_embeds], dim=0).to(dev)   # :1711
-        time_ids = torch.tensor([[H, W, 0, 0, H, W]], dtype=torch.float32, device=dev).repeat(2 * B, 1)  # :1681-1713
+        if skip:
+            pe, add_text = prompt_embeds.to(dev), pooled_prompt_embeds.to(dev)
+        else:
+            pe = torch.cat([negative_prompt_embeds, prompt_embeds], dim=0).to(dev)             # :1710
+            add_text = torch.cat([negative_pooled_prompt_embeds, pooled_prompt_embeds], dim=0).to(dev)   # :1711
+        time_ids = torch.tensor([[H, W, 0, 0, H, W]], dtype=torch.float32, device=dev).repeat(rows, 1)  # :1681-1713
         if image_embeds is None:
             image_embeds = self.resampler(ip_hidden_states.to(dev))                        # :1726 (encoder_hid_proj)
         ctx_t = self.unet.encode_context(pe, image_embeds)
-        temb_t = self.unet.time_embeddings(timesteps, 2 * B, dict(text_embeds=add_text, time_ids=time_ids))
+        temb_t = self.unet.time_embeddings(timesteps, rows, dict(text_embeds=add_text, time_ids=time_ids))
         if gcache is None:
             # GarmentNet over consecutive timesteps per batch, blocks of 1, 2, 4, k, k, ... timesteps
             garm = dict(self._garment_inputs(cloth_lat, text_embeds_cloth, timesteps, B), gcache=None, gidx=None, garment_persons=None,
@@ -485,19 +538,24 @@ class TryonEngine:
         else:                                                # the same blocks drive the loop; their garment side is a read of the cache
             k, blocks = self._block_schedule(len(timesteps))
             if gcache.sizes is not None:                     # [features][2B]: the real tokens of person b % B's garment, in both CFG halves
-                per = [self.unet.feature_tokens(*sz) for sz in gcache.garment_sizes(gindex)]
-                gnk = torch.tensor([[p[f] for p in per] * 2 for f in range(len(per[0]))], dtype=torch.int32, device=dev)
+                per = [self.unet.feature_tokens(*sz) for sz in gcache.garment_sizes(gindex)]   # (uncond="skip": [features][B])
+                gnk = torch.tensor([[p[f] for p in per] * (rows // B) for f in range(len(per[0]))], dtype=torch.int32, device=dev)
             garm = dict(cloth=None, ctx_g=None, temb_g=None, k=k, blocks=blocks, temb_gk=None, cloth_k=None, ctx_gk=None,
                         gcache=gcache, gidx=gidx, garment_persons=B, gindex=gindex,
                         # the table the kernels read: person -> garment of the cache (a graph state keeps its own: person -> set slot)
                         gix=torch.tensor(gindex, dtype=torch.int32, device=dev) if gindex is not None else None,
                         # the second table, on a cache with sizes only: per garment feature the key count of every batch
                         gnk=gnk if gcache.sizes is not None else None)
-        coef = torch.tensor([list(sched.coeffs(t)) + [guidance_scale] for t in timesteps], dtype=torch.float32, device=dev)
+        if guided:                                           # [steps][3 + 2B], and the statistics scratch of idmvton_guided_step
+            coef = torch.tensor(sched.guided_coef_table(timesteps, g_b, phi_b), dtype=torch.float32, device=dev)
+            work = torch.empty(ops.guided_step_work_floats(B, h * w), dtype=torch.float32, device=dev) if not skip else None
+        else:
+            coef, work = torch.tensor(sched.coef_table(timesteps, guidance_scale), dtype=torch.float32, device=dev), None
         steps_noise = f32(noise["steps"]) if noise.get("steps") is not None and scheduler == "ddpm" else None
         return dict(B=B, h=h, w=w, gh=gh, gw=gw, timesteps=timesteps, latents=latents.contiguous(), cond=cond,
                     ctx_t=ctx_t, temb_t=temb_t, coef=coef, steps_noise=steps_noise, **garm,
-                    x_in=torch.empty(2 * B, h * w, self.unet.cin_pad, dtype=dt, device=dev),
+                    guided=guided, branches=1 if skip else 2, work=work,
+                    x_in=torch.empty(rows, h * w, self.unet.cin_pad, dtype=dt, device=dev),
                     trace=dict(masked_lat=masked_lat, pose_lat=pose_lat, cloth_lat=cloth_lat, image_embeds=image_embeds))
 
     # ---- blocks: one GarmentNet batch over k timesteps + the k TryonNet steps that consume it ------------------------------
@@ -516,12 +574,16 @@ class TryonEngine:
 
     def _tryon_main(self, st, temb_t, coef, noise, kv_j):
         B, h, w = st["B"], st["h"], st["w"]
-        ops.pack_input(st["latents"], st["cond"], st["x_in"])                              # :1769,1777
+        branches = st.get("branches", 2)                     # 1: uncond="skip", the conditional rows alone (garment segment from batch 0 on)
+        (ops.pack_input if branches == 2 else ops.pack_input_cond)(st["latents"], st["cond"], st["x_in"])   # :1769,1777
         # garment_persons: None = one garment entry per conditional batch (unet.forward's default); B on a GarmentCache call, where kv_j
         # holds G garments for the B persons (a shared segment when G < B)
-        eps, _ = self.unet.forward(st["x_in"], temb_t, st["ctx_t"], 2 * B, h, w, garment_kv=kv_j, garment_persons=st["garment_persons"],
+        eps, _ = self.unet.forward(st["x_in"], temb_t, st["ctx_t"], branches * B, h, w, garment_kv=kv_j, garment_persons=st["garment_persons"],
                                    garment_hw=(st["gh"], st["gw"]), garment_index=st.get("gix"), garment_nk=st.get("gnk"))   # :1796-1808
-        ops.cfg_step(eps, st["latents"], noise, coef)                                      # :1814-1823
+        if st.get("guided"):                                 # per-person guidance / rescale, or e = t of the conditional branch alone
+            ops.guided_step(eps, st["latents"], noise, coef, st["work"], branches)         # :1814-1823
+        else:
+            ops.cfg_step(eps, st["latents"], noise, coef)                                  # :1814-1823
         return eps
 
     def _discover_set_shapes(self, st):
@@ -775,6 +837,9 @@ class TryonEngine:
         if key in self._graphs:
             return self._graphs[key]
         G = {name: st[name] for name in ("B", "h", "w", "gh", "gw", "k", "garment_persons", "latents", "cond", "x_in", "ctx_t")}
+        # guided: the scratch of idmvton_guided_step, persistent like gix / gnk (the captures hold its pointer; its contents carry nothing
+        # from one step to the next, so the first call's buffer is adopted and never copied)
+        G.update(guided=st.get("guided", False), branches=st.get("branches", 2), work=st.get("work"))
         # indexed: the table person -> set slot, a persistent buffer whose pointer the captured graphs hold; its contents are copied per call
         G["gix"] = self._slot_table(st)
         # ragged: the key-count table, persistent in the same way (the sets copy whole slots, so it is the call's own table)

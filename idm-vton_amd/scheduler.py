@@ -45,3 +45,35 @@ class StepScheduler:
             sigma = max(bb_p / bb_t * b_t, 1e-20) ** 0.5 if t > 0 else 0.0
             return c_xt + c_x0 / ab_t ** 0.5, -c_x0 * (bb_t ** 0.5) / ab_t ** 0.5, sigma
         return (ab_p ** 0.5) / ab_t ** 0.5, bb_p ** 0.5 - (ab_p ** 0.5) * (bb_t ** 0.5) / ab_t ** 0.5, 0.0
+
+    def coef_table(self, timesteps, guidance_scale):
+        """[steps][4] rows {c_x, c_eps, sigma, g}: what idmvton_cfg_step reads, one guidance for the whole batch."""
+        return [list(self.coeffs(t)) + [float(guidance_scale)] for t in timesteps]
+
+    def guided_coef_table(self, timesteps, guidance_scales, guidance_rescales):
+        """[steps][3 + 2B] rows {c_x, c_eps, sigma, g[0..B), phi[0..B)}: what idmvton_guided_step reads -- a guidance scale and a
+        guidance_rescale per person, the same in every step."""
+        g, phi = [float(x) for x in guidance_scales], [float(x) for x in guidance_rescales]
+        if len(g) != len(phi) or not g:
+            raise ValueError(f"guided_coef_table: {len(g)} guidance scales and {len(phi)} rescales (one of each per person)")
+        return [list(self.coeffs(t)) + g + phi for t in timesteps]
+
+
+def per_person(value, B, name):
+    """A float or a sequence of B floats -> (list of B floats, whether a sequence was given).  ValueError naming the argument for a sequence
+    of another length or a value that is no number."""
+    if getattr(value, "ndim", None) == 0:                # a 0-d array / tensor is a scalar
+        value = float(value)
+    seq = hasattr(value, "__len__") or hasattr(value, "__iter__")
+    vals = [v for v in value] if seq else [value] * B
+    if seq and getattr(value, "ndim", 1) != 1:
+        raise ValueError(f"`{name}` takes a float or a sequence of {B} floats, got shape {tuple(value.shape)}")
+    if len(vals) != B:
+        raise ValueError(f"`{name}` has {len(vals)} values for {B} persons: pass a float or one value per person")
+    try:
+        vals = [float(v) for v in vals]
+    except (TypeError, ValueError):
+        raise ValueError(f"`{name}` takes a float or a sequence of {B} floats, got {value!r}") from None
+    if any(v != v for v in vals):
+        raise ValueError(f"`{name}` holds NaN")
+    return vals, seq

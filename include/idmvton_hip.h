@@ -407,6 +407,44 @@ typedef struct {
 } idmvton_cfg_step_args;
 int idmvton_cfg_step(const idmvton_cfg_step_args* a, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * idmvton_guided_step : idmvton_cfg_step with a guidance scale and a guidance_rescale PER PERSON, and a form for the conditional
+ * branch alone (tryon_pipeline.py:1814-1823 with rescale_noise_cfg, :101-113; `do_classifier_free_guidance` false, :1229-1230).
+ *   eps_nhwc : dtype NHWC [branches*B][hw][ldc], channels 0..3 used (channels 4.. are never read)
+ *              branches 2: rows [0, B) unconditional, [B, 2B) conditional;  branches 1: rows [0, B) are the conditional branch alone
+ *   latents, noise : fp32 NCHW [B][4][hw]; noise may be NULL
+ *   coef     : DEVICE pointer to one step's row {c_x, c_eps, sigma, g[0..B), phi[0..B)} (3 + 2B floats), read when the kernels run
+ *   work     : caller-owned device floats, 8-byte aligned, idmvton_guided_step_work_floats(B, hw) of them (capacity in `work_floats`);
+ *              needs no initialisation; branches 1 neither reads nor writes it (it may be NULL)
+ * Per person b, with u / t the unconditional / conditional value of an element:
+ *   branches 2: e = u + g_b*(t - u), the arithmetic of idmvton_cfg_step;     branches 1: e = t (g_b and phi_b are not used)
+ *   branches 2 and phi_b > 0:  e <- phi_b * e * (std(t) / std(e)) + (1 - phi_b) * e, std = torch.std's: unbiased (N - 1) over the N = 4*hw
+ *              elements of person b, from the fp32 values of t and e in fp64 sums; applied as ONE fp32 factor
+ *              f = phi_b * std(t)/std(e) + (1 - phi_b), formed in fp64 and rounded once.  std(e) == 0 is NOT guarded, as in the
+ *              reference: the person's latents become Inf / NaN
+ *   latents = c_x*latents + c_eps*e + sigma*noise
+ * A person with phi_b == 0 (or < 0, or NaN) gets bit for bit what idmvton_cfg_step writes for g = g_b and costs no reduction (its
+ * statistics workgroups return at once).  No atomics: the statistics are partial sums over fixed chunks of 1024 pixels (a fixed tree
+ * inside the chunk, chunks folded in order), an order that depends on hw alone -- person b's result bits do not depend on B, on its
+ * position in the batch or on the grid.
+ * Launches: branches 2 = statistics + apply (two plain launches), branches 1 = apply alone.  No allocation, no synchronisation, no state
+ * but `work`: capturable.  Refused before any launch: null pointers (work: branches 2), B <= 0 or > 65535, hw <= 0, ldc < 4 (E_SHAPE),
+ * a dtype that is neither f16 nor bf16 (E_DTYPE), branches not in {1, 2} (E_ARG), work misaligned (E_ALIGN) or too small (E_SHAPE).
+ * Additive: the ABI version stays 9; idmvton_cfg_step and its struct are unchanged.
+ * idmvton_guided_step_work_floats: 8 * B * ceil(hw / 1024); -1 for B <= 0, hw <= 0 or a count beyond int32.
+ * idmvton_pack_input_cond : idmvton_pack_input for the conditional branch alone -- the same struct, out NHWC [B][hw][cpad] =
+ * cat(latents | mask | masked | pose) from cond [B][hw][9]: the TryonNet input of a call that runs no unconditional rows.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t dtype; int32_t B, hw, ldc;
+    int32_t branches;           /* 2: [uncond | cond] rows, 1: the conditional rows alone */
+    int32_t work_floats;        /* capacity of `work` in floats */
+    const void* eps_nhwc; float* latents; const float* noise; const float* coef; float* work;
+} idmvton_guided_step_args;
+int idmvton_guided_step(const idmvton_guided_step_args* a, void* stream);
+int idmvton_guided_step_work_floats(int B, int hw);
+int idmvton_pack_input_cond(const idmvton_pack_input_args* a, void* stream);
+
 /* Layout / dtype conversion at the pipeline edges: NCHW fp32 <-> NHWC dtype with channel padding. */
 enum { IDMVTON_LAYOUT_SPLIT = 1 /* to_nhwc: dst is NHWC [2*cpad] = [hi | lo] */, IDMVTON_LAYOUT_NHWC_F32 = 2 /* to_nchw: src NHWC holds fp32 */ };
 typedef struct {
