@@ -14,7 +14,16 @@ hipGraph replay) and the decode.  RNG draws follow the reference's order (SURVEY
 guidance_scale <= 1 (no CFG) runs the batched step with guidance 1 (the conditional prediction to one fp32 rounding, at the cost of
 the unused half) -- or, with `pipe.skip_uncond = True`, the conditional branch alone, as the reference does (:1229-1230); strength < 1
 starts from the noised image latents as the reference does.  `guidance_scale` and `guidance_rescale` (:1818-1820) take a float or a list
-of one value per person: the persons of a batch are independent requests.
+of one value per person: the persons of a batch are independent requests.  `strength` does too (below).
+`strength=[s_0, .., s_B-1]` (each in (0, 1]; not in the reference, whose `strength` is one float): one batch mixes img2img depths.  Person
+i runs its last n_i = min(int(n * s_i), n) timesteps; the loop runs the n_max = max n_i steps of the deepest person and person i's latents
+rest at their own start until its first timestep comes up (TryonEngine.prepare).  Row i is bit-identical to row i of the call with the
+float s_i.  The list is validated before `check_inputs`, which sees the maximum.  RNG with a list: the init-image posterior draw is made
+for the whole batch when any s_i != 1 and `latents` is None; the DDPM step noise is drawn n_max times at batch shape, and person i's j-th
+ACTIVE step uses row i of draw j (the rows are shifted into the engine's loop-aligned tensor here).  With one generator per person, person i
+gets exactly the draws its scalar call makes -- its generator then makes the init-image draw only when s_i != 1 --, and the n_max - n_i
+surplus step draws are discarded: the generator's FINAL STATE differs from the scalar call's.  With one generator for the batch the
+persons share a stream, as they always did, and a person's draws are not those of another call.
 Loud differences: `padding_mask_crop`, `masked_image_latents=`, `timesteps=`,
 `denoising_start/end`, `cross_attention_kwargs`, step callbacks, `num_images_per_prompt != 1` and
 schedulers other than DDPM/DDIM raise NotImplementedError: the reference scripts use none of them.
@@ -444,6 +453,13 @@ class StableDiffusionXLInpaintPipeline:
 
         height = height or self.unet.config.sample_size * self.vae_scale_factor                  # :1486-1487
         width = width or self.unet.config.sample_size * self.vae_scale_factor
+        # strength per person: the reference's check_inputs is for scalars, so a list is validated first (ValueError naming `strength`) and
+        # the largest value goes on -- the loop runs its timestep list (n_exec below is n_max)
+        s_b = n_b = None
+        if getattr(strength, "ndim", None) != 0 and (hasattr(strength, "__len__") or hasattr(strength, "__iter__")):
+            persons = _to_tensor_image(image, "image", size=(height, width)).shape[0]
+            s_b, n_b = TryonEngine._person_steps(persons, strength, num_inference_steps)
+            strength = max(s_b)
         self.check_inputs(prompt, prompt_2, image, mask_image, height, width, strength, callback_steps, output_type,
                           negative_prompt, negative_prompt_2, prompt_embeds, negative_prompt_embeds,
                           callback_on_step_end_tensor_inputs, padding_mask_crop)
@@ -495,7 +511,14 @@ class StableDiffusionXLInpaintPipeline:
         # upcast (:913-915, DiagonalGaussianDistribution.sample); DDPM variance noise: the model output's dtype (DDPMScheduler.step).
         shape = (B, 4, h, w)
         # strength < 1 and no `latents=`: the init image is encoded first (prepare_latents :883-886 -> posterior draw), then the noise
-        n_img = _randn(shape, generator, device, torch.float32) if (strength != 1.0 and latents is None) else None
+        # With a strength per person the draw is made for the whole batch when any s_i != 1 -- except by a LIST of generators: person
+        # i's generator then draws only when s_i != 1, as that person's scalar call would (the row of a person at s_i == 1 is not read).
+        draw_img = latents is None and (strength != 1.0 if s_b is None else any(s != 1.0 for s in s_b))
+        if draw_img and s_b is not None and isinstance(generator, (list, tuple)) and len(generator) == B:
+            n_img = torch.cat([_randn((1,) + shape[1:], g, device, torch.float32) if s != 1.0 else torch.zeros((1,) + shape[1:], device=device)
+                               for g, s in zip(generator, s_b)])
+        else:                                               # (a generator list of another length is refused by _randn, here or just below)
+            n_img = _randn(shape, generator, device, torch.float32) if draw_img else None
         n_lat = latents.to(device).float() if latents is not None else _randn(shape, generator, device, prompt_embeds.dtype)
         n_masked, n_pose, n_cloth = (_randn(shape, generator, device, torch.float32), _randn(shape, None, device, torch.float32),
                                      _randn((B, 4) + cloth_hw, generator, device, torch.float32))        # the garment latent's shape
@@ -504,6 +527,10 @@ class StableDiffusionXLInpaintPipeline:
         steps_noise = None
         if kind == "ddpm":
             steps_noise = torch.stack([_randn(shape, generator, device, eng.dtype) for _ in range(n_exec)])
+            if n_b is not None:                             # person i's j-th ACTIVE step uses row i of draw j: shifted to the loop's steps
+                draws, steps_noise = steps_noise, torch.zeros_like(steps_noise)
+                for i, n_i in enumerate(n_b):
+                    steps_noise[n_exec - n_i:, i] = draws[:n_i, i]
         image_states = self.prepare_ip_adapter_image_embeds(ip_adapter_image, device, 1)        # :1720-1723
 
         call = dict(image=img, mask_image=msk, pose_img=pose, cloth=clo, prompt_embeds=prompt_embeds,
@@ -512,7 +539,7 @@ class StableDiffusionXLInpaintPipeline:
                     noise=dict(latents=n_lat, masked=n_masked, pose=n_pose, cloth=n_cloth, steps=steps_noise, image=n_img,
                                latents_given=latents is not None),
                     num_inference_steps=num_inference_steps, guidance_scale=guidance_scale, ip_hidden_states=image_states,
-                    strength=strength, scheduler=kind, height=height, width=width)
+                    strength=strength if s_b is None else list(s_b), scheduler=kind, height=height, width=width)
         # passed only when they say something: a call without them is, keyword for keyword, the call it always was (trace_call below)
         if hasattr(guidance_rescale, "__len__") or guidance_rescale != 0.0:
             call["guidance_rescale"] = guidance_rescale                                          # :1818-1820

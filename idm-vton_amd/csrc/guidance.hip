@@ -1,5 +1,6 @@
 // guidance.hip -- the per-person CFG step: guidance scale and guidance_rescale per batch element, and the form for the conditional branch
-// alone (include/idmvton_hip.h, idmvton_guided_step); the TryonNet input of that form (idmvton_pack_input_cond).
+// alone (include/idmvton_hip.h, idmvton_guided_step); the TryonNet input of that form (idmvton_pack_input_cond); and the same step with a
+// strength per person (idmvton_person_step, further down): a person that has not started yet is skipped.
 //
 // Two kernels.  guided_stats_kernel: per (chunk of GS_CHUNK pixels, person) the four fp64 sums {sum t, sum t^2, sum e, sum e^2} over the
 // chunk's 4 channels -- every thread adds its pixels in index order, a wave folds by butterfly (a fixed tree), the four waves are added in
@@ -133,6 +134,116 @@ extern "C" int idmvton_guided_step(const idmvton_guided_step_args* a, void* stre
         else hipLaunchKernelGGL((guided_apply_kernel<f16_t, 1>), grid, block, 0, st, *a, nchunks);
     }
     CHECK_LAUNCH("guided_step");
+    return IDMVTON_OK;
+}
+
+// ---- the per-person step with a strength per person (idmvton_person_step): the guided step for the persons that are ACTIVE in this loop
+// step, nothing at all for the DORMANT ones.  The coefficient row carries a third per-person column, active[0..B).  A workgroup lies inside
+// one person, so dormancy is uniform over it: both kernels return before the first load of that person's eps, latents or noise and before
+// any store -- a skip, not a product with zero, so a dormant person's eps rows may hold Inf or NaN and its latents and `work` region keep
+// their bits.  For an active person every operation, in its order, is the one of the guided kernels above (cfg_combine, sched_update, the
+// chunked fp64 sums, the chunk-order fold): the same bits.
+__device__ __forceinline__ bool dormant(const float* coef, int B, int b) { return !(coef[3 + 2 * B + b] > 0.f); }   // (NaN: dormant)
+
+template <typename T>
+__global__ __launch_bounds__(256) void person_stats_kernel(const idmvton_person_step_args a) {
+    const int b = blockIdx.y, tid = threadIdx.x;
+    if (dormant(a.coef, a.B, b)) return;                         // uniform over the workgroup: before any load of this person's rows
+    const float g = a.coef[3 + b], phi = a.coef[3 + a.B + b];
+    if (!rescaled(phi)) return;
+    const T* eu = (const T*)a.eps_nhwc + (size_t)b * a.hw * a.ldc;
+    const T* ec = (const T*)a.eps_nhwc + (size_t)(a.B + b) * a.hw * a.ldc;
+    double st = 0.0, stt = 0.0, se = 0.0, see = 0.0;
+#pragma unroll
+    for (int i = 0; i < GS_CHUNK / 256; ++i) {
+        const int pix = blockIdx.x * GS_CHUNK + i * 256 + tid;
+        if (pix < a.hw) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const float u = (float)eu[(size_t)pix * a.ldc + c], t = (float)ec[(size_t)pix * a.ldc + c];
+                const float e = cfg_combine(u, t, g);
+                st += (double)t; stt += (double)t * (double)t;
+                se += (double)e; see += (double)e * (double)e;
+            }
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        st += __shfl_xor(st, o); stt += __shfl_xor(stt, o); se += __shfl_xor(se, o); see += __shfl_xor(see, o);
+    }
+    __shared__ double red[4][4];
+    if ((tid & 63) == 0) { red[tid >> 6][0] = st; red[tid >> 6][1] = stt; red[tid >> 6][2] = se; red[tid >> 6][3] = see; }
+    __syncthreads();
+    if (tid < 4) {
+        double* dst = (double*)a.work + ((size_t)b * gridDim.x + blockIdx.x) * 4;
+        dst[tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    }
+}
+
+template <typename T, int BR>
+__global__ __launch_bounds__(256) void person_apply_kernel(const idmvton_person_step_args a, int nchunks) {
+    const int b = blockIdx.y, tid = threadIdx.x;
+    if (dormant(a.coef, a.B, b)) return;                         // uniform over the workgroup: no load, no store, no barrier passed
+    const int pix = blockIdx.x * 256 + tid;                      // one thread per (b, pixel); a workgroup lies inside one person
+    const float c_x = a.coef[0], c_eps = a.coef[1], sigma = a.coef[2];
+    const float g = a.coef[3 + b], phi = a.coef[3 + a.B + b];
+    const bool rs = BR == 2 && rescaled(phi);                    // uniform over the workgroup
+    float f = 1.f;
+    if (rs) {
+        __shared__ float s_f;
+        if (tid == 0) {
+            const double* part = (const double*)a.work + (size_t)b * nchunks * 4;
+            double st = 0.0, stt = 0.0, se = 0.0, see = 0.0;
+            for (int k = 0; k < nchunks; ++k) { st += part[4 * k]; stt += part[4 * k + 1]; se += part[4 * k + 2]; see += part[4 * k + 3]; }
+            const double n = 4.0 * (double)a.hw;
+            const double var_t = (stt - st * st / n) / (n - 1.0), var_e = (see - se * se / n) / (n - 1.0);   // unbiased: torch.std
+            s_f = (float)((double)phi * (sqrt(var_t) / sqrt(var_e)) + (1.0 - (double)phi));                  // std(e) == 0: not guarded
+        }
+        __syncthreads();
+        f = s_f;
+    }
+    if (pix >= a.hw) return;
+    const T* eu = (const T*)a.eps_nhwc + ((size_t)b * a.hw + pix) * a.ldc;
+    const T* ec = (const T*)a.eps_nhwc + ((size_t)(a.B + b) * a.hw + pix) * a.ldc;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const size_t o = ((size_t)b * 4 + c) * a.hw + pix;
+        float eps;
+        if (BR == 2) {
+            eps = cfg_combine((float)eu[c], (float)ec[c], g);
+            if (rs) eps = eps * f;
+        } else {
+            eps = (float)eu[c];                                  // rows [0, B) are the conditional branch
+        }
+        a.latents[o] = sched_update(c_x, c_eps, sigma, a.latents[o], eps, a.noise ? a.noise + o : nullptr);
+    }
+}
+
+extern "C" int idmvton_person_step(const idmvton_person_step_args* a, void* stream) {
+    CHECK_ARG(a && a->eps_nhwc && a->latents && a->coef, IDMVTON_E_ARG, "person_step: null pointer");
+    CHECK_ARG(a->dtype == IDMVTON_F16 || a->dtype == IDMVTON_BF16, IDMVTON_E_DTYPE, "person_step: dtype %d", a->dtype);
+    CHECK_ARG(a->branches == 1 || a->branches == 2, IDMVTON_E_ARG, "person_step: branches=%d (1: the conditional rows alone, 2: [uncond | cond])", a->branches);
+    CHECK_ARG(a->B > 0 && a->B <= 65535 && a->hw > 0 && a->ldc >= 4, IDMVTON_E_SHAPE, "person_step: B=%d hw=%d ldc=%d", a->B, a->hw, a->ldc);
+    const int nchunks = (a->hw + GS_CHUNK - 1) / GS_CHUNK;
+    if (a->branches == 2) {
+        CHECK_ARG(a->work, IDMVTON_E_ARG, "person_step: null pointer (work)");
+        CHECK_ARG(((uintptr_t)a->work & 7) == 0, IDMVTON_E_ALIGN, "person_step: work is not 8-byte aligned");
+        const int need = idmvton_guided_step_work_floats(a->B, a->hw);
+        CHECK_ARG(need > 0 && a->work_floats >= need, IDMVTON_E_SHAPE, "person_step: work holds %d floats, needs %d", a->work_floats, need);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 block(256), grid((a->hw + 255) / 256, a->B);
+    if (a->branches == 2) {
+        const dim3 sgrid(nchunks, a->B);
+        if (a->dtype == IDMVTON_BF16) hipLaunchKernelGGL((person_stats_kernel<bf16_t>), sgrid, block, 0, st, *a);
+        else hipLaunchKernelGGL((person_stats_kernel<f16_t>), sgrid, block, 0, st, *a);
+        CHECK_LAUNCH("person_step (statistics)");
+        if (a->dtype == IDMVTON_BF16) hipLaunchKernelGGL((person_apply_kernel<bf16_t, 2>), grid, block, 0, st, *a, nchunks);
+        else hipLaunchKernelGGL((person_apply_kernel<f16_t, 2>), grid, block, 0, st, *a, nchunks);
+    } else {
+        if (a->dtype == IDMVTON_BF16) hipLaunchKernelGGL((person_apply_kernel<bf16_t, 1>), grid, block, 0, st, *a, nchunks);
+        else hipLaunchKernelGGL((person_apply_kernel<f16_t, 1>), grid, block, 0, st, *a, nchunks);
+    }
+    CHECK_LAUNCH("person_step");
     return IDMVTON_OK;
 }
 

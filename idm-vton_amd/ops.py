@@ -676,6 +676,26 @@ def guided_step(eps_nhwc, latents, noise, coef_row, work, branches=2):
     return latents
 
 
+def person_step(eps_nhwc, latents, noise, coef_row, work, branches=2):
+    """guided_step with a strength per person (idmvton_person_step): coef_row is the float32 device tensor {c_x, c_eps, sigma, g[0..B),
+    phi[0..B), active[0..B)}; person b takes the step when active[b] > 0, and is skipped otherwise -- its eps, latents, noise and part of
+    `work` are neither read nor written.  The other operands are guided_step's.  Updates the active persons' latents in place."""
+    a = ffi.PersonStepArgs()
+    B = latents.shape[0]
+    hw = latents.numel() // (B * 4)
+    if coef_row.numel() != 3 + 3 * B or coef_row.dtype != torch.float32:
+        raise ValueError(f"person_step: coef_row holds {coef_row.numel()} {coef_row.dtype} values, needs 3 + 3B = {3 + 3 * B} float32")
+    if eps_nhwc.shape[0] != branches * B:
+        raise ValueError(f"person_step: eps of {eps_nhwc.shape[0]} rows for branches={branches} and {B} persons")
+    if work is not None and work.dtype != torch.float32:
+        raise ValueError(f"person_step: work must be float32, got {work.dtype}")
+    a.dtype, a.B, a.hw, a.ldc, a.branches = _dt(eps_nhwc), B, hw, eps_nhwc.shape[-1], branches
+    a.work, a.work_floats = _ptr(work), 0 if work is None else work.numel()
+    a.eps_nhwc, a.latents, a.noise, a.coef = _ptr(eps_nhwc), _ptr(latents), _ptr(noise), _ptr(coef_row)
+    _call("idmvton_person_step", a)
+    return latents
+
+
 def to_nhwc(src_nchw_f32, dtype, cpad=None, scale=1.0, shift=0.0, out=None, split=False):
     """fp32 NCHW -> NHWC [cpad] of `dtype`; split=True: NHWC [2*cpad] = [hi | lo] (the split-precision VAE path)."""
     B, Cc = src_nchw_f32.shape[:2]

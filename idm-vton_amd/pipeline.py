@@ -54,6 +54,9 @@ PLAIN state ([steps][4] coef table, idmvton_cfg_step); anything else the GUIDED 
 idmvton_guided_step: the reference's rescale_noise_cfg fused into the step), with a graph state of its own.  uncond="skip" -- no person with
 guidance -- runs the conditional branch alone: B TryonNet rows, the garment segment from batch 0 on, e = t; every form and every kind of cache
 below serves it, since what they fill is the garment side.
+Strength is per person too (prepare: strength as a float or one value per person).  A float is the call it always was; a sequence gives the
+PERSON state ([steps][3 + 3B] table with an `active` column, idmvton_person_step): the loop runs the longest timestep list, and the step skips
+the persons whose own list has not begun -- the only thing of a loop step that depends on the person.
 
 `denoise` asks once whether the call is live or on a cache, wraps the step in the per-step hooks (`trace`, `on_step`) and drives the
 blocks.  The K / V^T layout of sets and cache (timestep-major) has one owner, garment_cache.timestep_run.
@@ -205,8 +208,12 @@ class TryonEngine:
         state serves every pool size and every assignment.  A cache with `sizes` adds "ragged" (its forwards read a key-count table that a plain
         state's captures do not have); gh, gw are then the SLOT size, and the garments' own sizes are not in the key.  A GUIDED state (per-person
         guidance: another `cf` width, a `work` buffer, idmvton_guided_step in its captures) adds ("guided", branches) -- branches 1 being
-        uncond="skip", whose captures run B TryonNet rows; a plain state's key is what it always was."""
+        uncond="skip", whose captures run B TryonNet rows; a plain state's key is what it always was.  A PERSON state (a strength per
+        person: a `cf` of 3 + 3B, idmvton_person_step in its captures -- which takes the guidance per person too) has ("person", branches) in
+        that place, whatever its guidance."""
         guided = (("guided", st.get("branches", 2)),) if st.get("guided") else ()
+        if st.get("person"):
+            guided = (("person", st.get("branches", 2)),)
         if live:
             return (st["B"], st["h"], st["w"], st["gh"], st["gw"], st["k"], st["steps_noise"] is not None) + guided
         return (st["B"], st["h"], st["w"], st["gh"], st["gw"], st["k"], st["steps_noise"] is not None, "cached",
@@ -233,6 +240,22 @@ class TryonEngine:
         g = [x if x > 1 else 1.0 for x in g]
         guided = skip or g_seq or phi_seq or guidance_rescale != 0.0
         return g, phi, guided, skip
+
+    @staticmethod
+    def _person_steps(B, strength, n):
+        """prepare's `strength` -> (None, None) for a float: the call it always was -- or, for a sequence of B floats in (0, 1], (the
+        strengths, person i's own step count n_i = min(int(n * s_i), n)): checked here, before anything is launched."""
+        if getattr(strength, "ndim", None) == 0 or not (hasattr(strength, "__len__") or hasattr(strength, "__iter__")):
+            return None, None
+        s_b, _ = per_person(strength, B, "strength")
+        if any(not 0.0 < s <= 1.0 for s in s_b):
+            raise ValueError(f"`strength` lies in (0, 1] for every person, got {strength!r}")
+        n_b = [min(int(n * s), n) for s in s_b]
+        for s, n_i in zip(s_b, n_b):
+            if n_i < 1:                                                                    # :1568-1572, for the person it is true of
+                raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {s}, the number of pipeline"
+                                 f"steps is {n_i} which is < 1 and not appropriate for this pipeline.")
+        return s_b, n_b
 
     def weights_identity(self):
         """What a GarmentCache depends on besides its inputs: every GarmentNet weight, and TryonNet's attn1.to_k / to_v (the projections of
@@ -439,7 +462,21 @@ class TryonEngine:
         e = t in the step.  negative_* are not read; ip_hidden_states / image_embeds may hold B rows or 2B (the first B are dropped).
         uncond="run" (the default) keeps the batched step with guidance 1 for such a call.
         A sequence of the wrong length, a rescale outside [0, 1], an unknown `uncond` or uncond="skip" with a g > 1 is a ValueError naming
-        the argument, before anything is launched."""
+        the argument, before anything is launched.
+        strength: a float -- the call it always was: same state, table, kernel and graph key --, or a sequence of B floats in (0, 1]: one
+        batch mixes img2img depths.  Person i's step count is n_i = min(int(n * s_i), n); the loop runs the timestep list of the largest,
+        n_max (every person's list is a suffix of it, so the cache, the time embeddings and the block schedule are the loop's, not a
+        person's); person i is DORMANT in loop steps [0, n_max - n_i) -- its latents hold its own start, add_noise(encode(image_i),
+        noise_i, its first timestep) or noise_i at s_i == 1, and the step neither reads nor writes them -- and active after that.  Person
+        i's result is bit-identical to row i of the same batch run with the scalar strength s_i.  Dormant rows still run through TryonNet
+        and their eps is dropped: a call costs n_max full-batch steps, whatever the other strengths (running an active prefix of the batch
+        alone is not done).  noise['steps'] is aligned to LOOP steps, [n_max, B, 4, h, w]: the scalar call at s_i gets
+        noise['steps'][n_max - n_i:]; a dormant person's rows are not read.  noise['image'] is needed when some s_i < 1 (unless
+        latents_given).  A sequence gives the PERSON state (st["person"]): a [steps][3 + 3B] coef table {.., g, phi, active},
+        idmvton_person_step -- which applies guidance_scale / guidance_rescale per person too, and runs under uncond="skip" -- and a graph
+        state of its own; stats["person_steps"] counts its steps.  A wrong length, a value outside (0, 1], NaN or an n_i < 1 (the
+        reference's message) is a ValueError naming `strength`, before anything is launched.  A step count per person stays out: a garment
+        cache is keyed to one timestep list."""
         dev, dt = self.device, self.dtype
         self._release_streamed()
         f32 = lambda t: t.to(dev, torch.float32).contiguous()
@@ -453,6 +490,10 @@ class TryonEngine:
             raise ValueError("a GarmentCache with `sizes` holds garments of several sizes: pass garment_index (person i wears garment "
                              "garment_index[i]; the i % G rule of a plain cache does not apply)")
         g_b, phi_b, guided, skip = self._guidance(image.shape[0], guidance_scale, guidance_rescale, uncond)
+        s_b, n_b = self._person_steps(image.shape[0], strength, num_inference_steps)
+        s_min = strength if s_b is None else min(s_b)
+        if s_b is not None:                                  # the loop runs the longest list: every person's is a suffix of it
+            strength = max(s_b)
         if gcache is not None:
             gidx = gcache.check(timesteps=self._timesteps(scheduler, num_inference_steps, strength)[1],
                                 h=(height or image.shape[-2]) // 8, w=(width or image.shape[-1]) // 8, dtype=dt, attn_fp8=self.unet.attn_fp8,
@@ -473,7 +514,7 @@ class TryonEngine:
         if H % 8 or W % 8:
             raise ValueError(f"`height` and `width` have to be divisible by 8 but are {H} and {W}.")
         start_is_given = bool(noise.get("latents_given"))    # the reference's `latents=` argument: used as the start as they are (:880-882)
-        if strength < 1.0 and noise.get("image") is None and not start_is_given:
+        if s_min < 1.0 and noise.get("image") is None and not start_is_given:
             raise ValueError("strength < 1 starts from add_noise(encode(image)): pass the posterior draw of the init-image encode as "
                              "noise['image'] (the reference's first random draw, tryon_pipeline.py:883-889), or set noise['latents_given'] "
                              "when noise['latents'] already is the start (the reference's `latents=` argument)")
@@ -497,7 +538,10 @@ class TryonEngine:
         init_image = 2.0 * image - 1.0                                                     # preprocess :1588-1591
         mask = (mask_image >= 0.5).float()                                                 # mask_processor :1593-1595
         masked_image = init_image * (mask < 0.5)                                           # :1602
-        if strength == 1.0 or start_is_given:
+        if s_b is not None:
+            latents = self._person_starts(sched, timesteps, s_b, n_b, noise, start_is_given,
+                                          init_image if image_dtype is None else init_image.to(image_dtype).float())
+        elif strength == 1.0 or start_is_given:
             latents = f32(noise["latents"]) * sched.init_noise_sigma                       # :889-893
         else:                                                                              # image + noise start (:883-891)
             src = init_image if image_dtype is None else init_image.to(image_dtype).float()    # prepare_latents casts the image (:884)
@@ -546,7 +590,10 @@ class TryonEngine:
                         gix=torch.tensor(gindex, dtype=torch.int32, device=dev) if gindex is not None else None,
                         # the second table, on a cache with sizes only: per garment feature the key count of every batch
                         gnk=gnk if gcache.sizes is not None else None)
-        if guided:                                           # [steps][3 + 2B], and the statistics scratch of idmvton_guided_step
+        if s_b is not None:                                  # [steps][3 + 3B]: the guided row and who takes the step; the same scratch
+            coef = torch.tensor(sched.person_coef_table(timesteps, g_b, phi_b, n_b), dtype=torch.float32, device=dev)
+            work = torch.empty(ops.guided_step_work_floats(B, h * w), dtype=torch.float32, device=dev) if not skip else None
+        elif guided:                                         # [steps][3 + 2B], and the statistics scratch of idmvton_guided_step
             coef = torch.tensor(sched.guided_coef_table(timesteps, g_b, phi_b), dtype=torch.float32, device=dev)
             work = torch.empty(ops.guided_step_work_floats(B, h * w), dtype=torch.float32, device=dev) if not skip else None
         else:
@@ -554,9 +601,27 @@ class TryonEngine:
         steps_noise = f32(noise["steps"]) if noise.get("steps") is not None and scheduler == "ddpm" else None
         return dict(B=B, h=h, w=w, gh=gh, gw=gw, timesteps=timesteps, latents=latents.contiguous(), cond=cond,
                     ctx_t=ctx_t, temb_t=temb_t, coef=coef, steps_noise=steps_noise, **garm,
-                    guided=guided, branches=1 if skip else 2, work=work,
+                    guided=guided, branches=1 if skip else 2, work=work, **(dict(person=True, n_active=n_b) if s_b is not None else {}),
                     x_in=torch.empty(rows, h * w, self.unet.cin_pad, dtype=dt, device=dev),
                     trace=dict(masked_lat=masked_lat, pose_lat=pose_lat, cloth_lat=cloth_lat, image_embeds=image_embeds))
+
+    def _person_starts(self, sched, timesteps, s_b, n_b, noise, start_is_given, src):
+        """The start latents of a call with a strength per person: person i's row is what the scalar call at s_i forms for it -- the noise
+        as it is at s_i == 1 (or when the latents are given), else add_noise(encode(image_i), noise_i, its own first timestep), with the scalar
+        path's Python-float arithmetic, one alpha-bar per person.  The image encode is the scalar call's: one pass over the whole batch."""
+        f32 = lambda t: t.to(self.device, torch.float32).contiguous()
+        nz = f32(noise["latents"])
+        if start_is_given or min(s_b) == 1.0:
+            return nz * sched.init_noise_sigma                                             # :889-893
+        enc = self.vae.encode_sample(src, f32(noise["image"]))
+        rows = []
+        for i, (s, n_i) in enumerate(zip(s_b, n_b)):
+            if s == 1.0:
+                rows.append(nz[i:i + 1] * sched.init_noise_sigma)
+            else:                                                                          # image + noise start (:883-891)
+                ab = float(sched.alphas_cumprod[int(timesteps[len(timesteps) - n_i])])
+                rows.append(ab ** 0.5 * enc[i:i + 1] + (1.0 - ab) ** 0.5 * nz[i:i + 1])
+        return torch.cat(rows)
 
     # ---- blocks: one GarmentNet batch over k timesteps + the k TryonNet steps that consume it ------------------------------
     # The GarmentNet batch of block b+1 -- and the attn1 K / V^T projections of its features with TryonNet's weights -- can run on a
@@ -580,7 +645,10 @@ class TryonEngine:
         # holds G garments for the B persons (a shared segment when G < B)
         eps, _ = self.unet.forward(st["x_in"], temb_t, st["ctx_t"], branches * B, h, w, garment_kv=kv_j, garment_persons=st["garment_persons"],
                                    garment_hw=(st["gh"], st["gw"]), garment_index=st.get("gix"), garment_nk=st.get("gnk"))   # :1796-1808
-        if st.get("guided"):                                 # per-person guidance / rescale, or e = t of the conditional branch alone
+        if st.get("person"):                                 # a strength per person: the guided step for those the coef row calls active
+            self.stats["person_steps"] += 1
+            ops.person_step(eps, st["latents"], noise, coef, st["work"], branches)
+        elif st.get("guided"):                               # per-person guidance / rescale, or e = t of the conditional branch alone
             ops.guided_step(eps, st["latents"], noise, coef, st["work"], branches)         # :1814-1823
         else:
             ops.cfg_step(eps, st["latents"], noise, coef)                                  # :1814-1823
@@ -839,7 +907,7 @@ class TryonEngine:
         G = {name: st[name] for name in ("B", "h", "w", "gh", "gw", "k", "garment_persons", "latents", "cond", "x_in", "ctx_t")}
         # guided: the scratch of idmvton_guided_step, persistent like gix / gnk (the captures hold its pointer; its contents carry nothing
         # from one step to the next, so the first call's buffer is adopted and never copied)
-        G.update(guided=st.get("guided", False), branches=st.get("branches", 2), work=st.get("work"))
+        G.update(guided=st.get("guided", False), branches=st.get("branches", 2), work=st.get("work"), person=st.get("person", False))
         # indexed: the table person -> set slot, a persistent buffer whose pointer the captured graphs hold; its contents are copied per call
         G["gix"] = self._slot_table(st)
         # ragged: the key-count table, persistent in the same way (the sets copy whole slots, so it is the call's own table)
@@ -865,6 +933,8 @@ class TryonEngine:
                 if gc.features:                              # garment_projections counts the blocks of calls: not the warm-up's
                     self.stats["garment_projections"] -= 1
             self._tryon_main(G, G["tt"], G["cf"], G["nz"], G["sets"][0]["step"][0])
+            if G["person"]:                                  # person_steps counts the steps of calls: not the warm-up's
+                self.stats["person_steps"] -= 1
         torch.cuda.current_stream().wait_stream(warm)
         torch.cuda.synchronize()
         self._release_streamed()                             # (the warm-up fill of a host-resident cache has completed)
@@ -885,6 +955,8 @@ class TryonEngine:
                 self.stats["garment_batches"] -= 1               # captured, not run: replays are counted
             else:
                 self._tryon_main(G, G["tt"], G["cf"], G["nz"], G["sets"][par]["step"][j])
+                if G["person"]:
+                    self.stats["person_steps"] -= 1              # captured, not run: replays are counted
         G["latents"].copy_(keep)                                     # capture does not execute, but keep the state explicit
         G["graphs"][gk] = g
         return g
@@ -914,6 +986,8 @@ class TryonEngine:
             tt.copy_(st["temb_t"][i]); cf.copy_(st["coef"][i])
             if nz is not None:
                 nz.copy_(st["steps_noise"][i])
+            if G["person"]:
+                self.stats["person_steps"] += 1
             graphs[("tryon", p, j)].replay()
 
         return garment, step, G["latents"], (G["side"], G["ready"], G["free"]) if overlap else None

@@ -58,6 +58,19 @@ class StepScheduler:
             raise ValueError(f"guided_coef_table: {len(g)} guidance scales and {len(phi)} rescales (one of each per person)")
         return [list(self.coeffs(t)) + g + phi for t in timesteps]
 
+    def person_coef_table(self, timesteps, guidance_scales, guidance_rescales, n_active):
+        """[steps][3 + 3B] rows {c_x, c_eps, sigma, g[0..B), phi[0..B), active[0..B)}: what idmvton_person_step reads -- the guided row plus,
+        per person, whether it takes this step.  n_active[b] in [1, len(timesteps)] is person b's own step count (its strength): it is
+        dormant (0.0) in the first len(timesteps) - n_active[b] loop steps and active (1.0) from then on, so its steps are the LAST
+        n_active[b] timesteps -- what a call at its strength alone runs."""
+        n, n_active = len(timesteps), [int(x) for x in n_active]
+        rows = self.guided_coef_table(timesteps, guidance_scales, guidance_rescales)
+        if len(n_active) != len(guidance_scales):
+            raise ValueError(f"person_coef_table: {len(n_active)} step counts for {len(guidance_scales)} persons (one per person)")
+        if any(not 1 <= x <= n for x in n_active):
+            raise ValueError(f"person_coef_table: step counts {n_active} for a loop of {n} steps (each in [1, {n}])")
+        return [row + [1.0 if i >= n - x else 0.0 for x in n_active] for i, row in enumerate(rows)]
+
 
 def per_person(value, B, name):
     """A float or a sequence of B floats -> (list of B floats, whether a sequence was given).  ValueError naming the argument for a sequence

@@ -445,6 +445,27 @@ int idmvton_guided_step(const idmvton_guided_step_args* a, void* stream);
 int idmvton_guided_step_work_floats(int B, int hw);
 int idmvton_pack_input_cond(const idmvton_pack_input_args* a, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * idmvton_person_step : idmvton_guided_step with a STRENGTH per person -- one batch mixes img2img depths.  The loop runs the timestep
+ * list of the deepest person; a person whose own list is shorter is DORMANT until its first timestep comes up, and its latents hold its
+ * own start until then.
+ *   coef : DEVICE pointer to one step's row {c_x, c_eps, sigma, g[0..B), phi[0..B), active[0..B)} (3 + 3B floats); person b takes the
+ *          step when active[b] > 0 and is dormant otherwise (NaN included).  Every other field is idmvton_guided_step's.
+ * Active person: the operations of idmvton_guided_step in their order -- the same bits, for branches 1 and 2, with and without noise,
+ * whatever phi.  Dormant person: its statistics workgroups return before any load, its apply workgroups before any load or store.  It is
+ * a skip, not a product with zero: the person's eps rows may hold Inf or NaN; its latents and its region of `work` keep their bits; its
+ * noise rows are not read.  As there, no atomics, and person b's bits depend neither on B nor on its position in the batch.
+ * `work` is sized by idmvton_guided_step_work_floats.  Launches, capture and refusals are idmvton_guided_step's (messages name person_step).
+ * Additive: the ABI version stays 9; idmvton_guided_step and its struct are unchanged.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t dtype; int32_t B, hw, ldc;
+    int32_t branches;           /* 2: [uncond | cond] rows, 1: the conditional rows alone */
+    int32_t work_floats;        /* capacity of `work` in floats */
+    const void* eps_nhwc; float* latents; const float* noise; const float* coef; float* work;
+} idmvton_person_step_args;
+int idmvton_person_step(const idmvton_person_step_args* a, void* stream);
+
 /* Layout / dtype conversion at the pipeline edges: NCHW fp32 <-> NHWC dtype with channel padding. */
 enum { IDMVTON_LAYOUT_SPLIT = 1 /* to_nhwc: dst is NHWC [2*cpad] = [hi | lo] */, IDMVTON_LAYOUT_NHWC_F32 = 2 /* to_nchw: src NHWC holds fp32 */ };
 typedef struct {
