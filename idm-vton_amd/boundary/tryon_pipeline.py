@@ -108,6 +108,7 @@ class StableDiffusionXLInpaintPipeline:
         self._guidance_scale = 7.5
         self._guidance_rescale = 0.0
         self.skip_uncond = False                            # True: a call in which no person has guidance_scale > 1 runs the conditional branch alone
+        self.rows = "all"                                   # "needed": a loop step runs only the TryonNet rows its persons need (TryonEngine.prepare; a GarmentCache call)
         self.use_graph, self.overlap = True, True          # engine execution mode (hipGraph replay, two-stream loop)
         self.host_transport = "kernel"                      # how a host-resident GarmentCache crosses the host link ("kernel" | "copy": TryonEngine.denoise)
 
@@ -408,6 +409,14 @@ class StableDiffusionXLInpaintPipeline:
         return self.hip_engine().empty_garment_cache(garments, garment_height, garment_width, num_inference_steps, scheduler=self._scheduler_kind(),
                                                      strength=strength, height=height, width=width)
 
+    def _rows_keyword(self):
+        """`pipe.rows` as the engine call takes it: nothing for "all" -- the call is then, keyword for keyword, what it always was --, the
+        keyword otherwise; ValueError naming `rows` for a value the engine does not know."""
+        if self.rows not in TryonEngine.ROWS:
+            raise ValueError(f"rows={self.rows!r}: \"all\" (every loop step runs the [uncond | cond] rows of every person) or \"needed\" (a "
+                             "step runs only the rows its persons need)")
+        return {} if self.rows == "all" else {"rows": self.rows}
+
     # ------------------------------------------------------------------------------------------ the call
     @torch.no_grad()
     def __call__(self, prompt=None, prompt_2=None, image=None, mask_image=None, masked_image_latents=None, height=None,
@@ -425,6 +434,7 @@ class StableDiffusionXLInpaintPipeline:
         callback = kwargs.pop("callback", None)              # deprecated form, still honoured by the reference (:1855-1863)
         # not in the reference's signature (a fixture pins the positional one): with cloth=<GarmentCache>, person i wears garment garment_index[i]
         garment_index = kwargs.pop("garment_index", None)
+        self._rows_keyword()                                 # an unknown `pipe.rows` is refused here, before any work
         self._interrupt = False                              # :1519
         if callback_on_step_end is not None and any(k != "latents" for k in (callback_on_step_end_tensor_inputs or [])):
             raise NotImplementedError("callback_on_step_end_tensor_inputs other than 'latents': the text / image conditioning is projected once "
@@ -547,6 +557,7 @@ class StableDiffusionXLInpaintPipeline:
             call["uncond"] = "skip"                                                              # the conditional branch alone (:1229-1230)
         if garment_index is not None:
             call["garment_index"] = garment_index
+        call.update(self._rows_keyword())                                                        # the row plan (opt-in)
         if isinstance(getattr(self, "trace_call", None), dict):    # test hook: what crossed the engine boundary (an oracle can replay it)
             self.trace_call.update(call)
         on_step = None

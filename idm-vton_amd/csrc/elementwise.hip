@@ -239,6 +239,7 @@ extern "C" int idmvton_sizeof(const char* name) {
     SZ(idmvton_groupnorm_args) SZ(idmvton_pack_input_args) SZ(idmvton_cfg_step_args) SZ(idmvton_layout_args)
     SZ(idmvton_vae_sample_args) SZ(idmvton_softmax_args) SZ(idmvton_attn_small_args) SZ(idmvton_attn_f8_args) SZ(idmvton_quant_f8_args) SZ(idmvton_split_args) SZ(idmvton_xattn)
     SZ(idmvton_kv_unpack_desc) SZ(idmvton_kv_unpack_args) SZ(idmvton_kv_stream_desc) SZ(idmvton_kv_stream_args) SZ(idmvton_guided_step_args) SZ(idmvton_person_step_args)
+    SZ(idmvton_pack_rows_args) SZ(idmvton_row_step_args)
 #undef SZ
     return -1;
 }

@@ -77,6 +77,16 @@ class PersonStepArgs(C.Structure):                       # idmvton_guided_step_a
     _fields_ = list(GuidedStepArgs._fields_)
 
 
+class PackRowsArgs(C.Structure):                         # a row plan's TryonNet input: row r is person row_person[r] (a device table)
+    _fields_ = [("dtype", i32), ("B", i32), ("R", i32), ("hw", i32), ("cpad", i32), ("latents", vp), ("cond", vp), ("out", vp),
+                ("row_person", vp)]
+
+
+class RowStepArgs(C.Structure):                          # the person step with eps rows looked up in the device table {urow[B], crow[B]}
+    _fields_ = [("dtype", i32), ("B", i32), ("R", i32), ("hw", i32), ("ldc", i32), ("work_floats", i32), ("eps_nhwc", vp),
+                ("latents", vp), ("noise", vp), ("coef", vp), ("work", vp), ("rows", vp)]
+
+
 class LayoutArgs(C.Structure):
     _fields_ = [("dtype", i32), ("B", i32), ("C", i32), ("HW", i32), ("cpad", i32), ("to_nhwc", i32), ("src", vp),
                 ("dst", vp), ("scale", f32), ("shift", f32), ("flags", i32)]
@@ -133,7 +143,8 @@ STRUCTS = {"idmvton_seg": Seg, "idmvton_gemm_conv_args": GemmConvArgs, "idmvton_
            "idmvton_attn_small_args": AttnSmallArgs, "idmvton_attn_f8_args": AttnF8Args, "idmvton_quant_f8_args": QuantF8Args,
            "idmvton_split_args": SplitArgs, "idmvton_xattn": XAttn, "idmvton_kv_unpack_desc": KvUnpackDesc,
            "idmvton_kv_unpack_args": KvUnpackArgs, "idmvton_kv_stream_desc": KvStreamDesc, "idmvton_kv_stream_args": KvStreamArgs,
-           "idmvton_guided_step_args": GuidedStepArgs, "idmvton_person_step_args": PersonStepArgs}
+           "idmvton_guided_step_args": GuidedStepArgs, "idmvton_person_step_args": PersonStepArgs,
+           "idmvton_pack_rows_args": PackRowsArgs, "idmvton_row_step_args": RowStepArgs}
 
 # every symbol include/idmvton_hip.h declares
 SYMBOLS = ["idmvton_last_error", "idmvton_abi_version", "idmvton_sizeof", "idmvton_gemm_conv", "idmvton_attn_fwd",
@@ -144,7 +155,7 @@ SYMBOLS = ["idmvton_last_error", "idmvton_abi_version", "idmvton_sizeof", "idmvt
            "idmvton_attn_f8_shared", "idmvton_attn_fwd_indexed", "idmvton_attn_f8_indexed",
            "idmvton_attn_fwd_ragged", "idmvton_attn_f8_ragged", "idmvton_kv_unpack", "idmvton_kv_stream",
            "idmvton_host_device_ptr", "idmvton_kv_fill", "idmvton_kv_place", "idmvton_guided_step", "idmvton_guided_step_work_floats",
-           "idmvton_pack_input_cond", "idmvton_person_step"]
+           "idmvton_pack_input_cond", "idmvton_person_step", "idmvton_pack_rows", "idmvton_row_step"]
 
 _lib = None
 
@@ -179,7 +190,7 @@ def lib():
     for s in ("idmvton_gemm_conv", "idmvton_attn_fwd", "idmvton_layernorm", "idmvton_groupnorm",
               "idmvton_pack_input", "idmvton_cfg_step", "idmvton_layout", "idmvton_vae_sample", "idmvton_softmax_rows",
               "idmvton_attn_small", "idmvton_attn_f8", "idmvton_quant_f8", "idmvton_split", "idmvton_guided_step", "idmvton_pack_input_cond",
-              "idmvton_person_step"):
+              "idmvton_person_step", "idmvton_pack_rows", "idmvton_row_step"):
         getattr(L, s).argtypes = [vp, vp]
         getattr(L, s).restype = C.c_int
     for s in ("idmvton_attn_fwd_shared", "idmvton_attn_f8_shared"):          # (args*, const int32_t seg_nb[2], stream)

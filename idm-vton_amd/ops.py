@@ -696,6 +696,46 @@ def person_step(eps_nhwc, latents, noise, coef_row, work, branches=2):
     return latents
 
 
+def _int32_table(t, n, what):
+    if t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous():
+        raise ValueError(f"{what} holds {t.numel()} {t.dtype} values, needs {n} contiguous int32")
+
+
+def pack_rows(latents, cond, out, row_person):
+    """The TryonNet input of a row plan (idmvton_pack_rows): out NHWC [R][hw][cpad], row r = cat(latents[p] | cond[p]) for p =
+    row_person[r] -- an int32 DEVICE table of R entries, read by the kernel (clamped to [0, B - 1]); cond [B][hw][9], one row per person."""
+    a = ffi.PackRowsArgs()
+    B, hw = latents.shape[0], latents.shape[2] * latents.shape[3] if latents.dim() == 4 else latents.shape[2]
+    R = out.shape[0]
+    if cond.shape[0] != B:
+        raise ValueError(f"pack_rows: {B} persons, cond of {cond.shape[0]} rows (one per person)")
+    _int32_table(row_person, R, f"pack_rows: row_person for out of {R} rows")
+    a.dtype, a.B, a.R, a.hw, a.cpad = _dt(out), B, R, hw, out.shape[-1]
+    a.latents, a.cond, a.out, a.row_person = _ptr(latents), _ptr(cond), _ptr(out), _ptr(row_person)
+    _call("idmvton_pack_rows", a)
+    return out
+
+
+def row_step(eps_nhwc, latents, noise, coef_row, work, rows):
+    """person_step with a person's eps rows looked up (idmvton_row_step): eps_nhwc NHWC [R][hw][ldc]; rows: the int32 DEVICE table
+    {urow[0..B), crow[0..B)} -- person b's unconditional / conditional row of eps, or -1: no conditional row = the person is skipped (eps,
+    latents, noise and its part of `work` neither read nor written), no unconditional row = e = t.  coef_row is guided_step's
+    {c_x, c_eps, sigma, g[0..B), phi[0..B)}; work: guided_step_work_floats(B, hw) float32, never None.  Updates latents in place."""
+    a = ffi.RowStepArgs()
+    B = latents.shape[0]
+    hw = latents.numel() // (B * 4)
+    if coef_row.numel() != 3 + 2 * B or coef_row.dtype != torch.float32:
+        raise ValueError(f"row_step: coef_row holds {coef_row.numel()} {coef_row.dtype} values, needs 3 + 2B = {3 + 2 * B} float32")
+    _int32_table(rows, 2 * B, f"row_step: rows for {B} persons")
+    if work is None or work.dtype != torch.float32:
+        raise ValueError(f"row_step: work must be a float32 tensor, got {None if work is None else work.dtype}")
+    a.dtype, a.B, a.R, a.hw, a.ldc = _dt(eps_nhwc), B, eps_nhwc.shape[0], hw, eps_nhwc.shape[-1]
+    a.work, a.work_floats = _ptr(work), work.numel()
+    a.eps_nhwc, a.latents, a.noise, a.coef, a.rows = _ptr(eps_nhwc), _ptr(latents), _ptr(noise), _ptr(coef_row), _ptr(rows)
+    _call("idmvton_row_step", a)
+    return latents
+
+
 def to_nhwc(src_nchw_f32, dtype, cpad=None, scale=1.0, shift=0.0, out=None, split=False):
     """fp32 NCHW -> NHWC [cpad] of `dtype`; split=True: NHWC [2*cpad] = [hi | lo] (the split-precision VAE path)."""
     B, Cc = src_nchw_f32.shape[:2]

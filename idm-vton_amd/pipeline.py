@@ -57,6 +57,10 @@ below serves it, since what they fill is the garment side.
 Strength is per person too (prepare: strength as a float or one value per person).  A float is the call it always was; a sequence gives the
 PERSON state ([steps][3 + 3B] table with an `active` column, idmvton_person_step): the loop runs the longest timestep list, and the step skips
 the persons whose own list has not begun -- the only thing of a loop step that depends on the person.
+Rows per step (prepare: rows="needed", opt-in, on a GarmentCache): a loop step runs only the TryonNet rows its persons need -- none for a
+dormant person, no unconditional row for a person without guidance (_row_plans).  A call with something to skip is a ROW state
+(st["rows"]: idmvton_pack_rows, TryonNet at R rows, idmvton_row_step; one graph state per call shape with captures per (R, a)); a call with
+nothing to skip is the state it always was.  The garment side -- drive_blocks, the sets, _cached_fill -- does not know about it.
 
 `denoise` asks once whether the call is live or on a cache, wraps the step in the per-step hooks (`trace`, `on_step`) and drives the
 blocks.  The K / V^T layout of sets and cache (timestep-major) has one owner, garment_cache.timestep_run.
@@ -214,6 +218,8 @@ class TryonEngine:
         guided = (("guided", st.get("branches", 2)),) if st.get("guided") else ()
         if st.get("person"):
             guided = (("person", st.get("branches", 2)),)
+        if st.get("rows"):                                   # a ROW state (rows="needed" with something to skip): captures per (R, a) inside it
+            guided = (("rows", st.get("branches", 2)),)
         if live:
             return (st["B"], st["h"], st["w"], st["gh"], st["gw"], st["k"], st["steps_noise"] is not None) + guided
         return (st["B"], st["h"], st["w"], st["gh"], st["gw"], st["k"], st["steps_noise"] is not None, "cached",
@@ -256,6 +262,40 @@ class TryonEngine:
                 raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {s}, the number of pipeline"
                                  f"steps is {n_i} which is < 1 and not appropriate for this pipeline.")
         return s_b, n_b
+
+    ROWS = ("all", "needed")
+
+    @staticmethod
+    def _row_plans(B, n_b, g_b, n_max):
+        """The row plan of every loop step of a call under rows="needed" -> (plan index per step, the distinct plans), or None when no
+        step has fewer than 2B rows to run that today's states do not already skip.  n_b: the persons' own step counts (None: everyone
+        takes all n_max steps); g_b: their guidance scales.  Person i is active in loop steps [n_max - n_i, n_max) (the person state's
+        rule).  Step j runs the unconditional rows of the active persons with g > 1, then the conditional rows of the active persons, both
+        in ascending person order.  A plan: persons (A, a of them), uncond (u of them), R = u + a, row_person[R], urow[B] / crow[B] (a
+        person's row, or -1) and full_rows[R] (the same rows' indices in the [uncond B | cond B] layout).  Activity is nested over the loop
+        and g is fixed, so there are at most B distinct plans and a shape (R, a) names one.
+        None: every person active in every step and either everyone with g > 1 (the plain / guided / person state) or no one (the
+        conditional branch alone: today's branches = 1 state)."""
+        n_b = [n_max] * B if n_b is None else list(n_b)
+        cfg = [g > 1 for g in g_b]
+        if all(n == n_max for n in n_b) and (all(cfg) or not any(cfg)):
+            return None
+        index, plans, seen = [], [], {}
+        for j in range(n_max):
+            A = [i for i in range(B) if j >= n_max - n_b[i]]
+            U = [i for i in A if cfg[i]]
+            key = (len(U) + len(A), len(A))
+            if key not in seen:
+                urow, crow = [-1] * B, [-1] * B
+                for r, i in enumerate(U):
+                    urow[i] = r
+                for r, i in enumerate(A):
+                    crow[i] = len(U) + r
+                seen[key] = len(plans)
+                plans.append(dict(persons=A, uncond=U, a=len(A), u=len(U), R=len(U) + len(A), row_person=U + A, urow=urow, crow=crow,
+                                  full_rows=U + [B + i for i in A]))
+            index.append(seen[key])
+        return index, plans
 
     def weights_identity(self):
         """What a GarmentCache depends on besides its inputs: every GarmentNet weight, and TryonNet's attn1.to_k / to_v (the projections of
@@ -430,7 +470,7 @@ class TryonEngine:
     def prepare(self, *, image, mask_image, pose_img, cloth, prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds,
                 negative_pooled_prompt_embeds, text_embeds_cloth, noise, num_inference_steps, guidance_scale,
                 ip_hidden_states=None, image_embeds=None, scheduler="ddpm", height=None, width=None, strength=1.0,
-                image_dtype=None, garment_index=None, guidance_rescale=0.0, uncond="run"):
+                image_dtype=None, garment_index=None, guidance_rescale=0.0, uncond="run", rows="all"):
         """Everything before the loop (tryon_pipeline.py:1495-1762).  image in [0,1]; pose_img / cloth in [-1,1];
         noise: dict(latents, masked, pose [B,4,h,w] fp32; cloth [B,4,gh,gw] fp32; steps [n,B,4,h,w] fp32 or None; image [B,4,h,w] when
         strength < 1) -- RNG order SURVEY A.4.
@@ -476,8 +516,29 @@ class TryonEngine:
         idmvton_person_step -- which applies guidance_scale / guidance_rescale per person too, and runs under uncond="skip" -- and a graph
         state of its own; stats["person_steps"] counts its steps.  A wrong length, a value outside (0, 1], NaN or an n_i < 1 (the
         reference's message) is a ValueError naming `strength`, before anything is launched.  A step count per person stays out: a garment
-        cache is keyed to one timestep list."""
+        cache is keyed to one timestep list.
+        rows: "all" (the default: nothing changes) or "needed" (opt-in, on a GarmentCache): loop step j runs only the TryonNet rows its
+        persons need -- the unconditional rows of the persons active at j with g > 1, then the conditional rows of the persons active
+        at j, each in ascending person order (_row_plans).  A person with g <= 1 gets e = t, what uncond="skip" computes: its bits may
+        differ from rows="all" by one fp32 rounding of eps, and at sizes where the GEMM tile follows the row count a person's bits follow
+        the rows its steps ran with, which is why this is opt-in.  A call with nothing to skip is the state it is today,
+        key for key and kernel for kernel (all g <= 1 and nobody dormant: the branches = 1 state of uncond="skip"); a call in which some
+        step has fewer than 2B rows is a ROW state: st["rows"] = the plans and the step -> plan map, `cond` [B][hw][9], a guided coef
+        table, idmvton_pack_rows / idmvton_row_step, TryonNet at R rows, a graph state of its own.  The full-layout context and time
+        embeddings are computed as ever (2B rows: the bits of rows="all") and gathered per plan.  A cache without garment_index is read
+        through the index i % G.  The garment fills are untouched: all B persons' garments are moved for every step, a dormant
+        person's slot is not read.  stats["tryon_rows"] / ["row_steps"] count the rows and steps of such calls.  Any other value, a live
+        call (an index on a live call is still out) or an attn_fp8 engine is a ValueError naming `rows` / `attn_fp8`, before anything is
+        launched."""
         dev, dt = self.device, self.dtype
+        if rows not in self.ROWS:
+            raise ValueError(f"rows={rows!r}: \"all\" (every loop step runs the [uncond | cond] rows of every person) or \"needed\" (a step "
+                             "runs only the rows its persons need)")
+        if rows == "needed" and not isinstance(cloth, GarmentCache):
+            raise ValueError("rows=\"needed\" reads the garments through an index table, and an index on a live call is still out: pass a "
+                             "GarmentCache as `cloth=`")
+        if rows == "needed" and self.unet.attn_fp8:
+            raise ValueError("rows=\"needed\": attn_fp8 mismatch (the row plan is not run by an attn_fp8 engine)")
         self._release_streamed()
         f32 = lambda t: t.to(dev, torch.float32).contiguous()
         gcache = cloth if isinstance(cloth, GarmentCache) else None
@@ -494,12 +555,20 @@ class TryonEngine:
         s_min = strength if s_b is None else min(s_b)
         if s_b is not None:                                  # the loop runs the longest list: every person's is a suffix of it
             strength = max(s_b)
+        plans = None
+        if rows == "needed":                                 # the row plan, or None: nothing to skip -- the state the call is today
+            plans = self._row_plans(image.shape[0], n_b, g_b, len(self._timesteps(scheduler, num_inference_steps, strength)[1]))
+            if plans is None and max(g_b) <= 1:              # nobody with guidance, nobody dormant: the conditional branch alone
+                skip = True
+            guided = guided or skip or plans is not None
         if gcache is not None:
             gidx = gcache.check(timesteps=self._timesteps(scheduler, num_inference_steps, strength)[1],
                                 h=(height or image.shape[-2]) // 8, w=(width or image.shape[-1]) // 8, dtype=dt, attn_fp8=self.unet.attn_fp8,
                                 f8_exp=self.unet.f8_exp, weights_id=self.weights_identity(), persons=image.shape[0], garment_index=garment_index)
             if garment_index is not None:
                 gidx, gindex = gidx
+            elif plans is not None:                          # a row state reads every garment through a table: the i % G rule, written out
+                gindex = [i % gcache.G for i in range(image.shape[0])]
             if gcache.host_resident:
                 self._check_host_cache(gcache)
         image, mask_image, pose_img = f32(image), f32(mask_image), f32(pose_img)
@@ -519,7 +588,8 @@ class TryonEngine:
                              "noise['image'] (the reference's first random draw, tryon_pipeline.py:883-889), or set noise['latents_given'] "
                              "when noise['latents'] already is the start (the reference's `latents=` argument)")
         sched, timesteps = self._timesteps(scheduler, num_inference_steps, strength)
-        if skip:                                             # the conditional branch alone: nothing unconditional is read
+        lay1 = skip and plans is None                        # (a row state builds the full [uncond | cond] layout and gathers from it)
+        if lay1:                                             # the conditional branch alone: nothing unconditional is read
             if ip_hidden_states is not None and ip_hidden_states.shape[0] == 2 * B:
                 ip_hidden_states = ip_hidden_states[B:]
             if image_embeds is not None and image_embeds.shape[0] == 2 * B:
@@ -562,19 +632,19 @@ class TryonEngine:
                 cloth_lat = self.vae.encode_sample(cloth, f32(noise["cloth"]))
         # step-invariant 9 conditioning channels of the 13-channel input, NHWC, both CFG halves (:955,977,1649-1652,1777)
         cond = torch.cat([mask_l, masked_lat, pose_lat], dim=1).permute(0, 2, 3, 1).reshape(B, h * w, 9)
-        rows = B if skip else 2 * B                          # TryonNet rows: [uncond | cond], or the conditional branch alone
-        cond = (cond if skip else torch.cat([cond, cond], dim=0)).to(dt).contiguous()
+        nrows = B if lay1 else 2 * B                         # TryonNet rows: [uncond | cond], or the conditional branch alone
+        cond = (cond if lay1 or plans is not None else torch.cat([cond, cond], dim=0)).to(dt).contiguous()   # (a row state: one row per person)
 
-        if skip:
+        if lay1:
             pe, add_text = prompt_embeds.to(dev), pooled_prompt_embeds.to(dev)
         else:
             pe = torch.cat([negative_prompt_embeds, prompt_embeds], dim=0).to(dev)             # :1710
             add_text = torch.cat([negative_pooled_prompt_embeds, pooled_prompt_embeds], dim=0).to(dev)   # :1711
-        time_ids = torch.tensor([[H, W, 0, 0, H, W]], dtype=torch.float32, device=dev).repeat(rows, 1)  # :1681-1713
+        time_ids = torch.tensor([[H, W, 0, 0, H, W]], dtype=torch.float32, device=dev).repeat(nrows, 1)  # :1681-1713
         if image_embeds is None:
             image_embeds = self.resampler(ip_hidden_states.to(dev))                        # :1726 (encoder_hid_proj)
         ctx_t = self.unet.encode_context(pe, image_embeds)
-        temb_t = self.unet.time_embeddings(timesteps, rows, dict(text_embeds=add_text, time_ids=time_ids))
+        temb_t = self.unet.time_embeddings(timesteps, nrows, dict(text_embeds=add_text, time_ids=time_ids))
         if gcache is None:
             # GarmentNet over consecutive timesteps per batch, blocks of 1, 2, 4, k, k, ... timesteps
             garm = dict(self._garment_inputs(cloth_lat, text_embeds_cloth, timesteps, B), gcache=None, gidx=None, garment_persons=None,
@@ -583,27 +653,47 @@ class TryonEngine:
             k, blocks = self._block_schedule(len(timesteps))
             if gcache.sizes is not None:                     # [features][2B]: the real tokens of person b % B's garment, in both CFG halves
                 per = [self.unet.feature_tokens(*sz) for sz in gcache.garment_sizes(gindex)]   # (uncond="skip": [features][B])
-                gnk = torch.tensor([[p[f] for p in per] * (rows // B) for f in range(len(per[0]))], dtype=torch.int32, device=dev)
+                gnk = torch.tensor([[p[f] for p in per] * (nrows // B) for f in range(len(per[0]))], dtype=torch.int32, device=dev)
             garm = dict(cloth=None, ctx_g=None, temb_g=None, k=k, blocks=blocks, temb_gk=None, cloth_k=None, ctx_gk=None,
                         gcache=gcache, gidx=gidx, garment_persons=B, gindex=gindex,
                         # the table the kernels read: person -> garment of the cache (a graph state keeps its own: person -> set slot)
                         gix=torch.tensor(gindex, dtype=torch.int32, device=dev) if gindex is not None else None,
                         # the second table, on a cache with sizes only: per garment feature the key count of every batch
                         gnk=gnk if gcache.sizes is not None else None)
-        if s_b is not None:                                  # [steps][3 + 3B]: the guided row and who takes the step; the same scratch
+        if s_b is not None and plans is None:                # [steps][3 + 3B]: the guided row and who takes the step; the same scratch
             coef = torch.tensor(sched.person_coef_table(timesteps, g_b, phi_b, n_b), dtype=torch.float32, device=dev)
             work = torch.empty(ops.guided_step_work_floats(B, h * w), dtype=torch.float32, device=dev) if not skip else None
         elif guided:                                         # [steps][3 + 2B], and the statistics scratch of idmvton_guided_step
             coef = torch.tensor(sched.guided_coef_table(timesteps, g_b, phi_b), dtype=torch.float32, device=dev)
-            work = torch.empty(ops.guided_step_work_floats(B, h * w), dtype=torch.float32, device=dev) if not skip else None
+            work = torch.empty(ops.guided_step_work_floats(B, h * w), dtype=torch.float32, device=dev) if not lay1 else None
         else:
             coef, work = torch.tensor(sched.coef_table(timesteps, guidance_scale), dtype=torch.float32, device=dev), None
         steps_noise = f32(noise["steps"]) if noise.get("steps") is not None and scheduler == "ddpm" else None
         return dict(B=B, h=h, w=w, gh=gh, gw=gw, timesteps=timesteps, latents=latents.contiguous(), cond=cond,
                     ctx_t=ctx_t, temb_t=temb_t, coef=coef, steps_noise=steps_noise, **garm,
-                    guided=guided, branches=1 if skip else 2, work=work, **(dict(person=True, n_active=n_b) if s_b is not None else {}),
-                    x_in=torch.empty(rows, h * w, self.unet.cin_pad, dtype=dt, device=dev),
+                    guided=guided, branches=1 if lay1 else 2, work=work, **(dict(person=True, n_active=n_b) if s_b is not None and plans is None else {}),
+                    **(dict(rows=self._bind_rows(plans, ctx_t, temb_t, garm)) if plans is not None else {}),
+                    x_in=torch.empty(max(p["R"] for p in plans[1]) if plans is not None else nrows, h * w, self.unet.cin_pad, dtype=dt, device=dev),
                     trace=dict(masked_lat=masked_lat, pose_lat=pose_lat, cloth_lat=cloth_lat, image_embeds=image_embeds))
+
+    def _bind_rows(self, plans, ctx_t, temb_t, garm):
+        """st["rows"] of a row state: _row_plans' result with what each plan's steps read, gathered from the full [uncond B | cond B]
+        layout (so every value has the bits of the rows="all" call): per plan the device tables row_person[R] and {urow | crow}[2B], the
+        context K rows / V^T entries of full_rows for every attn2, the key-count columns of full_rows (a cache with sizes) and the active
+        persons' garment index; per step the time embeddings of its plan's rows."""
+        dev = self.device
+        index, plans = plans
+        i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=dev)
+        bound = []
+        for p in plans:
+            fr, act = torch.tensor(p["full_rows"], device=dev), torch.tensor(p["persons"], device=dev)
+            ctx = {**ctx_t, "B": p["R"], "kv": {}}
+            for name, ent in ctx_t["kv"].items():            # K [2B * r][C] -> the rows' r-row runs; V^T [2B][C][r] -> the rows' entries
+                ctx["kv"][name] = {kind: (t.view(ctx_t["B"], -1, t.shape[-1])[fr].reshape(-1, t.shape[-1]) if kind in ("kt", "ki") else t[fr]).contiguous()
+                                   for kind, t in ent.items()}
+            bound.append(dict(p, persons_t=act, row_person_t=i32(p["row_person"]), table=i32(p["urow"] + p["crow"]), ctx=ctx,
+                              gix=garm["gix"][act].contiguous(), gnk=garm["gnk"][:, fr].contiguous() if garm["gnk"] is not None else None))
+        return dict(step=index, plans=bound, temb=[temb_t[j][torch.tensor(plans[pi]["full_rows"], device=dev)] for j, pi in enumerate(index)])
 
     def _person_starts(self, sched, timesteps, s_b, n_b, noise, start_is_given, src):
         """The start latents of a call with a strength per person: person i's row is what the scalar call at s_i forms for it -- the noise
@@ -637,8 +727,17 @@ class TryonEngine:
     def _garment_side(self, st, temb_gk, fset, c=None):
         self.unet.project_garment_kv(self._garment_feats(st, temb_gk, fset["feats"], c), out=fset["kv"])
 
-    def _tryon_main(self, st, temb_t, coef, noise, kv_j):
+    def _tryon_main(self, st, temb_t, coef, noise, kv_j, plan=None):
         B, h, w = st["B"], st["h"], st["w"]
+        if plan is not None:                                 # a row state: the step's R = u + a rows, the last a of them conditional
+            R = plan["R"]
+            x = ops.pack_rows(st["latents"], st["cond"], st["x_in"][:R], plan["row_person_t"])
+            eps, _ = self.unet.forward(x, temb_t, plan["ctx"], R, h, w, garment_kv=kv_j, garment_persons=plan["a"], garment_hw=(st["gh"], st["gw"]),
+                                       garment_index=plan["gix"], garment_nk=plan["gnk"])
+            self.stats["tryon_rows"] += R
+            self.stats["row_steps"] += 1
+            ops.row_step(eps, st["latents"], noise, coef, st["work"], plan["table"])
+            return eps
         branches = st.get("branches", 2)                     # 1: uncond="skip", the conditional rows alone (garment segment from batch 0 on)
         (ops.pack_input if branches == 2 else ops.pack_input_cond)(st["latents"], st["cond"], st["x_in"])   # :1769,1777
         # garment_persons: None = one garment entry per conditional batch (unet.forward's default); B on a GarmentCache call, where kv_j
@@ -876,12 +975,17 @@ class TryonEngine:
             sets = [self._alloc_set((), shapes, len(st["gcache"].timesteps), st["k"], slots) for _ in range(2 if overlap else 1)]
             garment = self._cached_fill(st, sets)
             st = dict(st, gix=self._slot_table(st))          # with garment_index: person -> set slot (the same tensors otherwise)
+            if st.get("rows"):                               # (a row state: each plan's active persons -> set slots)
+                st["rows"] = dict(st["rows"], plans=[dict(p, gix=st["gix"][p["persons_t"]].contiguous()) for p in st["rows"]["plans"]])
             kv = lambda i, j, p: sets[p]["step"][j]
         else:                                                # nothing to launch, so nothing to overlap: TryonNet reads the cache's own views
             overlap = False
             garment = lambda bi, p: None
             kv = lambda i, j, p: st["gcache"].step(st["gidx"][i])
         step = lambda i, j, p: self._tryon_main(st, st["temb_t"][i], st["coef"][i], self._noise(st, i), kv(i, j, p))
+        if st.get("rows"):                                   # the step is handed its plan
+            rw = st["rows"]
+            step = lambda i, j, p: self._tryon_main(st, rw["temb"][i], st["coef"][i], self._noise(st, i), kv(i, j, p), rw["plans"][rw["step"][i]])
         if not overlap:
             return garment, step, st["latents"], None
         if self._side is None:
@@ -904,14 +1008,20 @@ class TryonEngine:
         key = self._graph_key(st, live)                      # garment size included: calls with different garment sizes share nothing here
         if key in self._graphs:
             return self._graphs[key]
-        G = {name: st[name] for name in ("B", "h", "w", "gh", "gw", "k", "garment_persons", "latents", "cond", "x_in", "ctx_t")}
+        rows = st.get("rows")
+        G = {name: st[name] for name in ("B", "h", "w", "gh", "gw", "k", "garment_persons", "latents", "cond", "x_in") + (() if rows else ("ctx_t",))}
+        if rows:
+            # a ROW state serves every plan of every call of its shape: x_in and tt hold 2B rows and a step uses their first R; what a
+            # plan's captures read besides -- context, index, key counts, the two plan tables -- lives in persistent buffers per (R, a),
+            # made on first use and copied per call (_state_rows)
+            G.update(x_in=torch.empty(2 * st["B"], *st["x_in"].shape[1:], dtype=self.dtype, device=self.device), rows={})
         # guided: the scratch of idmvton_guided_step, persistent like gix / gnk (the captures hold its pointer; its contents carry nothing
         # from one step to the next, so the first call's buffer is adopted and never copied)
         G.update(guided=st.get("guided", False), branches=st.get("branches", 2), work=st.get("work"), person=st.get("person", False))
         # indexed: the table person -> set slot, a persistent buffer whose pointer the captured graphs hold; its contents are copied per call
-        G["gix"] = self._slot_table(st)
+        G["gix"] = self._slot_table(st) if not rows else None
         # ragged: the key-count table, persistent in the same way (the sets copy whole slots, so it is the call's own table)
-        G["gnk"] = st["gnk"].clone() if st.get("gnk") is not None else None
+        G["gnk"] = st["gnk"].clone() if st.get("gnk") is not None and not rows else None
         G.update(tt=st["temb_t"][0].clone(), cf=st["coef"][0].clone(), nz=st["steps_noise"][0].clone() if has_noise else None, graphs={},
                  side=torch.cuda.Stream(), ready=[torch.cuda.Event(), torch.cuda.Event()], free=[torch.cuda.Event(), torch.cuda.Event()],
                  # graphs that replay one after another on ONE stream may share a memory pool: all TryonNet graphs (main stream), all
@@ -932,7 +1042,12 @@ class TryonEngine:
                 self._cached_fill(st, G["sets"][:1], blocks=(0,))(0, 0)   # (a table of block 0 alone: complete before the synchronize below)
                 if gc.features:                              # garment_projections counts the blocks of calls: not the warm-up's
                     self.stats["garment_projections"] -= 1
-            self._tryon_main(G, G["tt"], G["cf"], G["nz"], G["sets"][0]["step"][0])
+            if rows:                                         # the warm-up step is the call's first; tryon_rows / row_steps count calls
+                plan = self._state_rows(G, st)[rows["step"][0]]
+                self._tryon_main(G, G["tt"][:plan["R"]], G["cf"], G["nz"], G["sets"][0]["step"][0], plan)
+                self._uncount_rows(plan)
+            else:
+                self._tryon_main(G, G["tt"], G["cf"], G["nz"], G["sets"][0]["step"][0])
             if G["person"]:                                  # person_steps counts the steps of calls: not the warm-up's
                 self.stats["person_steps"] -= 1
         torch.cuda.current_stream().wait_stream(warm)
@@ -942,8 +1057,36 @@ class TryonEngine:
         self._graphs[key] = G
         return G
 
-    def _graph(self, G, kind, par, j=0):
-        gk = (kind, par, j)
+    def _state_rows(self, G, st):
+        """A call's plans -> the persistent plans of a row graph state, one per shape (R, a): made on first use as clones of the call's,
+        otherwise the call's context, key counts and plan tables are copied into them -- and always the table active person -> set slot,
+        which a call does not have.  -> the state's plans in the order of the call's."""
+        slot, out = self._slot_table(st), []
+        for p in st["rows"]["plans"]:
+            key = (p["R"], p["a"])
+            mine = G["rows"].get(key)
+            if mine is None:
+                clone = lambda t: t.clone() if t is not None else None
+                mine = G["rows"][key] = dict(p, row_person_t=p["row_person_t"].clone(), table=p["table"].clone(), gnk=clone(p["gnk"]), gix=torch.empty_like(p["gix"]),
+                                             ctx={**p["ctx"], "kv": {n: {kind: t.clone() for kind, t in ent.items()} for n, ent in p["ctx"]["kv"].items()}})
+            else:
+                for name in ("row_person_t", "table", "gnk"):
+                    if mine[name] is not None:
+                        mine[name].copy_(p[name])
+                for n, ent in p["ctx"]["kv"].items():
+                    for kind, t in ent.items():
+                        mine["ctx"]["kv"][n][kind].copy_(t)
+            mine["gix"].copy_(slot[p["persons_t"]])
+            out.append(mine)
+        return out
+
+    def _uncount_rows(self, plan):
+        """A warm-up or a capture ran _tryon_main's counting: tryon_rows / row_steps count the launches and replays of calls."""
+        self.stats["tryon_rows"] -= plan["R"]
+        self.stats["row_steps"] -= 1
+
+    def _graph(self, G, kind, par, j=0, plan=None):
+        gk = (kind, par, j) + ((plan["R"], plan["a"]) if plan is not None else ())
         if gk in G["graphs"]:
             return G["graphs"][gk]
         keep = G["latents"].clone()
@@ -953,6 +1096,9 @@ class TryonEngine:
             if kind == "garm":                                   # j = timesteps in the batch
                 self._garment_side(G, G["tgk"], G["sets"][par], j)
                 self.stats["garment_batches"] -= 1               # captured, not run: replays are counted
+            elif plan is not None:                               # a row state's step at this plan's shape: prefix views of tt and x_in
+                self._tryon_main(G, G["tt"][:plan["R"]], G["cf"], G["nz"], G["sets"][par]["step"][j], plan)
+                self._uncount_rows(plan)                         # captured, not run: replays are counted
             else:
                 self._tryon_main(G, G["tt"], G["cf"], G["nz"], G["sets"][par]["step"][j])
                 if G["person"]:
@@ -966,8 +1112,14 @@ class TryonEngine:
         if G["latents"] is not st["latents"]:
             _copy_state(G, dict(st, gix=self._slot_table(st)))                             # new call -> persistent buffers
         blocks, graphs = st["blocks"], G["graphs"]
+        rows = st.get("rows")
         # capture everything this call needs before the loop (a capture must not interleave with work in flight on the side stream)
-        for p in ((0, 1) if overlap and len(blocks) > 1 else (0,)):
+        if rows:                                             # ('tryon', p, j, R, a): the steps of this call, each at its plan's shape
+            plans = self._state_rows(G, st)
+            for bi, (s0, c) in enumerate(blocks):
+                for j in range(c):
+                    self._graph(G, "tryon", (bi & 1) if overlap and len(blocks) > 1 else 0, j, plans[rows["step"][s0 + j]])
+        for p in ((0, 1) if overlap and len(blocks) > 1 else (0,)) if not rows else ():
             for j in range(st["k"]):
                 self._graph(G, "tryon", p, j)
         if live:
@@ -990,6 +1142,17 @@ class TryonEngine:
                 self.stats["person_steps"] += 1
             graphs[("tryon", p, j)].replay()
 
+        def row_step(i, j, p):
+            plan = plans[rows["step"][i]]
+            tt[:plan["R"]].copy_(rows["temb"][i]); cf.copy_(st["coef"][i])
+            if nz is not None:
+                nz.copy_(st["steps_noise"][i])
+            self.stats["tryon_rows"] += plan["R"]
+            self.stats["row_steps"] += 1
+            graphs[("tryon", p, j, plan["R"], plan["a"])].replay()
+
+        if rows:
+            step = row_step
         return garment, step, G["latents"], (G["side"], G["ready"], G["free"]) if overlap else None
 
     @torch.no_grad()

@@ -466,6 +466,45 @@ typedef struct {
 } idmvton_person_step_args;
 int idmvton_person_step(const idmvton_person_step_args* a, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * The edge kernels of a ROW PLAN: a loop step runs only the TryonNet rows its persons need -- u unconditional rows (the active persons
+ * with guidance) followed by a conditional rows (the active persons), R = u + a of them, in place of [uncond B | cond B].
+ * idmvton_pack_rows : idmvton_pack_input for such a step -- out NHWC [R][hw][cpad], row r = cat(latents[p] | cond[p]) with
+ *   p = row_person[r], channels [13, cpad) zero.
+ *   row_person : DEVICE int32 [R], read when the kernel runs; an entry is clamped to [0, B - 1]
+ *   cond       : dtype NHWC [B][hw][9], one row per PERSON (not the duplicated [2B] buffer of idmvton_pack_input)
+ *   latents    : fp32 NCHW [B][4][hw]
+ *   The casts are idmvton_pack_input's: a row's bits are those of the same person's row there.  Refused before the launch: null
+ *   pointers, B <= 0, R <= 0, hw <= 0, cpad < 13, R * hw beyond int32 (E_SHAPE), a dtype that is neither f16 nor bf16 (E_DTYPE).
+ * idmvton_row_step : idmvton_person_step with a person's eps rows looked up, not implied.
+ *   eps_nhwc : dtype NHWC [R][hw][ldc], channels 0..3 used
+ *   rows     : DEVICE int32 {urow[0..B), crow[0..B)}: the row of person b's unconditional / conditional prediction, or -1; read when
+ *              the kernels run, each entry clamped to [-1, R - 1]
+ *   coef     : DEVICE pointer to the guided row {c_x, c_eps, sigma, g[0..B), phi[0..B)} (3 + 2B floats)
+ *   work     : idmvton_guided_step_work_floats(B, hw) floats, 8-byte aligned; never NULL
+ *   crow[b] < 0 : person b is DORMANT -- idmvton_person_step's contract: its statistics workgroups return before any load, its apply
+ *              workgroups before any load or store; its latents and its region of `work` keep their bits, its noise is not read.
+ *   urow[b] < 0 <= crow[b] : e = t, no rescale -- the bits of idmvton_guided_step(branches = 1) on that row.
+ *   both >= 0 : the bits of idmvton_person_step(branches = 2) on an eps tensor holding those two rows at b and B + b: the same
+ *              operations in the same order (the chunked fp64 sums folded in chunk order), no atomics.  A person's bits depend neither on
+ *              R, on B nor on where its rows or the person stand.
+ *   Launches: statistics + apply, always (who has a rescale is read from the table by the kernels).  No allocation, no
+ *   synchronisation, no state but `work`: capturable.  Refusals are idmvton_guided_step's (messages name row_step), plus R <= 0 or
+ *   > 65535 (E_SHAPE) and a null `rows` or `work` (E_ARG).
+ * Additive: the ABI version stays 9; no other entry point or struct changes.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t dtype; int32_t B, R, hw, cpad;
+    const float* latents; const void* cond; void* out; const int32_t* row_person;
+} idmvton_pack_rows_args;
+int idmvton_pack_rows(const idmvton_pack_rows_args* a, void* stream);
+typedef struct {
+    int32_t dtype; int32_t B, R, hw, ldc;
+    int32_t work_floats;        /* capacity of `work` in floats */
+    const void* eps_nhwc; float* latents; const float* noise; const float* coef; float* work; const int32_t* rows;
+} idmvton_row_step_args;
+int idmvton_row_step(const idmvton_row_step_args* a, void* stream);
+
 /* Layout / dtype conversion at the pipeline edges: NCHW fp32 <-> NHWC dtype with channel padding. */
 enum { IDMVTON_LAYOUT_SPLIT = 1 /* to_nhwc: dst is NHWC [2*cpad] = [hi | lo] */, IDMVTON_LAYOUT_NHWC_F32 = 2 /* to_nchw: src NHWC holds fp32 */ };
 typedef struct {
