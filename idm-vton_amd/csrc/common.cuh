@@ -143,6 +143,19 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
 }
 
+// One pixel of a TryonNet input row (idmvton_pack_input, _pack_input_cond, _pack_rows; `a` is either argument struct): output pixel idx of
+// NHWC [rows][hw][cpad] = cat(person p's 4 latent channels at pix, cast | the 9 channels of pixel cpx of cond, its row's pix | zeros).
+template <typename T, typename A>
+__device__ __forceinline__ void pack_pixel(const A& a, int idx, int p, int pix, size_t cpx) {
+    T* o = (T*)a.out + (size_t)idx * a.cpad;
+    const T* cond = (const T*)a.cond + cpx * 9;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) o[c] = (T)a.latents[((size_t)p * 4 + c) * a.hw + pix];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) o[4 + c] = cond[c];
+    for (int c = 13; c < a.cpad; ++c) o[c] = (T)0.f;
+}
+
 // ---- host side -------------------------------------------------------------------------------------------------
 int idmvton_set_error(int code, const char* fmt, ...);
 #define CHECK_ARG(cond, code, ...) do { if (!(cond)) return idmvton_set_error(code, __VA_ARGS__); } while (0)

@@ -18,14 +18,7 @@ __global__ void pack_input_kernel(const idmvton_pack_input_args a) {
     const int total = 2 * a.B * a.hw;
     if (idx >= total) return;
     const int b2 = idx / a.hw, pix = idx - b2 * a.hw;
-    const int b = b2 % a.B;                                     // both CFG halves see the same latents
-    T* o = (T*)a.out + (size_t)idx * a.cpad;
-    const T* cond = (const T*)a.cond + (size_t)idx * 9;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) o[c] = (T)a.latents[((size_t)b * 4 + c) * a.hw + pix];
-#pragma unroll
-    for (int c = 0; c < 9; ++c) o[4 + c] = cond[c];
-    for (int c = 13; c < a.cpad; ++c) o[c] = (T)0.f;
+    pack_pixel<T>(a, idx, b2 % a.B, pix, idx);                  // both CFG halves see the same latents
 }
 extern "C" int idmvton_pack_input(const idmvton_pack_input_args* a, void* stream) {
     CHECK_ARG(a && a->latents && a->cond && a->out, IDMVTON_E_ARG, "pack_input: null pointer");

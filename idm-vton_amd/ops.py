@@ -656,22 +656,32 @@ def guided_step_work_floats(B, hw):
     return n
 
 
+def _step_operands(name, a, eps_nhwc, latents, noise, coef_row, work, width, branches=None):
+    """What guided_step, person_step and row_step share: B and hw from the latents, the check of the coefficient row {c_x, c_eps, sigma,
+    `width` columns of B} and of `work`, and the fields the three argument structs have in common.  branches: of an entry whose eps rows
+    are [branches * B]; None: the rows are looked up, and `work` is always needed.  -> B"""
+    B = latents.shape[0]
+    hw = latents.numel() // (B * 4)
+    if coef_row.numel() != 3 + width * B or coef_row.dtype != torch.float32:
+        raise ValueError(f"{name}: coef_row holds {coef_row.numel()} {coef_row.dtype} values, needs 3 + {width}B = {3 + width * B} float32")
+    if branches is not None:
+        if eps_nhwc.shape[0] != branches * B:
+            raise ValueError(f"{name}: eps of {eps_nhwc.shape[0]} rows for branches={branches} and {B} persons")
+        a.branches = branches
+    if (work is None and branches is None) or (work is not None and work.dtype != torch.float32):
+        raise ValueError(f"{name}: work must be {'float32' if branches else 'a float32 tensor'}, got {None if work is None else work.dtype}")
+    a.dtype, a.B, a.hw, a.ldc = _dt(eps_nhwc), B, hw, eps_nhwc.shape[-1]
+    a.work, a.work_floats = _ptr(work), 0 if work is None else work.numel()
+    a.eps_nhwc, a.latents, a.noise, a.coef = _ptr(eps_nhwc), _ptr(latents), _ptr(noise), _ptr(coef_row)
+    return B
+
+
 def guided_step(eps_nhwc, latents, noise, coef_row, work, branches=2):
     """The CFG combine + scheduler update with a guidance scale and a guidance_rescale per person (idmvton_guided_step).  eps_nhwc: NHWC
     [branches * B][hw][ldc]; coef_row: float32 device tensor {c_x, c_eps, sigma, g[0..B), phi[0..B)}; work: float32 device tensor of at
     least guided_step_work_floats(B, hw) elements (branches=1 takes None: the conditional rows alone, e = t).  Updates latents in place."""
     a = ffi.GuidedStepArgs()
-    B = latents.shape[0]
-    hw = latents.numel() // (B * 4)
-    if coef_row.numel() != 3 + 2 * B or coef_row.dtype != torch.float32:
-        raise ValueError(f"guided_step: coef_row holds {coef_row.numel()} {coef_row.dtype} values, needs 3 + 2B = {3 + 2 * B} float32")
-    if eps_nhwc.shape[0] != branches * B:
-        raise ValueError(f"guided_step: eps of {eps_nhwc.shape[0]} rows for branches={branches} and {B} persons")
-    if work is not None and work.dtype != torch.float32:
-        raise ValueError(f"guided_step: work must be float32, got {work.dtype}")
-    a.dtype, a.B, a.hw, a.ldc, a.branches = _dt(eps_nhwc), B, hw, eps_nhwc.shape[-1], branches
-    a.work, a.work_floats = _ptr(work), 0 if work is None else work.numel()
-    a.eps_nhwc, a.latents, a.noise, a.coef = _ptr(eps_nhwc), _ptr(latents), _ptr(noise), _ptr(coef_row)
+    _step_operands("guided_step", a, eps_nhwc, latents, noise, coef_row, work, 2, branches)
     _call("idmvton_guided_step", a)
     return latents
 
@@ -681,17 +691,7 @@ def person_step(eps_nhwc, latents, noise, coef_row, work, branches=2):
     phi[0..B), active[0..B)}; person b takes the step when active[b] > 0, and is skipped otherwise -- its eps, latents, noise and part of
     `work` are neither read nor written.  The other operands are guided_step's.  Updates the active persons' latents in place."""
     a = ffi.PersonStepArgs()
-    B = latents.shape[0]
-    hw = latents.numel() // (B * 4)
-    if coef_row.numel() != 3 + 3 * B or coef_row.dtype != torch.float32:
-        raise ValueError(f"person_step: coef_row holds {coef_row.numel()} {coef_row.dtype} values, needs 3 + 3B = {3 + 3 * B} float32")
-    if eps_nhwc.shape[0] != branches * B:
-        raise ValueError(f"person_step: eps of {eps_nhwc.shape[0]} rows for branches={branches} and {B} persons")
-    if work is not None and work.dtype != torch.float32:
-        raise ValueError(f"person_step: work must be float32, got {work.dtype}")
-    a.dtype, a.B, a.hw, a.ldc, a.branches = _dt(eps_nhwc), B, hw, eps_nhwc.shape[-1], branches
-    a.work, a.work_floats = _ptr(work), 0 if work is None else work.numel()
-    a.eps_nhwc, a.latents, a.noise, a.coef = _ptr(eps_nhwc), _ptr(latents), _ptr(noise), _ptr(coef_row)
+    _step_operands("person_step", a, eps_nhwc, latents, noise, coef_row, work, 3, branches)
     _call("idmvton_person_step", a)
     return latents
 
@@ -722,16 +722,9 @@ def row_step(eps_nhwc, latents, noise, coef_row, work, rows):
     latents, noise and its part of `work` neither read nor written), no unconditional row = e = t.  coef_row is guided_step's
     {c_x, c_eps, sigma, g[0..B), phi[0..B)}; work: guided_step_work_floats(B, hw) float32, never None.  Updates latents in place."""
     a = ffi.RowStepArgs()
-    B = latents.shape[0]
-    hw = latents.numel() // (B * 4)
-    if coef_row.numel() != 3 + 2 * B or coef_row.dtype != torch.float32:
-        raise ValueError(f"row_step: coef_row holds {coef_row.numel()} {coef_row.dtype} values, needs 3 + 2B = {3 + 2 * B} float32")
+    B = _step_operands("row_step", a, eps_nhwc, latents, noise, coef_row, work, 2)
     _int32_table(rows, 2 * B, f"row_step: rows for {B} persons")
-    if work is None or work.dtype != torch.float32:
-        raise ValueError(f"row_step: work must be a float32 tensor, got {None if work is None else work.dtype}")
-    a.dtype, a.B, a.R, a.hw, a.ldc = _dt(eps_nhwc), B, eps_nhwc.shape[0], hw, eps_nhwc.shape[-1]
-    a.work, a.work_floats = _ptr(work), work.numel()
-    a.eps_nhwc, a.latents, a.noise, a.coef, a.rows = _ptr(eps_nhwc), _ptr(latents), _ptr(noise), _ptr(coef_row), _ptr(rows)
+    a.R, a.rows = eps_nhwc.shape[0], _ptr(rows)
     _call("idmvton_row_step", a)
     return latents
 

@@ -206,6 +206,17 @@ class TryonEngine:
         return (st["B"], st["gh"], st["gw"], st["k"]) + (("cond-only",) if st.get("branches", 2) == 1 else ())
 
     @staticmethod
+    def _kind(st):
+        """The kind of a call's state or of a graph state, named in this one place: "rows" (a row plan: pack_rows, TryonNet at R rows,
+        row_step), "person" (a strength per person: person_step), "guided" (guidance per person, or the conditional branch alone:
+        guided_step) or "plain" (cfg_step).  It is the suffix of the graph key, the step _tryon_main launches and what a step counts."""
+        if st.get("rows") is not None:                       # (a graph state's is a dict that fills on first use: empty, and a row state)
+            return "rows"
+        if st.get("person"):
+            return "person"
+        return "guided" if st.get("guided") else "plain"
+
+    @staticmethod
     def _graph_key(st, live):
         """One persistent graph state per shape of a call: persons, person latent size, garment latent size, block size, step noise, and on a
         GarmentCache its garment count -- or, with garment_index, nothing more: the sets of an indexed state have one slot per PERSON, so one
@@ -215,11 +226,8 @@ class TryonEngine:
         uncond="skip", whose captures run B TryonNet rows; a plain state's key is what it always was.  A PERSON state (a strength per
         person: a `cf` of 3 + 3B, idmvton_person_step in its captures -- which takes the guidance per person too) has ("person", branches) in
         that place, whatever its guidance."""
-        guided = (("guided", st.get("branches", 2)),) if st.get("guided") else ()
-        if st.get("person"):
-            guided = (("person", st.get("branches", 2)),)
-        if st.get("rows"):                                   # a ROW state (rows="needed" with something to skip): captures per (R, a) inside it
-            guided = (("rows", st.get("branches", 2)),)
+        kind = TryonEngine._kind(st)                         # (a ROW state: rows="needed" with something to skip; captures per (R, a) inside it)
+        guided = ((kind, st.get("branches", 2)),) if kind != "plain" else ()
         if live:
             return (st["B"], st["h"], st["w"], st["gh"], st["gw"], st["k"], st["steps_noise"] is not None) + guided
         return (st["B"], st["h"], st["w"], st["gh"], st["gw"], st["k"], st["steps_noise"] is not None, "cached",
@@ -727,15 +735,23 @@ class TryonEngine:
     def _garment_side(self, st, temb_gk, fset, c=None):
         self.unet.project_garment_kv(self._garment_feats(st, temb_gk, fset["feats"], c), out=fset["kv"])
 
+    def _count_step(self, st, plan=None):
+        """The one place a loop step of a call is counted, by the `step` of either execution form (a launch or a replay; warm-ups and
+        captures are not steps of a call).  A kind that has no counter lists none in stats."""
+        kind = self._kind(st)
+        if kind == "person":
+            self.stats["person_steps"] += 1
+        elif kind == "rows":
+            self.stats["tryon_rows"] += plan["R"]
+            self.stats["row_steps"] += 1
+
     def _tryon_main(self, st, temb_t, coef, noise, kv_j, plan=None):
-        B, h, w = st["B"], st["h"], st["w"]
-        if plan is not None:                                 # a row state: the step's R = u + a rows, the last a of them conditional
+        B, h, w, kind = st["B"], st["h"], st["w"], self._kind(st)
+        if kind == "rows":                                   # the step's plan: R = u + a rows, the last a of them conditional
             R = plan["R"]
             x = ops.pack_rows(st["latents"], st["cond"], st["x_in"][:R], plan["row_person_t"])
             eps, _ = self.unet.forward(x, temb_t, plan["ctx"], R, h, w, garment_kv=kv_j, garment_persons=plan["a"], garment_hw=(st["gh"], st["gw"]),
                                        garment_index=plan["gix"], garment_nk=plan["gnk"])
-            self.stats["tryon_rows"] += R
-            self.stats["row_steps"] += 1
             ops.row_step(eps, st["latents"], noise, coef, st["work"], plan["table"])
             return eps
         branches = st.get("branches", 2)                     # 1: uncond="skip", the conditional rows alone (garment segment from batch 0 on)
@@ -744,10 +760,9 @@ class TryonEngine:
         # holds G garments for the B persons (a shared segment when G < B)
         eps, _ = self.unet.forward(st["x_in"], temb_t, st["ctx_t"], branches * B, h, w, garment_kv=kv_j, garment_persons=st["garment_persons"],
                                    garment_hw=(st["gh"], st["gw"]), garment_index=st.get("gix"), garment_nk=st.get("gnk"))   # :1796-1808
-        if st.get("person"):                                 # a strength per person: the guided step for those the coef row calls active
-            self.stats["person_steps"] += 1
+        if kind == "person":                                 # a strength per person: the guided step for those the coef row calls active
             ops.person_step(eps, st["latents"], noise, coef, st["work"], branches)
-        elif st.get("guided"):                               # per-person guidance / rescale, or e = t of the conditional branch alone
+        elif kind == "guided":                               # per-person guidance / rescale, or e = t of the conditional branch alone
             ops.guided_step(eps, st["latents"], noise, coef, st["work"], branches)         # :1814-1823
         else:
             ops.cfg_step(eps, st["latents"], noise, coef)                                  # :1814-1823
@@ -982,10 +997,12 @@ class TryonEngine:
             overlap = False
             garment = lambda bi, p: None
             kv = lambda i, j, p: st["gcache"].step(st["gidx"][i])
-        step = lambda i, j, p: self._tryon_main(st, st["temb_t"][i], st["coef"][i], self._noise(st, i), kv(i, j, p))
-        if st.get("rows"):                                   # the step is handed its plan
-            rw = st["rows"]
-            step = lambda i, j, p: self._tryon_main(st, rw["temb"][i], st["coef"][i], self._noise(st, i), kv(i, j, p), rw["plans"][rw["step"][i]])
+        rw = st.get("rows")
+
+        def step(i, j, p):
+            plan = rw["plans"][rw["step"][i]] if rw else None                              # a row state: the step is handed its plan
+            self._count_step(st, plan)
+            self._tryon_main(st, (rw["temb"] if rw else st["temb_t"])[i], st["coef"][i], self._noise(st, i), kv(i, j, p), plan)
         if not overlap:
             return garment, step, st["latents"], None
         if self._side is None:
@@ -1008,7 +1025,7 @@ class TryonEngine:
         key = self._graph_key(st, live)                      # garment size included: calls with different garment sizes share nothing here
         if key in self._graphs:
             return self._graphs[key]
-        rows = st.get("rows")
+        rows = st["rows"] if self._kind(st) == "rows" else None
         G = {name: st[name] for name in ("B", "h", "w", "gh", "gw", "k", "garment_persons", "latents", "cond", "x_in") + (() if rows else ("ctx_t",))}
         if rows:
             # a ROW state serves every plan of every call of its shape: x_in and tt hold 2B rows and a step uses their first R; what a
@@ -1017,7 +1034,7 @@ class TryonEngine:
             G.update(x_in=torch.empty(2 * st["B"], *st["x_in"].shape[1:], dtype=self.dtype, device=self.device), rows={})
         # guided: the scratch of idmvton_guided_step, persistent like gix / gnk (the captures hold its pointer; its contents carry nothing
         # from one step to the next, so the first call's buffer is adopted and never copied)
-        G.update(guided=st.get("guided", False), branches=st.get("branches", 2), work=st.get("work"), person=st.get("person", False))
+        G.update(guided=st.get("guided", False), branches=st.get("branches", 2), work=st.get("work"), person=self._kind(st) == "person")
         # indexed: the table person -> set slot, a persistent buffer whose pointer the captured graphs hold; its contents are copied per call
         G["gix"] = self._slot_table(st) if not rows else None
         # ragged: the key-count table, persistent in the same way (the sets copy whole slots, so it is the call's own table)
@@ -1042,14 +1059,7 @@ class TryonEngine:
                 self._cached_fill(st, G["sets"][:1], blocks=(0,))(0, 0)   # (a table of block 0 alone: complete before the synchronize below)
                 if gc.features:                              # garment_projections counts the blocks of calls: not the warm-up's
                     self.stats["garment_projections"] -= 1
-            if rows:                                         # the warm-up step is the call's first; tryon_rows / row_steps count calls
-                plan = self._state_rows(G, st)[rows["step"][0]]
-                self._tryon_main(G, G["tt"][:plan["R"]], G["cf"], G["nz"], G["sets"][0]["step"][0], plan)
-                self._uncount_rows(plan)
-            else:
-                self._tryon_main(G, G["tt"], G["cf"], G["nz"], G["sets"][0]["step"][0])
-            if G["person"]:                                  # person_steps counts the steps of calls: not the warm-up's
-                self.stats["person_steps"] -= 1
+            self._state_step(G, 0, 0, self._state_rows(G, st)[rows["step"][0]] if rows else None)   # (the warm-up step is the call's first)
         torch.cuda.current_stream().wait_stream(warm)
         torch.cuda.synchronize()
         self._release_streamed()                             # (the warm-up fill of a host-resident cache has completed)
@@ -1080,10 +1090,10 @@ class TryonEngine:
             out.append(mine)
         return out
 
-    def _uncount_rows(self, plan):
-        """A warm-up or a capture ran _tryon_main's counting: tryon_rows / row_steps count the launches and replays of calls."""
-        self.stats["tryon_rows"] -= plan["R"]
-        self.stats["row_steps"] -= 1
+    def _state_step(self, G, par, j, plan=None):
+        """One TryonNet step of a graph state on its persistent buffers, timestep slice j of set par (a row state's at its plan's shape:
+        prefix views of tt and x_in): the warm-up, and what a capture records."""
+        self._tryon_main(G, G["tt"] if plan is None else G["tt"][:plan["R"]], G["cf"], G["nz"], G["sets"][par]["step"][j], plan)
 
     def _graph(self, G, kind, par, j=0, plan=None):
         gk = (kind, par, j) + ((plan["R"], plan["a"]) if plan is not None else ())
@@ -1096,13 +1106,8 @@ class TryonEngine:
             if kind == "garm":                                   # j = timesteps in the batch
                 self._garment_side(G, G["tgk"], G["sets"][par], j)
                 self.stats["garment_batches"] -= 1               # captured, not run: replays are counted
-            elif plan is not None:                               # a row state's step at this plan's shape: prefix views of tt and x_in
-                self._tryon_main(G, G["tt"][:plan["R"]], G["cf"], G["nz"], G["sets"][par]["step"][j], plan)
-                self._uncount_rows(plan)                         # captured, not run: replays are counted
             else:
-                self._tryon_main(G, G["tt"], G["cf"], G["nz"], G["sets"][par]["step"][j])
-                if G["person"]:
-                    self.stats["person_steps"] -= 1              # captured, not run: replays are counted
+                self._state_step(G, par, j, plan)
         G["latents"].copy_(keep)                                     # capture does not execute, but keep the state explicit
         G["graphs"][gk] = g
         return g
@@ -1135,24 +1140,17 @@ class TryonEngine:
         tt, cf, nz = G["tt"], G["cf"], G["nz"]
 
         def step(i, j, p):
-            tt.copy_(st["temb_t"][i]); cf.copy_(st["coef"][i])
+            plan = plans[rows["step"][i]] if rows else None
+            if plan is None:
+                tt.copy_(st["temb_t"][i])
+            else:
+                tt[:plan["R"]].copy_(rows["temb"][i])
+            cf.copy_(st["coef"][i])
             if nz is not None:
                 nz.copy_(st["steps_noise"][i])
-            if G["person"]:
-                self.stats["person_steps"] += 1
-            graphs[("tryon", p, j)].replay()
+            self._count_step(G, plan)
+            graphs[("tryon", p, j) + ((plan["R"], plan["a"]) if plan is not None else ())].replay()
 
-        def row_step(i, j, p):
-            plan = plans[rows["step"][i]]
-            tt[:plan["R"]].copy_(rows["temb"][i]); cf.copy_(st["coef"][i])
-            if nz is not None:
-                nz.copy_(st["steps_noise"][i])
-            self.stats["tryon_rows"] += plan["R"]
-            self.stats["row_steps"] += 1
-            graphs[("tryon", p, j, plan["R"], plan["a"])].replay()
-
-        if rows:
-            step = row_step
         return garment, step, G["latents"], (G["side"], G["ready"], G["free"]) if overlap else None
 
     @torch.no_grad()
